@@ -4,6 +4,8 @@ of a full V4 train step -- encoder + decoder + discriminator forward/backward,
 WGAN-GP D-step, Chamfer, both Adams -- on synthetic mmGait10-shaped batches).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full           # + every other measurement (see below)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs, DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # outside a torchrun environment: starts that same command as a child
@@ -17,7 +19,14 @@ points, C=4 features, K=8 classes, inputs resident in HBM before the timed
 region; data parallel over N GPUs (weak scaling: global batch 64*N, RCCL
 all-reduce of the flat gradient buffers).  One JSON line on rank 0.
 
-At N=1 the same line also carries the other BASELINE configs as extra keys, each
+A plain run sets up, warms up (``--warmup`` steps), times exactly ``--steps`` steps
+in one window (barrier + synchronize on both sides), writes ``--dump-outputs`` if
+asked and prints the line: ``value`` and ``ms_per_step`` come from that window.
+
+With ``--full`` the timed region is repeated (5 windows, the median is ``value``),
+the dominant GEMM kernel is timed for ``roofline``, at N>1 (or with ``--dp-force``)
+every exchange scheme is timed under ``dp_legs``, and at N=1 the line also carries
+the other BASELINE configs as extra keys, each
 measured in this run (none of them is ``value``): ``parity_mode`` (config[1] in the
 parity-grade modes the 1e-4 tests run in: split-fp16 "fp16x3", and exact fp32 under ``exact_fp32``), ``sweep`` (config[3], the
 point-subsampling sweep N in {32,64,128,256}), ``infer`` (config[4], open-set
@@ -50,9 +59,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--windows", type=int, default=None,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is repeated this many "
-                         "times; ms_per_step / value are the MEDIAN window, all windows are in config.windows_ms_per_step")
+                         "times; ms_per_step / value are the MEDIAN window, all windows are in config.windows_ms_per_step "
+                         "(default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the repeated windows, the dominant kernel's "
+                         "roofline, the CPU baseline, the parity-mode / batcher / section legs, the other BASELINE configs "
+                         "(sweep, infer, c5, ref_default, loop, dp_emulated) and, at N > 1 or with --dp-force, every "
+                         "exchange scheme (dp_legs); --workload infer: its CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (losses, labels, logits, embeddings) "
+                         "as DIR/<name>.npy in float32 / float64 (rank 0; train workload)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp16x3"])
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--points", type=int, default=128)
@@ -102,7 +120,7 @@ def parse():
         a.grad_compress = "bf16" if a.precision == "bf16" else "none"
     if a.dp_mode == "auto":
         a.dp_mode = "gather" if a.precision == "bf16" else "allreduce"
-    a.windows = max(1, a.windows)
+    a.windows = max(1, a.windows if a.windows is not None else (5 if a.full else 1))
     return a
 
 
@@ -308,6 +326,37 @@ def time_single_gpu(run, steps, windows):
 
 def spread(ms_list):
     return {"median": statistics.median(ms_list), "min": min(ms_list), "max": max(ms_list), "windows": len(ms_list)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory):
+    """What a caller of the timed step receives (its returned dict: losses, argmax labels, logits, embeddings) as
+    ``directory/<name>.npy``: floating tensors as float32 (float64 stays float64), integer ones as float64 (exact).
+    Non-numeric entries are left out.  Over DUMP_LIMIT_BYTES in all, every array larger than an equal share of the
+    limit is replaced by a fixed sample of its elements (flattened, positions drawn from seed 0: the same for the same
+    shape).  The inputs and fills are seeded, so two runs with the same arguments compute from the same inputs; at
+    config[1] and at the B=8, N=32 shape of tests/test_bench_options.py the two dumps have been the same bits.
+    -> {name: shape written}"""
+    import numpy as np
+    arrays = {}
+    for name, v in out.items():
+        if torch.is_tensor(v):
+            t = v.detach().cpu()
+            arrays[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            arrays[name] = np.asarray(v, dtype=np.float64)
+    if sum(x.nbytes for x in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for name, x in arrays.items():
+            if x.nbytes > share:
+                pick = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+                arrays[name] = x.reshape(-1)[pick]
+    os.makedirs(directory, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), x)
+    return {name: list(x.shape) for name, x in arrays.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -596,7 +645,7 @@ def workload_infer(a, dev):
     from opensetgaitrecognition_pcaa_amd import constants, functional as F_hip
     constants.NFEATURES = a.features
     F_hip.set_precision(a.precision)
-    ent = leg_infer(a, dev, a.steps, a.windows, with_cpu=not a.no_cpu_baseline)
+    ent = leg_infer(a, dev, a.steps, a.windows, with_cpu=a.full and not a.no_cpu_baseline)
     line = {"metric": "gait sequences/sec (open-set inference)", "value": ent["value"], "unit": "sequences/s",
             "n_gpus": 1, "steps": a.steps, "warmup": 2, "ms_per_step": ent["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -676,6 +725,8 @@ def main():
     if a.workload != "train":
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("bench.py: --workload sweep / infer are single-GPU workloads")
+        if a.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the train workload's outputs")
         dev = torch.device("cuda", int(os.environ.get("PCAA_BENCH_DEVICE", "0")))
         torch.cuda.set_device(dev)
         if a.workload == "loop":
@@ -736,7 +787,7 @@ def main():
         out = tr.step_graphed(pcs, gt, z0, al, warmup=0)
         run_step = tr.step_graphed
     timer = None
-    if not a.no_kernel_timing:
+    if a.full and not a.no_kernel_timing:
         # HIP events on the kernel family the roofline reports: the start/stop events ride on the launch
         # itself (hipExtLaunchKernelGGL through pcaa_time_next_gemm), i.e. they are the kernel's own begin/end
         # timestamps -- the quantity rocprofv3's kernel trace reports -- on the stream it is launched on
@@ -760,6 +811,8 @@ def main():
         windows_s.append(max_over_ranks(time.perf_counter() - t0))
         ops.set_timer(None)
     dt = statistics.median(windows_s)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
     loss_ok = bool(torch.isfinite(out["tot_loss"]).item())
     comm = dict(tr.comm)
     single = world == 1 and not a.dp_force and not a.dp_emulate
@@ -786,11 +839,11 @@ def main():
         return max_over_ranks(time.perf_counter() - t_0)
 
     sections = None
-    if single and not a.no_extra_legs and not use_graph:
+    if a.full and single and not a.no_extra_legs and not use_graph:
         sections = leg_sections(tr, (pcs, gt, z0, al))
 
     batcher_leg = None
-    if not a.no_batcher_leg and not use_graph and single:
+    if a.full and not a.no_batcher_leg and not use_graph and single:
         # datasets.py batch collation inside the timed loop: a packed point-major store of `pool` synthetic crops
         # resident in HBM, every step's batch gathered from it in the DataLoader's shuffled order
         # (DeviceBatcher = pcaa_gather_rows), then the same train step
@@ -816,7 +869,7 @@ def main():
     torch.cuda.empty_cache()
 
     parity_leg = None
-    if a.precision == "bf16" and not a.no_parity_mode and not use_graph and single:
+    if a.full and a.precision == "bf16" and not a.no_parity_mode and not use_graph and single:
         # the SAME workload in the two parity-grade modes -- the modes the 1e-4 / bit-exact label tests run in
         # (tests/test_round2_parity.py::test_config1_full_size_fp32_step_vs_oracle, both parametrisations):
         # "fp16x3": fp32 storage, PointNet products as three bf16 MFMA passes over [hi | lo] operand images;
@@ -836,12 +889,12 @@ def main():
         parity_leg["exact_fp32"] = legs["fp32"]
         F_hip.set_precision(a.precision)
 
-    # Data-parallel legs (round 4): the driver runs `bench.py --gpus N` ONCE per N, so that one
-    # invocation also times every exchange scheme the trainer has -- (all-reduce | ZeRO-1 reduce-scatter + sharded Adam +
+    # Data-parallel legs (round 4): one `bench.py --gpus N --full` invocation per N
+    # also times every exchange scheme the trainer has -- (all-reduce | ZeRO-1 reduce-scatter + sharded Adam +
     # all-gather) x (fp32 | bf16 gradient buckets), and SyncBN -- each with the communication time the step could not
     # hide.  ``value`` is the documented default (bf16 mode: gathered operands; parity modes: all-reduce; per-rank BatchNorm).
     dp_legs = None
-    if (world > 1 or a.dp_force) and not a.no_extra_legs:
+    if a.full and (world > 1 or a.dp_force) and not a.no_extra_legs:
         import copy
         dp_legs = []
         combos = [("allreduce", "bf16", False), ("allreduce", "none", False), ("zero", "bf16", False),
@@ -876,7 +929,7 @@ def main():
             torch.cuda.empty_cache()
 
     sweep = infer = c5 = ref_default = dp_emulated = loop = None
-    if single and not a.no_extra_legs and a.precision == "bf16":
+    if a.full and single and not a.no_extra_legs and a.precision == "bf16":
         esteps = max(1, min(a.steps, 10))
         # the drop-in loop itself (north_star: "keeping ... the train_AAE.py/PCAA_ablation.py training-loop API")
         loop = leg_loop(a, dev, N)
@@ -1013,7 +1066,7 @@ def main():
                                 "other_timed": {k: {"ms_per_step": v["ms"] / timed_steps,
                                                     "achieved": v["flops"] / (v["ms"] * 1e-3) / 1e12}
                                                 for k, v in agg.items() if k != name}}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B, N, C, K, T)
             if sections is not None:
                 # the two breakdowns side by side, per phase: CPU seconds (at the sample's batch) and GPU microseconds

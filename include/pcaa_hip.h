@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 16 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 17 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -81,6 +81,11 @@ int pcaa_gemm_num_splits(int math, int K, int split_k);
  * over split_k[i] ranges of the contraction): the caller zeroes it. */
 int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* const* B, void* const* C, const int* M,
                            const int* N, const int* K, const int* split_k, void* stream);
+/* ABI 17: the same products without atomics: slabs_i holds pcaa_gemm_num_splits(PCAA_F32, K_i, split_k[i]) slabs
+ * [M_i, N_i], range s of the contraction overwrites slab s; pcaa_splitk_reduce then sums them in a fixed order (the same
+ * result every run). */
+int pcaa_gemm_group_rc_f32_slabs(int n, const void* const* A, const void* const* B, void* const* slabs, const int* M,
+                                 const int* N, const int* K, const int* split_k, void* stream);
 /* Which tile loop serves the bf16 / split-fp16 KC x KC products without K splits (whole 256 x 256 tiles, contraction
  * >= 320 deep): 1 (default; environment PCAA_GEMM_V2=0 to start with 0) = the 4-wave loop of round 4 (csrc/gemm_v2.h:
  * 128 x 128 wave tiles, both operands requested two K steps ahead, the request stream continuous across tiles), 0 = the
@@ -167,6 +172,14 @@ int pcaa_pointnet_in_bwd_onepass(const void* da, int dtype, const float* x, int 
                                  const float* scale, const float* shift, const float* mean, const float* rstd,
                                  double* stats, int nrep, float* G, long P, int cout, const double* pivot_mom,
                                  double pivot_inv_count, void* stream);
+/* ABI 17: the same pass without atomics on G: workgroup b STORES its partial to row b of
+ * G[pcaa_pointnet_in_bwd_g_rows(P)][cout,C] (no zeroing needed); pass that row count as the combine's nrep, which sums
+ * the rows in a fixed order -- dW is then the same every run. */
+int pcaa_pointnet_in_bwd_onepass_rows(const void* da, int dtype, const float* x, int C, const float* W,
+                                      const float* scale, const float* shift, const float* mean, const float* rstd,
+                                      double* stats, int nrep, float* G, long P, int cout, const double* pivot_mom,
+                                      double pivot_inv_count, void* stream);
+int pcaa_pointnet_in_bwd_g_rows(long P);
 int pcaa_points_moments_size(void);
 int pcaa_points_moments(const float* x, int C, long P, double* mom, void* stream);
 /* Round 4: G is accumulated against the points centred on a pivot, pivot[c] = (float)(pivot_mom[64 + c] *

@@ -97,11 +97,11 @@ __device__ __forceinline__ void f_store_tile(float* __restrict__ s, const f32x4 
 // shared epilogue: bias, store / atomic, BatchNorm column statistics
 template <typename TC>
 __device__ __forceinline__ void epilogue(const GemmParams& p, f32x16 (&acc)[2][2], float* smem,
-                                         int tm, int tn, int tid) {
+                                         int tm, int tn, int tid, int split) {
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, half = lane >> 5;
-  TC* C = reinterpret_cast<TC*>(p.C) + (long)blockIdx.z * p.c_split_stride;   // slab split-K (0 otherwise)
-  const bool add_bias = p.bias != nullptr && (!p.atomic || blockIdx.z == 0);
+  TC* C = reinterpret_cast<TC*>(p.C) + (long)split * p.c_split_stride;   // slab split-K (0 otherwise)
+  const bool add_bias = p.bias != nullptr && (!p.atomic || split == 0);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int gn = tn * BN + wn * 64 + j * 32 + l31;
@@ -218,7 +218,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, int bid, int 
       __syncthreads();
     }
   }
-  epilogue<TC>(p, acc, smem, tm, tn, tid);
+  epilogue<TC>(p, acc, smem, tm, tn, tid, split);
 }
 
 template <typename TA, typename TB, typename TC, int ALAY, int BLAY, bool VEC>
@@ -231,7 +231,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
 // launches of 1-24 tiles x <= 15 K ranges each, 26-47 us apiece in a chain on the weight-gradient stream: 0.23 ms at
 // N = 32 and, sharing hardware queues with it, in the way of the dgrad chain -- without them the N = 32 step is 0.17 ms
 // shorter).  Block b of the launch belongs to product i with first[i] <= b < first[i + 1]; within it the tile number runs
-// fastest, then the K range.  fp32 RC x RC operands, fp32 result accumulated atomically (the caller zeroes it).
+// fastest, then the K range.  fp32 RC x RC operands, fp32 result accumulated atomically (the caller zeroes it), or -- the
+// slab form -- K range s of product i stores its partial product to C_i + s * M_i * N_i (no atomics: the caller sums
+// the slabs in a fixed order, so the result is the same every run).
 constexpr int GROUP_MAX = 8;
 struct GemmGroup {
   GemmParams p[GROUP_MAX];
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
       __syncthreads();
     }
   }
-  epilogue<TC>(p, acc, smem_f, tm, tn, tid);
+  epilogue<TC>(p, acc, smem_f, tm, tn, tid, (int)blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------
@@ -499,9 +501,10 @@ extern "C" int pcaa_gemm(int math,
 
 /* n <= 8 products C_i[M_i, N_i] += A_i^T . B_i in one launch: A_i [K_i, M_i], B_i [K_i, N_i], C_i [M_i, N_i] fp32, contiguous
  * rows (lda = M_i, ldb = N_i, ldc = N_i), 16-B aligned, M_i and N_i multiples of 4; C_i is ACCUMULATED into (atomics over
- * the K ranges): the caller zeroes it.  split_k[i]: how many ranges product i's contraction is cut into. */
-extern "C" int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* const* B, void* const* C, const int* M,
-                                      const int* N, const int* K, const int* split_k, void* stream) {
+ * the K ranges): the caller zeroes it.  split_k[i]: how many ranges product i's contraction is cut into.
+ * slabs: C_i instead holds pcaa_gemm_num_splits(PCAA_F32, K_i, split_k[i]) slabs [M_i, N_i], K range s overwrites slab s. */
+static int gemm_group_rc_f32(int n, const void* const* A, const void* const* B, void* const* C, const int* M,
+                             const int* N, const int* K, const int* split_k, bool slabs, void* stream) {
   PCAA_CHECK_ARG(n >= 1 && n <= GROUP_MAX && A && B && C && M && N && K && split_k, "pcaa_gemm_group_rc_f32: bad args (n <= %d)",
                  GROUP_MAX);
   GemmGroup g;
@@ -518,7 +521,8 @@ extern "C" int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* c
     p.lda = M[i]; p.ldb = N[i]; p.ldc = N[i];
     p.M = M[i]; p.N = N[i]; p.K = K[i];
     p.nrep = 1;
-    p.atomic = 1;
+    p.atomic = slabs ? 0 : 1;
+    p.c_split_stride = slabs ? (long)M[i] * N[i] : 0;
     p.nsplit = 1;
     int kps = 0;
     const int nsplit = gemm_num_splits(PCAA_F32, K[i], split_k[i], &kps);
@@ -531,6 +535,16 @@ extern "C" int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* c
   PCAA_CHECK_ARG(total < (1L << 31), "pcaa_gemm_group_rc_f32: too many blocks");
   hipLaunchKernelGGL(gemm_f32_group_kernel, dim3((unsigned)total), dim3(256), 0, as_stream(stream), g);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_gemm_group_rc_f32");
+}
+
+extern "C" int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* const* B, void* const* C, const int* M,
+                                      const int* N, const int* K, const int* split_k, void* stream) {
+  return gemm_group_rc_f32(n, A, B, C, M, N, K, split_k, false, stream);
+}
+
+extern "C" int pcaa_gemm_group_rc_f32_slabs(int n, const void* const* A, const void* const* B, void* const* slabs,
+                                            const int* M, const int* N, const int* K, const int* split_k, void* stream) {
+  return gemm_group_rc_f32(n, A, B, slabs, M, N, K, split_k, true, stream);
 }
 
 // split-K without atomics: split s writes its partial product to slabs + s * slab_stride

@@ -4,7 +4,9 @@
 // Chamfer: one workgroup per (batch, time) frame.  Both point sets of the frame
 // (2 * N * C floats) sit in LDS; work item w < N handles prediction j = w
 // (min over ground-truth points, loss_1), work item N + i handles ground-truth
-// point i (min over predictions, loss_2, gradient scattered with LDS atomics).
+// point i (min over predictions, loss_2).  The gradient w.r.t. prediction j is gathered afterwards from the
+// recorded nearest neighbours in a fixed order (its own term, then ground-truth points i ascending): no atomics, the
+// same sums every run.
 // The N x N distance matrix is never materialised.  Distances use the
 // reference's expanded form |g|^2 + |p|^2 - 2 g.p so values and argmins follow
 // the same rounding behaviour.
@@ -26,7 +28,7 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_kernel(
   float* sp = sg + (long)N * MAXC;   // [N][MAXC] predictions
   float* rg = sp + (long)N * MAXC;   // [N] |g|^2
   float* rp = rg + N;                // [N] |p|^2
-  float* sgrad = rp + N;             // [N][MAXC] gradient w.r.t. predictions
+  int* nn = reinterpret_cast<int*>(rp + N);   // [2N] nearest neighbour of item w (w < N: of prediction w; else of gt w - N)
   __shared__ float red[CH_THREADS / 64];
 
   const int frame = blockIdx.x;
@@ -38,7 +40,6 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_kernel(
     const int n = e / MAXC, c = e - n * MAXC;
     sg[e] = (c < C) ? gb[c * g_sc + n * g_sn] : 0.f;
     sp[e] = (c < C) ? pb[c * p_sc + n * p_sn] : 0.f;
-    sgrad[e] = 0.f;
   }
   __syncthreads();
   for (int n = threadIdx.x; n < N; n += CH_THREADS) {
@@ -76,16 +77,7 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_kernel(
       if (P < best) { best = P; bi = o; }
     }
     loss += best;
-    if (dpreds) {
-      // d/dpred_j (|g_i|^2 + |p_j|^2 - 2 g_i.p_j) = 2 (p_j - g_i)
-      const int j = dir1 ? me : bi;
-      const int i = dir1 ? bi : me;
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) {
-        const float gval = 2.f * w * (sp[j * MAXC + c] - sg[i * MAXC + c]);
-        atomicAdd(&sgrad[j * MAXC + c], gval);
-      }
-    }
+    nn[item] = bi;
   }
   loss = wave_sum(loss);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
@@ -96,11 +88,17 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_kernel(
     frame_loss[frame] = tot;
   }
   if (dpreds) {
+    __syncthreads();                 // nn[] complete
     float* db = dpreds + b * d_sb + t * d_st;
     // walk (c, n) with n fastest: contiguous in the decoder's [B,C,T,N] layout
+    // d/dpred_n (|g_i|^2 + |p_n|^2 - 2 g_i.p_n) = 2 (p_n - g_i), for i = nn[n] and for every i with nn[N + i] == n
     for (int e = threadIdx.x; e < N * C; e += CH_THREADS) {
       const int c = e / N, n = e - c * N;
-      db[c * d_sc + n * d_sn] = sgrad[n * MAXC + c];
+      const float pv = sp[n * MAXC + c];
+      float g = 2.f * w * (pv - sg[nn[n] * MAXC + c]);
+      for (int i = 0; i < N; ++i)
+        if (nn[N + i] == n) g += 2.f * w * (pv - sg[i * MAXC + c]);
+      db[c * d_sc + n * d_sn] = g;
     }
   }
 }
@@ -149,7 +147,7 @@ extern "C" int pcaa_chamfer_fwd_bwd(const float* preds, long p_sb, long p_sc, lo
                                     const float* grad_per_b, void* stream) {
   PCAA_CHECK_ARG(preds && gts && frame_loss, "pcaa_chamfer_fwd_bwd: null pointer");
   PCAA_CHECK_ARG(B >= 1 && T >= 1 && N >= 1 && C >= 1 && C <= MAXC, "pcaa_chamfer_fwd_bwd: need 1<=C<=%d (C=%d)", MAXC, C);
-  const size_t lds = ((size_t)3 * N * MAXC + 2 * (size_t)N) * sizeof(float);
+  const size_t lds = ((size_t)2 * N * MAXC + 4 * (size_t)N) * sizeof(float);   // sg, sp, rg, rp, nn[2N]
   PCAA_CHECK_ARG(lds <= 150 * 1024, "pcaa_chamfer_fwd_bwd: N=%d too large for one LDS tile", N);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(chamfer_kernel),

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void pointnet_in_bwd_kernel(const T* __restric
                                                               double* __restrict__ stats, int nrep,
                                                               float* __restrict__ dW, long P, int cout, BnTail tail,
                                                               const double* __restrict__ pivot_mom = nullptr,
-                                                              double pivot_inv_count = 0.0) {
+                                                              double pivot_inv_count = 0.0, int g_row_per_wg = 0) {
   __shared__ int tail_flag;
   __shared__ float xs[1024 * CP];     // points [WG_ROWS][CP], later the [rl][cout][CP] row-lane combine (rl*cout = 1024)
   const int qpr = cout >> 2, rl = 256 / qpr;
@@ -340,9 +340,12 @@ __global__ __launch_bounds__(256) void pointnet_in_bwd_kernel(const T* __restric
       const int ch = o / C, c = o - ch * C;
       float v = 0.f;
       for (int l = 0; l < rl; ++l) v += red[(l * cout + ch) * CP + c];
-      // MODE 3 spreads the 1 920 workgroups' adds over nrep replicas of G (all of them into ONE [cout, C] image ran at the
-      // contended atomic rate: the pass took 0.14 ms for a 252 MB read); the combine kernel sums the replicas
-      atomicAdd(&dW[(MODE == 3 ? (long)(blockIdx.x % nrep) * cout * C : 0L) + o], v);
+      // MODE 3, g_row_per_wg: row b of G belongs to workgroup b (a store, no atomics) and the combine kernel sums the
+      // rows in a fixed order, so dW does not depend on the order the workgroups finish in.  Otherwise the workgroups'
+      // adds are spread over nrep replicas of G (all of them into ONE [cout, C] image ran at the contended atomic rate:
+      // the pass took 0.14 ms for a 252 MB read); the combine kernel sums the replicas
+      if (MODE == 3 && g_row_per_wg) dW[(long)blockIdx.x * cout * C + o] = v;
+      else atomicAdd(&dW[(MODE == 3 ? (long)(blockIdx.x % nrep) * cout * C : 0L) + o], v);
     }
   }
   if (MODE == 0 || MODE == 3) bn_tail_run(tail, threadIdx.x, 256, gridDim.x, &tail_flag);
@@ -428,17 +431,28 @@ __global__ void pointnet_in_moment_stats_kernel(const double* __restrict__ mom, 
 // The term pivot_c * sum_p dy[p][o] that completes sum dy x is dropped: sum_p dy = 0 for every channel (BatchNorm's
 // backward removes the mean; under SyncBN the pivot is the GLOBAL mean, the same on every rank, so the ranks' terms
 // cancel in the gradient all-reduce) -- it only ever held rounding noise times the pivot.
-__global__ void pointnet_in_bwd_combine_kernel(const float* __restrict__ G, int nrep, const float* __restrict__ W,
-                                               const double* __restrict__ mom, const float* __restrict__ coef,
-                                               float* __restrict__ dW, int cout, int C, double P,
-                                               const double* __restrict__ pivot_mom, double pivot_inv_count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cout * C) return;
+// One workgroup per (o, c): G' = the sum of G's g_rows rows, in a fixed order (strided per lane, then the wave and
+// workgroup trees).
+__global__ __launch_bounds__(256) void pointnet_in_bwd_combine_kernel(const float* __restrict__ G, int g_rows,
+                                                                      const float* __restrict__ W,
+                                                                      const double* __restrict__ mom,
+                                                                      const float* __restrict__ coef,
+                                                                      float* __restrict__ dW, int cout, int C, double P,
+                                                                      const double* __restrict__ pivot_mom,
+                                                                      double pivot_inv_count) {
+  __shared__ double red[4];
+  const int i = blockIdx.x;
   const int o = i / C, c = i - o * C;
+  double g = 0.0;
+  for (int r = threadIdx.x; r < g_rows; r += 256) g += (double)G[(long)r * cout * C + i];
+  g = wave_sum_d(g);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = g;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  g = (red[0] + red[1]) + (red[2] + red[3]);
   const double piv = pivot_mom ? (double)(float)(pivot_mom[MAXC * MAXC + c] * pivot_inv_count) : 0.0;
-  double yx = 0.0, g = 0.0;
+  double yx = 0.0;
   for (int k = 0; k < C; ++k) yx += (double)W[o * C + k] * (mom[k * MAXC + c] - piv * mom[MAXC * MAXC + k]);
-  for (int r = 0; r < nrep; ++r) g += (double)G[(long)r * cout * C + i];
   dW[i] = (float)((double)coef[o] * g + (double)coef[cout + o] * yx +
                   (double)coef[2 * cout + o] * (mom[MAXC * MAXC + c] - P * piv));
 }
@@ -633,11 +647,12 @@ extern "C" int pcaa_pointnet_in_bwd_wgrad(const void* da, int dtype, const float
 }
 
 /* One-pass backward of the recompute layer (round 3): statistics AND G = dz^T . x from one read of da
- * (pointnet_in_bwd_kernel MODE 3), then pcaa_pointnet_in_bwd_combine with the points' moments. */
-extern "C" int pcaa_pointnet_in_bwd_onepass(const void* da, int dtype, const float* x, int C, const float* W,
-                                            const float* scale, const float* shift, const float* mean,
-                                            const float* rstd, double* stats, int nrep, float* G, long P, int cout,
-                                            const double* pivot_mom, double pivot_inv_count, void* stream) {
+ * (pointnet_in_bwd_kernel MODE 3), then pcaa_pointnet_in_bwd_combine with the points' moments.  g_row_per_wg: G has
+ * pcaa_pointnet_in_bwd_g_rows(P) rows, workgroup b stores row b; else workgroup b adds into replica b % nrep. */
+static int pointnet_in_bwd_onepass(const void* da, int dtype, const float* x, int C, const float* W, const float* scale,
+                                   const float* shift, const float* mean, const float* rstd, double* stats, int nrep,
+                                   float* G, long P, int cout, const double* pivot_mom, double pivot_inv_count,
+                                   int g_row_per_wg, void* stream) {
   PCAA_CHECK_ARG(da && x && W && scale && shift && mean && rstd && stats && G && P >= 1 && nrep >= 1,
                  "pcaa_pointnet_in_bwd_onepass: bad args");
   PCAA_CHECK_ARG(shape_ok(C, cout), "pcaa_pointnet_in_bwd_onepass: need C<=%d and cout/4 dividing 256 (C=%d cout=%d)", MAXC, C, cout);
@@ -645,13 +660,31 @@ extern "C" int pcaa_pointnet_in_bwd_onepass(const void* da, int dtype, const flo
   const BnTail tail = pcaa_take_bn_tail(stats);
   if (dtype == PCAA_F32)
     LAUNCH_BWD(float, 3, (const float*)da, x, C, W, scale, shift, mean, rstd, nullptr, stats, nrep, G, P, cout, tail,
-               pivot_mom, pivot_inv_count);
+               pivot_mom, pivot_inv_count, g_row_per_wg);
   else if (dtype == PCAA_BF16)
     LAUNCH_BWD(bf16_t, 3, (const bf16_t*)da, x, C, W, scale, shift, mean, rstd, nullptr, stats, nrep, G, P, cout, tail,
-               pivot_mom, pivot_inv_count);
+               pivot_mom, pivot_inv_count, g_row_per_wg);
   else { pcaa_set_error("pcaa_pointnet_in_bwd_onepass: bad dtype"); return PCAA_ERR_INVALID_ARG; }
   PCAA_RETURN_LAUNCH_STATUS("pcaa_pointnet_in_bwd_onepass");
 }
+
+extern "C" int pcaa_pointnet_in_bwd_onepass(const void* da, int dtype, const float* x, int C, const float* W,
+                                            const float* scale, const float* shift, const float* mean,
+                                            const float* rstd, double* stats, int nrep, float* G, long P, int cout,
+                                            const double* pivot_mom, double pivot_inv_count, void* stream) {
+  return pointnet_in_bwd_onepass(da, dtype, x, C, W, scale, shift, mean, rstd, stats, nrep, G, P, cout, pivot_mom,
+                                 pivot_inv_count, 0, stream);
+}
+
+extern "C" int pcaa_pointnet_in_bwd_onepass_rows(const void* da, int dtype, const float* x, int C, const float* W,
+                                                 const float* scale, const float* shift, const float* mean,
+                                                 const float* rstd, double* stats, int nrep, float* G, long P, int cout,
+                                                 const double* pivot_mom, double pivot_inv_count, void* stream) {
+  return pointnet_in_bwd_onepass(da, dtype, x, C, W, scale, shift, mean, rstd, stats, nrep, G, P, cout, pivot_mom,
+                                 pivot_inv_count, 1, stream);
+}
+
+extern "C" int pcaa_pointnet_in_bwd_g_rows(long P) { return (int)cdiv(P, BWD_ROWS); }
 
 extern "C" int pcaa_points_moments_size(void) { return MAXC * MAXC + MAXC; }
 
@@ -682,7 +715,7 @@ extern "C" int pcaa_pointnet_in_bwd_combine(const float* G, int nrep, const floa
                                             const double* pivot_mom, double pivot_inv_count, void* stream) {
   PCAA_CHECK_ARG(G && W && mom && coef && dW && cout >= 1 && C >= 1 && C <= MAXC && nrep >= 1,
                  "pcaa_pointnet_in_bwd_combine: bad args");
-  hipLaunchKernelGGL(pointnet_in_bwd_combine_kernel, dim3((unsigned)cdiv((long)cout * C, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(pointnet_in_bwd_combine_kernel, dim3((unsigned)(cout * C)), dim3(256), 0,
                      as_stream(stream), G, nrep, W, mom, coef, dW, cout, C, (double)P, pivot_mom, pivot_inv_count);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_pointnet_in_bwd_combine");
 }

@@ -424,22 +424,30 @@ def gemm(A, a_layout, B, b_layout, M, N, K, *, lda=None, ldb=None, out=None, out
 
 def gemm_group_rc_f32(products):
     """``products``: up to 8 tuples (A [K,M] fp32, B [K,N] fp32, C [M,N] fp32 -- accumulated into, the caller zeroes it --,
-    split_k): all of them C += A^T . B on the exact-fp32 matrix pipe in ONE launch (pcaa_gemm_group_rc_f32)."""
+    split_k): all of them C += A^T . B on the exact-fp32 matrix pipe in ONE launch (pcaa_gemm_group_rc_f32_slabs), whose K
+    ranges write slabs that pcaa_splitk_reduce then adds into C in a fixed order (no atomics: the same result every run)."""
     n = len(products)
     if not 1 <= n <= 8:
         raise ValueError("gemm_group_rc_f32: 1..8 products")
     ptr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
     ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    lib = _lib.load()
+    splits = []
     for A, B, C, sk in products:
         _chk(A, "gemm_group.A", torch.float32, 2)
         _chk(B, "gemm_group.B", torch.float32, 2)
         _chk(C, "gemm_group.C", torch.float32)
         if A.shape[0] != B.shape[0] or C.numel() != A.shape[1] * B.shape[1] or A.stride(0) != A.shape[1] or B.stride(0) != B.shape[1]:
             raise ValueError("gemm_group_rc_f32: A [K,M], B [K,N] with contiguous rows, C [M,N]")
-    check(_lib.load().pcaa_gemm_group_rc_f32(
-        n, ptr([p[0] for p in products]), ptr([p[1] for p in products]), ptr([p[2] for p in products]),
+        splits.append(lib.pcaa_gemm_num_splits(PCAA_F32, A.shape[0], int(sk)))
+    sizes = [ns * p[2].numel() for ns, p in zip(splits, products)]          # multiples of 4 floats: 16-B aligned slices
+    slabs = torch.empty(sum(sizes), dtype=torch.float32, device=products[0][2].device).split(sizes)
+    check(lib.pcaa_gemm_group_rc_f32_slabs(
+        n, ptr([p[0] for p in products]), ptr([p[1] for p in products]), ptr(slabs),
         ints([p[0].shape[1] for p in products]), ints([p[1].shape[1] for p in products]), ints([p[0].shape[0] for p in products]),
-        ints([p[3] for p in products]), _s()), "pcaa_gemm_group_rc_f32")
+        ints([p[3] for p in products]), _s()), "pcaa_gemm_group_rc_f32_slabs")
+    for (_, _, C, _), sl, ns in zip(products, slabs, splits):
+        check(lib.pcaa_splitk_reduce(_p(sl), ns, C.numel(), C.numel(), _p(C), 1, _s()), "pcaa_splitk_reduce")
 
 
 def gemm_slabs(A, a_layout, B, b_layout, M, N, K, split_k, out=None, accumulate=False, math=PCAA_BF16,
@@ -930,22 +938,17 @@ def pointnet_in_bwd_onepass(da, x2d, W2d, scale, shift, mean, rstd, tail, mom=No
         pivot_mom = mom.clone()
         pivot_count = tail.sync(pivot_mom, P)
     stats = new_stats(cout, da.device)
-    # replica b % NREP of workgroup b; zeroed with the step's statistics (StatsPool.begin: one fill per step) -- a fill of
-    # its own sat on the critical path between the last product of the backward and this launch
-    nG = NREP * cout * C
-    raw = STATS_POOL.take_raw((nG + 1) // 2) if (STATS_POOL is not None and STATS_POOL.buf.device == da.device) else None
-    if raw is None:
-        G = torch.zeros((NREP, cout, C), dtype=torch.float32, device=da.device)
-    else:
-        G = raw.view(torch.float32)[:nG].view(NREP, cout, C)
+    # one row per workgroup, stored (not accumulated): the combine sums the rows in a fixed order
+    g_rows = lib.pcaa_pointnet_in_bwd_g_rows(P)
+    G = torch.empty((g_rows, cout, C), dtype=torch.float32, device=da.device)
     tail.arm(stats)
-    check(lib.pcaa_pointnet_in_bwd_onepass(_p(da), _dt(da), _p(x2d), C, _p(W2d), _p(scale), _p(shift), _p(mean), _p(rstd),
-                                           _p(stats), NREP, _p(G), P, cout, _p(pivot_mom), 1.0 / pivot_count, _s()),
-          "pcaa_pointnet_in_bwd_onepass")
+    check(lib.pcaa_pointnet_in_bwd_onepass_rows(_p(da), _dt(da), _p(x2d), C, _p(W2d), _p(scale), _p(shift), _p(mean),
+                                                _p(rstd), _p(stats), NREP, _p(G), P, cout, _p(pivot_mom), 1.0 / pivot_count,
+                                                _s()), "pcaa_pointnet_in_bwd_onepass_rows")
     coef, _, _ = tail.resolve(stats)
     if out is None:
         out = torch.empty((cout, C), dtype=torch.float32, device=da.device)
-    check(lib.pcaa_pointnet_in_bwd_combine(_p(G), NREP, _p(W2d), _p(mom), _p(coef), _p(out), cout, C, P, _p(pivot_mom),
+    check(lib.pcaa_pointnet_in_bwd_combine(_p(G), g_rows, _p(W2d), _p(mom), _p(coef), _p(out), cout, C, P, _p(pivot_mom),
                                            1.0 / pivot_count, _s()), "pcaa_pointnet_in_bwd_combine")
     return out
 

@@ -470,7 +470,7 @@ def test_bench_multi_rank_branch_runs_on_two_gloo_ranks():
     env = dict(os.environ, PCAA_BENCH_DEVICE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--windows", "2", "--backend", "gloo", "--no-cpu-baseline"]
+           "--windows", "2", "--backend", "gloo", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
