@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 17 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 18 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -487,6 +487,45 @@ int pcaa_dtc_conv_fwd(const float* src, const float* scale, const float* shift, 
 int pcaa_dtc_conv_fwd_bf16(const float* src, const float* scale, const float* shift, const float* W, float* y,
                       float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
                       int ksplit, long slab_stride, void* stream);
+
+/* ABI 18: the same layer in eval form (col and stats must be NULL) on a WINDOWED source.  `table` is a frame-feature table
+ * [table_rows, cin]: the eval-mode PointNet block plus the mean over a frame's points is a function of one frame
+ * (models.py:6-34, 82-105, 242-243, 279-282), and consecutive crops of a track share T - hop of their T frames
+ * (datasets.py:16-25, 297-302), so each frame is encoded once and a crop is a window of T rows of the table.  Sequence b,
+ * step t reads table row win_row[b] + t (win_row: [B] device ints), or row (win_row[b] + t) % ring_rows with ring_rows > 0
+ * (a ring of the last ring_rows frames of a live stream; T <= ring_rows <= table_rows) -- only the staging address of
+ * pcaa_dtc_conv_fwd changes (one kernel body serves both), so the [B*T, cin] input of overlapping windows is never
+ * written out.  ksplit / slab_stride as above.  The caller checks the range of win_row (0 <= win_row[b],
+ * win_row[b] + T <= table_rows, or win_row[b] < ring_rows) on the host copy of the plan that produced it: the kernel
+ * does not.  Same values staged, same instruction sequence: y equals what pcaa_dtc_conv_fwd gives on the materialised
+ * windows bit for bit where that call takes the one-sequence kernel (always for cout < 64 or cin < 128; a windowed source
+ * never takes the two-sequence kernels). */
+int pcaa_dtc_conv_fwd_win(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                          float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
+                          int ksplit, long slab_stride, const int* win_row, long table_rows, long ring_rows,
+                          void* stream);
+int pcaa_dtc_conv_fwd_win_bf16(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                          float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
+                          int ksplit, long slab_stride, const int* win_row, long table_rows, long ring_rows,
+                          void* stream);
+
+/* ------------------------------------------------------------------ frame-deduplicated inference (track_infer.hip)
+ * Which consecutive crops of a sequentially ordered split share frames.  Crops are cut with a hop of CROP_STEP out of
+ * tracks whose frames were standardised one by one before the cut (datasets.py:16-25, 143-146, 297-302), so a shared
+ * frame has the same bits in every crop that holds it.  crops: M crops of crop_elems floats, each T frames of
+ * frame_elems floats (point-major [M, T, N, C]: frame_elems = N * C).  same[i] = 1 iff the first T - hop frames of crop
+ * i + 1 equal the last T - hop frames of crop i compared as 32-bit WORDS (-0.0 != +0.0, equal NaN payloads are equal),
+ * else 0; every same[i] is written (no pre-set needed).  One workgroup per pair; 16-byte loads when frame_elems % 4 == 0
+ * and crops is 16-B aligned, 4-byte loads otherwise (pcaa_crop_overlap_vec_bytes tells which: 16 or 4).  M == 1: no
+ * launch.  Frames merged on this mask have equal bits, hence equal features, whatever the reason for the equality. */
+int pcaa_crop_overlap_vec_bytes(const float* crops, long crop_elems, long frame_elems);
+int pcaa_crop_overlap(const float* crops, long crop_elems, long frame_elems, int M, int T, int hop, int* same,
+                      void* stream);
+/* pcaa_gather_rows for rows that are a multiple of 4 but not of 16 bytes (a frame of N = 150 points x C = 5 features is
+ * 3 000 bytes): dst[r] = src[idx[r]], rows of row_words 32-bit words; an index outside [0, n_src_rows) zero-fills its
+ * row and sets *err_flag (may be NULL). */
+int pcaa_gather_rows_w4(const void* src, long n_src_rows, long row_words, const long long* idx, void* dst,
+                        long n_rows, int* err_flag, void* stream);
 
 /* The adjoint w.r.t. the layer input in one launch (replaces dcol = dy . W on the im2col layout followed by
  * pcaa_dtc_col2im): da[(b,t)][ci] = sum_{co,tap} dy[b][t+(2-tap)*d][co] * W[co][ci][tap].

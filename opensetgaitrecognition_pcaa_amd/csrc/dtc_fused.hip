@@ -65,7 +65,22 @@ struct DtcFwdParams {
   int B, T, cin, cout, dil, nrep;
   long slab_stride;     // gridDim.z > 1: split z writes its partial product to y + z*slab_stride
   BnTail tail;          // the BatchNorm finalize of ``stats``, run by the last workgroup (bn_tail.h); kind 0: none
+  // windowed source (pcaa_dtc_conv_fwd_win): sequence b, step t reads row win_row[b] + t of a frame-feature table (modulo
+  // ring_rows if > 0) instead of row b*T + t; null = the addressing above
+  const int* win_row;
+  long ring_rows;
 };
+
+// first source row of sequence b and the row of step r from it (ring: T <= ring_rows, so one conditional subtraction wraps)
+__device__ __forceinline__ long dtc_src_row0(const DtcFwdParams& p, int b) {
+  if (p.win_row == nullptr) return (long)b * p.T;
+  const long r0 = p.win_row[b];
+  return p.ring_rows > 0 ? r0 % p.ring_rows : r0;
+}
+__device__ __forceinline__ long dtc_src_row(const DtcFwdParams& p, long row0, int r) {
+  const long row = row0 + r;
+  return (p.ring_rows > 0 && row >= p.ring_rows) ? row - p.ring_rows : row;
+}
 
 constexpr int CC = 32;              // input channels per chunk: 3*CC = 96-deep contraction per trip
 constexpr int WP = 3 * CC + 4;      // weight tile pitch: 36*row mod 64 walks all 16 four-bank groups
@@ -133,9 +148,10 @@ __global__ __launch_bounds__(256) void dtc_fwd_kernel(DtcFwdParams p) {
   {
     const int q4 = cr >> 2;
     const bool act = p.scale != nullptr;
+    const long row0 = dtc_src_row0(p, b);
     for (int q = tid; q < T * q4; q += 256) {
       const int r = q / q4, c4 = (q - r * q4) << 2;
-      f32x4 v = load4(p.src + ((long)b * T + r) * cin + cz0 + c4);
+      f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
       if (act) {
         const f32x4 sc = load4(p.scale + cz0 + c4), sh = load4(p.shift + cz0 + c4);
         v.x = elu_stage(fmaf(sc.x, v.x, sh.x));
@@ -276,9 +292,10 @@ __global__ __launch_bounds__(256) void dtc_fwd_bf16_kernel(DtcFwdParams p) {
   {
     const int q4 = cr >> 2;
     const bool act = p.scale != nullptr;
+    const long row0 = dtc_src_row0(p, b);
     for (int q = tid; q < T * q4; q += 256) {
       const int r = q / q4, c4 = (q - r * q4) << 2;
-      f32x4 v = load4(p.src + ((long)b * T + r) * cin + cz0 + c4);
+      f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
       if (act) {
         const f32x4 sc = load4(p.scale + cz0 + c4), sh = load4(p.shift + cz0 + c4);
         v.x = elu_stage(fmaf(sc.x, v.x, sh.x));
@@ -1028,7 +1045,8 @@ extern "C" int pcaa_dtc_conv_ksplit(int B, int cin, int cout) {
 
 static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, const float* shift, const float* W, float* y,
                              float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
-                             int ksplit, long slab_stride, void* stream) {
+                             int ksplit, long slab_stride, void* stream, const int* win_row = nullptr,
+                             long ring_rows = 0) {
   PCAA_CHECK_ARG(src && W && y && B >= 1 && dilation >= 1 && ksplit >= 1, "pcaa_dtc_conv_fwd: bad args");
   PCAA_CHECK_ARG(pcaa_dtc_conv_supported(T, cin, cout), "pcaa_dtc_conv_fwd: needs T <= %d, cin %% 4 == 0, cout %% 16 == 0",
                  ROWS);
@@ -1042,7 +1060,8 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
                  "(pcaa_dtc_conv_ksplit)", MAX_CR);
   PCAA_CHECK_ARG(ksplit == 1 || (stats == nullptr && slab_stride >= (long)B * T * cout),
                  "pcaa_dtc_conv_fwd: ksplit > 1 writes slabs (no statistics): slab_stride >= B*T*cout");
-  if (pair_takes(cin, cout, ksplit, false)) {
+  // a windowed source always takes the one-sequence kernels (the block's first layer, 1024 -> 16, is theirs anyway)
+  if (win_row == nullptr && pair_takes(cin, cout, ksplit, false)) {
     DtcPairParams pp{src, scale, shift, nullptr, nullptr, nullptr, nullptr, W, y, col, stats, nrep,
                      nullptr, nullptr, nullptr, nullptr, nullptr, B, T, cin, cout, dilation,
                      stats != nullptr ? pcaa_take_bn_tail(stats) : BnTail{}};
@@ -1054,7 +1073,7 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
     PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
   }
   DtcFwdParams p{src, scale, shift, W, y, col, stats, B, T, cin, cout, dilation, nrep, ksplit > 1 ? slab_stride : 0,
-                 (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}};
+                 (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}, win_row, ring_rows};
   if (bf16) hipLaunchKernelGGL(dtc_fwd_bf16_kernel, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
   else hipLaunchKernelGGL(dtc_fwd_kernel, dim3(B, (cout + 31) / 32, ksplit), dim3(256), 0, as_stream(stream), p);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
@@ -1068,6 +1087,35 @@ extern "C" int pcaa_dtc_conv_fwd_bf16(const float* src, const float* scale, cons
                                       float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
                                       int ksplit, long slab_stride, void* stream) {
   return dtc_conv_fwd_impl(true, src, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dilation, ksplit, slab_stride, stream);
+}
+
+
+// The eval form (col and stats null) on a windowed source: see include/pcaa_hip.h.  The range of win_row is the caller's to
+// check (on the host copy of the plan it came from); here only what the host can see.
+static int dtc_conv_fwd_win_impl(bool bf16, const float* table, const float* scale, const float* shift, const float* W,
+                                 float* y, float* col, double* stats, int nrep, int B, int T, int cin, int cout,
+                                 int dilation, int ksplit, long slab_stride, const int* win_row, long table_rows,
+                                 long ring_rows, void* stream) {
+  PCAA_CHECK_ARG(col == nullptr && stats == nullptr, "pcaa_dtc_conv_fwd_win: eval form only (col and stats null)");
+  PCAA_CHECK_ARG(win_row != nullptr && table_rows >= T && ring_rows >= 0 && ring_rows <= table_rows &&
+                 (ring_rows == 0 || ring_rows >= T),
+                 "pcaa_dtc_conv_fwd_win: needs win_row, T <= table_rows, ring_rows 0 or in [T, table_rows]");
+  return dtc_conv_fwd_impl(bf16, table, scale, shift, W, y, nullptr, nullptr, nrep, B, T, cin, cout, dilation, ksplit,
+                           slab_stride, stream, win_row, ring_rows);
+}
+extern "C" int pcaa_dtc_conv_fwd_win(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                                     float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
+                                     int ksplit, long slab_stride, const int* win_row, long table_rows, long ring_rows,
+                                     void* stream) {
+  return dtc_conv_fwd_win_impl(false, table, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dilation, ksplit,
+                               slab_stride, win_row, table_rows, ring_rows, stream);
+}
+extern "C" int pcaa_dtc_conv_fwd_win_bf16(const float* table, const float* scale, const float* shift, const float* W,
+                                          float* y, float* col, double* stats, int nrep, int B, int T, int cin, int cout,
+                                          int dilation, int ksplit, long slab_stride, const int* win_row,
+                                          long table_rows, long ring_rows, void* stream) {
+  return dtc_conv_fwd_win_impl(true, table, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dilation, ksplit,
+                               slab_stride, win_row, table_rows, ring_rows, stream);
 }
 
 /* channel split for the dgrad (its contraction runs over the OUTPUT channels of the convolution; a workgroup

@@ -19,6 +19,7 @@ Numerics modes (``set_precision``):
     bf16 MFMA pipe with fp32 accumulation; everything else fp32.
 """
 import contextlib
+import math
 import os
 import itertools
 
@@ -569,13 +570,24 @@ def _dtc_bf16(mode, kc, nc, adj=False):
     return on and kc >= 128 and kc % 32 == 0 and nc >= 64 and nc % 4 == 0
 
 
-def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32"):
-    """a2d: [B*T, Cin] fp32 rows (b,t).  Causal dilated conv = (implicit) im2col + contraction."""
+def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0):
+    """a2d: [B*T, Cin] fp32 rows (b,t).  Causal dilated conv = (implicit) im2col + contraction.
+    ``win_row`` (ops.WindowRows, eval only): a2d is a frame-feature table [table_rows, Cin] instead and sequence b is
+    its T rows from win_row[b] on (modulo ``ring_rows`` if > 0).  Only the first layer reads the table: fused, through
+    the windowed form of its launch; otherwise the windows are written out with one gather and today's path runs."""
     saves = []
     a = a2d
     nl = len(layers)
     fused = _FUSE_DTC and a2d.dtype == torch.float32 and all(
         ops.dtc_conv_supported(T, l.conv1d.weight.shape[1], l.conv1d.weight.shape[0]) for l in layers)
+    if win_row is not None:
+        if training:
+            raise ValueError("dtc_forward: win_row is an eval-mode form (train-mode BatchNorm needs every row's statistics)")
+        if ring_rows != win_row.ring_rows or len(win_row) != B or win_row.T != T or win_row.table_rows != a2d.shape[0]:
+            raise ValueError("dtc_forward: win_row does not describe B windows of T rows of this table / ring_rows")
+        if not fused:
+            a = ops.gather_frames(a2d.contiguous(), win_row.row_index())
+            win_row = None
     prev = None          # (scale, shift) of the layer whose bias-free output `a` is (fused path)
     for li, layer in enumerate(layers):
         conv, bn = layer.conv1d, layer.batch_norm
@@ -587,7 +599,7 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32"):
             tail = ops.BnTailFwd(a.shape[0], conv.bias, bn, cout, sync=_sync_fn()) if training else None
             y, col = ops.dtc_conv_fwd(a, prev[0] if prev else None, prev[1] if prev else None, W2d, B, T,
                                       layer.dilation, stats=stats, want_col=training, tail=tail,
-                                      bf16=_dtc_bf16(mode, cin, cout))
+                                      bf16=_dtc_bf16(mode, cin, cout), win_row=win_row if li == 0 else None)
             if training:
                 scale, shift, mean, rstd = tail.out
                 count = tail.count_out
@@ -875,6 +887,12 @@ def encoder_forward(enc, x, training, mode=None, gph=None):
     x4, st.dtc = dtc_forward(x2, B, T, enc.tc_block.layers(), training, pool_time=True, mode=mode)     # [B, 512]
     st.x4 = x4
     mark("enc_fwd.dtc")
+    return _encoder_heads(enc, st, x4, gph)
+
+
+def _encoder_heads(enc, st, x4, gph=None):
+    """x4 [B, 512] -> the MLP heads (models.py:252-277, 284-292); fills st, returns (logits, sup_fv, st)."""
+    B = x4.shape[0]
     st.h = st.hproj = None
     if _heads_fusable(enc, gph, B, False):
         m1, mh, m2, mg = _heads_mods(enc, gph)
@@ -891,6 +909,48 @@ def encoder_forward(enc, x, training, mode=None, gph=None):
     if gph is not None:
         st.hproj = linear_act_forward(st.sup_fv, gph[0], ACT_ELU)
     return st.logits, st.sup_fv, st
+
+
+def frame_pad_quantum(N, mode=None):
+    """Frames per chunk must be a multiple of this for the eval PointNet to stay on the fused-epilogue GEMM in bf16 mode
+    (pcaa_gemm_affine_elu takes whole 256-row tiles: U * N % 256 == 0); 1 where that path does not apply."""
+    mode = get_precision() if mode is None else mode
+    if not (_FUSE_EVAL_EPILOGUE and mode == "bf16" and N in (32, 64, 128)):
+        return 1
+    return 256 // math.gcd(N, 256)
+
+
+def encoder_frame_features(enc, frames, mode=None):
+    """Eval-mode PointNet block + mean over the points, frame by frame (models.py:82-105, 242-243, 279-282): point-major
+    frames [U, N, C] fp32 -> ([U, 1024] fp32, saves).  A frame's features do not depend on its neighbours, which is what
+    lets overlapping crops share them."""
+    mode = get_precision() if mode is None else mode
+    _require_gpu(frames, "CGEncoder")
+    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
+        raise ValueError(f"encoder_frame_features expects contiguous fp32 [U,N,C], got {tuple(frames.shape)} {frames.dtype}")
+    U, N, C = frames.shape
+    l1 = enc.pc_block.pointnet1.module[0]
+    if C != l1.weight.shape[1]:
+        raise RuntimeError(f"CGEncoder: input has {C} features, first layer expects {l1.weight.shape[1]}")
+    if N != enc.nmax_points:
+        raise RuntimeError(f"CGEncoder: N={N} points but nmax_points={enc.nmax_points} "
+                           "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
+    return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N)
+
+
+def encoder_forward_windows(enc, table, win_row, T, mode=None):
+    """Eval-mode temporal block, mean over T and heads on windows of a frame-feature table [table_rows, 1024]
+    (encoder_frame_features): window b = rows win_row[b] .. + T - 1 (an ops.WindowRows; its ring_rows > 0: modulo).
+    Returns (logits, sup_fv, st) as encoder_forward does for the materialised crops."""
+    mode = get_precision() if mode is None else mode
+    _require_gpu(table, "CGEncoder")
+    B = len(win_row)
+    st = EncoderState()
+    st.B, st.T, st.mode, st.training = B, T, mode, False
+    x4, st.dtc = dtc_forward(table, B, T, enc.tc_block.layers(), False, pool_time=True, mode=mode, win_row=win_row,
+                             ring_rows=win_row.ring_rows)
+    st.x4 = x4
+    return _encoder_heads(enc, st, x4)
 
 
 def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, before_pointnet=None,

@@ -75,6 +75,35 @@ def youden_threshold(known_mask: np.ndarray, scores: np.ndarray) -> float:
     return float(thr[np.argmax(tps / tps[-1] - fps / fps[-1])])
 
 
+def window_count(n_frames, T=constants.NSTEPS, hop=constants.CROP_STEP):
+    """Number of crops the reference cuts out of a processed track of ``n_frames`` frames (its ``crop_with_step``,
+    datasets.py:16-25, 297-302): one per start in ``arange(n_frames - T, step=hop)``.  The rule drops the last aligned
+    window when ``(n_frames - T) % hop == 0`` and gives none for ``n_frames == T``."""
+    return len(np.arange(int(n_frames) - int(T), step=int(hop)))
+
+
+def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
+    """Host plan of the deduplicated pass over M sequentially ordered crops.  ``same`` [M - 1]: nonzero where crop i + 1
+    starts with the last T - hop frames of crop i (``ops.crop_overlap``).  Returns ``(frame_src, win_row)``:
+    ``frame_src`` int64 [U]: for every unique frame its index (crop * T + t) in the flat [M * T] frame array -- a run of
+    L chained crops gives the first crop's T frames and the last ``hop`` frames of each later one;
+    ``win_row`` int64 [M]: the row of the unique-frame table where crop i's window of T rows starts."""
+    M, T, hop = int(M), int(T), int(hop)
+    same = np.asarray(same).reshape(-1) != 0
+    if M < 0 or same.size != max(M - 1, 0) or not 1 <= hop <= T:
+        raise ValueError(f"plan_frames: needs a mask of M - 1 = {max(M - 1, 0)} entries and 1 <= hop <= T")
+    if M == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    new = np.full(M, T, np.int64)
+    new[1:][same] = hop                                   # frames crop i adds to the table
+    ends = np.cumsum(new)                                 # table row after crop i's last frame
+    win_row = ends - T
+    # crop i's new frames are its LAST new[i] ones: t = T - new[i] .. T - 1
+    first_t = np.repeat(np.arange(M, dtype=np.int64) * T + (T - new), new)
+    within = np.arange(int(ends[-1]), dtype=np.int64) - np.repeat(ends - new, new)
+    return first_t + within, win_row
+
+
 class OpenSetScorer:
     """Encoder + centroids -> predictions, likelihoods, threshold, k-window votes."""
 
@@ -84,10 +113,16 @@ class OpenSetScorer:
         self.means = discriminator_means.float().to(dev).contiguous()
         self.batch_size = batch_size
         self.threshold = None
+        self.last_frames_encoded = None      # unique frames the last deduplicated embed / embed_track encoded (no padding)
+        self.last_pointnet_saves = None      # the PointNet layer records of its last chunk (which path ran)
 
     @torch.no_grad()
-    def embed(self, pcs: torch.Tensor):
-        """pcs [M,C,T,N] on the device -> (preds [M] int64, sup_fv [M,32], likelihood [M] f64)."""
+    def embed(self, pcs: torch.Tensor, dedup_frames: bool = False, hop: int = constants.CROP_STEP):
+        """pcs [M,C,T,N] on the device -> (preds [M] int64, sup_fv [M,32], likelihood [M] f64).
+        ``dedup_frames``: for sequentially ordered crops (cut with ``hop``), encode every frame that consecutive crops
+        share bit for bit once (``_embed_dedup``); same triple, same order, one entry per crop."""
+        if dedup_frames:
+            return self._embed_dedup(pcs, hop)
         preds, fvs = [], []
         for i in range(0, pcs.shape[0], self.batch_size):
             logits, sup_fv, _ = F_hip.encoder_forward(self.encoder, pcs[i:i + self.batch_size], False)
@@ -96,6 +131,86 @@ class OpenSetScorer:
             fvs.append(sup_fv)
         preds, fvs = torch.cat(preds), torch.cat(fvs)
         return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
+
+    def _embed_dedup(self, pcs, hop):
+        """overlap mask (one launch, one small copy to the host) -> plan -> unique frames through the PointNet block ->
+        windows of the frame-feature table through the temporal block and the heads"""
+        F_hip._require_gpu(pcs, "CGEncoder")
+        if pcs.dim() != 4:
+            raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(pcs.shape)}")
+        M, C, T, N = pcs.shape
+        xp = F_hip._point_major(pcs)                                       # [M, T, N, C] storage
+        same = ops.crop_overlap(xp, hop).cpu().numpy() if M > 1 else np.zeros(0, np.int32)
+        frame_src, win_row = plan_frames(same, M, T, hop)
+        frames = xp.view(M * T, N * C)
+        U = len(frame_src)
+        q = F_hip.frame_pad_quantum(N)
+        padded = np.concatenate([frame_src, np.zeros((-U) % q, np.int64)])     # whole GEMM row tiles; features dropped
+        idx = torch.from_numpy(padded).to(pcs.device)
+        step = max(self.batch_size * T // q, 1) * q
+        feats = []
+        for a in range(0, len(padded), step):
+            rows = ops.gather_frames(frames, idx[a:a + step].contiguous())
+            f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, rows.view(-1, N, C))
+            feats.append(f)
+        table = feats[0] if len(feats) == 1 else torch.cat(feats)
+        self.last_frames_encoded = U
+        return self._score_windows(table, ops.WindowRows(win_row, T, table.shape[0], device=pcs.device), T)
+
+    def _score_windows(self, table, plan, T):
+        """windows of a frame-feature table, ``batch_size`` at a time -> the triple ``embed`` returns"""
+        preds, fvs = [], []
+        for i in range(0, len(plan), self.batch_size):
+            logits, sup_fv, _ = F_hip.encoder_forward_windows(self.encoder, table, plan.slice(i, i + self.batch_size), T)
+            _, _, p = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
+            preds.append(p)
+            fvs.append(sup_fv)
+        preds, fvs = torch.cat(preds), torch.cat(fvs)
+        return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
+
+    @torch.no_grad()
+    def embed_track(self, track: torch.Tensor, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True):
+        """track [F,N,C] fp32 on the device (a processed track as the packed store keeps it) -> the triple of ``embed``
+        for its ``window_count(F)`` windows of NSTEPS frames, as if ``embed`` had been called on the reference's crops
+        of it -- every frame encoded once, no crop ever written out.  ``drop_last_aligned=False`` also takes the
+        aligned last window the reference's rule drops when ``(F - NSTEPS) % hop == 0``."""
+        if not isinstance(track, torch.Tensor) or not track.is_cuda:
+            raise RuntimeError("embed_track: the track must live on the HIP device; this package has no CPU path")
+        if track.dim() != 3 or track.dtype != torch.float32 or not track.is_contiguous():
+            raise ValueError(f"embed_track expects contiguous fp32 [F,N,C], got {tuple(track.shape)} {track.dtype}")
+        F, N, C = track.shape
+        T, hop = constants.NSTEPS, int(hop)
+        W = window_count(F, T, hop) if drop_last_aligned else (0 if F < T else (F - T) // hop + 1)
+        dev = track.device
+        if W == 0:
+            self.last_frames_encoded = 0
+            D = self.encoder.MLP_sup1[0].weight.shape[0]
+            return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.float64, device=dev))
+        U = (W - 1) * hop + T                                              # frames any window uses
+        q = F_hip.frame_pad_quantum(N)
+        step = max(self.batch_size * T // q, 1) * q
+        feats = []
+        for a in range(0, U, step):
+            b = min(a + step, U)
+            pad = (a - b) % q              # whole GEMM row tiles: neighbouring frames of the track where it has them (a
+            lo = 0                         # view), zeros otherwise; the extra frames' features are dropped
+            if pad and b + pad <= F:
+                chunk = track[a:b + pad]
+            elif pad and a >= pad:
+                chunk, lo = track[a - pad:b], pad
+            elif pad:
+                chunk = torch.cat([track[a:b], track.new_zeros((pad, N, C))])
+            else:
+                chunk = track[a:b]
+            f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, chunk)
+            feats.append(f[lo:lo + b - a])
+        table = feats[0] if len(feats) == 1 else torch.cat(feats)
+        self.last_frames_encoded = U
+        starts = hop * np.arange(W, dtype=np.int64)
+        plan = ops.WindowRows(starts, T, table.shape[0], device=dev,
+                              dev=torch.arange(0, W * hop, hop, dtype=torch.int32, device=dev))
+        return self._score_windows(table, plan, T)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
         """ROC-optimal (Youden J) separation of known-test vs held-out-unseen likelihoods
@@ -162,7 +277,8 @@ def naive_sequential_procedure(k, encoder, discriminator_means, *args, **kwargs)
 
 
 def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_folder, model_folder,
-                                      scenarios_list=None, seed=0, unseen_valid_ratio=0.2, force_pc_subsampling=0):
+                                      scenarios_list=None, seed=0, unseen_valid_ratio=0.2, force_pc_subsampling=0,
+                                      dedup_frames=False):
     import json
     from sklearn.metrics import f1_score
     from .constants import SPLIT
@@ -173,7 +289,8 @@ def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_f
     known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
     unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
     preds, labels, _ = naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pcs, known_labels, unseen_pcs,
-                                                          unseen_labels, seed=seed, unseen_valid_ratio=unseen_valid_ratio)
+                                                          unseen_labels, seed=seed, unseen_valid_ratio=unseen_valid_ratio,
+                                                          dedup_frames=dedup_frames)
     labels = labels.astype(int)
     out_log = {"n_steps": k, "accuracy": float(np.equal(labels, preds).sum() / max(len(labels), 1)),
                "f1_micro": float(f1_score(labels, preds, average="micro")),
@@ -191,11 +308,13 @@ def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_f
 
 
 def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pcs, known_labels, unseen_pcs,
-                                       unseen_labels, seed=0, unseen_valid_ratio=0.2, batch_size=1024):
+                                       unseen_labels, seed=0, unseen_valid_ratio=0.2, batch_size=1024,
+                                       dedup_frames=False):
     """The reference's procedure on in-memory, temporally ordered crops: (1) likelihoods of
     known-test and unseen crops, 20 % of the unseen SUBJECTS (rng seed 0) held out to pick the
     threshold; (2) k-window votes on the known test set and on the remaining unseen subjects.
-    Returns (open-set predictions, open-set labels, threshold)."""
+    Returns (open-set predictions, open-set labels, threshold).  ``dedup_frames``: frames that
+    consecutive crops share are encoded once (``OpenSetScorer.embed``)."""
     rng = np.random.default_rng(seed)
     scorer = OpenSetScorer(encoder, discriminator_means, batch_size)
     n_labels = int(len(np.unique(known_labels.cpu().numpy())))
@@ -203,8 +322,8 @@ def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pc
     subjects = np.unique(u_lab)
     val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
     val_mask = np.isin(u_lab, val_subjects)
-    k_preds, _, k_lik = scorer.embed(known_pcs)
-    u_preds, _, u_lik = scorer.embed(unseen_pcs)
+    k_preds, _, k_lik = scorer.embed(known_pcs, dedup_frames=dedup_frames)
+    u_preds, _, u_lik = scorer.embed(unseen_pcs, dedup_frames=dedup_frames)
     vm = torch.from_numpy(val_mask).to(u_lik.device)
     thr = scorer.fit_threshold(k_lik, u_lik[vm])
     preds, labels = [], []
@@ -241,13 +360,14 @@ def _sequential_split_on_device(split, scenarios_list, device):
 
 
 def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None, variation=False,
-                    generate_dataset=True, device=None):
+                    generate_dataset=True, device=None, dedup_frames=False):
     """Open-set evaluation driver with the reference's call surface and output files
     (inference_PCAA.py:382-469): for every model and k, the naive sequential procedure on the sequentially
     ordered test / unseen splits; writes ``naive_seq_log_{k}*.json`` (accuracy, F1 micro / macro / weighted),
     ``final_preds_{k}*.npy`` / ``final_labels_{k}*.npy`` and ``naive_seq_log_subsampled{n}.json`` under
     ``models/<name>/``.  Not reproduced: the confusion-matrix PNG (plotting).  The splits are regenerated once per
-    call (the reference regenerates them for every (model, k) with identical arguments)."""
+    call (the reference regenerates them for every (model, k) with identical arguments).  ``dedup_frames`` (opt-in):
+    every frame that consecutive crops of the sequential splits share is encoded once."""
     import json
     from sklearn.metrics import f1_score
     from .constants import SPLIT
@@ -274,7 +394,8 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
         unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
         for k in ks:
             preds, labels, thr = naive_sequential_procedure(k, enc, means, known_pcs, known_labels, unseen_pcs,
-                                                            unseen_labels, seed=0, unseen_valid_ratio=0.2)
+                                                            unseen_labels, seed=0, unseen_valid_ratio=0.2,
+                                                            dedup_frames=dedup_frames)
             labels = labels.astype(int)
             metrics = {"n_steps": k, "accuracy": float(np.equal(labels, preds).sum() / max(len(labels), 1)),
                        "f1_micro": float(f1_score(labels, preds, average="micro")),
@@ -289,3 +410,109 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
             json.dump(out_log, f)
     return out_log
 
+
+
+class StreamingScorer:
+    """Open-set scoring of a live track: frames arrive a few at a time, a decision is due every ``hop`` frames.
+
+    A device ring keeps the PointNet features of the last ``ring_rows >= NSTEPS + max_push`` frames.  ``push`` encodes the
+    new frames once, writes them into the ring (a push that wraps is two writes) and runs the temporal block, in its
+    windowed form over the ring, for every window whose last frame has now arrived: window j (frames ``j*hop .. j*hop +
+    NSTEPS - 1``) is returned by the very push that brings the track to ``NSTEPS + j*hop`` frames.  Windows are emitted
+    EAGERLY: for a track of F frames ``OpenSetScorer.embed_track`` under the reference's cropping rule holds one window
+    fewer when ``(F - NSTEPS) % hop == 0`` (``window_count``); the first ``window_count(F)`` windows are the same.
+    ``votes()`` is ``k_vote`` over the completed groups of k windows so far, ``reset()`` starts a new track.  The
+    precision mode (``functional.get_precision()``) is read at every push, as ``OpenSetScorer.embed`` does."""
+
+    def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
+                 hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None):
+        self.encoder = encoder
+        self._check_eval()
+        self.T, self.hop, self.k, self.n_labels = constants.NSTEPS, int(hop), int(k), int(n_labels)
+        self.threshold, self.max_push = float(threshold), int(max_push)
+        if not 1 <= self.hop <= self.T or self.max_push < 1 or self.k < 1:
+            raise ValueError("StreamingScorer: needs 1 <= hop <= NSTEPS, max_push >= 1, k >= 1")
+        need = self.T + self.max_push
+        self.ring_rows = need if ring_rows is None else int(ring_rows)
+        if self.ring_rows < need:
+            raise ValueError(f"StreamingScorer: ring_rows={self.ring_rows} < NSTEPS + max_push = {need}")
+        dev = next(encoder.parameters()).device
+        self.means = means.float().to(dev).contiguous()
+        self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
+        width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]
+        self.ring = torch.zeros((self.ring_rows, width), dtype=torch.float32, device=dev)
+        # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
+        # once, long enough that the windows of any one push are a contiguous slice of it (no upload per push)
+        self._period = self.ring_rows // np.gcd(self.ring_rows, self.hop)
+        self._max_win = self.max_push // self.hop + 1
+        self._starts = (np.arange(self._period + self._max_win, dtype=np.int64) * self.hop) % self.ring_rows
+        self._starts_dev = torch.from_numpy(self._starts.astype(np.int32)).to(dev)
+        self.last_pointnet_saves = None
+        self.reset()
+
+    def _check_eval(self):
+        if self.encoder.training:
+            raise RuntimeError("StreamingScorer: the encoder is in training mode (train-mode BatchNorm mixes the frames of "
+                               "a batch: a frame's features would depend on its neighbours); call encoder.eval()")
+
+    def reset(self):
+        """forget the track: the next pushed frame is frame 0 of a new one"""
+        self.n_frames = 0
+        self.n_windows = 0
+        self._preds, self._lik = [], []
+
+    @torch.no_grad()
+    def push(self, frames: torch.Tensor):
+        """frames [n,N,C] fp32 on the device, the next n frames of the track -> (preds, sup_fv, likelihood) of the windows
+        they complete (possibly none: empty tensors)."""
+        self._check_eval()
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise RuntimeError("StreamingScorer.push: frames must live on the HIP device; this package has no CPU path")
+        if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
+            raise ValueError(f"StreamingScorer.push expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
+        out = [self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)]
+        out = [o for o in out if o is not None]
+        dev = self.ring.device
+        if not out:
+            D = self.encoder.MLP_sup1[0].weight.shape[0]
+            return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.float64, device=dev))
+        if len(out) == 1:
+            return out[0]
+        return tuple(torch.cat([o[i] for o in out]) for i in range(3))
+
+    def _push(self, frames):
+        n, N, C = frames.shape
+        q = F_hip.frame_pad_quantum(N)
+        if n % q:                                   # whole GEMM row tiles in bf16 mode; the padding's features are dropped
+            frames = torch.cat([frames, frames.new_zeros(((-n) % q, N, C))])
+        feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames)
+        pos = self.n_frames % self.ring_rows
+        first = min(n, self.ring_rows - pos)
+        self.ring[pos:pos + first].copy_(feats[:first])
+        if first < n:                               # the push wraps: second write from row 0
+            self.ring[:n - first].copy_(feats[first:n])
+        self.n_frames += n
+        done = 0 if self.n_frames < self.T else (self.n_frames - self.T) // self.hop + 1
+        j0, nw = self.n_windows, done - self.n_windows
+        if nw == 0:
+            return None
+        o = j0 % self._period
+        plan = ops.WindowRows(self._starts[o:o + nw], self.T, self.ring_rows, self.ring_rows, dev=self._starts_dev[o:o + nw])
+        logits, sup_fv, _ = F_hip.encoder_forward_windows(self.encoder, self.ring, plan, self.T)
+        _, _, preds = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
+        lik = joint_likelihood(sup_fv.contiguous(), self.means)
+        self.n_windows = done
+        self._preds.append(preds)
+        self._lik.append(lik)
+        return preds, sup_fv, lik
+
+    def votes(self) -> torch.Tensor:
+        """``k_vote`` over the completed groups of k windows emitted since the last ``reset()`` -> [n_windows // k] int64"""
+        if not self._preds:
+            return torch.empty(0, dtype=torch.int64, device=self.ring.device)
+        preds, lik = torch.cat(self._preds), torch.cat(self._lik)
+        self._preds, self._lik = [preds], [lik]
+        n = (preds.numel() // self.k) * self.k
+        return k_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels,
+                      n_classes=self.n_classes)

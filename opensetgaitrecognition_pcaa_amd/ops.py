@@ -1436,6 +1436,93 @@ def gather_rows(src, idx, out=None, err_flag=None):
     return out
 
 
+def gather_rows_w4(src, idx, out=None, err_flag=None):
+    """``gather_rows`` for rows that are a multiple of 4 bytes only (pcaa_gather_rows_w4: a 3 000-byte frame of N = 150
+    points x C = 5 features)."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() >= 1):
+        raise RuntimeError("gather_rows_w4: src must be a contiguous tensor on the HIP device (this package has no CPU path)")
+    _chk(idx, "gather_rows_w4.idx", torch.int64, 1)
+    row_bytes = src[0].numel() * src.element_size() if src.dim() > 1 else src.element_size()
+    if row_bytes % 4 or row_bytes == 0:
+        raise ValueError(f"gather_rows_w4: rows of {row_bytes} bytes are not a multiple of 4")
+    n = idx.numel()
+    if out is None:
+        out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    elif out.shape != (n,) + tuple(src.shape[1:]) or out.dtype != src.dtype or not out.is_contiguous():
+        raise ValueError("gather_rows_w4: out does not match")
+    if err_flag is not None:
+        _chk(err_flag, "gather_rows_w4.err_flag", torch.int32)
+    if n:
+        check(_lib.load().pcaa_gather_rows_w4(_p(src), src.shape[0], row_bytes // 4, _p(idx), _p(out), n, _p(err_flag), _s()),
+              "pcaa_gather_rows_w4")
+    return out
+
+
+def gather_frames(src, idx):
+    """dst[r] = src[idx[r]] for rows of any whole number of 32-bit words: the 16-byte gather where a row allows it."""
+    row_bytes = src[0].numel() * src.element_size()
+    return gather_rows(src, idx) if row_bytes % 16 == 0 else gather_rows_w4(src, idx)
+
+
+def crop_overlap_vec_bytes(crops):
+    """16 or 4: the load width pcaa_crop_overlap takes for this tensor."""
+    _chk(crops, "crop_overlap.crops", torch.float32, 4)
+    M, T, N, C = crops.shape
+    return int(_lib.load().pcaa_crop_overlap_vec_bytes(_p(crops), T * N * C, N * C))
+
+
+def crop_overlap(crops, hop):
+    """crops: point-major [M, T, N, C] fp32 -> int32 [M - 1]: 1 where the first T - hop frames of crop i + 1 equal the last
+    T - hop frames of crop i bit for bit (pcaa_crop_overlap).  M == 1: empty, no launch."""
+    _chk(crops, "crop_overlap.crops", torch.float32, 4)
+    M, T, N, C = crops.shape
+    hop = int(hop)
+    if M < 1 or not 1 <= hop <= T:
+        raise ValueError(f"crop_overlap: needs M >= 1 and 1 <= hop <= T, got M={M} T={T} hop={hop}")
+    same = torch.empty(M - 1, dtype=torch.int32, device=crops.device)
+    if M > 1:
+        check(_lib.load().pcaa_crop_overlap(_p(crops), T * N * C, N * C, M, T, hop, _p(same), _s()), "pcaa_crop_overlap")
+    return same
+
+
+class WindowRows:
+    """The start rows of B windows of T rows in a frame-feature table, range-checked on the HOST copy of the plan they
+    come from (the kernels trust them: pcaa_dtc_conv_fwd_win).  ``ring_rows`` > 0: the table is a ring of that many rows
+    and a window may wrap.  ``dev``: the same values already on the device (int32), else they are uploaded here."""
+    __slots__ = ("host", "dev", "T", "table_rows", "ring_rows")
+
+    def __init__(self, host, T, table_rows, ring_rows=0, device=None, dev=None):
+        import numpy as np
+        host = np.ascontiguousarray(host, dtype=np.int64).reshape(-1)
+        T, table_rows, ring_rows = int(T), int(table_rows), int(ring_rows)
+        if ring_rows and not T <= ring_rows <= table_rows:
+            raise ValueError(f"WindowRows: ring_rows={ring_rows} must lie in [T={T}, table_rows={table_rows}]")
+        if host.size:
+            lo, hi = int(host.min()), int(host.max())
+            if lo < 0 or (hi >= ring_rows if ring_rows else hi + T > table_rows):
+                raise ValueError(f"WindowRows: window starts {lo}..{hi} (T={T}) leave the table of {table_rows} rows"
+                                 + (f" (ring of {ring_rows})" if ring_rows else ""))
+        if dev is None:
+            dev = torch.from_numpy(host.astype(np.int32)).to(device)
+        elif dev.dtype != torch.int32 or dev.numel() != host.size or not dev.is_cuda or not dev.is_contiguous():
+            raise ValueError("WindowRows: dev must be a contiguous int32 device tensor with one entry per window")
+        self.host, self.dev, self.T, self.table_rows, self.ring_rows = host, dev, T, table_rows, ring_rows
+
+    def __len__(self):
+        return self.host.size
+
+    def slice(self, a, b):
+        return WindowRows(self.host[a:b], self.T, self.table_rows, self.ring_rows, dev=self.dev[a:b])
+
+    def row_index(self):
+        """int64 [B*T] device: the table row of every (window, step), for the one-gather fallback"""
+        t = torch.arange(self.T, device=self.dev.device, dtype=torch.int64)
+        idx = self.dev.to(torch.int64)[:, None] + t[None, :]
+        if self.ring_rows:
+            idx = idx % self.ring_rows
+        return idx.reshape(-1).contiguous()
+
+
 def dtc_im2col(a, B, T, Cin, d):
     _chk(a, "im2col.a", torch.float32, 2)
     col = torch.empty((B * T, 3 * Cin), dtype=torch.float32, device=a.device)
@@ -1752,12 +1839,23 @@ def dtc_conv_supported(T, cin, cout):
     return bool(_lib.load().pcaa_dtc_conv_supported(int(T), int(cin), int(cout)))
 
 
-def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=False, tail=None, bf16=False):
-    """One DilTempConv1d layer forward in one launch (see pcaa_dtc_conv_fwd): returns (y, col or None)."""
+def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=False, tail=None, bf16=False, win_row=None):
+    """One DilTempConv1d layer forward in one launch (see pcaa_dtc_conv_fwd): returns (y, col or None).
+    ``win_row`` (a WindowRows of B windows): ``src`` is a frame-feature table [table_rows, cin] and sequence b reads its T
+    rows from win_row[b] on (pcaa_dtc_conv_fwd_win; eval form: no statistics, no im2col)."""
     _chk(src, "dtc_conv_fwd.src", torch.float32, 2)
     _chk(W2d, "dtc_conv_fwd.W", torch.float32, 2)
     rows, cin = src.shape
     cout = W2d.shape[0]
+    if win_row is not None:
+        if not isinstance(win_row, WindowRows):
+            raise TypeError("dtc_conv_fwd: win_row must be an ops.WindowRows (it carries the host-side range check)")
+        if stats is not None or want_col or tail is not None:
+            raise ValueError("dtc_conv_fwd: a windowed source is eval-only (no statistics, no im2col)")
+        if len(win_row) != B or win_row.T != T or win_row.table_rows != rows:
+            raise ValueError(f"dtc_conv_fwd: win_row describes {len(win_row)} windows of {win_row.T} rows in a table of "
+                             f"{win_row.table_rows}, got B={B} T={T} table {tuple(src.shape)}")
+        rows = B * T
     if rows != B * T or W2d.shape[1] != cin * 3 or not dtc_conv_supported(T, cin, cout):
         raise ValueError(f"dtc_conv_fwd: unsupported shapes src {tuple(src.shape)} W {tuple(W2d.shape)} B={B} T={T}")
     if scale is not None:
@@ -1773,6 +1871,12 @@ def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=Fa
     col = torch.empty((rows, cin * 3), dtype=torch.float32, device=src.device) if want_col else None
     lib = _lib.load()
     fwd = lib.pcaa_dtc_conv_fwd_bf16 if bf16 else lib.pcaa_dtc_conv_fwd       # bf16: the throughput mode's MFMA variant
+    if win_row is not None:
+        win = lib.pcaa_dtc_conv_fwd_win_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_win
+        wargs = (_p(win_row.dev), win_row.table_rows, win_row.ring_rows)
+
+        def fwd(*args):        # same arguments, the window description before the stream
+            return win(*args[:-1], *wargs, args[-1])
     ksplit = lib.pcaa_dtc_conv_ksplit(B, cin, cout)
     if ksplit > 1:
         stride = rows * cout
