@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 18 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 19 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -509,6 +509,20 @@ int pcaa_dtc_conv_fwd_win_bf16(const float* table, const float* scale, const flo
                           int ksplit, long slab_stride, const int* win_row, long table_rows, long ring_rows,
                           void* stream);
 
+/* ABI 19: the windowed eval form on SEGMENTED rings (the rings of many live streams in one table).  `table` is n_seg
+ * rings of ring_rows rows back to back ([n_seg * ring_rows, cin]); win_row[b] is an ABSOLUTE table row and the window wraps
+ * inside the ring it starts in: with base = (win_row[b] / ring_rows) * ring_rows, step t reads row
+ * base + (win_row[b] - base + t) % ring_rows.  Needs ring_rows >= T, n_seg >= 1; the range of win_row (0 <= win_row[b] <
+ * n_seg * ring_rows) is the caller's to check on the host plan, as for pcaa_dtc_conv_fwd_win.  Eval only (no col, no
+ * statistics); only the staging address differs from pcaa_dtc_conv_fwd_win, whose result it equals bit for bit when
+ * n_seg == 1. */
+int pcaa_dtc_conv_fwd_seg(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                          int B, int T, int cin, int cout, int dilation, int ksplit, long slab_stride,
+                          const int* win_row, long n_seg, long ring_rows, void* stream);
+int pcaa_dtc_conv_fwd_seg_bf16(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                          int B, int T, int cin, int cout, int dilation, int ksplit, long slab_stride,
+                          const int* win_row, long n_seg, long ring_rows, void* stream);
+
 /* ------------------------------------------------------------------ frame-deduplicated inference (track_infer.hip)
  * Which consecutive crops of a sequentially ordered split share frames.  Crops are cut with a hop of CROP_STEP out of
  * tracks whose frames were standardised one by one before the cut (datasets.py:16-25, 143-146, 297-302), so a shared
@@ -527,6 +541,25 @@ int pcaa_crop_overlap(const float* crops, long crop_elems, long frame_elems, int
 int pcaa_gather_rows_w4(const void* src, long n_src_rows, long row_words, const long long* idx, void* dst,
                         long n_rows, int* err_flag, void* stream);
 
+/* ABI 19: the inverse of the row gather: dst[dst_row[r]] = src[r] for n_rows rows of row_words 32-bit words (dst_row:
+ * [n_rows] device ints).  dst_row[r] < 0 skips the row (padding); dst_row[r] >= n_dst_rows skips it and sets *err_flag
+ * (may be NULL).  Duplicate destinations are the caller's error.  16-byte copies when row_words % 4 == 0 and src and dst
+ * are 16-B aligned, 4-byte copies otherwise. */
+int pcaa_scatter_rows(const void* src, const int* dst_row, long n_rows, long row_words, void* dst, long n_dst_rows,
+                      int* err_flag, void* stream);
+/* ABI 19: one tick of a multi-stream scorer in one launch: for the tick's nw windows preds[i] (first maximal softmax
+ * probability: the want_preds rule of pcaa_cross_entropy) and lik[i] (the expression of pcaa_joint_likelihood, same bits),
+ * and for every window with win_j[i] % k == k - 1 the vote of group win_j[i] / k by the rule of pcaa_kvote, written to
+ * votes[vote_pos[i]] (vote_pos[i] < 0: none).  The windows of one stream are a contiguous run of the arrays with ascending
+ * win_j: run r is [run_start[r], run_start[r + 1]) (run_start: [n_runs + 1], run_start[0] = 0, run_start[n_runs] = nw),
+ * win_stream[i] in [0, max_streams) its stream, a stream has at most one run per call.  hist_lik / hist_pred
+ * [max_streams, k] keep a stream's current, incomplete vote group between calls (slot j % k = window j): a vote reads
+ * the predecessors that are not in this call from them, and the last k windows of a run are written back.  One
+ * workgroup per run, so the number of launches does not depend on the number of streams. */
+int pcaa_stream_score(const float* logits, const float* sup_fv, const float* means, const int* run_start, int n_runs,
+                      const int* win_stream, const int* win_j, const int* vote_pos, int nw, int K, int D, int Kc,
+                      double threshold, int k, int n_labels, int n_classes, double* hist_lik, long long* hist_pred,
+                      int max_streams, long long* preds, double* lik, long long* votes, int n_votes, void* stream);
 /* The adjoint w.r.t. the layer input in one launch (replaces dcol = dy . W on the im2col layout followed by
  * pcaa_dtc_col2im): da[(b,t)][ci] = sum_{co,tap} dy[b][t+(2-tap)*d][co] * W[co][ci][tap].
  *  - dy given, or formed on load from this layer's dz, y and the coefficients of pcaa_bn_bwd_finalize

@@ -69,17 +69,29 @@ struct DtcFwdParams {
   // ring_rows if > 0) instead of row b*T + t; null = the addressing above
   const int* win_row;
   long ring_rows;
+  // segmented rings (pcaa_dtc_conv_fwd_seg): the table is rings of ring_rows rows back to back, win_row[b] is an absolute
+  // row and the window wraps inside the ring it starts in; 0 = one ring from row 0
+  int seg;
+};
+
+// the source rows of one sequence: step r reads row base + (row0 + r), wrapped inside the ring
+struct DtcSrc {
+  long base, row0;
 };
 
 // first source row of sequence b and the row of step r from it (ring: T <= ring_rows, so one conditional subtraction wraps)
-__device__ __forceinline__ long dtc_src_row0(const DtcFwdParams& p, int b) {
-  if (p.win_row == nullptr) return (long)b * p.T;
+__device__ __forceinline__ DtcSrc dtc_src_row0(const DtcFwdParams& p, int b) {
+  if (p.win_row == nullptr) return DtcSrc{0, (long)b * p.T};
   const long r0 = p.win_row[b];
-  return p.ring_rows > 0 ? r0 % p.ring_rows : r0;
+  if (p.seg) {
+    const long base = (r0 / p.ring_rows) * p.ring_rows;
+    return DtcSrc{base, r0 - base};
+  }
+  return DtcSrc{0, p.ring_rows > 0 ? r0 % p.ring_rows : r0};
 }
-__device__ __forceinline__ long dtc_src_row(const DtcFwdParams& p, long row0, int r) {
-  const long row = row0 + r;
-  return (p.ring_rows > 0 && row >= p.ring_rows) ? row - p.ring_rows : row;
+__device__ __forceinline__ long dtc_src_row(const DtcFwdParams& p, const DtcSrc& s, int r) {
+  const long row = s.row0 + r;
+  return s.base + ((p.ring_rows > 0 && row >= p.ring_rows) ? row - p.ring_rows : row);
 }
 
 constexpr int CC = 32;              // input channels per chunk: 3*CC = 96-deep contraction per trip
@@ -148,7 +160,7 @@ __global__ __launch_bounds__(256) void dtc_fwd_kernel(DtcFwdParams p) {
   {
     const int q4 = cr >> 2;
     const bool act = p.scale != nullptr;
-    const long row0 = dtc_src_row0(p, b);
+    const DtcSrc row0 = dtc_src_row0(p, b);
     for (int q = tid; q < T * q4; q += 256) {
       const int r = q / q4, c4 = (q - r * q4) << 2;
       f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
@@ -292,7 +304,7 @@ __global__ __launch_bounds__(256) void dtc_fwd_bf16_kernel(DtcFwdParams p) {
   {
     const int q4 = cr >> 2;
     const bool act = p.scale != nullptr;
-    const long row0 = dtc_src_row0(p, b);
+    const DtcSrc row0 = dtc_src_row0(p, b);
     for (int q = tid; q < T * q4; q += 256) {
       const int r = q / q4, c4 = (q - r * q4) << 2;
       f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
@@ -1046,7 +1058,7 @@ extern "C" int pcaa_dtc_conv_ksplit(int B, int cin, int cout) {
 static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, const float* shift, const float* W, float* y,
                              float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
                              int ksplit, long slab_stride, void* stream, const int* win_row = nullptr,
-                             long ring_rows = 0) {
+                             long ring_rows = 0, int seg = 0) {
   PCAA_CHECK_ARG(src && W && y && B >= 1 && dilation >= 1 && ksplit >= 1, "pcaa_dtc_conv_fwd: bad args");
   PCAA_CHECK_ARG(pcaa_dtc_conv_supported(T, cin, cout), "pcaa_dtc_conv_fwd: needs T <= %d, cin %% 4 == 0, cout %% 16 == 0",
                  ROWS);
@@ -1073,7 +1085,7 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
     PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
   }
   DtcFwdParams p{src, scale, shift, W, y, col, stats, B, T, cin, cout, dilation, nrep, ksplit > 1 ? slab_stride : 0,
-                 (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}, win_row, ring_rows};
+                 (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}, win_row, ring_rows, seg};
   if (bf16) hipLaunchKernelGGL(dtc_fwd_bf16_kernel, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
   else hipLaunchKernelGGL(dtc_fwd_kernel, dim3(B, (cout + 31) / 32, ksplit), dim3(256), 0, as_stream(stream), p);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
@@ -1116,6 +1128,28 @@ extern "C" int pcaa_dtc_conv_fwd_win_bf16(const float* table, const float* scale
                                           long table_rows, long ring_rows, void* stream) {
   return dtc_conv_fwd_win_impl(true, table, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dilation, ksplit,
                                slab_stride, win_row, table_rows, ring_rows, stream);
+}
+
+// Segmented rings: n_seg rings of ring_rows rows back to back, win_row[b] an absolute table row (include/pcaa_hip.h).
+static int dtc_conv_fwd_seg_impl(bool bf16, const float* table, const float* scale, const float* shift, const float* W,
+                                 float* y, int B, int T, int cin, int cout, int dilation, int ksplit, long slab_stride,
+                                 const int* win_row, long n_seg, long ring_rows, void* stream) {
+  PCAA_CHECK_ARG(win_row != nullptr && n_seg >= 1 && ring_rows >= T && T >= 1,
+                 "pcaa_dtc_conv_fwd_seg: needs win_row, n_seg >= 1, ring_rows >= T");
+  return dtc_conv_fwd_impl(bf16, table, scale, shift, W, y, nullptr, nullptr, 1, B, T, cin, cout, dilation, ksplit,
+                           slab_stride, stream, win_row, ring_rows, 1);
+}
+extern "C" int pcaa_dtc_conv_fwd_seg(const float* table, const float* scale, const float* shift, const float* W, float* y,
+                                     int B, int T, int cin, int cout, int dilation, int ksplit, long slab_stride,
+                                     const int* win_row, long n_seg, long ring_rows, void* stream) {
+  return dtc_conv_fwd_seg_impl(false, table, scale, shift, W, y, B, T, cin, cout, dilation, ksplit, slab_stride, win_row,
+                               n_seg, ring_rows, stream);
+}
+extern "C" int pcaa_dtc_conv_fwd_seg_bf16(const float* table, const float* scale, const float* shift, const float* W,
+                                          float* y, int B, int T, int cin, int cout, int dilation, int ksplit,
+                                          long slab_stride, const int* win_row, long n_seg, long ring_rows, void* stream) {
+  return dtc_conv_fwd_seg_impl(true, table, scale, shift, W, y, B, T, cin, cout, dilation, ksplit, slab_stride, win_row,
+                               n_seg, ring_rows, stream);
 }
 
 /* channel split for the dgrad (its contraction runs over the OUTPUT channels of the convolution; a workgroup

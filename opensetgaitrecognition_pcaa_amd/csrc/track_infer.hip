@@ -5,7 +5,8 @@
 // track share 24 frames, with the same bits.  In eval mode the PointNet block and the mean over a frame's points see one
 // frame at a time (models.py:82-105, 242-243), so a shared frame needs encoding once.  Here:
 //   * pcaa_crop_overlap    -- which consecutive crops share their overlap bit for bit (the mask the plan is built from);
-//   * pcaa_gather_rows_w4  -- the row gather for frames that are not a multiple of 16 bytes (N = 150, C = 5: 3 000 B).
+//   * pcaa_gather_rows_w4  -- the row gather for frames that are not a multiple of 16 bytes (N = 150, C = 5: 3 000 B);
+//   * pcaa_scatter_rows    -- the inverse of the row gather: a tick's frame features into the rings of many live streams.
 // The windowed read of the frame-feature table is an addressing mode of the temporal block's kernels (dtc_fused.hip).
 #include "common.h"
 
@@ -68,6 +69,25 @@ __global__ __launch_bounds__(256) void gather_rows_w4_kernel(const uint32_t* __r
   }
 }
 
+// dst[dst_row[r]] = src[r], rows of row_vec vectors: a 4-KB feature row is 256 16-B vectors, one per lane of a workgroup.
+// dst_row[r] < 0: the row is dropped (padding); >= n_dst: dropped and flagged.  Plain vector loads and stores.
+template <typename V>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const V* __restrict__ src, const int* __restrict__ dst_row,
+                                                           long n_dst, V* __restrict__ dst, long n_rows, long row_vec,
+                                                           int* __restrict__ err) {
+  const long total = n_rows * row_vec;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long)gridDim.x * 256) {
+    const long r = v / row_vec, off = v - r * row_vec;
+    const long d = dst_row[r];
+    if (d < 0) continue;
+    if (d >= n_dst) {
+      if (err != nullptr && off == 0) atomicOr(err, 1);
+      continue;
+    }
+    dst[d * row_vec + off] = src[v];
+  }
+}
+
 }  // namespace
 
 extern "C" int pcaa_crop_overlap_vec_bytes(const float* crops, long crop_elems, long frame_elems) {
@@ -102,4 +122,23 @@ extern "C" int pcaa_gather_rows_w4(const void* src, long n_src_rows, long row_wo
                      as_stream(stream), reinterpret_cast<const uint32_t*>(src), idx, n_src_rows,
                      reinterpret_cast<uint32_t*>(dst), n_rows, row_words, err_flag);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_gather_rows_w4");
+}
+
+extern "C" int pcaa_scatter_rows(const void* src, const int* dst_row, long n_rows, long row_words, void* dst,
+                                 long n_dst_rows, int* err_flag, void* stream) {
+  PCAA_CHECK_ARG(src && dst_row && dst && n_rows >= 1 && row_words >= 1 && n_dst_rows >= 1, "pcaa_scatter_rows: bad args");
+  PCAA_CHECK_ARG(((uintptr_t)src % 4) == 0 && ((uintptr_t)dst % 4) == 0, "pcaa_scatter_rows: 4-B alignment");
+  const bool v16 = row_words % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
+  const long row_vec = v16 ? row_words / 4 : row_words;
+  const long want = cdiv(n_rows * row_vec, 256);
+  const dim3 grid((unsigned)(want > 4096 ? 4096 : want));
+  if (v16)
+    hipLaunchKernelGGL(scatter_rows_kernel<uint4>, grid, dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const uint4*>(src), dst_row, n_dst_rows, reinterpret_cast<uint4*>(dst), n_rows,
+                       row_vec, err_flag);
+  else
+    hipLaunchKernelGGL(scatter_rows_kernel<uint32_t>, grid, dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const uint32_t*>(src), dst_row, n_dst_rows, reinterpret_cast<uint32_t*>(dst), n_rows,
+                       row_vec, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_scatter_rows");
 }

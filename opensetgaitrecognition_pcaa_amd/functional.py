@@ -140,7 +140,63 @@ class _LayerSave:
         self.mom = None
 
 
-def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer):
+class EncoderEvalConstants:
+    """What an eval-mode forward derives from a FROZEN encoder alone, computed once by the kernels that compute it in every
+    forward otherwise (same bits): the folded BatchNorm coefficients ``(scale, shift)`` of the ten BatchNorm layers and, in
+    bf16 mode, the bf16 images of the weights of PointNet layers 2-4.  It records what it was made from -- the encoder, the
+    precision mode, and ``_version`` and storage address of every parameter and buffer -- and ``valid_for`` compares that,
+    so a holder notices ``load_state_dict``, an optimizer step, a move to another dtype or device, or a mode switch.  (The
+    tensors are the ones the encoder had when this was made: a Parameter OBJECT swapped for another is only noticed
+    through ``encoder_eval_constants`` being called again.)  Never shared between encoders."""
+    __slots__ = ("mode", "bn", "w16", "enc_id", "tensors", "stamp")
+
+    def _stamp(self):
+        return [(t._version, t.data_ptr()) for t in self.tensors]
+
+    def valid_for(self, enc, mode):
+        return id(enc) == self.enc_id and mode == self.mode and self._stamp() == self.stamp
+
+
+def encoder_eval_constants(enc, mode=None):
+    """-> EncoderEvalConstants of ``enc`` for ``mode`` (default: the current precision mode): ten pcaa_bn_eval_coeffs launches
+    and, in bf16 mode, three weight casts, once instead of in every eval forward (``consts=`` of encoder_frame_features /
+    encoder_forward_windows)."""
+    mode = get_precision() if mode is None else mode
+    if mode not in ("fp32", "bf16", "fp16x3"):
+        raise ValueError("precision must be 'fp32', 'bf16' or 'fp16x3'")
+    if enc.training:
+        raise RuntimeError("encoder_eval_constants: the encoder is in training mode (its BatchNorm uses batch statistics)")
+    c = EncoderEvalConstants()
+    c.mode, c.bn, c.w16, c.enc_id = mode, {}, {}, id(enc)
+    c.tensors = list(itertools.chain(enc.parameters(), enc.buffers()))
+    c.stamp = c._stamp()
+    with torch.no_grad():
+        for li, layer in enumerate(enc.pc_block.layers()):
+            conv, bn = layer.module[0], layer.module[1]
+            cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+            c.bn[id(bn)] = ops.bn_eval_coeffs(bn, cout, conv.bias)
+            if mode == "bf16" and li > 0 and cin % 8 == 0:
+                c.w16[id(conv)] = ops.cast_bf16(conv.weight.view(cout, cin), True, False)[0]
+        for layer in enc.tc_block.layers():
+            c.bn[id(layer.batch_norm)] = ops.bn_eval_coeffs(layer.batch_norm, layer.conv1d.weight.shape[0], layer.conv1d.bias)
+    return c
+
+
+def _eval_coeffs(consts, bn, cout, lin_bias):
+    """eval-mode (scale, shift) of one BatchNorm layer: from the frozen constants when given, else computed now"""
+    if consts is not None:
+        return consts.bn[id(bn)]
+    return ops.bn_eval_coeffs(bn, cout, lin_bias)
+
+
+def _eval_w16(consts, conv, W2d):
+    """the bf16 image of an eval-mode PointNet weight: from the frozen constants when given, else cast now"""
+    if consts is not None:
+        return consts.w16[id(conv)]
+    return ops.cast_bf16(W2d, True, False)[0]
+
+
+def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None, conv=None):
     """y = a_in @ W2d^T (the linear bias is NOT added: it cancels in train-mode BatchNorm and
     is folded into ``shift`` in eval mode; see bn_finalize_kernel) with BatchNorm statistics;
     returns the bias-free y and the BN coefficients that apply to it."""
@@ -164,7 +220,10 @@ def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer):
     elif use_bf16:
         # bf16 shadow of the weights so both operands stream by LDS-DMA (the transposed copy
         # serves the dgrad GEMM of the backward pass)
-        w16, wt16 = ops.cast_bf16(W2d, True, training)
+        if consts is not None and not training:
+            w16, wt16 = _eval_w16(consts, conv, W2d), None
+        else:
+            w16, wt16 = ops.cast_bf16(W2d, True, training)
         _W16_CACHE[W2d.data_ptr()] = wt16
         y = ops.gemm(a_in, KC, w16, KC, rows, cout, cin, colstats=stats, out_dtype=out_dtype, math=PCAA_BF16, tail=tail)
     else:
@@ -181,16 +240,20 @@ def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer):
         scale, shift, mean, rstd = tail.out
         count = tail.count_out
     else:
-        scale, shift = ops.bn_eval_coeffs(bn, cout, lin_bias)
+        scale, shift = _eval_coeffs(consts, bn, cout, lin_bias)
         mean = rstd = None
         count = rows
     return y, scale, shift, mean, rstd, count
 
 
-def pointnet_forward(xp2d, layers, training, mode, pool_rows=0):
+def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
     """xp2d: [P, C] fp32.  Returns (output, saves).  If pool_rows>0 the last
     layer's ELU output is mean-pooled over groups of pool_rows rows (fp32
-    [P/pool_rows, ch]); else the last activation [P, ch] is returned."""
+    [P/pool_rows, ch]); else the last activation [P, ch] is returned.
+    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing them."""
+    if consts is not None and (training or consts.mode != mode):
+        raise ValueError("pointnet_forward: consts are eval-mode constants of one precision mode "
+                         f"(made for {consts.mode!r}, asked for {mode!r}, training={training})")
     saves = []
     a = xp2d
     nl = len(layers)
@@ -221,7 +284,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0):
                 scale, shift, mean, rstd = tail.out
                 count = tail.count_out
             else:
-                scale, shift = ops.bn_eval_coeffs(bn, cout, conv.bias)
+                scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
                 mean = rstd = None
                 count = rows
             s = _LayerSave()
@@ -238,8 +301,8 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0):
                 and ops.gemm_dgrad_bn_supported(a.shape[0], cout, cin)):
             # eval mode: BatchNorm is a fixed per-channel affine map -> BN + ELU (and the mean over the frame's
             # points for the last layer) in the GEMM epilogue: no stored y, no separate pass
-            scale, shift = ops.bn_eval_coeffs(bn, cout, conv.bias)
-            w16, _ = ops.cast_bf16(W2d, True, False)
+            scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
+            w16 = _eval_w16(consts, conv, W2d)
             a_next = ops.gemm_affine_elu(a, w16, scale, shift, pool_rows if last_pool else 0)
             s = _LayerSave()
             s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, None, scale, shift, None, None
@@ -249,7 +312,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0):
                 return a_next, saves
             a = a_next
             continue
-        y, scale, shift, mean, rstd, count = _linear_bn(a, W2d, conv.bias, bn, training, mode, True)
+        y, scale, shift, mean, rstd, count = _linear_bn(a, W2d, conv.bias, bn, training, mode, True, consts, conv)
         s = _LayerSave()
         s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, y, scale, shift, mean, rstd
         s.rows, s.cin, s.cout, s.dil = count, cin, cout, 0
@@ -570,11 +633,14 @@ def _dtc_bf16(mode, kc, nc, adj=False):
     return on and kc >= 128 and kc % 32 == 0 and nc >= 64 and nc % 4 == 0
 
 
-def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0):
+def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0, consts=None):
     """a2d: [B*T, Cin] fp32 rows (b,t).  Causal dilated conv = (implicit) im2col + contraction.
     ``win_row`` (ops.WindowRows, eval only): a2d is a frame-feature table [table_rows, Cin] instead and sequence b is
     its T rows from win_row[b] on (modulo ``ring_rows`` if > 0).  Only the first layer reads the table: fused, through
-    the windowed form of its launch; otherwise the windows are written out with one gather and today's path runs."""
+    the windowed form of its launch; otherwise the windows are written out with one gather and today's path runs.
+    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing the BatchNorm coefficients."""
+    if consts is not None and training:
+        raise ValueError("dtc_forward: consts are eval-mode constants")
     saves = []
     a = a2d
     nl = len(layers)
@@ -604,13 +670,14 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
                 scale, shift, mean, rstd = tail.out
                 count = tail.count_out
             else:
-                scale, shift = ops.bn_eval_coeffs(bn, cout, conv.bias)
+                scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
                 mean = rstd = None
                 count = y.shape[0]
             a_in = None
         else:
             col = ops.dtc_im2col(a, B, T, cin, layer.dilation)
-            y, scale, shift, mean, rstd, count = _linear_bn(col, W2d, conv.bias, bn, training, "fp32", None)
+            y, scale, shift, mean, rstd, count = _linear_bn(col, W2d, conv.bias, bn, training, "fp32", None,
+                                                            consts if not training else None)
             a_in = a
         s = _LayerSave()
         s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a_in, col, y, scale, shift, mean, rstd
@@ -920,10 +987,11 @@ def frame_pad_quantum(N, mode=None):
     return 256 // math.gcd(N, 256)
 
 
-def encoder_frame_features(enc, frames, mode=None):
+def encoder_frame_features(enc, frames, mode=None, consts=None):
     """Eval-mode PointNet block + mean over the points, frame by frame (models.py:82-105, 242-243, 279-282): point-major
     frames [U, N, C] fp32 -> ([U, 1024] fp32, saves).  A frame's features do not depend on its neighbours, which is what
-    lets overlapping crops share them."""
+    lets overlapping crops share them.  ``consts``: ``encoder_eval_constants(enc, mode)`` of a frozen encoder (same bits,
+    the constants are not recomputed); None: they are computed in this call."""
     mode = get_precision() if mode is None else mode
     _require_gpu(frames, "CGEncoder")
     if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
@@ -935,12 +1003,13 @@ def encoder_frame_features(enc, frames, mode=None):
     if N != enc.nmax_points:
         raise RuntimeError(f"CGEncoder: N={N} points but nmax_points={enc.nmax_points} "
                            "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
-    return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N)
+    return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N, consts=consts)
 
 
-def encoder_forward_windows(enc, table, win_row, T, mode=None):
+def encoder_forward_windows(enc, table, win_row, T, mode=None, consts=None):
     """Eval-mode temporal block, mean over T and heads on windows of a frame-feature table [table_rows, 1024]
-    (encoder_frame_features): window b = rows win_row[b] .. + T - 1 (an ops.WindowRows; its ring_rows > 0: modulo).
+    (encoder_frame_features): window b = rows win_row[b] .. + T - 1 (an ops.WindowRows; its ring_rows > 0: modulo, its
+    segments > 0: modulo inside the ring the window starts in).  ``consts``: as for encoder_frame_features.
     Returns (logits, sup_fv, st) as encoder_forward does for the materialised crops."""
     mode = get_precision() if mode is None else mode
     _require_gpu(table, "CGEncoder")
@@ -948,7 +1017,7 @@ def encoder_forward_windows(enc, table, win_row, T, mode=None):
     st = EncoderState()
     st.B, st.T, st.mode, st.training = B, T, mode, False
     x4, st.dtc = dtc_forward(table, B, T, enc.tc_block.layers(), False, pool_time=True, mode=mode, win_row=win_row,
-                             ring_rows=win_row.ring_rows)
+                             ring_rows=win_row.ring_rows, consts=consts)
     st.x4 = x4
     return _encoder_heads(enc, st, x4)
 

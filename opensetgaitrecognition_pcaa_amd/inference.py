@@ -422,7 +422,11 @@ class StreamingScorer:
     EAGERLY: for a track of F frames ``OpenSetScorer.embed_track`` under the reference's cropping rule holds one window
     fewer when ``(F - NSTEPS) % hop == 0`` (``window_count``); the first ``window_count(F)`` windows are the same.
     ``votes()`` is ``k_vote`` over the completed groups of k windows so far, ``reset()`` starts a new track.  The
-    precision mode (``functional.get_precision()``) is read at every push, as ``OpenSetScorer.embed`` does."""
+    precision mode (``functional.get_precision()``) is read at every push, as ``OpenSetScorer.embed`` does.
+
+    One object serves ONE track, and it keeps the predictions and likelihoods of every past window (``votes()`` recomputes
+    all groups), so its memory grows for as long as the track lives.  ``MultiStreamScorer`` scores many concurrent tracks
+    in one batched tick with O(k) state per track."""
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None):
@@ -516,3 +520,261 @@ class StreamingScorer:
         n = (preds.numel() // self.k) * self.k
         return k_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels,
                       n_classes=self.n_classes)
+
+
+class TickPlan:
+    """What ``plan_tick`` returns: see there."""
+    __slots__ = ("dst_row", "win_row", "win_stream", "win_j", "vote_pos", "run_start", "vote_stream", "vote_group",
+                 "n_frames", "n_windows", "packed", "offsets")
+
+
+def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1):
+    """Host plan of one tick of ``MultiStreamScorer``: a pure function of the streams' counters, numpy only.
+
+    ``n_frames`` / ``n_windows``: per SLOT, the frames pushed and the windows emitted so far; ``sids``: the distinct slots
+    this tick feeds, ``counts[i]`` new frames of ``sids[i]`` (0 allowed), the frames concatenated in that order.  Slot s
+    owns rows ``s * ring_rows .. (s + 1) * ring_rows - 1`` of the feature table, frame f of its track lives in row
+    ``s * ring_rows + f % ring_rows``; a stream with n frames has ``0 if n < T else (n - T) // hop + 1`` windows, window j
+    starts at frame ``j * hop``; group ``j // k`` is voted on by the window with ``j % k == k - 1``.  Returns a TickPlan:
+
+    * ``dst_row`` int32 [P]: the table row of every frame; P = the frames padded up to a multiple of ``pad_to``, the
+      padding rows marked -1 (skip);
+    * ``win_row`` / ``win_stream`` / ``win_j`` int32 [nw]: start row (absolute), slot and index within its stream of every
+      window the tick completes, ordered by the position of the stream in ``sids``, ascending within a stream;
+    * ``vote_pos`` int32 [nw]: where the group a window completes goes in the tick's votes, -1 if it completes none;
+      ``vote_stream`` / ``vote_group`` int64 [g]: slot and group index of every vote;
+    * ``run_start`` int32 [runs + 1]: the windows of one stream are ``run_start[r] .. run_start[r + 1]``;
+    * ``n_frames`` / ``n_windows`` int64 [len(sids)]: the counters of ``sids`` after the tick;
+    * ``packed`` int32: all six int32 arrays in one buffer (one upload), ``offsets[name] = (start, stop)`` in it."""
+    T, hop, k, ring_rows, pad_to = int(T), int(hop), int(k), int(ring_rows), int(pad_to)
+    n_frames = np.asarray(n_frames, dtype=np.int64).reshape(-1)
+    n_windows = np.asarray(n_windows, dtype=np.int64).reshape(-1)
+    sids = np.asarray(sids, dtype=np.int64).reshape(-1)
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    n_slots, S = n_frames.size, sids.size
+    if not 1 <= hop <= T or k < 1 or pad_to < 1 or ring_rows < T or n_slots != n_windows.size:
+        raise ValueError("plan_tick: needs 1 <= hop <= T <= ring_rows, k >= 1, pad_to >= 1, one counter pair per slot")
+    if S != counts.size:
+        raise ValueError(f"plan_tick: {S} streams but {counts.size} counts")
+    if n_slots * ring_rows >= 2 ** 31:
+        raise ValueError("plan_tick: the table rows do not fit 32-bit indices")
+    plan = TickPlan()
+    if S == 0:
+        z = np.zeros(0, np.int64)
+        nf1 = done = nwin = win_stream = j = z
+        dst_row, complete, total, nw = np.zeros(0, np.int32), np.zeros(0, bool), 0, 0
+    else:
+        if sids.min() < 0 or sids.max() >= n_slots:
+            raise ValueError(f"plan_tick: a stream id outside 0..{n_slots - 1}")
+        seen = np.zeros(n_slots, bool)
+        seen[sids] = True
+        if np.count_nonzero(seen) != S:
+            raise ValueError("plan_tick: a stream id appears twice in one tick")
+        if counts.min() < 0 or counts.max() + T > ring_rows:
+            raise ValueError(f"plan_tick: counts must lie in 0..ring_rows - T = {ring_rows - T} (a larger push would "
+                             "overwrite frames its own windows still read)")
+        nf0, w0 = n_frames[sids], n_windows[sids]
+        nf1 = nf0 + counts
+        done = np.where(nf1 < T, 0, (nf1 - T) // hop + 1)
+        nwin = done - w0
+        if nwin.min() < 0:
+            raise ValueError("plan_tick: a stream has emitted more windows than its frames hold")
+        if done.max() >= 2 ** 31:
+            raise ValueError("plan_tick: a window index does not fit 32 bits")
+        total, nw = int(counts.sum()), int(nwin.sum())
+        # frame f of the tick: f - (frames of the streams before its own) + (frames its stream had) = its index in its track
+        base = sids * ring_rows
+        dst = np.arange(total, dtype=np.int64) + np.repeat(nf0 - (np.cumsum(counts) - counts), counts)
+        dst %= ring_rows
+        dst += np.repeat(base, counts)
+        pad = (-total) % pad_to
+        dst_row = dst.astype(np.int32) if not pad else np.concatenate([dst, np.full(pad, -1, np.int64)]).astype(np.int32)
+        wstart = np.cumsum(nwin) - nwin
+        j = np.arange(nw, dtype=np.int64) + np.repeat(w0 - wstart, nwin)
+        win_stream = np.repeat(sids, nwin)
+        complete = j % k == k - 1
+    plan.dst_row = dst_row
+    plan.win_row = (win_stream * ring_rows + (j * hop) % ring_rows).astype(np.int32)
+    plan.win_stream, plan.win_j = win_stream.astype(np.int32), j.astype(np.int32)
+    plan.vote_pos = np.where(complete, np.cumsum(complete) - 1, -1).astype(np.int32)
+    plan.vote_stream, plan.vote_group = win_stream[complete], j[complete] // k
+    plan.run_start = np.append(wstart[nwin > 0], nw).astype(np.int32) if S else np.zeros(1, np.int32)
+    plan.n_frames, plan.n_windows = nf1, done
+    parts = (plan.dst_row, plan.win_row, plan.win_stream, plan.win_j, plan.vote_pos, plan.run_start)
+    plan.offsets, a = {}, 0
+    for name, arr in zip(("dst_row", "win_row", "win_stream", "win_j", "vote_pos", "run_start"), parts):
+        plan.offsets[name] = (a, a + arr.size)
+        a += arr.size
+    plan.packed = np.concatenate(parts)
+    return plan
+
+
+class Tick:
+    """The result of one ``MultiStreamScorer.push``.  ``stream`` / ``window`` int64 [nw] and ``vote_stream`` /
+    ``vote_group`` int64 [g]: host numpy arrays (known from the plan: no device sync); ``preds`` int64 [nw], ``sup_fv``
+    fp32 [nw, 32], ``lik`` f64 [nw], ``votes`` int64 [g]: device tensors.  Windows are ordered by the position of their
+    stream in ``sids``, ascending within a stream."""
+    __slots__ = ("stream", "window", "vote_stream", "vote_group", "preds", "sup_fv", "lik", "votes")
+
+    def __len__(self):
+        return self.stream.size
+
+
+class MultiStreamScorer:
+    """Open-set scoring of up to ``max_streams`` live tracks in one batched tick.
+
+    Every slot owns a ring of ``ring_rows >= NSTEPS + max_push`` rows in one ``[max_streams * ring_rows, 1024]`` feature
+    table.  ``push(sids, counts, frames)`` takes the new frames of any subset of the open slots (ragged) and runs ONE eval
+    PointNet pass over all of them, ONE scatter into the rings, ONE temporal block + heads pass over every window the tick
+    completes (the segmented windowed form of the first temporal layer) and ONE scoring launch (argmax, likelihood, vote
+    state, votes): the number of launches does not depend on the number of streams.  The window rule is
+    ``StreamingScorer``'s (eager: window j comes back from the tick that brings its stream to ``NSTEPS + j * hop`` frames).
+    ``push`` synchronises nothing and copies nothing to the host; the tick's plan (``plan_tick``) goes up as one pinned
+    buffer.  The encoder's eval constants (``functional.encoder_eval_constants``) are folded once and rebuilt when a
+    parameter, a buffer or the precision mode changes.  Per-stream state is O(k): the incomplete vote group."""
+
+    def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
+                 max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
+                 batch_size: int = 1024):
+        self.encoder = encoder
+        self._check_eval()
+        self.T, self.hop, self.k, self.n_labels = constants.NSTEPS, int(hop), int(k), int(n_labels)
+        self.threshold, self.max_push, self.max_streams = float(threshold), int(max_push), int(max_streams)
+        self.batch_size = int(batch_size)
+        if (not 1 <= self.hop <= self.T or self.max_push < 1 or self.k < 1 or self.max_streams < 1
+                or self.batch_size < 1):
+            raise ValueError("MultiStreamScorer: needs 1 <= hop <= NSTEPS, max_push >= 1, k >= 1, max_streams >= 1, "
+                             "batch_size >= 1")
+        need = self.T + self.max_push
+        self.ring_rows = need if ring_rows is None else int(ring_rows)
+        if self.ring_rows < need:
+            raise ValueError(f"MultiStreamScorer: ring_rows={self.ring_rows} < NSTEPS + max_push = {need}")
+        dev = next(encoder.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("MultiStreamScorer: the encoder must live on the HIP device; this package has no CPU path")
+        self.means = means.float().to(dev).contiguous()
+        self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
+        self._D = encoder.MLP_sup1[0].weight.shape[0]
+        width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]
+        self.ring = torch.zeros((self.max_streams * self.ring_rows, width), dtype=torch.float32, device=dev)
+        self.hist_lik = torch.zeros((self.max_streams, self.k), dtype=torch.float64, device=dev)
+        self.hist_pred = torch.zeros((self.max_streams, self.k), dtype=torch.int64, device=dev)
+        self.scatter_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a scatter destination out of range
+        self.n_frames = np.zeros(self.max_streams, np.int64)
+        self.n_windows = np.zeros(self.max_streams, np.int64)
+        self._open = np.zeros(self.max_streams, bool)
+        self._consts = None
+        self._zeros = None
+        self.last_pointnet_saves = None
+
+    def _check_eval(self):
+        if self.encoder.training:
+            raise RuntimeError("MultiStreamScorer: the encoder is in training mode (train-mode BatchNorm mixes the frames "
+                               "of a batch: a frame's features would depend on its neighbours); call encoder.eval()")
+
+    def open(self) -> int:
+        """-> the lowest free slot; its frame and window counters start at 0 (its ring rows are not cleared: a window only
+        reads rows written since)"""
+        free = np.flatnonzero(~self._open)
+        if free.size == 0:
+            raise ValueError(f"MultiStreamScorer.open: all {self.max_streams} slots are in use")
+        sid = int(free[0])
+        self._open[sid] = True
+        self.n_frames[sid] = self.n_windows[sid] = 0
+        return sid
+
+    def close(self, sid: int):
+        """end the track in slot ``sid``; the slot may be handed out again"""
+        self._slots([sid], "close")
+        self._open[int(sid)] = False
+
+    def _slots(self, sids, what):
+        try:
+            arr = np.asarray(sids)
+            ok = arr.ndim == 1 and (arr.size == 0 or arr.dtype.kind in "iu")
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"MultiStreamScorer.{what}: stream ids must be a 1-D sequence of host ints")
+        arr = arr.astype(np.int64)
+        if arr.size and (arr.min() < 0 or arr.max() >= self.max_streams or not self._open[arr].all()):
+            raise ValueError(f"MultiStreamScorer.{what}: unknown or closed stream id in {arr.tolist()}")
+        return arr
+
+    def _empty(self, plan, dev):
+        t = Tick()
+        t.stream, t.window = plan.win_stream.astype(np.int64), plan.win_j.astype(np.int64)
+        t.vote_stream, t.vote_group = plan.vote_stream, plan.vote_group
+        t.preds = torch.empty(0, dtype=torch.int64, device=dev)
+        t.sup_fv = torch.empty((0, self._D), dtype=torch.float32, device=dev)
+        t.lik = torch.empty(0, dtype=torch.float64, device=dev)
+        t.votes = torch.empty(0, dtype=torch.int64, device=dev)
+        return t
+
+    @torch.no_grad()
+    def push(self, sids, counts, frames: torch.Tensor) -> Tick:
+        """``sids``: distinct open slots (host ints); ``counts[i]`` new frames of ``sids[i]`` (0 allowed, at most
+        ``max_push``); ``frames`` [sum(counts), N, C] fp32 on the device, concatenated in that order -> the Tick of the
+        windows these frames complete (possibly none: empty tensors, no temporal pass)."""
+        self._check_eval()
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise RuntimeError("MultiStreamScorer.push: frames must live on the HIP device; this package has no CPU path")
+        if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
+            raise ValueError(f"MultiStreamScorer.push expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
+        sids = self._slots(sids, "push")
+        try:
+            counts = np.asarray(counts)
+            ok = counts.ndim == 1 and (counts.size == 0 or counts.dtype.kind in "iu")
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or counts.size != sids.size:
+            raise ValueError("MultiStreamScorer.push: counts must be host ints, one per stream id")
+        counts = counts.astype(np.int64)
+        if counts.size and (counts.min() < 0 or counts.max() > self.max_push):
+            raise ValueError(f"MultiStreamScorer.push: counts must lie in 0..max_push = {self.max_push}")
+        if int(counts.sum()) != frames.shape[0]:
+            raise ValueError(f"MultiStreamScorer.push: counts add up to {int(counts.sum())} frames, got {frames.shape[0]}")
+        n, N, C = frames.shape
+        dev = self.ring.device
+        mode = F_hip.get_precision()
+        q = F_hip.frame_pad_quantum(N, mode)
+        plan = plan_tick(self.n_frames, self.n_windows, sids, counts, self.T, self.hop, self.k, self.ring_rows, q)
+        if n == 0:
+            return self._empty(plan, dev)
+        if self._consts is None or not self._consts.valid_for(self.encoder, mode):
+            self._consts = F_hip.encoder_eval_constants(self.encoder, mode)
+        # the whole plan in one pinned buffer, one asynchronous copy (the pinned block is recycled by torch's host
+        # allocator only after the copy has run)
+        host = torch.empty(plan.packed.size, dtype=torch.int32, pin_memory=True)
+        host.numpy()[:] = plan.packed
+        packed = host.to(dev, non_blocking=True)
+        part = {name: packed[a:b] for name, (a, b) in plan.offsets.items()}
+        pad = plan.dst_row.size - n
+        if pad:                                       # whole GEMM row tiles in bf16 mode, once per TICK; features dropped
+            if self._zeros is None or tuple(self._zeros.shape[1:]) != (N, C) or self._zeros.shape[0] < pad:
+                self._zeros = frames.new_zeros((max(pad, q), N, C))
+            frames = torch.cat([frames, self._zeros[:pad]])
+        feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames, mode, consts=self._consts)
+        ops.scatter_rows(feats, part["dst_row"], self.ring, err_flag=self.scatter_err)
+        self.n_frames[sids], self.n_windows[sids] = plan.n_frames, plan.n_windows
+        nw = plan.win_row.size
+        if nw == 0:
+            return self._empty(plan, dev)
+        rows = ops.WindowRows(plan.win_row, self.T, self.ring.shape[0], self.ring_rows, dev=part["win_row"],
+                              segments=self.max_streams)
+        logits, fvs = [], []
+        for i in range(0, nw, self.batch_size):
+            lg, fv, _ = F_hip.encoder_forward_windows(self.encoder, self.ring, rows.slice(i, i + self.batch_size) if
+                                                      nw > self.batch_size else rows, self.T, mode, consts=self._consts)
+            logits.append(lg)
+            fvs.append(fv)
+        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
+        sup_fv = (fvs[0] if len(fvs) == 1 else torch.cat(fvs)).contiguous()
+        t = Tick()
+        t.stream, t.window = plan.win_stream.astype(np.int64), plan.win_j.astype(np.int64)
+        t.vote_stream, t.vote_group = plan.vote_stream, plan.vote_group
+        t.sup_fv = sup_fv
+        t.preds, t.lik, t.votes = ops.stream_score(
+            logits.contiguous(), sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
+            plan.vote_group.size, self.threshold, self.k, self.n_labels, self.n_classes, self.hist_lik, self.hist_pred)
+        return t

@@ -1488,18 +1488,24 @@ def crop_overlap(crops, hop):
 class WindowRows:
     """The start rows of B windows of T rows in a frame-feature table, range-checked on the HOST copy of the plan they
     come from (the kernels trust them: pcaa_dtc_conv_fwd_win).  ``ring_rows`` > 0: the table is a ring of that many rows
-    and a window may wrap.  ``dev``: the same values already on the device (int32), else they are uploaded here."""
-    __slots__ = ("host", "dev", "T", "table_rows", "ring_rows")
+    and a window may wrap.  ``segments`` > 0 (needs ``ring_rows``): the table is that many rings of ``ring_rows`` rows back
+    to back (``table_rows == segments * ring_rows``), a start is an absolute table row and the window wraps inside the
+    ring it starts in (pcaa_dtc_conv_fwd_seg: the rings of many live streams).  ``dev``: the same values already on the
+    device (int32), else they are uploaded here."""
+    __slots__ = ("host", "dev", "T", "table_rows", "ring_rows", "segments")
 
-    def __init__(self, host, T, table_rows, ring_rows=0, device=None, dev=None):
+    def __init__(self, host, T, table_rows, ring_rows=0, device=None, dev=None, segments=0):
         import numpy as np
         host = np.ascontiguousarray(host, dtype=np.int64).reshape(-1)
-        T, table_rows, ring_rows = int(T), int(table_rows), int(ring_rows)
+        T, table_rows, ring_rows, segments = int(T), int(table_rows), int(ring_rows), int(segments)
+        if segments < 0 or (segments and (ring_rows < T or table_rows != segments * ring_rows)):
+            raise ValueError(f"WindowRows: segments={segments} needs ring_rows={ring_rows} >= T={T} and table_rows="
+                             f"{table_rows} == segments * ring_rows")
         if ring_rows and not T <= ring_rows <= table_rows:
             raise ValueError(f"WindowRows: ring_rows={ring_rows} must lie in [T={T}, table_rows={table_rows}]")
         if host.size:
             lo, hi = int(host.min()), int(host.max())
-            if lo < 0 or (hi >= ring_rows if ring_rows else hi + T > table_rows):
+            if lo < 0 or (hi >= table_rows if segments else hi >= ring_rows if ring_rows else hi + T > table_rows):
                 raise ValueError(f"WindowRows: window starts {lo}..{hi} (T={T}) leave the table of {table_rows} rows"
                                  + (f" (ring of {ring_rows})" if ring_rows else ""))
         if dev is None:
@@ -1507,20 +1513,84 @@ class WindowRows:
         elif dev.dtype != torch.int32 or dev.numel() != host.size or not dev.is_cuda or not dev.is_contiguous():
             raise ValueError("WindowRows: dev must be a contiguous int32 device tensor with one entry per window")
         self.host, self.dev, self.T, self.table_rows, self.ring_rows = host, dev, T, table_rows, ring_rows
+        self.segments = segments
 
     def __len__(self):
         return self.host.size
 
     def slice(self, a, b):
-        return WindowRows(self.host[a:b], self.T, self.table_rows, self.ring_rows, dev=self.dev[a:b])
+        return WindowRows(self.host[a:b], self.T, self.table_rows, self.ring_rows, dev=self.dev[a:b], segments=self.segments)
 
     def row_index(self):
         """int64 [B*T] device: the table row of every (window, step), for the one-gather fallback"""
         t = torch.arange(self.T, device=self.dev.device, dtype=torch.int64)
-        idx = self.dev.to(torch.int64)[:, None] + t[None, :]
+        start = self.dev.to(torch.int64)[:, None]
+        if self.segments:
+            base = torch.div(start, self.ring_rows, rounding_mode="floor") * self.ring_rows
+            idx = base + (start - base + t[None, :]) % self.ring_rows
+            return idx.reshape(-1).contiguous()
+        idx = start + t[None, :]
         if self.ring_rows:
             idx = idx % self.ring_rows
         return idx.reshape(-1).contiguous()
+
+
+def scatter_rows(src, dst_row, dst, err_flag=None):
+    """dst[dst_row[r]] = src[r] along dim 0, one launch (pcaa_scatter_rows): ``dst_row`` int32 [n] on the device, negative =
+    skip the row, >= dst.shape[0] = skip it and set ``err_flag`` (int32 [1]).  Duplicate destinations are the caller's
+    error.  Rows of whole 32-bit words; 16-byte copies where the row size and the alignment allow."""
+    for t, name in ((src, "src"), (dst, "dst")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dim() == 2):
+            raise RuntimeError(f"scatter_rows: {name} must be a contiguous 2-D tensor on the HIP device (this package has no "
+                               "CPU path)")
+    _chk(dst_row, "scatter_rows.dst_row", torch.int32, 1)
+    if src.dtype != dst.dtype or src.shape[1] != dst.shape[1]:
+        raise ValueError(f"scatter_rows: rows of src {tuple(src.shape)} {src.dtype} and dst {tuple(dst.shape)} {dst.dtype} differ")
+    row_bytes = src.shape[1] * src.element_size()
+    if row_bytes % 4 or row_bytes == 0:
+        raise ValueError(f"scatter_rows: rows of {row_bytes} bytes are not a multiple of 4")
+    n = dst_row.numel()
+    if n > src.shape[0]:
+        raise ValueError(f"scatter_rows: {n} destinations for {src.shape[0]} source rows")
+    if err_flag is not None:
+        _chk(err_flag, "scatter_rows.err_flag", torch.int32)
+    if n and dst.shape[0]:
+        check(_lib.load().pcaa_scatter_rows(_p(src), _p(dst_row), n, row_bytes // 4, _p(dst), dst.shape[0], _p(err_flag),
+                                            _s()), "pcaa_scatter_rows")
+    return dst
+
+
+def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
+                 n_classes, hist_lik, hist_pred):
+    """One tick of many live streams in one launch (pcaa_stream_score) -> (preds [nw] int64, lik [nw] f64, votes [n_votes]
+    int64).  ``run_start`` [n_runs + 1], ``win_stream`` / ``win_j`` / ``vote_pos`` [nw]: int32 on the device, from
+    ``inference.plan_tick`` (a stream's windows are one contiguous ascending run).  ``hist_lik`` f64 / ``hist_pred`` int64
+    [max_streams, k]: the streams' incomplete vote groups, read and updated in place."""
+    _chk(logits, "stream_score.logits", torch.float32, 2)
+    _chk(sup_fv, "stream_score.sup_fv", torch.float32, 2)
+    _chk(means, "stream_score.means", torch.float32, 2)
+    _chk(hist_lik, "stream_score.hist_lik", torch.float64, 2)
+    _chk(hist_pred, "stream_score.hist_pred", torch.int64, 2)
+    for t, name in ((run_start, "run_start"), (win_stream, "win_stream"), (win_j, "win_j"), (vote_pos, "vote_pos")):
+        _chk(t, "stream_score." + name, torch.int32, 1)
+    nw, K = logits.shape
+    D = sup_fv.shape[1]
+    k, n_votes, n_runs = int(k), int(n_votes), run_start.numel() - 1
+    if (sup_fv.shape[0] != nw or means.shape[1] != D or win_stream.numel() != nw or win_j.numel() != nw
+            or vote_pos.numel() != nw or k < 1 or tuple(hist_lik.shape) != tuple(hist_pred.shape)
+            or hist_lik.shape[1] != k or not 0 <= n_votes <= nw or not (1 <= n_runs <= nw or nw == 0)):
+        raise ValueError("stream_score: shapes do not describe one tick")
+    dev = logits.device
+    preds = torch.empty(nw, dtype=torch.int64, device=dev)
+    lik = torch.empty(nw, dtype=torch.float64, device=dev)
+    votes = torch.empty(n_votes, dtype=torch.int64, device=dev)
+    if nw:
+        check(_lib.load().pcaa_stream_score(
+            _p(logits), _p(sup_fv), _p(means), _p(run_start), n_runs, _p(win_stream), _p(win_j), _p(vote_pos), nw, K, D,
+            means.shape[0], ctypes.c_double(float(threshold)), k, int(n_labels), int(n_classes), _p(hist_lik),
+            _p(hist_pred), hist_lik.shape[0], _p(preds), _p(lik), _p(votes) if n_votes else None, n_votes, _s()),
+            "pcaa_stream_score")
+    return preds, lik, votes
 
 
 def dtc_im2col(a, B, T, Cin, d):
@@ -1842,7 +1912,8 @@ def dtc_conv_supported(T, cin, cout):
 def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=False, tail=None, bf16=False, win_row=None):
     """One DilTempConv1d layer forward in one launch (see pcaa_dtc_conv_fwd): returns (y, col or None).
     ``win_row`` (a WindowRows of B windows): ``src`` is a frame-feature table [table_rows, cin] and sequence b reads its T
-    rows from win_row[b] on (pcaa_dtc_conv_fwd_win; eval form: no statistics, no im2col)."""
+    rows from win_row[b] on (pcaa_dtc_conv_fwd_win, or pcaa_dtc_conv_fwd_seg for segmented rings; eval form: no
+    statistics, no im2col)."""
     _chk(src, "dtc_conv_fwd.src", torch.float32, 2)
     _chk(W2d, "dtc_conv_fwd.W", torch.float32, 2)
     rows, cin = src.shape
@@ -1872,11 +1943,18 @@ def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=Fa
     lib = _lib.load()
     fwd = lib.pcaa_dtc_conv_fwd_bf16 if bf16 else lib.pcaa_dtc_conv_fwd       # bf16: the throughput mode's MFMA variant
     if win_row is not None:
-        win = lib.pcaa_dtc_conv_fwd_win_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_win
-        wargs = (_p(win_row.dev), win_row.table_rows, win_row.ring_rows)
+        if win_row.segments:
+            seg = lib.pcaa_dtc_conv_fwd_seg_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_seg
+            sargs = (_p(win_row.dev), win_row.segments, win_row.ring_rows)
 
-        def fwd(*args):        # same arguments, the window description before the stream
-            return win(*args[:-1], *wargs, args[-1])
+            def fwd(*args):    # (src, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dil, ksplit, stride, stream)
+                return seg(*args[:5], *args[8:15], *sargs, args[15])
+        else:
+            win = lib.pcaa_dtc_conv_fwd_win_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_win
+            wargs = (_p(win_row.dev), win_row.table_rows, win_row.ring_rows)
+
+            def fwd(*args):        # same arguments, the window description before the stream
+                return win(*args[:-1], *wargs, args[-1])
     ksplit = lib.pcaa_dtc_conv_ksplit(B, cin, cout)
     if ksplit > 1:
         stride = rows * cout
