@@ -53,10 +53,14 @@ def mark(name):
         _MARKS.append((name, ev))
 
 
-def set_precision(mode: str):
+def _check_precision(mode):
     if mode not in ("fp32", "bf16", "fp16x3"):
         raise ValueError("precision must be 'fp32', 'bf16' or 'fp16x3'")
-    _PRECISION["mode"] = mode
+    return mode
+
+
+def set_precision(mode: str):
+    _PRECISION["mode"] = _check_precision(mode)
 
 
 def get_precision() -> str:
@@ -135,9 +139,20 @@ def _point_major(x):
 class _LayerSave:
     __slots__ = ("a_in", "col", "y", "scale", "shift", "mean", "rstd", "rows", "cin", "cout", "dil", "pool_e", "mom")
 
-    def __init__(self):
-        self.pool_e = None
-        self.mom = None
+    def __init__(self, a_in, col, y, scale, shift, mean, rstd, rows, cin, cout, dil, pool_e=None, mom=None):
+        self.a_in = a_in             # (one plain store per slot: ten of these are built in every forward)
+        self.col = col
+        self.y = y
+        self.scale = scale
+        self.shift = shift
+        self.mean = mean
+        self.rstd = rstd
+        self.rows = rows
+        self.cin = cin
+        self.cout = cout
+        self.dil = dil
+        self.pool_e = pool_e
+        self.mom = mom
 
 
 class EncoderEvalConstants:
@@ -161,9 +176,7 @@ def encoder_eval_constants(enc, mode=None):
     """-> EncoderEvalConstants of ``enc`` for ``mode`` (default: the current precision mode): ten pcaa_bn_eval_coeffs launches
     and, in bf16 mode, three weight casts, once instead of in every eval forward (``consts=`` of encoder_frame_features /
     encoder_forward_windows)."""
-    mode = get_precision() if mode is None else mode
-    if mode not in ("fp32", "bf16", "fp16x3"):
-        raise ValueError("precision must be 'fp32', 'bf16' or 'fp16x3'")
+    mode = get_precision() if mode is None else _check_precision(mode)
     if enc.training:
         raise RuntimeError("encoder_eval_constants: the encoder is in training mode (its BatchNorm uses batch statistics)")
     c = EncoderEvalConstants()
@@ -287,11 +300,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
                 scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
                 mean = rstd = None
                 count = rows
-            s = _LayerSave()
-            s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, None, scale, shift, mean, rstd
-            s.rows, s.cin, s.cout, s.dil = count, cin, cout, 0
-            s.mom = mom
-            saves.append(s)
+            saves.append(_LayerSave(a, None, None, scale, shift, mean, rstd, count, cin, cout, 0, mom=mom))
             a = ops.pointnet_in_apply(a, W2d, scale, shift, torch.bfloat16 if mode == "bf16" else
                                       (ops.SplitImage.dtype if split else torch.float32))
             continue
@@ -304,18 +313,13 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
             scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
             w16 = _eval_w16(consts, conv, W2d)
             a_next = ops.gemm_affine_elu(a, w16, scale, shift, pool_rows if last_pool else 0)
-            s = _LayerSave()
-            s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, None, scale, shift, None, None
-            s.rows, s.cin, s.cout, s.dil = a.shape[0], cin, cout, 0
-            saves.append(s)
+            saves.append(_LayerSave(a, None, None, scale, shift, None, None, a.shape[0], cin, cout, 0))
             if last_pool:
                 return a_next, saves
             a = a_next
             continue
         y, scale, shift, mean, rstd, count = _linear_bn(a, W2d, conv.bias, bn, training, mode, True, consts, conv)
-        s = _LayerSave()
-        s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, y, scale, shift, mean, rstd
-        s.rows, s.cin, s.cout, s.dil = count, cin, cout, 0
+        s = _LayerSave(a, None, y, scale, shift, mean, rstd, count, cin, cout, 0)
         saves.append(s)
         if li == nl - 1 and pool_rows:
             if training:
@@ -679,9 +683,7 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
             y, scale, shift, mean, rstd, count = _linear_bn(col, W2d, conv.bias, bn, training, "fp32", None,
                                                             consts if not training else None)
             a_in = a
-        s = _LayerSave()
-        s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a_in, col, y, scale, shift, mean, rstd
-        s.rows, s.cin, s.cout, s.dil = count, cin, cout, layer.dilation
+        s = _LayerSave(a_in, col, y, scale, shift, mean, rstd, count, cin, cout, layer.dilation)
         saves.append(s)
         if li == nl - 1 and pool_time:
             if training:
@@ -929,6 +931,16 @@ def _heads_fusable(enc, gph, B, backward):
         (lh is None or lh.weight.shape[1] == l1.weight.shape[0])
 
 
+def _check_encoder_input(enc, C, N):
+    """C features per point and N points per frame are the ones ``enc`` was built for"""
+    cin = enc.pc_block.pointnet1.module[0].weight.shape[1]
+    if C != cin:
+        raise RuntimeError(f"CGEncoder: input has {C} features, first layer expects {cin}")
+    if N != enc.nmax_points:
+        raise RuntimeError(f"CGEncoder: N={N} points but nmax_points={enc.nmax_points} "
+                           "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
+
+
 def encoder_forward(enc, x, training, mode=None, gph=None):
     """``gph``: optional decoder projection head ``Sequential(Linear(32,64), ELU)`` evaluated in the
     same launch as the MLP heads (``st.hproj``)."""
@@ -937,12 +949,7 @@ def encoder_forward(enc, x, training, mode=None, gph=None):
     if x.dim() != 4:
         raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(x.shape)}")
     B, C, T, N = x.shape
-    l1 = enc.pc_block.pointnet1.module[0]
-    if C != l1.weight.shape[1]:
-        raise RuntimeError(f"CGEncoder: input has {C} features, first layer expects {l1.weight.shape[1]}")
-    if N != enc.nmax_points:
-        raise RuntimeError(f"CGEncoder: N={N} points but nmax_points={enc.nmax_points} "
-                           "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
+    _check_encoder_input(enc, C, N)
     st = EncoderState()
     st.B, st.C, st.T, st.N, st.mode, st.training = B, C, T, N, mode, training
     xp = _point_major(x).view(B * T * N, C)
@@ -997,12 +1004,7 @@ def encoder_frame_features(enc, frames, mode=None, consts=None):
     if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
         raise ValueError(f"encoder_frame_features expects contiguous fp32 [U,N,C], got {tuple(frames.shape)} {frames.dtype}")
     U, N, C = frames.shape
-    l1 = enc.pc_block.pointnet1.module[0]
-    if C != l1.weight.shape[1]:
-        raise RuntimeError(f"CGEncoder: input has {C} features, first layer expects {l1.weight.shape[1]}")
-    if N != enc.nmax_points:
-        raise RuntimeError(f"CGEncoder: N={N} points but nmax_points={enc.nmax_points} "
-                           "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
+    _check_encoder_input(enc, C, N)
     return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N, consts=consts)
 
 
@@ -1491,10 +1493,7 @@ class _GmlFn(torch.autograd.Function):
         for lin_i, bn_i in ((0, 1), (3, 4), (6, 7)):
             lin, bn = m[lin_i], m[bn_i]
             y, scale, shift, mean, rstd, count = _linear_bn(a, lin.weight, lin.bias, bn, gml.training, "fp32", None)
-            s = _LayerSave()
-            s.a_in, s.col, s.y, s.scale, s.shift, s.mean, s.rstd = a, None, y, scale, shift, mean, rstd
-            s.rows, s.cin, s.cout, s.dil = count, lin.weight.shape[1], lin.weight.shape[0], 0
-            saves.append(s)
+            saves.append(_LayerSave(a, None, y, scale, shift, mean, rstd, count, lin.weight.shape[1], lin.weight.shape[0], 0))
             a = ops.bn_act_fwd(y, scale, shift)
         out = linear_act_forward(a, m[9], ACT_NONE)
         ctx.gml, ctx.saves, ctx.a_last, ctx.training = gml, saves, a, gml.training

@@ -104,6 +104,20 @@ def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
     return first_t + within, win_row
 
 
+def _check_frames(frames, who):
+    """what every entry point that takes frames refuses: a host tensor, anything but contiguous fp32 [n,N,C]"""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise RuntimeError(f"{who}: frames must live on the HIP device; this package has no CPU path")
+    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
+        raise ValueError(f"{who} expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
+
+
+def _empty_triple(D, dev):
+    """(preds, sup_fv, likelihood) of no window at all"""
+    return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
+            torch.empty(0, dtype=torch.float64, device=dev))
+
+
 class OpenSetScorer:
     """Encoder + centroids -> predictions, likelihoods, threshold, k-window votes."""
 
@@ -123,9 +137,13 @@ class OpenSetScorer:
         share bit for bit once (``_embed_dedup``); same triple, same order, one entry per crop."""
         if dedup_frames:
             return self._embed_dedup(pcs, hop)
+        return self._score(F_hip.encoder_forward(self.encoder, pcs[i:i + self.batch_size], False)[:2]
+                           for i in range(0, pcs.shape[0], self.batch_size))
+
+    def _score(self, batches):
+        """(logits, sup_fv) of one batch after the other -> the triple ``embed`` returns"""
         preds, fvs = [], []
-        for i in range(0, pcs.shape[0], self.batch_size):
-            logits, sup_fv, _ = F_hip.encoder_forward(self.encoder, pcs[i:i + self.batch_size], False)
+        for logits, sup_fv in batches:
             _, _, p = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
             preds.append(p)
             fvs.append(sup_fv)
@@ -159,14 +177,8 @@ class OpenSetScorer:
 
     def _score_windows(self, table, plan, T):
         """windows of a frame-feature table, ``batch_size`` at a time -> the triple ``embed`` returns"""
-        preds, fvs = [], []
-        for i in range(0, len(plan), self.batch_size):
-            logits, sup_fv, _ = F_hip.encoder_forward_windows(self.encoder, table, plan.slice(i, i + self.batch_size), T)
-            _, _, p = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
-            preds.append(p)
-            fvs.append(sup_fv)
-        preds, fvs = torch.cat(preds), torch.cat(fvs)
-        return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
+        return self._score(F_hip.encoder_forward_windows(self.encoder, table, plan.slice(i, i + self.batch_size), T)[:2]
+                           for i in range(0, len(plan), self.batch_size))
 
     @torch.no_grad()
     def embed_track(self, track: torch.Tensor, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True):
@@ -174,19 +186,14 @@ class OpenSetScorer:
         for its ``window_count(F)`` windows of NSTEPS frames, as if ``embed`` had been called on the reference's crops
         of it -- every frame encoded once, no crop ever written out.  ``drop_last_aligned=False`` also takes the
         aligned last window the reference's rule drops when ``(F - NSTEPS) % hop == 0``."""
-        if not isinstance(track, torch.Tensor) or not track.is_cuda:
-            raise RuntimeError("embed_track: the track must live on the HIP device; this package has no CPU path")
-        if track.dim() != 3 or track.dtype != torch.float32 or not track.is_contiguous():
-            raise ValueError(f"embed_track expects contiguous fp32 [F,N,C], got {tuple(track.shape)} {track.dtype}")
+        _check_frames(track, "embed_track")
         F, N, C = track.shape
         T, hop = constants.NSTEPS, int(hop)
         W = window_count(F, T, hop) if drop_last_aligned else (0 if F < T else (F - T) // hop + 1)
         dev = track.device
         if W == 0:
             self.last_frames_encoded = 0
-            D = self.encoder.MLP_sup1[0].weight.shape[0]
-            return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
-                    torch.empty(0, dtype=torch.float64, device=dev))
+            return _empty_triple(self.encoder.MLP_sup1[0].weight.shape[0], dev)
         U = (W - 1) * hop + T                                              # frames any window uses
         q = F_hip.frame_pad_quantum(N)
         step = max(self.batch_size * T // q, 1) * q
@@ -276,14 +283,32 @@ def naive_sequential_procedure(k, encoder, discriminator_means, *args, **kwargs)
     return naive_sequential_procedure_tensors(k, encoder, discriminator_means, *args, **kwargs)
 
 
+def _metrics(k, preds, labels):
+    """the ``naive_seq_log_{k}*.json`` record: accuracy and F1 micro / macro / weighted of the open-set votes"""
+    from sklearn.metrics import f1_score
+    return {"n_steps": k, "accuracy": float(np.equal(labels, preds).sum() / max(len(labels), 1)),
+            "f1_micro": float(f1_score(labels, preds, average="micro")),
+            "f1_macro": float(f1_score(labels, preds, average="macro")),
+            "f1_weighted": float(f1_score(labels, preds, average="weighted"))}
+
+
+def _file_suffix(force_pc_subsampling, scenarios_list):
+    """what the reference appends to its output file names: ``_subsampled{n}`` or ``_scenarios...`` when ONE of the two
+    differs from its default, nothing when neither does; None when both do (the reference has no name for that)"""
+    default_scen = list(scenarios_list) == list(constants.TRAIN_SCENARIOS)
+    if force_pc_subsampling and not default_scen:
+        return None
+    if force_pc_subsampling:
+        return f"_subsampled{force_pc_subsampling}"
+    return "" if default_scen else "_scenarios" + "_".join(sc.value for sc in scenarios_list)
+
+
 def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_folder, model_folder,
                                       scenarios_list=None, seed=0, unseen_valid_ratio=0.2, force_pc_subsampling=0,
                                       dedup_frames=False):
     import json
-    from sklearn.metrics import f1_score
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    default_scen = list(scenarios_list) == list(constants.TRAIN_SCENARIOS)
     dev = next(encoder.parameters()).device
     os.makedirs(figures_folder, exist_ok=True)
     known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
@@ -292,16 +317,8 @@ def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_f
                                                           unseen_labels, seed=seed, unseen_valid_ratio=unseen_valid_ratio,
                                                           dedup_frames=dedup_frames)
     labels = labels.astype(int)
-    out_log = {"n_steps": k, "accuracy": float(np.equal(labels, preds).sum() / max(len(labels), 1)),
-               "f1_micro": float(f1_score(labels, preds, average="micro")),
-               "f1_macro": float(f1_score(labels, preds, average="macro")),
-               "f1_weighted": float(f1_score(labels, preds, average="weighted"))}
-    if force_pc_subsampling and default_scen:
-        name = f"naive_seq_log_{k}_subsampled{force_pc_subsampling}.json"
-    elif not force_pc_subsampling and not default_scen:
-        name = f"naive_seq_log_{k}_scenarios" + "_".join(sc.value for sc in scenarios_list) + ".json"
-    else:
-        name = f"naive_seq_log_{k}.json"
+    out_log = _metrics(k, preds, labels)
+    name = f"naive_seq_log_{k}{_file_suffix(force_pc_subsampling, scenarios_list) or ''}.json"    # both given: the plain name
     with open(os.path.join(model_folder, name), "w") as f:
         json.dump(out_log, f)
     return out_log, preds, labels
@@ -369,19 +386,12 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
     call (the reference regenerates them for every (model, k) with identical arguments).  ``dedup_frames`` (opt-in):
     every frame that consecutive crops of the sequential splits share is encoded once."""
     import json
-    from sklearn.metrics import f1_score
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    default_scen = list(scenarios_list) == list(constants.TRAIN_SCENARIOS)
-    if force_pc_subsampling and not default_scen:
+    suffix = _file_suffix(force_pc_subsampling, scenarios_list)
+    if suffix is None:
         raise ValueError("force_pc_subsampling and scenarios_list cannot be both different from default")
     dev = torch.device(device or constants.DEVICE)
-    if force_pc_subsampling and default_scen:
-        suffix = f"_subsampled{force_pc_subsampling}"
-    elif not force_pc_subsampling and not default_scen:
-        suffix = "_scenarios" + "_".join(sc.value for sc in scenarios_list)
-    else:
-        suffix = ""
     out_log = {}
     generated = not generate_dataset
     for model_name in model_names:
@@ -397,10 +407,7 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
                                                             unseen_labels, seed=0, unseen_valid_ratio=0.2,
                                                             dedup_frames=dedup_frames)
             labels = labels.astype(int)
-            metrics = {"n_steps": k, "accuracy": float(np.equal(labels, preds).sum() / max(len(labels), 1)),
-                       "f1_micro": float(f1_score(labels, preds, average="micro")),
-                       "f1_macro": float(f1_score(labels, preds, average="macro")),
-                       "f1_weighted": float(f1_score(labels, preds, average="weighted"))}
+            metrics = _metrics(k, preds, labels)
             with open(os.path.join(folder, f"naive_seq_log_{k}{suffix}.json"), "w") as f:
                 json.dump(metrics, f)
             np.save(os.path.join(folder, f"final_preds_{k}{suffix}.npy"), preds)
@@ -411,8 +418,35 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
     return out_log
 
 
+class _LiveScorer:
+    """What the two live scorers are built from: the window rule's arguments checked, the ring sized
+    (``ring_rows >= NSTEPS + max_push``), the centroids on the encoder's device, the encoder's widths."""
 
-class StreamingScorer:
+    def __init__(self, encoder, means, threshold, k, n_labels, hop, max_push, ring_rows):
+        self.encoder = encoder
+        self._check_eval()
+        who = type(self).__name__
+        self.T, self.hop, self.k, self.n_labels = constants.NSTEPS, int(hop), int(k), int(n_labels)
+        self.threshold, self.max_push = float(threshold), int(max_push)
+        if not 1 <= self.hop <= self.T or self.max_push < 1 or self.k < 1:
+            raise ValueError(f"{who}: needs 1 <= hop <= NSTEPS, max_push >= 1, k >= 1")
+        need = self.T + self.max_push
+        self.ring_rows = need if ring_rows is None else int(ring_rows)
+        if self.ring_rows < need:
+            raise ValueError(f"{who}: ring_rows={self.ring_rows} < NSTEPS + max_push = {need}")
+        self.means = means.float().to(next(encoder.parameters()).device).contiguous()
+        self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
+        self._D = encoder.MLP_sup1[0].weight.shape[0]                          # embedding width
+        self._width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]      # frame-feature width: a ring row
+        self.last_pointnet_saves = None
+
+    def _check_eval(self):
+        if self.encoder.training:
+            raise RuntimeError(f"{type(self).__name__}: the encoder is in training mode (train-mode BatchNorm mixes the "
+                               "frames of a batch: a frame's features would depend on its neighbours); call encoder.eval()")
+
+
+class StreamingScorer(_LiveScorer):
     """Open-set scoring of a live track: frames arrive a few at a time, a decision is due every ``hop`` frames.
 
     A device ring keeps the PointNet features of the last ``ring_rows >= NSTEPS + max_push`` frames.  ``push`` encodes the
@@ -430,34 +464,16 @@ class StreamingScorer:
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None):
-        self.encoder = encoder
-        self._check_eval()
-        self.T, self.hop, self.k, self.n_labels = constants.NSTEPS, int(hop), int(k), int(n_labels)
-        self.threshold, self.max_push = float(threshold), int(max_push)
-        if not 1 <= self.hop <= self.T or self.max_push < 1 or self.k < 1:
-            raise ValueError("StreamingScorer: needs 1 <= hop <= NSTEPS, max_push >= 1, k >= 1")
-        need = self.T + self.max_push
-        self.ring_rows = need if ring_rows is None else int(ring_rows)
-        if self.ring_rows < need:
-            raise ValueError(f"StreamingScorer: ring_rows={self.ring_rows} < NSTEPS + max_push = {need}")
-        dev = next(encoder.parameters()).device
-        self.means = means.float().to(dev).contiguous()
-        self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
-        width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]
-        self.ring = torch.zeros((self.ring_rows, width), dtype=torch.float32, device=dev)
+        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
+        dev = self.means.device
+        self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
         # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
         # once, long enough that the windows of any one push are a contiguous slice of it (no upload per push)
         self._period = self.ring_rows // np.gcd(self.ring_rows, self.hop)
         self._max_win = self.max_push // self.hop + 1
         self._starts = (np.arange(self._period + self._max_win, dtype=np.int64) * self.hop) % self.ring_rows
         self._starts_dev = torch.from_numpy(self._starts.astype(np.int32)).to(dev)
-        self.last_pointnet_saves = None
         self.reset()
-
-    def _check_eval(self):
-        if self.encoder.training:
-            raise RuntimeError("StreamingScorer: the encoder is in training mode (train-mode BatchNorm mixes the frames of "
-                               "a batch: a frame's features would depend on its neighbours); call encoder.eval()")
 
     def reset(self):
         """forget the track: the next pushed frame is frame 0 of a new one"""
@@ -470,17 +486,11 @@ class StreamingScorer:
         """frames [n,N,C] fp32 on the device, the next n frames of the track -> (preds, sup_fv, likelihood) of the windows
         they complete (possibly none: empty tensors)."""
         self._check_eval()
-        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-            raise RuntimeError("StreamingScorer.push: frames must live on the HIP device; this package has no CPU path")
-        if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
-            raise ValueError(f"StreamingScorer.push expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
+        _check_frames(frames, "StreamingScorer.push")
         out = [self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)]
         out = [o for o in out if o is not None]
-        dev = self.ring.device
         if not out:
-            D = self.encoder.MLP_sup1[0].weight.shape[0]
-            return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
-                    torch.empty(0, dtype=torch.float64, device=dev))
+            return _empty_triple(self._D, self.ring.device)
         if len(out) == 1:
             return out[0]
         return tuple(torch.cat([o[i] for o in out]) for i in range(3))
@@ -620,7 +630,27 @@ class Tick:
         return self.stream.size
 
 
-class MultiStreamScorer:
+def _tick(plan, preds, sup_fv, lik, votes):
+    """a Tick: which windows and votes they are from the plan, what they scored from the device"""
+    t = Tick()
+    t.stream, t.window = plan.win_stream.astype(np.int64), plan.win_j.astype(np.int64)
+    t.vote_stream, t.vote_group = plan.vote_stream, plan.vote_group
+    t.preds, t.sup_fv, t.lik, t.votes = preds, sup_fv, lik, votes
+    return t
+
+
+def _host_ints(x):
+    """a 1-D sequence of host ints -> int64 array; None for anything else"""
+    try:
+        arr = np.asarray(x)
+    except (TypeError, ValueError):
+        return None
+    if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+        return None
+    return arr.astype(np.int64)
+
+
+class MultiStreamScorer(_LiveScorer):
     """Open-set scoring of up to ``max_streams`` live tracks in one batched tick.
 
     Every slot owns a ring of ``ring_rows >= NSTEPS + max_push`` rows in one ``[max_streams * ring_rows, 1024]`` feature
@@ -636,27 +666,14 @@ class MultiStreamScorer:
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
                  batch_size: int = 1024):
-        self.encoder = encoder
-        self._check_eval()
-        self.T, self.hop, self.k, self.n_labels = constants.NSTEPS, int(hop), int(k), int(n_labels)
-        self.threshold, self.max_push, self.max_streams = float(threshold), int(max_push), int(max_streams)
-        self.batch_size = int(batch_size)
-        if (not 1 <= self.hop <= self.T or self.max_push < 1 or self.k < 1 or self.max_streams < 1
-                or self.batch_size < 1):
-            raise ValueError("MultiStreamScorer: needs 1 <= hop <= NSTEPS, max_push >= 1, k >= 1, max_streams >= 1, "
-                             "batch_size >= 1")
-        need = self.T + self.max_push
-        self.ring_rows = need if ring_rows is None else int(ring_rows)
-        if self.ring_rows < need:
-            raise ValueError(f"MultiStreamScorer: ring_rows={self.ring_rows} < NSTEPS + max_push = {need}")
-        dev = next(encoder.parameters()).device
+        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
+        self.max_streams, self.batch_size = int(max_streams), int(batch_size)
+        if self.max_streams < 1 or self.batch_size < 1:
+            raise ValueError("MultiStreamScorer: needs max_streams >= 1, batch_size >= 1")
+        dev = self.means.device
         if dev.type != "cuda":
             raise RuntimeError("MultiStreamScorer: the encoder must live on the HIP device; this package has no CPU path")
-        self.means = means.float().to(dev).contiguous()
-        self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
-        self._D = encoder.MLP_sup1[0].weight.shape[0]
-        width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]
-        self.ring = torch.zeros((self.max_streams * self.ring_rows, width), dtype=torch.float32, device=dev)
+        self.ring = torch.zeros((self.max_streams * self.ring_rows, self._width), dtype=torch.float32, device=dev)
         self.hist_lik = torch.zeros((self.max_streams, self.k), dtype=torch.float64, device=dev)
         self.hist_pred = torch.zeros((self.max_streams, self.k), dtype=torch.int64, device=dev)
         self.scatter_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a scatter destination out of range
@@ -665,12 +682,6 @@ class MultiStreamScorer:
         self._open = np.zeros(self.max_streams, bool)
         self._consts = None
         self._zeros = None
-        self.last_pointnet_saves = None
-
-    def _check_eval(self):
-        if self.encoder.training:
-            raise RuntimeError("MultiStreamScorer: the encoder is in training mode (train-mode BatchNorm mixes the frames "
-                               "of a batch: a frame's features would depend on its neighbours); call encoder.eval()")
 
     def open(self) -> int:
         """-> the lowest free slot; its frame and window counters start at 0 (its ring rows are not cleared: a window only
@@ -689,27 +700,15 @@ class MultiStreamScorer:
         self._open[int(sid)] = False
 
     def _slots(self, sids, what):
-        try:
-            arr = np.asarray(sids)
-            ok = arr.ndim == 1 and (arr.size == 0 or arr.dtype.kind in "iu")
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
+        arr = _host_ints(sids)
+        if arr is None:
             raise ValueError(f"MultiStreamScorer.{what}: stream ids must be a 1-D sequence of host ints")
-        arr = arr.astype(np.int64)
         if arr.size and (arr.min() < 0 or arr.max() >= self.max_streams or not self._open[arr].all()):
             raise ValueError(f"MultiStreamScorer.{what}: unknown or closed stream id in {arr.tolist()}")
         return arr
 
     def _empty(self, plan, dev):
-        t = Tick()
-        t.stream, t.window = plan.win_stream.astype(np.int64), plan.win_j.astype(np.int64)
-        t.vote_stream, t.vote_group = plan.vote_stream, plan.vote_group
-        t.preds = torch.empty(0, dtype=torch.int64, device=dev)
-        t.sup_fv = torch.empty((0, self._D), dtype=torch.float32, device=dev)
-        t.lik = torch.empty(0, dtype=torch.float64, device=dev)
-        t.votes = torch.empty(0, dtype=torch.int64, device=dev)
-        return t
+        return _tick(plan, *_empty_triple(self._D, dev), torch.empty(0, dtype=torch.int64, device=dev))
 
     @torch.no_grad()
     def push(self, sids, counts, frames: torch.Tensor) -> Tick:
@@ -717,19 +716,11 @@ class MultiStreamScorer:
         ``max_push``); ``frames`` [sum(counts), N, C] fp32 on the device, concatenated in that order -> the Tick of the
         windows these frames complete (possibly none: empty tensors, no temporal pass)."""
         self._check_eval()
-        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-            raise RuntimeError("MultiStreamScorer.push: frames must live on the HIP device; this package has no CPU path")
-        if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
-            raise ValueError(f"MultiStreamScorer.push expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
+        _check_frames(frames, "MultiStreamScorer.push")
         sids = self._slots(sids, "push")
-        try:
-            counts = np.asarray(counts)
-            ok = counts.ndim == 1 and (counts.size == 0 or counts.dtype.kind in "iu")
-        except (TypeError, ValueError):
-            ok = False
-        if not ok or counts.size != sids.size:
+        counts = _host_ints(counts)
+        if counts is None or counts.size != sids.size:
             raise ValueError("MultiStreamScorer.push: counts must be host ints, one per stream id")
-        counts = counts.astype(np.int64)
         if counts.size and (counts.min() < 0 or counts.max() > self.max_push):
             raise ValueError(f"MultiStreamScorer.push: counts must lie in 0..max_push = {self.max_push}")
         if int(counts.sum()) != frames.shape[0]:
@@ -770,11 +761,7 @@ class MultiStreamScorer:
             fvs.append(fv)
         logits = logits[0] if len(logits) == 1 else torch.cat(logits)
         sup_fv = (fvs[0] if len(fvs) == 1 else torch.cat(fvs)).contiguous()
-        t = Tick()
-        t.stream, t.window = plan.win_stream.astype(np.int64), plan.win_j.astype(np.int64)
-        t.vote_stream, t.vote_group = plan.vote_stream, plan.vote_group
-        t.sup_fv = sup_fv
-        t.preds, t.lik, t.votes = ops.stream_score(
+        preds, lik, votes = ops.stream_score(
             logits.contiguous(), sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
             plan.vote_group.size, self.threshold, self.k, self.n_labels, self.n_classes, self.hist_lik, self.hist_pred)
-        return t
+        return _tick(plan, preds, sup_fv, lik, votes)

@@ -1415,47 +1415,38 @@ def pack_points(x):
     return out
 
 
-def gather_rows(src, idx, out=None, err_flag=None):
-    """out[r] = src[idx[r]] along dim 0 (device-side batch assembly; rows must be multiples of 16 bytes)."""
+def _gather(who, unit, src, idx, out, err_flag):
+    """the body of gather_rows (``unit`` = 16 bytes: pcaa_gather_rows takes the row size in bytes) and gather_rows_w4
+    (4 bytes: pcaa_gather_rows_w4 takes it in 32-bit words)"""
     if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() >= 1):
-        raise RuntimeError("gather_rows: src must be a contiguous tensor on the HIP device (this package has no CPU path)")
-    _chk(idx, "gather_rows.idx", torch.int64, 1)
+        raise RuntimeError(f"{who}: src must be a contiguous tensor on the HIP device (this package has no CPU path)")
+    _chk(idx, who + ".idx", torch.int64, 1)
     row_bytes = src[0].numel() * src.element_size() if src.dim() > 1 else src.element_size()
-    if row_bytes % 16:
-        raise ValueError(f"gather_rows: rows of {row_bytes} bytes are not a multiple of 16")
+    if row_bytes % unit or (unit == 4 and row_bytes == 0):
+        raise ValueError(f"{who}: rows of {row_bytes} bytes are not a multiple of {unit}")
     n = idx.numel()
     if out is None:
         out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
     elif out.shape != (n,) + tuple(src.shape[1:]) or out.dtype != src.dtype or not out.is_contiguous():
-        raise ValueError("gather_rows: out does not match")
+        raise ValueError(f"{who}: out does not match")
     if err_flag is not None:
-        _chk(err_flag, "gather_rows.err_flag", torch.int32)
+        _chk(err_flag, who + ".err_flag", torch.int32)
     if n:
-        check(_lib.load().pcaa_gather_rows(_p(src), src.shape[0], row_bytes, _p(idx), _p(out), n, _p(err_flag), _s()),
-              "pcaa_gather_rows")
+        fn = getattr(_lib.load(), "pcaa_" + who)
+        check(fn(_p(src), src.shape[0], row_bytes if unit == 16 else row_bytes // 4, _p(idx), _p(out), n, _p(err_flag), _s()),
+              "pcaa_" + who)
     return out
+
+
+def gather_rows(src, idx, out=None, err_flag=None):
+    """out[r] = src[idx[r]] along dim 0 (device-side batch assembly; rows must be multiples of 16 bytes)."""
+    return _gather("gather_rows", 16, src, idx, out, err_flag)
 
 
 def gather_rows_w4(src, idx, out=None, err_flag=None):
     """``gather_rows`` for rows that are a multiple of 4 bytes only (pcaa_gather_rows_w4: a 3 000-byte frame of N = 150
     points x C = 5 features)."""
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() >= 1):
-        raise RuntimeError("gather_rows_w4: src must be a contiguous tensor on the HIP device (this package has no CPU path)")
-    _chk(idx, "gather_rows_w4.idx", torch.int64, 1)
-    row_bytes = src[0].numel() * src.element_size() if src.dim() > 1 else src.element_size()
-    if row_bytes % 4 or row_bytes == 0:
-        raise ValueError(f"gather_rows_w4: rows of {row_bytes} bytes are not a multiple of 4")
-    n = idx.numel()
-    if out is None:
-        out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-    elif out.shape != (n,) + tuple(src.shape[1:]) or out.dtype != src.dtype or not out.is_contiguous():
-        raise ValueError("gather_rows_w4: out does not match")
-    if err_flag is not None:
-        _chk(err_flag, "gather_rows_w4.err_flag", torch.int32)
-    if n:
-        check(_lib.load().pcaa_gather_rows_w4(_p(src), src.shape[0], row_bytes // 4, _p(idx), _p(out), n, _p(err_flag), _s()),
-              "pcaa_gather_rows_w4")
-    return out
+    return _gather("gather_rows_w4", 4, src, idx, out, err_flag)
 
 
 def gather_frames(src, idx):
@@ -1525,14 +1516,11 @@ class WindowRows:
         """int64 [B*T] device: the table row of every (window, step), for the one-gather fallback"""
         t = torch.arange(self.T, device=self.dev.device, dtype=torch.int64)
         start = self.dev.to(torch.int64)[:, None]
-        if self.segments:
-            base = torch.div(start, self.ring_rows, rounding_mode="floor") * self.ring_rows
-            idx = base + (start - base + t[None, :]) % self.ring_rows
-            return idx.reshape(-1).contiguous()
-        idx = start + t[None, :]
-        if self.ring_rows:
-            idx = idx % self.ring_rows
-        return idx.reshape(-1).contiguous()
+        # one rule: a window wraps inside the ring it starts in (a flat table is one ring that no window leaves, a single
+        # ring is segment 0)
+        ring = self.ring_rows or self.table_rows or 1
+        off = start % ring
+        return (start - off + (off + t[None, :]) % ring).reshape(-1).contiguous()
 
 
 def scatter_rows(src, dst_row, dst, err_flag=None):
@@ -1941,38 +1929,34 @@ def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=Fa
     y = torch.empty((rows, cout), dtype=torch.float32, device=src.device)
     col = torch.empty((rows, cin * 3), dtype=torch.float32, device=src.device) if want_col else None
     lib = _lib.load()
-    fwd = lib.pcaa_dtc_conv_fwd_bf16 if bf16 else lib.pcaa_dtc_conv_fwd       # bf16: the throughput mode's MFMA variant
-    if win_row is not None:
-        if win_row.segments:
-            seg = lib.pcaa_dtc_conv_fwd_seg_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_seg
-            sargs = (_p(win_row.dev), win_row.segments, win_row.ring_rows)
-
-            def fwd(*args):    # (src, scale, shift, W, y, col, stats, nrep, B, T, cin, cout, dil, ksplit, stride, stream)
-                return seg(*args[:5], *args[8:15], *sargs, args[15])
-        else:
-            win = lib.pcaa_dtc_conv_fwd_win_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_win
-            wargs = (_p(win_row.dev), win_row.table_rows, win_row.ring_rows)
-
-            def fwd(*args):        # same arguments, the window description before the stream
-                return win(*args[:-1], *wargs, args[-1])
     ksplit = lib.pcaa_dtc_conv_ksplit(B, cin, cout)
-    if ksplit > 1:
+    if ksplit > 1:                 # split K: the partial products go to slabs, a reduction pass makes y (and the statistics)
         stride = rows * cout
-        slabs = torch.empty(ksplit * stride, dtype=torch.float32, device=src.device)
-        check(fwd(_p(src), _p(scale), _p(shift), _p(W2d), _p(slabs), _p(col), None, NREP,
-                                    B, T, cin, cout, int(dilation), ksplit, stride, _s()), "pcaa_dtc_conv_fwd")
-        if stats is not None:
-            check(lib.pcaa_splitk_reduce_stats(_p(slabs), ksplit, stride, _p(y), _p(stats), NREP, rows, cout, _s()),
-                  "pcaa_splitk_reduce_stats")
-            if tail is not None:
-                tail.resolve(stats)
-        else:
-            check(lib.pcaa_splitk_reduce(_p(slabs), ksplit, stride, stride, _p(y), 0, _s()), "pcaa_splitk_reduce")
-        return y, col
-    if tail is not None and stats is not None:
-        tail.arm(stats)
-    check(fwd(_p(src), _p(scale), _p(shift), _p(W2d), _p(y), _p(col), _p(stats), NREP,
-              B, T, cin, cout, int(dilation), 1, 0, _s()), "pcaa_dtc_conv_fwd")
+        dst = torch.empty(ksplit * stride, dtype=torch.float32, device=src.device)
+        dst_stats, split = None, (ksplit, stride)
+    else:
+        dst, dst_stats, split = y, stats, (1, 0)
+        if tail is not None and stats is not None:
+            tail.arm(stats)
+    operands = (_p(src), _p(scale), _p(shift), _p(W2d), _p(dst))
+    shape = (B, T, cin, cout, int(dilation))
+    # one call per entry point (_bf16: the throughput mode's MFMA variant): plain, windowed, segmented
+    if win_row is None:
+        fwd = lib.pcaa_dtc_conv_fwd_bf16 if bf16 else lib.pcaa_dtc_conv_fwd
+        rc = fwd(*operands, _p(col), _p(dst_stats), NREP, *shape, *split, _s())
+    elif not win_row.segments:
+        fwd = lib.pcaa_dtc_conv_fwd_win_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_win
+        rc = fwd(*operands, _p(col), _p(dst_stats), NREP, *shape, *split,
+                 _p(win_row.dev), win_row.table_rows, win_row.ring_rows, _s())
+    else:                          # eval only: the entry point takes neither col nor statistics
+        fwd = lib.pcaa_dtc_conv_fwd_seg_bf16 if bf16 else lib.pcaa_dtc_conv_fwd_seg
+        rc = fwd(*operands, *shape, *split, _p(win_row.dev), win_row.segments, win_row.ring_rows, _s())
+    check(rc, "pcaa_dtc_conv_fwd")
+    if ksplit > 1 and stats is not None:
+        check(lib.pcaa_splitk_reduce_stats(_p(dst), ksplit, stride, _p(y), _p(stats), NREP, rows, cout, _s()),
+              "pcaa_splitk_reduce_stats")
+    elif ksplit > 1:
+        check(lib.pcaa_splitk_reduce(_p(dst), ksplit, stride, stride, _p(y), 0, _s()), "pcaa_splitk_reduce")
     if tail is not None and stats is not None:
         tail.resolve(stats)
     return y, col
