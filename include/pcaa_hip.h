@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 19 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 20 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -560,6 +560,28 @@ int pcaa_stream_score(const float* logits, const float* sup_fv, const float* mea
                       const int* win_stream, const int* win_j, const int* vote_pos, int nw, int K, int D, int Kc,
                       double threshold, int k, int n_labels, int n_classes, double* hist_lik, long long* hist_pred,
                       int max_streams, long long* preds, double* lik, long long* votes, int n_votes, void* stream);
+
+/* ------------------------------------------------------------------ raw radar detections -> frames (raw_frames.hip)
+ * ABI 20: what datasets.process_track does per frame on the host (reference datasets.py:79-161), for the n frames of a
+ * tick in one launch.  points [P, 5] (x, y, z, doppler, linear power; fp32, or fp64 when points_f64: the reference's
+ * on-disk type), offsets [n + 1]: frame f owns rows offsets[f] .. offsets[f + 1] - 1 (card = the difference).
+ * out [n_out, N, C] fp32, n_out >= n: out[f, p] = the first C columns of the frame's point pick[f, p], the power as
+ * 10 log10(p + 1e-8) (C == 5 only), minus the per-column mean over the frame's N output points when standardize, divided
+ * by (population std + 1e-8) when also divide_by_std; gather, dB, mean and std in fp64 in a fixed order, one rounding to
+ * fp32.  Rows n .. n_out - 1 are written as zeros (whole-tile padding for the bf16 eval GEMM).
+ * pick [n, N] given: used as is (the host-drawn picks of the reference's generator: the parity path).  pick NULL: drawn
+ * on the device from frame_key [n, 2] and seed with the counter-based hash documented in raw_frames.hip (card < N: identity
+ * then (uint64(h(card + d)) * card) >> 32; card >= N: the N smallest of the keys (h(i), i), in key order);
+ * datasets.device_picks_host restates it integer for integer.  pick_out [n, N] (may be NULL): the picks used.
+ * A frame depends on its own detections and picks / key only: not on n, its position in the launch, or the grid.
+ * A frame with card < 1 or card > PCAA_RAW_MAX_CARD, with offsets outside [0, P], or with a supplied pick outside
+ * [0, card) is written as zeros (pick_out: -1) and *err_flag (may be NULL) is set; nothing faults, nothing is checked on
+ * the host.  One workgroup per output frame; 1 <= N <= PCAA_RAW_MAX_POINTS, 1 <= C <= 5. */
+#define PCAA_RAW_MAX_CARD 1024   /* detections of one raw frame */
+#define PCAA_RAW_MAX_POINTS 1024 /* N: points of one processed frame */
+int pcaa_frames_from_raw(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
+                         const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
+                         float* out, int n_out, int* pick_out, int* err_flag, void* stream);
 /* The adjoint w.r.t. the layer input in one launch (replaces dcol = dy . W on the im2col layout followed by
  * pcaa_dtc_col2im): da[(b,t)][ci] = sum_{co,tap} dy[b][t+(2-tap)*d][co] * W[co][ci][tap].
  *  - dy given, or formed on load from this layer's dz, y and the coefficients of pcaa_bn_bwd_finalize

@@ -97,6 +97,118 @@ def process_track(track, standardize_point_cloud=True, divide_by_std=False, forc
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# process_track in two halves -- which raw point goes where (the only part that draws random numbers), and the
+# arithmetic on the picked points -- so that the second half can run on the device (ops.frames_from_raw) with the picks
+# of the first: draw_picks + frames_from_picks == process_track bit for bit.
+
+def draw_picks(cards, nmax, force_pc_subsampling=0):
+    """The picks ``process_track`` makes for frames of the cardinalities ``cards`` -> int32 ``[n, nmax]``: output point p
+    of frame f is raw point ``picks[f, p]`` of that frame.  Same calls to numpy's GLOBAL generator (and to
+    ``default_rng(0)`` for the forced-subsampling quirk) in the same order as ``process_track``: repeat-pad gives
+    ``concat(arange(card), choice(card, nmax - card))``, subsampling ``choice(card, nmax, replace=False)``; with
+    ``force_pc_subsampling`` the indices go through ``keep`` so that they address the frame's ORIGINAL points."""
+    sub_rng = np.random.default_rng(0)
+    cards = np.asarray(cards).reshape(-1)
+    picks = np.empty((cards.size, int(nmax)), dtype=np.int32)
+    for fi, card in enumerate(cards.tolist()):
+        keep = None
+        if 0 < force_pc_subsampling < card:
+            card = force_pc_subsampling
+            keep = sub_rng.choice(card, force_pc_subsampling, replace=False)
+        if card < nmax:
+            idx = np.concatenate([np.arange(card), np.random.choice(card, nmax - card)])
+        else:
+            idx = np.random.choice(card, nmax, replace=False)
+        picks[fi] = idx if keep is None else keep[idx]
+    return picks
+
+
+def _raw_columns(frame):
+    """a raw frame dict -> float64 [card, 5]: x, y, z, doppler, LINEAR power"""
+    return np.concatenate([frame["elements"], frame["z_coord"][:, np.newaxis], frame["dopplers"][:, np.newaxis],
+                           frame["powers"][:, np.newaxis]], axis=1).astype(np.float64, copy=False)
+
+
+def frames_from_picks(raw_frames, picks, nfeatures, divide_by_std=False):
+    """The arithmetic half of ``process_track`` on given picks (``draw_picks``, ``device_picks_host``, or the ``pick_out``
+    of ``ops.frames_from_raw``): powers to dB, the first ``nfeatures`` columns, ``arr[picks[f]]``, per-frame centring
+    (and division by ``std + 1e-8``) -> float64 ``[n, nmax, nfeatures]``."""
+    picks = np.asarray(picks)
+    out = np.empty((len(raw_frames), picks.shape[1], int(nfeatures)), dtype=np.float64)
+    for fi, frame in enumerate(raw_frames):
+        arr = _raw_columns(frame)
+        arr[:, 4] = 10 * np.log10(arr[:, 4] + 1e-8)
+        final = arr[:, :nfeatures][picks[fi], :]
+        mean = final.mean(axis=0)
+        std = final.std(axis=0)
+        final = final - mean
+        if divide_by_std:
+            final = final / (std + 1e-8)
+        out[fi] = final
+    return out
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(x):
+    """the 32-bit mixer of csrc/raw_frames.hip ("lowbias32") on uint64 arrays holding 32-bit values"""
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & _M32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def _absorb32(s, w):
+    return _mix32(((s ^ w) + np.uint64(0x9E3779B9)) & _M32)
+
+
+def device_picks_host(seed, keys, cards, N):
+    """What ``pcaa_frames_from_raw`` draws when it is given no picks, restated in numpy, integer for integer -> int32
+    ``[n, N]``.  ``keys`` int ``[n, 2]``, ``cards`` ``[n]`` (1 <= card), ``seed`` any Python int (its low 64 bits)."""
+    keys = np.asarray(keys).reshape(-1, 2)
+    cards = np.asarray(cards).reshape(-1)
+    N, seed = int(N), int(seed) & 0xFFFFFFFFFFFFFFFF
+    picks = np.empty((cards.size, N), dtype=np.int32)
+    s0 = _absorb32(_absorb32(np.uint64(0x9E3779B9), np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
+    for fi, card in enumerate(cards.tolist()):
+        s = _absorb32(_absorb32(s0, np.uint64(int(keys[fi, 0]) & 0xFFFFFFFF)), np.uint64(int(keys[fi, 1]) & 0xFFFFFFFF))
+        if card < N:
+            h = _absorb32(s, np.arange(card, N, dtype=np.uint64))
+            picks[fi, :card] = np.arange(card)
+            picks[fi, card:] = (h * np.uint64(card)) >> np.uint64(32)
+        else:
+            h = _absorb32(s, np.arange(card, dtype=np.uint64))
+            picks[fi] = np.lexsort((np.arange(card), h))[:N]         # rank by (h, i): the N smallest, in key order
+    return picks
+
+
+def pack_raw_frames(raw_frames, dtype=torch.float32):
+    """A list of raw frame dicts -> ``(points [P, 5] dtype, offsets [n + 1] int32)``: the layout ``ops.frames_from_raw``
+    and the scorers' ``push_raw`` take -- columns x, y, z, doppler, linear power, frame f in rows ``offsets[f] ..
+    offsets[f + 1] - 1``.  Host tensors, pinned where there is a device to copy them to (``.cuda(non_blocking=True)``)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"pack_raw_frames: float32 or float64, got {dtype}")
+    cards = np.array([len(fr["z_coord"]) for fr in raw_frames], dtype=np.int64)
+    total = int(cards.sum())
+    if total >= 2 ** 31:
+        raise ValueError("pack_raw_frames: the offsets do not fit 32 bits")
+    pin = torch.cuda.is_available()
+    points = torch.empty((total, 5), dtype=dtype, pin_memory=pin)
+    offsets = torch.empty(len(raw_frames) + 1, dtype=torch.int32, pin_memory=pin)
+    off = offsets.numpy()
+    off[0] = 0
+    np.cumsum(cards, out=off[1:])
+    if raw_frames:
+        pts = points.numpy()
+        pts[:, :2] = np.concatenate([fr["elements"] for fr in raw_frames])
+        for col, name in ((2, "z_coord"), (3, "dopplers"), (4, "powers")):
+            pts[:, col] = np.concatenate([fr[name] for fr in raw_frames])
+    return points, offsets
+
+
 LABEL_DICT = {i: f"target{i}" for i in range(10)}        # reference datasets.py:51-62
 
 

@@ -112,6 +112,30 @@ def _check_frames(frames, who):
         raise ValueError(f"{who} expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
 
 
+def _check_raw(points, offsets, pick, N, who):
+    """what every entry point that takes raw detections refuses before it touches its state -> the number of frames"""
+    for t, name in ((points, "points"), (offsets, "offsets")) + (((pick, "pick"),) if pick is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} must live on the HIP device; this package has no CPU path")
+    if points.dim() != 2 or points.shape[1] != 5 or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{who} expects points fp32 or fp64 [P,5], got {tuple(points.shape)} {points.dtype}")
+    if offsets.dim() != 1 or offsets.dtype != torch.int32 or offsets.numel() < 1:
+        raise ValueError(f"{who} expects offsets int32 [n + 1], got {tuple(offsets.shape)} {offsets.dtype}")
+    n = offsets.numel() - 1
+    if pick is not None and (pick.dtype != torch.int32 or tuple(pick.shape) != (n, N)):
+        raise ValueError(f"{who} expects pick int32 [{n}, {N}], got {tuple(pick.shape)} {pick.dtype}")
+    return n
+
+
+def _upload_keys(serial, first, n, dev):
+    """the keys (track serial, frame index) of frames first .. first + n - 1 of one track: int32 [n, 2], one pinned copy"""
+    host = torch.empty((n, 2), dtype=torch.int32, pin_memory=True)
+    k = host.numpy()
+    k[:, 0] = np.int64(serial).astype(np.int32)
+    k[:, 1] = (np.arange(n, dtype=np.int64) + int(first)).astype(np.int32)
+    return host.to(dev, non_blocking=True)
+
+
 def _empty_triple(D, dev):
     """(preds, sup_fv, likelihood) of no window at all"""
     return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
@@ -129,6 +153,7 @@ class OpenSetScorer:
         self.threshold = None
         self.last_frames_encoded = None      # unique frames the last deduplicated embed / embed_track encoded (no padding)
         self.last_pointnet_saves = None      # the PointNet layer records of its last chunk (which path ran)
+        self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
 
     @torch.no_grad()
     def embed(self, pcs: torch.Tensor, dedup_frames: bool = False, hop: int = constants.CROP_STEP):
@@ -218,6 +243,22 @@ class OpenSetScorer:
         plan = ops.WindowRows(starts, T, table.shape[0], device=dev,
                               dev=torch.arange(0, W * hop, hop, dtype=torch.int32, device=dev))
         return self._score_windows(table, plan, T)
+
+    @torch.no_grad()
+    def embed_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None, seed: int = 0,
+                        track_key: int = 0, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True):
+        """``embed_track`` from the radar's detections: ``points`` [P,5] fp32 / fp64 and ``offsets`` int32 [F + 1] on the
+        device (``datasets.pack_raw_frames``) -> one ``ops.frames_from_raw`` launch for the whole track (centred, not
+        divided by std, as ``generate_splits`` prepares the crops) -> exactly ``embed_track`` on those frames.  ``pick``
+        int32 [F, N]: host-drawn picks (``datasets.draw_picks``); None: drawn on the device, frame f under the key
+        ``(track_key, f)`` and ``seed``.  ``raw_err`` (int32 [1], device) is set by a frame that could not be processed."""
+        enc = self.encoder
+        N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
+        F = _check_raw(points, offsets, pick, N, "embed_raw_track")
+        dev = points.device
+        keys = _upload_keys(track_key, 0, F, dev) if pick is None and F else None
+        frames = ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=self.raw_err)
+        return self.embed_track(frames, hop, drop_last_aligned)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
         """ROC-optimal (Youden J) separation of known-test vs held-out-unseen likelihoods
@@ -438,6 +479,7 @@ class _LiveScorer:
         self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
         self._D = encoder.MLP_sup1[0].weight.shape[0]                          # embedding width
         self._width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]      # frame-feature width: a ring row
+        self._N, self._C = encoder.nmax_points, encoder.pc_block.pointnet1.module[0].weight.shape[1]   # a raw frame becomes [N, C]
         self.last_pointnet_saves = None
 
     def _check_eval(self):
@@ -463,10 +505,12 @@ class StreamingScorer(_LiveScorer):
     in one batched tick with O(k) state per track."""
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
-                 hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None):
+                 hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         dev = self.means.device
         self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
+        self.seed, self.serial = int(seed), -1           # push_raw: frame f of the track is drawn under (serial, f)
+        self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
         # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
         # once, long enough that the windows of any one push are a contiguous slice of it (no upload per push)
         self._period = self.ring_rows // np.gcd(self.ring_rows, self.hop)
@@ -476,7 +520,9 @@ class StreamingScorer(_LiveScorer):
         self.reset()
 
     def reset(self):
-        """forget the track: the next pushed frame is frame 0 of a new one"""
+        """forget the track: the next pushed frame is frame 0 of a new one (with a new serial: ``push_raw`` does not
+        replay the previous track's draws)"""
+        self.serial += 1
         self.n_frames = 0
         self.n_windows = 0
         self._preds, self._lik = [], []
@@ -487,7 +533,10 @@ class StreamingScorer(_LiveScorer):
         they complete (possibly none: empty tensors)."""
         self._check_eval()
         _check_frames(frames, "StreamingScorer.push")
-        out = [self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)]
+        return self._gather([self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)])
+
+    def _gather(self, out):
+        """the triples of a push's chunks (None: no window) -> one triple"""
         out = [o for o in out if o is not None]
         if not out:
             return _empty_triple(self._D, self.ring.device)
@@ -495,11 +544,34 @@ class StreamingScorer(_LiveScorer):
             return out[0]
         return tuple(torch.cat([o[i] for o in out]) for i in range(3))
 
+    @torch.no_grad()
+    def push_raw(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None):
+        """``push`` from the radar's detections: ``points`` [P,5] fp32 / fp64, ``offsets`` int32 [n + 1] on the device
+        (``datasets.pack_raw_frames``), the next n frames of the track -> one ``ops.frames_from_raw`` launch per
+        ``max_push`` frames (centred, padded to whole GEMM tiles by the same launch), then what ``push`` does.  ``pick``
+        int32 [n, N]: host-drawn picks; None: drawn on the device, frame f of the track under the key ``(serial, f)`` and
+        the constructor's ``seed``.  ``raw_err`` is set by a frame that could not be processed (its frame is zeros)."""
+        self._check_eval()
+        n = _check_raw(points, offsets, pick, self._N, "StreamingScorer.push_raw")
+        q = F_hip.frame_pad_quantum(self._N)
+        out = []
+        for a in range(0, n, self.max_push):
+            b = min(a + self.max_push, n)
+            keys = _upload_keys(self.serial, self.n_frames, b - a, points.device) if pick is None else None
+            frames = ops.frames_from_raw(points, offsets[a:b + 1], self._N, self._C, pick=None if pick is None else pick[a:b],
+                                         seed=self.seed, frame_key=keys, n_out=b - a + (a - b) % q, err_flag=self.raw_err)
+            out.append(self._push_padded(frames, b - a))
+        return self._gather(out)
+
     def _push(self, frames):
         n, N, C = frames.shape
         q = F_hip.frame_pad_quantum(N)
         if n % q:                                   # whole GEMM row tiles in bf16 mode; the padding's features are dropped
             frames = torch.cat([frames, frames.new_zeros(((-n) % q, N, C))])
+        return self._push_padded(frames, n)
+
+    def _push_padded(self, frames, n):
+        """``frames``: on the device, padded to whole tiles, the first ``n`` of them the track's next frames"""
         feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames)
         pos = self.n_frames % self.ring_rows
         first = min(n, self.ring_rows - pos)
@@ -535,10 +607,10 @@ class StreamingScorer(_LiveScorer):
 class TickPlan:
     """What ``plan_tick`` returns: see there."""
     __slots__ = ("dst_row", "win_row", "win_stream", "win_j", "vote_pos", "run_start", "vote_stream", "vote_group",
-                 "n_frames", "n_windows", "packed", "offsets")
+                 "n_frames", "n_windows", "packed", "offsets", "frame_key")
 
 
-def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1):
+def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1, serials=None):
     """Host plan of one tick of ``MultiStreamScorer``: a pure function of the streams' counters, numpy only.
 
     ``n_frames`` / ``n_windows``: per SLOT, the frames pushed and the windows emitted so far; ``sids``: the distinct slots
@@ -555,7 +627,12 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1)
       ``vote_stream`` / ``vote_group`` int64 [g]: slot and group index of every vote;
     * ``run_start`` int32 [runs + 1]: the windows of one stream are ``run_start[r] .. run_start[r + 1]``;
     * ``n_frames`` / ``n_windows`` int64 [len(sids)]: the counters of ``sids`` after the tick;
-    * ``packed`` int32: all six int32 arrays in one buffer (one upload), ``offsets[name] = (start, stop)`` in it."""
+    * ``packed`` int32: all six int32 arrays in one buffer (one upload), ``offsets[name] = (start, stop)`` in it.
+
+    ``serials`` (optional, per SLOT: the serial number of the track in it): the plan also carries ``frame_key`` int32
+    [frames, 2], the key ``(serial of its track, its index in its track)`` of every frame of the tick (no padding rows) --
+    what ``MultiStreamScorer.push_raw`` draws a frame's points under -- appended to ``packed`` as
+    ``offsets["frame_key"]`` (flattened); without ``serials`` it is None and ``packed`` is as before."""
     T, hop, k, ring_rows, pad_to = int(T), int(hop), int(k), int(ring_rows), int(pad_to)
     n_frames = np.asarray(n_frames, dtype=np.int64).reshape(-1)
     n_windows = np.asarray(n_windows, dtype=np.int64).reshape(-1)
@@ -569,6 +646,12 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1)
     if n_slots * ring_rows >= 2 ** 31:
         raise ValueError("plan_tick: the table rows do not fit 32-bit indices")
     plan = TickPlan()
+    plan.frame_key = None
+    if serials is not None:
+        serials = np.asarray(serials, dtype=np.int64).reshape(-1)
+        if serials.size != n_slots:
+            raise ValueError("plan_tick: one serial per slot")
+        plan.frame_key = np.zeros((0, 2), np.int32)
     if S == 0:
         z = np.zeros(0, np.int64)
         nf1 = done = nwin = win_stream = j = z
@@ -595,6 +678,8 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1)
         # frame f of the tick: f - (frames of the streams before its own) + (frames its stream had) = its index in its track
         base = sids * ring_rows
         dst = np.arange(total, dtype=np.int64) + np.repeat(nf0 - (np.cumsum(counts) - counts), counts)
+        if serials is not None:                                # here dst is still the frame's index in its track
+            plan.frame_key = np.stack([np.repeat(serials[sids], counts), dst], axis=1).astype(np.int32)
         dst %= ring_rows
         dst += np.repeat(base, counts)
         pad = (-total) % pad_to
@@ -615,6 +700,9 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1)
     for name, arr in zip(("dst_row", "win_row", "win_stream", "win_j", "vote_pos", "run_start"), parts):
         plan.offsets[name] = (a, a + arr.size)
         a += arr.size
+    if plan.frame_key is not None:
+        parts += (plan.frame_key.reshape(-1),)
+        plan.offsets["frame_key"] = (a, a + plan.frame_key.size)
     plan.packed = np.concatenate(parts)
     return plan
 
@@ -665,7 +753,7 @@ class MultiStreamScorer(_LiveScorer):
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
-                 batch_size: int = 1024):
+                 batch_size: int = 1024, seed: int = 0):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         self.max_streams, self.batch_size = int(max_streams), int(batch_size)
         if self.max_streams < 1 or self.batch_size < 1:
@@ -677,6 +765,10 @@ class MultiStreamScorer(_LiveScorer):
         self.hist_lik = torch.zeros((self.max_streams, self.k), dtype=torch.float64, device=dev)
         self.hist_pred = torch.zeros((self.max_streams, self.k), dtype=torch.int64, device=dev)
         self.scatter_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a scatter destination out of range
+        self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)         # set by a raw frame that could not be processed
+        self.seed = int(seed)                                  # push_raw draws frame f of a track under (its serial, f)
+        self.track_serial = np.zeros(self.max_streams, np.int64)             # per slot: bumped by open()
+        self._next_serial = 0
         self.n_frames = np.zeros(self.max_streams, np.int64)
         self.n_windows = np.zeros(self.max_streams, np.int64)
         self._open = np.zeros(self.max_streams, bool)
@@ -692,6 +784,8 @@ class MultiStreamScorer(_LiveScorer):
         sid = int(free[0])
         self._open[sid] = True
         self.n_frames[sid] = self.n_windows[sid] = 0
+        self.track_serial[sid] = self._next_serial             # a reused slot does not replay its previous track's draws
+        self._next_serial += 1
         return sid
 
     def close(self, sid: int):
@@ -717,21 +811,54 @@ class MultiStreamScorer(_LiveScorer):
         windows these frames complete (possibly none: empty tensors, no temporal pass)."""
         self._check_eval()
         _check_frames(frames, "MultiStreamScorer.push")
-        sids = self._slots(sids, "push")
+        n, N, C = frames.shape
+        sids, plan, part, mode = self._begin_tick(sids, counts, n, N, "push", False)
+        if n == 0:
+            return self._empty(plan, self.ring.device)
+        pad = plan.dst_row.size - n
+        if pad:                                       # whole GEMM row tiles in bf16 mode, once per TICK; features dropped
+            if self._zeros is None or tuple(self._zeros.shape[1:]) != (N, C) or self._zeros.shape[0] < pad:
+                self._zeros = frames.new_zeros((max(pad, F_hip.frame_pad_quantum(N, mode)), N, C))
+            frames = torch.cat([frames, self._zeros[:pad]])
+        return self._finish_tick(sids, plan, part, mode, frames)
+
+    @torch.no_grad()
+    def push_raw(self, sids, counts, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None) -> Tick:
+        """``push`` from the radar's detections: ``points`` [P,5] fp32 / fp64 and ``offsets`` int32 [sum(counts) + 1] on
+        the device (``datasets.pack_raw_frames`` of the tick's frames, concatenated in the order of ``sids``) -> the same
+        Tick, by ONE launch more than ``push`` (``ops.frames_from_raw``: the frames centred as ``process_track`` centres
+        them and padded to whole GEMM tiles) and no host work per frame.  ``pick`` int32 [sum(counts), N]: host-drawn picks
+        (``datasets.draw_picks``: the reference's draws); None: drawn on the device, frame f of a track under the key
+        ``(track_serial[slot], f)`` and the constructor's ``seed`` -- the keys travel in the tick's one pinned upload.
+        ``raw_err`` is set by a frame that could not be processed (it is encoded as zeros)."""
+        self._check_eval()
+        n = _check_raw(points, offsets, pick, self._N, "MultiStreamScorer.push_raw")
+        sids, plan, part, mode = self._begin_tick(sids, counts, n, self._N, "push_raw", pick is None)
+        if n == 0:
+            return self._empty(plan, self.ring.device)
+        frames = ops.frames_from_raw(points, offsets, self._N, self._C, pick=pick, seed=self.seed,
+                                     frame_key=part["frame_key"].view(n, 2) if pick is None else None,
+                                     n_out=plan.dst_row.size, err_flag=self.raw_err)
+        return self._finish_tick(sids, plan, part, mode, frames)
+
+    def _begin_tick(self, sids, counts, n, N, what, want_keys):
+        """the arguments of a tick checked, its plan made and (unless the tick is empty) uploaded -> (sids, plan, the
+        plan's parts on the device, precision mode)"""
+        sids = self._slots(sids, what)
         counts = _host_ints(counts)
         if counts is None or counts.size != sids.size:
-            raise ValueError("MultiStreamScorer.push: counts must be host ints, one per stream id")
+            raise ValueError(f"MultiStreamScorer.{what}: counts must be host ints, one per stream id")
         if counts.size and (counts.min() < 0 or counts.max() > self.max_push):
-            raise ValueError(f"MultiStreamScorer.push: counts must lie in 0..max_push = {self.max_push}")
-        if int(counts.sum()) != frames.shape[0]:
-            raise ValueError(f"MultiStreamScorer.push: counts add up to {int(counts.sum())} frames, got {frames.shape[0]}")
-        n, N, C = frames.shape
+            raise ValueError(f"MultiStreamScorer.{what}: counts must lie in 0..max_push = {self.max_push}")
+        if int(counts.sum()) != n:
+            raise ValueError(f"MultiStreamScorer.{what}: counts add up to {int(counts.sum())} frames, got {n}")
         dev = self.ring.device
         mode = F_hip.get_precision()
         q = F_hip.frame_pad_quantum(N, mode)
-        plan = plan_tick(self.n_frames, self.n_windows, sids, counts, self.T, self.hop, self.k, self.ring_rows, q)
+        plan = plan_tick(self.n_frames, self.n_windows, sids, counts, self.T, self.hop, self.k, self.ring_rows, q,
+                         serials=self.track_serial if want_keys else None)
         if n == 0:
-            return self._empty(plan, dev)
+            return sids, plan, None, mode
         if self._consts is None or not self._consts.valid_for(self.encoder, mode):
             self._consts = F_hip.encoder_eval_constants(self.encoder, mode)
         # the whole plan in one pinned buffer, one asynchronous copy (the pinned block is recycled by torch's host
@@ -739,12 +866,11 @@ class MultiStreamScorer(_LiveScorer):
         host = torch.empty(plan.packed.size, dtype=torch.int32, pin_memory=True)
         host.numpy()[:] = plan.packed
         packed = host.to(dev, non_blocking=True)
-        part = {name: packed[a:b] for name, (a, b) in plan.offsets.items()}
-        pad = plan.dst_row.size - n
-        if pad:                                       # whole GEMM row tiles in bf16 mode, once per TICK; features dropped
-            if self._zeros is None or tuple(self._zeros.shape[1:]) != (N, C) or self._zeros.shape[0] < pad:
-                self._zeros = frames.new_zeros((max(pad, q), N, C))
-            frames = torch.cat([frames, self._zeros[:pad]])
+        return sids, plan, {name: packed[a:b] for name, (a, b) in plan.offsets.items()}, mode
+
+    def _finish_tick(self, sids, plan, part, mode, frames):
+        """a tick from the point where its frames are on the device and padded to whole tiles"""
+        dev = self.ring.device
         feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames, mode, consts=self._consts)
         ops.scatter_rows(feats, part["dst_row"], self.ring, err_flag=self.scatter_err)
         self.n_frames[sids], self.n_windows[sids] = plan.n_frames, plan.n_windows

@@ -1548,6 +1548,57 @@ def scatter_rows(src, dst_row, dst, err_flag=None):
     return dst
 
 
+RAW_MAX_CARD = 1024       # PCAA_RAW_MAX_CARD / PCAA_RAW_MAX_POINTS of include/pcaa_hip.h
+RAW_MAX_POINTS = 1024
+
+
+def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True, divide_by_std=False,
+                    n_out=None, pick_out=None, err_flag=None):
+    """Raw radar detections -> processed frames in one launch (pcaa_frames_from_raw): ``points`` [P, 5] fp32 or fp64 (x,
+    y, z, doppler, linear power), ``offsets`` int32 [n + 1] (frame f owns rows ``offsets[f] .. offsets[f + 1] - 1``) ->
+    fp32 ``[n_out, N, C]``, rows ``n .. n_out - 1`` zero (``n_out`` defaults to n).  ``pick`` int32 [n, N]: output point p
+    of frame f is raw point ``pick[f, p]`` of that frame (``datasets.draw_picks``: the reference's draws); None: the
+    kernel draws them from ``frame_key`` int32 [n, 2] and ``seed`` (``datasets.device_picks_host`` restates the draw).
+    ``pick_out`` int32 [n, N]: receives the picks used.  A frame that cannot be processed (cardinality < 1 or >
+    RAW_MAX_CARD, offsets outside the points, a pick outside the frame) comes back as zeros and sets ``err_flag`` (int32
+    [1]); nothing is checked on the host."""
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise TypeError("frames_from_raw.points: expected a float32 or float64 tensor")
+    _chk(points, "frames_from_raw.points", None, 2)
+    _chk(offsets, "frames_from_raw.offsets", torch.int32, 1)
+    N, C, seed = int(N), int(C), int(seed)
+    n = offsets.numel() - 1
+    n_out = n if n_out is None else int(n_out)
+    if points.shape[1] != 5 or n < 0 or n_out < n or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
+        raise ValueError(f"frames_from_raw: needs points [P, 5], offsets [n + 1], n_out >= n, 1 <= N <= {RAW_MAX_POINTS}, "
+                         f"1 <= C <= 5; got points {tuple(points.shape)}, n={n}, n_out={n_out}, N={N}, C={C}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError("frames_from_raw: the seed must fit 64 bits")
+    if pick is not None:
+        _chk(pick, "frames_from_raw.pick", torch.int32, 2)
+        if tuple(pick.shape) != (n, N):
+            raise ValueError(f"frames_from_raw: pick must be [{n}, {N}], got {tuple(pick.shape)}")
+    elif n:
+        if frame_key is None:
+            raise ValueError("frames_from_raw: without picks every frame needs its key (frame_key int32 [n, 2])")
+        _chk(frame_key, "frames_from_raw.frame_key", torch.int32, 2)
+        if tuple(frame_key.shape) != (n, 2):
+            raise ValueError(f"frames_from_raw: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
+    if pick_out is not None:
+        _chk(pick_out, "frames_from_raw.pick_out", torch.int32, 2)
+        if tuple(pick_out.shape) != (n, N):
+            raise ValueError(f"frames_from_raw: pick_out must be [{n}, {N}], got {tuple(pick_out.shape)}")
+    if err_flag is not None:
+        _chk(err_flag, "frames_from_raw.err_flag", torch.int32)
+    out = torch.empty((n_out, N, C), dtype=torch.float32, device=points.device)
+    if n_out:
+        check(_lib.load().pcaa_frames_from_raw(
+            _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
+            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+            _p(out), n_out, _p(pick_out), _p(err_flag), _s()), "pcaa_frames_from_raw")
+    return out
+
+
 def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
                  n_classes, hist_lik, hist_pred):
     """One tick of many live streams in one launch (pcaa_stream_score) -> (preds [nw] int64, lik [nw] f64, votes [n_votes]
