@@ -1759,6 +1759,8 @@ def disc_workspace(B, K, device):
 
 
 def disc_forward(x, label, params):
+    """x [B, 32], label [B, K] with 0 <= K <= 32 -> D [B, 1].  K = 0 (a [B, 0] label, W1 [64, 32]) is the critic without a
+    label: accepted here and by the three entry points below, as the ABI accepts it."""
     _chk(x, "disc.x", torch.float32, 2)
     _chk(label, "disc.label", torch.float32, 2)
     B, K = label.shape
