@@ -100,7 +100,8 @@ int pcaa_gemm_slabs(int math,
  * (models.py:20-29 backward): da = dy[M,K] . Wt[N,K]^T never reaches memory; the epilogue reads that
  * layer's stored pre-activation y[M,N] and writes  dz = da * ELU'(y*scale+shift)  (bf16, same ld as y)
  * while adding {sum dz, sum dz*(y-mean)*rstd} per column into stats (as pcaa_bn_act_bwd_dz does in a
- * separate pass).  All operands bf16, M and N multiples of 256, K of 64.
+ * separate pass).  All operands bf16, N a multiple of 256, K of 64 and at least 320 (pcaa_gemm_dgrad_bn_supported);
+ * M need not be a multiple of 256 (then ld % 8 == 0 and 16-B aligned y / dz).
  * x, xc, W1: must be NULL / 0 / NULL -- the variant of rounds 1-4 that rebuilt y of the first PointNet layer from the
  * points in the epilogue (never faster than the separate statistics pass) left with the 8-wave kernel in round 5; y is
  * required. */

@@ -661,12 +661,12 @@ extern "C" int pcaa_gemm_dgrad_bn(const void* dy, long lddy, const void* Wt, lon
   (void)xc; (void)W1;
   PCAA_CHECK_ARG(y != nullptr && x == nullptr, "pcaa_gemm_dgrad_bn: y is required (the recompute variant -- x, xc, W1 -- was "
                  "removed in round 5)");
-  PCAA_CHECK_ARG(pcaa_gemm_dgrad_bn_supported(M, N, K), "pcaa_gemm_dgrad_bn: M, N must be multiples of 256 and K of 64 "
-                 "(M=%d N=%d K=%d)", M, N, K);
+  PCAA_CHECK_ARG(pcaa_gemm_dgrad_bn_supported(M, N, K), "pcaa_gemm_dgrad_bn: N must be a multiple of 256, K of 64 and at least "
+                 "320, with the 4-wave loops enabled (M: any; a partial last row tile is served) (M=%d N=%d K=%d)", M, N, K);
   PCAA_CHECK_ARG(lddy >= K && ldw >= K && ld >= N && (lddy % 8) == 0 && (ldw % 8) == 0 && (ld % 8) == 0 && nrep >= 1,
                  "pcaa_gemm_dgrad_bn: bad leading dimension / nrep");
-  PCAA_CHECK_ARG(ragged_out_ok(M, dz, ld, 2), "pcaa_gemm_dgrad_bn: a partial last row tile needs ceil(M / 256) * 256 * ld * 2 "
-                 "< 4 GiB (M=%d ld=%ld)", M, ld);
+  PCAA_CHECK_ARG(ragged_out_ok(M, dz, ld, 2), "pcaa_gemm_dgrad_bn: a partial last row tile needs ld %% 8 == 0, a 16-B aligned dz "
+                 "and ceil(M / 256) * 256 * ld * 2 < 4 GiB (M=%d ld=%ld)", M, ld);
   PCAA_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)Wt % 16) == 0 && (!y || ((uintptr_t)y % 16) == 0) &&
                  ((uintptr_t)dz % 16) == 0 && ((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0 &&
                  ((uintptr_t)mean % 16) == 0 && ((uintptr_t)rstd % 16) == 0, "pcaa_gemm_dgrad_bn: 16-B alignment");
@@ -693,8 +693,8 @@ extern "C" int pcaa_gemm_dgrad_bn_split3(const void* dy_img, long lddy, const vo
   PCAA_CHECK_ARG(dy_img && Wt_img && y && dz && scale && shift && mean && rstd && stats,
                  "pcaa_gemm_dgrad_bn_split3: null pointer");
   // (the split operands walk three K-long passes: the same shape rule as pcaa_gemm_split3)
-  PCAA_CHECK_ARG(pcaa_gemm_split3_supported(M, N, K), "pcaa_gemm_dgrad_bn_split3: M, N must be multiples of 256 and K "
-                 "of 64, 3 K >= 320 (M=%d N=%d K=%d)", M, N, K);
+  PCAA_CHECK_ARG(pcaa_gemm_split3_supported(M, N, K), "pcaa_gemm_dgrad_bn_split3: N must be a multiple of 256, K of 64 with "
+                 "3 K >= 320, M of 256 unless K >= 320, with the 4-wave loops enabled (M=%d N=%d K=%d)", M, N, K);
   PCAA_CHECK_ARG((long)K * 3 < (1L << 31) && lddy >= 2L * K && ldw >= 2L * K && ld >= N && (lddy % 8) == 0 &&
                  (ldw % 8) == 0 && (ld % 4) == 0 && nrep >= 1, "pcaa_gemm_dgrad_bn_split3: bad leading dimension / nrep");
   PCAA_CHECK_ARG(ragged_out_ok(M, dz, ld, 4), "pcaa_gemm_dgrad_bn_split3: a partial last row tile needs ld %% 8 == 0 and "
@@ -726,8 +726,8 @@ extern "C" int pcaa_gemm_affine_elu(const void* A, long lda, const void* W, long
   PCAA_CHECK_ARG(A && W && out && scale && shift, "pcaa_gemm_affine_elu: null pointer");
   PCAA_CHECK_ARG(pool_rows == 0 || pool_rows == 32 || pool_rows == 64 || pool_rows == 128,
                  "pcaa_gemm_affine_elu: pool_rows must be 0, 32, 64 or 128");
-  PCAA_CHECK_ARG(pcaa_gemm_dgrad_bn_supported(M, N, K), "pcaa_gemm_affine_elu: M, N must be multiples of 256 and K of 64 "
-                 "(M=%d N=%d K=%d)", M, N, K);
+  PCAA_CHECK_ARG(pcaa_gemm_dgrad_bn_supported(M, N, K), "pcaa_gemm_affine_elu: N must be a multiple of 256, K of 64 and at least "
+                 "320, with the 4-wave loops enabled (M: any; a partial last row tile is served) (M=%d N=%d K=%d)", M, N, K);
   PCAA_CHECK_ARG(lda >= K && ldw >= K && ldo >= N && (lda % 8) == 0 && (ldw % 8) == 0 && (pool_rows != 0 || (ldo % 8) == 0),
                  "pcaa_gemm_affine_elu: bad leading dimension");
   PCAA_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)out % 16) == 0,

@@ -345,9 +345,16 @@ _GEMM_V2_RC = os.environ.get("PCAA_GEMM_V2_RC", "1")[:1] != "0"     # read the s
 
 
 def _v2_takes(K, split_k=1, accumulate=False):
-    """the dispatch rule of csrc/gemm_bf16.hip (launch_dma): the 4-wave loop takes a KC x KC launch without K splits whose
-    contraction is at least five 64-deep steps long"""
+    """the dispatch rule of csrc/gemm_bf16.hip (launch_dma) for bf16 KC x KC operands: the 4-wave loop takes a launch
+    without K splits, atomics or slabs whose contraction is at least five 64-deep steps long (and whose result has a
+    leading dimension that is a multiple of 8 on a 16-B aligned base, which N % 256 == 0 and a torch allocation give)"""
     return _GEMM_V2["on"] and K // 64 >= 5 and int(split_k) <= 1 and not accumulate
+
+
+def _v2rc_takes(split_k=1, accumulate=False, bias=None, colstats=None):
+    """the same for bf16 RC x RC operands with an fp32 result (whole 256 x 256 tiles, K % 64 == 0): the 4-wave loop takes
+    a single K pass or slabs of any contraction length -- no atomics, no bias, no column statistics"""
+    return _GEMM_V2["on"] and _GEMM_V2_RC and int(split_k) <= 1 and not accumulate and bias is None and colstats is None
 
 
 def _dma_key(out_dtype, layout, v2=False):
@@ -402,7 +409,9 @@ def gemm(A, a_layout, B, b_layout, M, N, K, *, lda=None, ldb=None, out=None, out
             key = "gemm_f32_kernel"
         elif (A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and a_layout == b_layout
               and (M % 256 == 0 or (a_layout == KC and _v2_takes(K, split_k, accumulate))) and N % 256 == 0 and K % 64 == 0):
-            key = _dma_key(out.dtype, a_layout, _v2_takes(K, split_k, accumulate))   # same dispatch rule as pcaa_launch_gemm_bf16_big
+            # same dispatch rule as pcaa_launch_gemm_bf16_big
+            key = _dma_key(out.dtype, a_layout, _v2_takes(K, split_k, accumulate) if a_layout == KC
+                           else _v2rc_takes(split_k, accumulate, bias, colstats))
         else:
             key = "gemm_bf16_big_kernel"
         timer = timer if timer.wants(key) else None
@@ -473,7 +482,8 @@ def gemm_slabs(A, a_layout, B, b_layout, M, N, K, split_k, out=None, accumulate=
     if timer is not None:
         dma = (math == PCAA_BF16 and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and a_layout == b_layout
                and M % 256 == 0 and N % 256 == 0 and K % 64 == 0)
-        key = _dma_key(torch.float32, a_layout, M % 256 == 0 and N % 256 == 0 and (K // ns) % 64 == 0) if dma else ("gemm_bf16_big_kernel" if math == PCAA_BF16 else "gemm_f32_kernel")
+        # (slabs: the RC x RC loop takes them -- every K range is a multiple of 64 deep; the KC x KC loop takes no slabs)
+        key = _dma_key(torch.float32, a_layout, a_layout == RC) if dma else ("gemm_bf16_big_kernel" if math == PCAA_BF16 else "gemm_f32_kernel")
         timer = timer if timer.wants(key) else None
     if timer is not None:
         ev = _begin_timing(key)
