@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 20 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 21 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -59,9 +59,20 @@ int pcaa_abi_version(void);
  *   layer this GEMM produces.
  * split_k > 1 or accumulate != 0: fp32 atomic accumulation into C (C must be
  *   fp32 and pre-initialised); bias is added by split 0 only.
+ * Dispatch: every product entry point (pcaa_gemm, pcaa_gemm_slabs, pcaa_gemm_split3, pcaa_gemm_slabs_split3) first
+ *   PLANS the call from its arguments alone -- every argument check and every decision, no device memory read, no HIP
+ *   call -- and then launches the planned kernel, one of PCAA_GEMM_KERNEL_*.  The rule for the two 4-wave LDS-DMA loops
+ *   is stated once (pcaa_gemm_4wave_kernel, csrc/gemm_bf16.hip); the *_supported predicates ask that same function.
+ *   pcaa_gemm_route / pcaa_gemm_split3_route run the plan only and report the kernel (they work without a GPU);
+ *   pcaa_gemm_last_kernel reports what the calling thread's most recent GEMM launch actually started.
  * Replaces: Conv2d(1x1) models.py:20-27, Conv1d via im2col models.py:59-68,
  *   Linear models.py:252-277, 346-371, 409-416, and their autograd backward.
  */
+#define PCAA_GEMM_KERNEL_F32_TILE128 0 /* gemm_f32_kernel: 128 x 128 tiles, exact-fp32 MFMA, any dtype / layout */
+#define PCAA_GEMM_KERNEL_BF16_SMALL 1  /* gemm_bf16_kernel: 128 x 128 tiles, bf16 MFMA, KC operands (csrc/gemm.hip) */
+#define PCAA_GEMM_KERNEL_BF16_STAGED 2 /* gemm_bf16_big_kernel: 256 x 256 tiles, operands staged through registers */
+#define PCAA_GEMM_KERNEL_V2_KC 3       /* v2::gemm_bf16_v2_kernel: the 4-wave LDS-DMA loop, KC x KC (also the fused entries) */
+#define PCAA_GEMM_KERNEL_V2_RC 4       /* v2::gemm_bf16_v2rc_kernel: the 4-wave LDS-DMA loop, RC x RC -> fp32 */
 int pcaa_gemm(int math,
               const void* A, int a_dtype, int a_layout, long lda,
               const void* B, int b_dtype, int b_layout, long ldb,
@@ -75,6 +86,25 @@ int pcaa_gemm(int math,
  * out (=|+=).  pcaa_gemm_num_splits tells how many splits pcaa_gemm / pcaa_gemm_slabs will
  * actually run for a requested split_k (K is cut into multiples of the kernel's K step). */
 int pcaa_gemm_num_splits(int math, int K, int split_k);
+/* ABI 21: the plan step alone.  pcaa_gemm_route: the arguments of pcaa_gemm plus slab_stride -- 0: the pcaa_gemm form;
+ * non-zero: the pcaa_gemm_slabs form (C = slabs; c_dtype, ldc, bias, colstats, nrep and accumulate are then not looked at,
+ * as pcaa_gemm_slabs has none).  pcaa_gemm_split3_route: pcaa_gemm_split3 (split_k = 1, c_split_stride = 0) or
+ * pcaa_gemm_slabs_split3 (C = slabs, ldc = N, c_split_stride = slab_stride); out_scale decides nothing.  Both return the PCAA_GEMM_KERNEL_* the
+ * launch would take, or -1 with pcaa_last_error() set exactly as the launch would set it.  Pointers are inspected for
+ * NULL and alignment only; no HIP call is made.  The launched kernel differs from the planned one in a single case: a
+ * 4-wave launcher whose hipFuncSetAttribute fails hands the launch to the register-staged kernel.
+ * pcaa_gemm_last_kernel: the PCAA_GEMM_KERNEL_* that the calling thread's most recent GEMM launch (the fused entry
+ * points included) started; -1 before any. */
+int pcaa_gemm_route(int math,
+                    const void* A, int a_dtype, int a_layout, long lda,
+                    const void* B, int b_dtype, int b_layout, long ldb,
+                    const void* C, int c_dtype, long ldc,
+                    int M, int N, int K,
+                    const float* bias, const double* colstats, int nrep,
+                    int split_k, int accumulate, long slab_stride);
+int pcaa_gemm_split3_route(const void* A, const void* B, int layout, long lda, long ldb, const void* C, long ldc, int M,
+                           int N, int K, const double* colstats, int nrep, int split_k, long c_split_stride, float out_scale);
+int pcaa_gemm_last_kernel(void);
 /* ABI 14: n <= 8 small products C_i[M_i, N_i] += A_i^T . B_i in ONE launch (the temporal block's six weight gradients
  * dW_l = dy_l^T . col_l, reference models.py:108-160 through autograd): A_i [K_i, M_i], B_i [K_i, N_i], C_i [M_i, N_i], all
  * fp32 with contiguous rows, 16-B aligned, M_i and N_i multiples of 4; exact-fp32 MFMA; C_i is accumulated into (atomics
@@ -86,11 +116,10 @@ int pcaa_gemm_group_rc_f32(int n, const void* const* A, const void* const* B, vo
  * result every run). */
 int pcaa_gemm_group_rc_f32_slabs(int n, const void* const* A, const void* const* B, void* const* slabs, const int* M,
                                  const int* N, const int* K, const int* split_k, void* stream);
-/* Which tile loop serves the bf16 / split-fp16 KC x KC products without K splits (whole 256 x 256 tiles, contraction
- * >= 320 deep): 1 (default; environment PCAA_GEMM_V2=0 to start with 0) = the 4-wave loop of round 4 (csrc/gemm_v2.h:
- * 128 x 128 wave tiles, both operands requested two K steps ahead, the request stream continuous across tiles), 0 = the
- * 8-wave loop of rounds 1-3.  Same operands, same epilogues, same results up to the summation order inside a
- * 64-deep step (none: both accumulate k in the same order); kept switchable for same-process A/B (tools/gemm_lab.py). */
+/* Lab switch of the 4-wave LDS-DMA loops (csrc/gemm_v2.h): 1 (default; environment PCAA_GEMM_V2=0 to start with 0) =
+ * they take every launch pcaa_gemm_4wave_kernel admits; 0 = they decline every launch -- plain products then take the
+ * register-staged 256 x 256 kernel, the fused entry points and the split products report their shapes unsupported.
+ * Kept switchable for same-process A/B (tools/gemm_lab.py). */
 int pcaa_gemm_v2_enable(int on);
 int pcaa_gemm_slabs(int math,
                     const void* A, int a_dtype, int a_layout, long lda,

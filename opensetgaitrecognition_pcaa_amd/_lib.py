@@ -14,6 +14,8 @@ HEADER = os.path.join(os.path.dirname(PKG), "include", "pcaa_hip.h")
 LIB_PATH = os.path.join(PKG, "libpcaa_hip.so")
 
 PCAA_F32, PCAA_BF16 = 0, 1
+# PCAA_GEMM_KERNEL_* of include/pcaa_hip.h: what pcaa_gemm_route / pcaa_gemm_last_kernel answer
+GEMM_KERNEL_F32_TILE128, GEMM_KERNEL_BF16_SMALL, GEMM_KERNEL_BF16_STAGED, GEMM_KERNEL_V2_KC, GEMM_KERNEL_V2_RC = range(5)
 
 
 def _header_abi_version():

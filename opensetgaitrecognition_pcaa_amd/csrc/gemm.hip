@@ -19,6 +19,9 @@
 // re-read from that XCD's L2 and not from HBM.
 #include "gemm_common.h"
 
+thread_local int g_pcaa_gemm_last_kernel = -1;
+extern "C" int pcaa_gemm_last_kernel(void) { return g_pcaa_gemm_last_kernel; }
+
 namespace {
 
 constexpr int BM = 128, BN = 128;
@@ -386,6 +389,23 @@ void launch_f32_lay(const GemmParams& p, int al, int bl, bool vec, dim3 grid, hi
   else if (al == KC && bl == RC) launch_f32<TA, TB, TC, KC, RC>(p, vec, grid, s);
   else if (al == RC && bl == KC) launch_f32<TA, TB, TC, RC, KC>(p, vec, grid, s);
   else launch_f32<TA, TB, TC, RC, RC>(p, vec, grid, s);
+  g_pcaa_gemm_last_kernel = PCAA_GEMM_KERNEL_F32_TILE128;
+}
+
+// the fp32 kernel's dtype combinations: the launcher, or nullptr where there is none
+typedef void (*f32_launcher_t)(const GemmParams&, int, int, bool, dim3, hipStream_t);
+f32_launcher_t f32_launcher(int a_dtype, int b_dtype, int c_dtype) {
+  if (a_dtype == PCAA_F32 && b_dtype == PCAA_F32 && c_dtype == PCAA_F32) return launch_f32_lay<float, float, float>;
+  if (a_dtype == PCAA_BF16 && b_dtype == PCAA_BF16 && c_dtype == PCAA_F32) return launch_f32_lay<bf16_t, bf16_t, float>;
+  if (a_dtype == PCAA_BF16 && b_dtype == PCAA_F32 && c_dtype == PCAA_F32) return launch_f32_lay<bf16_t, float, float>;
+  if (a_dtype == PCAA_F32 && b_dtype == PCAA_F32 && c_dtype == PCAA_BF16) return launch_f32_lay<float, float, bf16_t>;
+  return nullptr;
+}
+
+template <typename TB, typename TC>
+void launch_bf16_small(const GemmParams& p, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_bf16_kernel<bf16_t, TB, TC>), grid, dim3(256), 0, s, p);
+  g_pcaa_gemm_last_kernel = PCAA_GEMM_KERNEL_BF16_SMALL;
 }
 
 inline size_t esize(int dt) { return dt == PCAA_BF16 ? 2 : 4; }
@@ -405,13 +425,11 @@ extern "C" int pcaa_gemm_num_splits(int math, int K, int split_k) {
   return gemm_num_splits(math, K, split_k, nullptr);
 }
 
-static int gemm_impl(int math,
-                     const void* A, int a_dtype, int a_layout, long lda,
-                     const void* B, int b_dtype, int b_layout, long ldb,
-                     void* C, int c_dtype, long ldc,
-                     int M, int N, int K,
-                     const float* bias, double* colstats, int nrep,
-                     int split_k, int accumulate, long c_split_stride, void* stream) {
+// The plan step of pcaa_gemm / pcaa_gemm_slabs: every argument check and every decision.  Host arithmetic on the
+// arguments only -- the pointers are looked at for NULL and alignment -- so pcaa_gemm_route can run it without a device.
+static int gemm_plan(GemmPlan& pl, int math, const void* A, int a_dtype, int a_layout, long lda, const void* B, int b_dtype,
+                     int b_layout, long ldb, const void* C, int c_dtype, long ldc, int M, int N, int K, const float* bias,
+                     const double* colstats, int nrep, int split_k, int accumulate, long c_split_stride) {
   PCAA_CHECK_ARG(A && B && C, "pcaa_gemm: null operand");
   PCAA_CHECK_ARG(M > 0 && N > 0 && K > 0, "pcaa_gemm: bad shape M=%d N=%d K=%d", M, N, K);
   PCAA_CHECK_ARG(math == PCAA_F32 || math == PCAA_BF16, "pcaa_gemm: bad math %d", math);
@@ -425,12 +443,14 @@ static int gemm_impl(int math,
   PCAA_CHECK_ARG(!(atomic && colstats), "pcaa_gemm: column statistics need a single K pass");
   PCAA_CHECK_ARG(!colstats || nrep >= 1, "pcaa_gemm: nrep must be >= 1 with colstats");
 
-  GemmParams p;
+  pl.a_dtype = a_dtype; pl.a_layout = a_layout; pl.b_dtype = b_dtype; pl.b_layout = b_layout; pl.c_dtype = c_dtype;
+  pl.vec = false;
+  GemmParams& p = pl.p;
   memset(&p, 0, sizeof(p));
-  p.A = A; p.B = B; p.C = C;
+  p.A = A; p.B = B; p.C = const_cast<void*>(C);
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K;
-  p.bias = bias; p.colstats = colstats; p.nrep = nrep > 0 ? nrep : 1;
+  p.bias = bias; p.colstats = const_cast<double*>(colstats); p.nrep = nrep > 0 ? nrep : 1;
   p.atomic = atomic;
   p.nsplit = 1;
   p.split_fast = 0;
@@ -441,26 +461,17 @@ static int gemm_impl(int math,
   p.k_per_split = kps;
   const long ntiles = cdiv(M, BM) * cdiv(N, BN);
   PCAA_CHECK_ARG(ntiles < (1L << 31), "pcaa_gemm: too many tiles");
-  dim3 grid((unsigned)ntiles, 1, (unsigned)nsplit);
-  hipStream_t s = as_stream(stream);
+  pl.grid = dim3((unsigned)ntiles, 1, (unsigned)nsplit);
 
   if (math == PCAA_BF16) {
-    // big shapes: 256x256-tile kernel (KC x KC forward/dgrad, RC x RC wgrad)
-    if (pcaa_launch_gemm_bf16_big(p, a_dtype, a_layout, b_dtype, b_layout, c_dtype, nsplit, s))
-      PCAA_RETURN_LAUNCH_STATUS("pcaa_gemm(bf16, 256x256)");
+    // big shapes: the 256x256-tile kernels (KC x KC forward/dgrad, RC x RC wgrad)
+    if (pcaa_plan_gemm_bf16_big(pl, nsplit)) return PCAA_OK;
     PCAA_CHECK_ARG(a_dtype == PCAA_BF16, "pcaa_gemm: bf16 math on this shape needs a bf16 A operand");
     PCAA_CHECK_ARG(a_layout == KC && b_layout == KC, "pcaa_gemm: bf16 math on this shape needs KC operands");
     PCAA_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "pcaa_gemm: bf16 math needs K, lda, ldb %% 8 == 0");
     PCAA_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "pcaa_gemm: bf16 math needs 16-B aligned operands");
-    if (b_dtype == PCAA_BF16 && c_dtype == PCAA_BF16)
-      hipLaunchKernelGGL((gemm_bf16_kernel<bf16_t, bf16_t, bf16_t>), grid, dim3(256), 0, s, p);
-    else if (b_dtype == PCAA_BF16 && c_dtype == PCAA_F32)
-      hipLaunchKernelGGL((gemm_bf16_kernel<bf16_t, bf16_t, float>), grid, dim3(256), 0, s, p);
-    else if (b_dtype == PCAA_F32 && c_dtype == PCAA_BF16)
-      hipLaunchKernelGGL((gemm_bf16_kernel<bf16_t, float, bf16_t>), grid, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_bf16_kernel<bf16_t, float, float>), grid, dim3(256), 0, s, p);
-    PCAA_RETURN_LAUNCH_STATUS("pcaa_gemm(bf16)");
+    pl.kernel = PCAA_GEMM_KERNEL_BF16_SMALL;
+    return PCAA_OK;
   }
 
   // vector (4-element) staging is legal when every 4-chunk is aligned and
@@ -471,32 +482,68 @@ static int gemm_impl(int math,
     if (lay == KC) return (K % 4) == 0;
     return (rows % 4) == 0;
   };
-  const bool vec = vec_ok(A, a_dtype, a_layout, lda, M) && vec_ok(B, b_dtype, b_layout, ldb, N);
-
-  if (a_dtype == PCAA_F32 && b_dtype == PCAA_F32 && c_dtype == PCAA_F32)
-    launch_f32_lay<float, float, float>(p, a_layout, b_layout, vec, grid, s);
-  else if (a_dtype == PCAA_BF16 && b_dtype == PCAA_BF16 && c_dtype == PCAA_F32)
-    launch_f32_lay<bf16_t, bf16_t, float>(p, a_layout, b_layout, vec, grid, s);
-  else if (a_dtype == PCAA_BF16 && b_dtype == PCAA_F32 && c_dtype == PCAA_F32)
-    launch_f32_lay<bf16_t, float, float>(p, a_layout, b_layout, vec, grid, s);
-  else if (a_dtype == PCAA_F32 && b_dtype == PCAA_F32 && c_dtype == PCAA_BF16)
-    launch_f32_lay<float, float, bf16_t>(p, a_layout, b_layout, vec, grid, s);
-  else {
+  pl.vec = vec_ok(A, a_dtype, a_layout, lda, M) && vec_ok(B, b_dtype, b_layout, ldb, N);
+  if (f32_launcher(a_dtype, b_dtype, c_dtype) == nullptr) {
     pcaa_set_error("pcaa_gemm: unsupported dtype combination a=%d b=%d c=%d for fp32 math", a_dtype, b_dtype, c_dtype);
     return PCAA_ERR_INVALID_ARG;
   }
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_gemm(f32)");
+  pl.kernel = PCAA_GEMM_KERNEL_F32_TILE128;
+  return PCAA_OK;
 }
 
-extern "C" int pcaa_gemm(int math,
-                         const void* A, int a_dtype, int a_layout, long lda,
-                         const void* B, int b_dtype, int b_layout, long ldb,
-                         void* C, int c_dtype, long ldc,
-                         int M, int N, int K,
-                         const float* bias, double* colstats, int nrep,
-                         int split_k, int accumulate, void* stream) {
-  return gemm_impl(math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, C, c_dtype, ldc, M, N, K, bias,
-                   colstats, nrep, split_k, accumulate, 0, stream);
+// The launch step of every product entry point: the planned kernel, on the existing instantiations.
+static int gemm_launch(const GemmPlan& pl, const char* what, hipStream_t s) {
+  static const char* const names[] = {"pcaa_gemm(f32)", "pcaa_gemm(bf16)", "pcaa_gemm(bf16, 256x256)"};
+  if (what == nullptr) what = names[pl.kernel < 2 ? pl.kernel : 2];
+  if (pl.kernel == PCAA_GEMM_KERNEL_F32_TILE128) {
+    f32_launcher(pl.a_dtype, pl.b_dtype, pl.c_dtype)(pl.p, pl.a_layout, pl.b_layout, pl.vec, pl.grid, s);
+  } else if (pl.kernel == PCAA_GEMM_KERNEL_BF16_SMALL) {
+    if (pl.b_dtype == PCAA_BF16)
+      (pl.c_dtype == PCAA_BF16 ? launch_bf16_small<bf16_t, bf16_t> : launch_bf16_small<bf16_t, float>)(pl.p, pl.grid, s);
+    else
+      (pl.c_dtype == PCAA_BF16 ? launch_bf16_small<float, bf16_t> : launch_bf16_small<float, float>)(pl.p, pl.grid, s);
+  } else if (!pcaa_launch_gemm_bf16_big(pl, s)) {
+    pcaa_set_error("%s: launch configuration failed", what);
+    return PCAA_ERR_LAUNCH;
+  }
+  PCAA_RETURN_LAUNCH_STATUS(what);
+}
+
+extern "C" int pcaa_gemm(int math, const void* A, int a_dtype, int a_layout, long lda, const void* B, int b_dtype, int b_layout,
+                         long ldb, void* C, int c_dtype, long ldc, int M, int N, int K, const float* bias, double* colstats,
+                         int nrep, int split_k, int accumulate, void* stream) {
+  GemmPlan pl;
+  const int rc = gemm_plan(pl, math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, C, c_dtype, ldc, M, N, K, bias,
+                           colstats, nrep, split_k, accumulate, 0);
+  return rc != PCAA_OK ? rc : gemm_launch(pl, nullptr, as_stream(stream));
+}
+
+// split-K without atomics: split s writes its partial product to slabs + s * slab_stride
+static int gemm_slabs_plan(GemmPlan& pl, int math, const void* A, int a_dtype, int a_layout, long lda, const void* B, int b_dtype,
+                           int b_layout, long ldb, const void* slabs, long slab_stride, int M, int N, int K, int split_k) {
+  PCAA_CHECK_ARG(slabs && slab_stride >= (long)M * N, "pcaa_gemm_slabs: slab stride must cover an M x N tile");
+  return gemm_plan(pl, math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, slabs, PCAA_F32, N, M, N, K, nullptr,
+                   nullptr, 0, split_k, 0, slab_stride);
+}
+
+extern "C" int pcaa_gemm_slabs(int math,
+                               const void* A, int a_dtype, int a_layout, long lda,
+                               const void* B, int b_dtype, int b_layout, long ldb,
+                               float* slabs, long slab_stride, int M, int N, int K, int split_k, void* stream) {
+  GemmPlan pl;
+  const int rc = gemm_slabs_plan(pl, math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, slabs, slab_stride, M, N, K, split_k);
+  return rc != PCAA_OK ? rc : gemm_launch(pl, nullptr, as_stream(stream));
+}
+
+extern "C" int pcaa_gemm_route(int math, const void* A, int a_dtype, int a_layout, long lda, const void* B, int b_dtype,
+                               int b_layout, long ldb, const void* C, int c_dtype, long ldc, int M, int N, int K, const float* bias,
+                               const double* colstats, int nrep, int split_k, int accumulate, long slab_stride) {
+  GemmPlan pl;
+  const int rc = slab_stride != 0
+      ? gemm_slabs_plan(pl, math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, C, slab_stride, M, N, K, split_k)
+      : gemm_plan(pl, math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, C, c_dtype, ldc, M, N, K, bias, colstats,
+                  nrep, split_k, accumulate, 0);
+  return rc != PCAA_OK ? -1 : pl.kernel;
 }
 
 /* n <= 8 products C_i[M_i, N_i] += A_i^T . B_i in one launch: A_i [K_i, M_i], B_i [K_i, N_i], C_i [M_i, N_i] fp32, contiguous
@@ -547,16 +594,6 @@ extern "C" int pcaa_gemm_group_rc_f32_slabs(int n, const void* const* A, const v
   return gemm_group_rc_f32(n, A, B, slabs, M, N, K, split_k, true, stream);
 }
 
-// split-K without atomics: split s writes its partial product to slabs + s * slab_stride
-extern "C" int pcaa_gemm_slabs(int math,
-                               const void* A, int a_dtype, int a_layout, long lda,
-                               const void* B, int b_dtype, int b_layout, long ldb,
-                               float* slabs, long slab_stride, int M, int N, int K, int split_k, void* stream) {
-  PCAA_CHECK_ARG(slabs && slab_stride >= (long)M * N, "pcaa_gemm_slabs: slab stride must cover an M x N tile");
-  return gemm_impl(math, A, a_dtype, a_layout, lda, B, b_dtype, b_layout, ldb, slabs, PCAA_F32, N, M, N, K, nullptr,
-                   nullptr, 0, split_k, 0, slab_stride, stream);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Split product (round 3): both fp32 operands are given as [hi | lo] fp16 images (pcaa_split_f16:
 // hi = fp16(s e), lo = fp16(s e - hi), s a power of two) and the product is hi.hi + lo.hi + hi.lo on the f16 MFMA
@@ -565,31 +602,36 @@ extern "C" int pcaa_gemm_slabs(int math,
 // MFMA.  (A bf16 pair carries 16 mantissa bits: 4.5e-6 per product, and the first PointNet layer's weight gradient
 // missed the 5e-4 gate at 5.7e-4; the fp16 pair carries 22.)  out_scale = 1 / (s_A s_B).  KC operands: [rows, 2K] (lo at column K + k); RC operands: [K, 2 rows] (lo at column rows + r).
 // ---------------------------------------------------------------------------------------------------------------
-bool pcaa_gemm_v2_is_enabled();      // gemm_bf16.hip
-// M need not be a multiple of 256 where the 4-wave tile loop serves the launch (round 4: it reads the rows past M as
-// zeros and skips them on the way out): contraction >= 320 deep, KC operands
-//  the predicates and the entry points' argument checks together state everything launch_dma asks of a
-// ragged launch, so that a shape reported as supported cannot end in PCAA_ERR_LAUNCH: the result (and the fused dgrad's
-// y) is addressed through 32-bit buffer offsets over ceil(M / 256) * 256 rows (the rows past M wrap otherwise), its
-// leading dimension is a multiple of 8 elements and 16-B aligned, and the first-layer recompute variant
-// (pcaa_gemm_dgrad_bn with x) has no ragged instantiation.
-static bool ragged_m_ok(int M, int N, int K) {
-  // N columns of at most 4 bytes: the predicate's bound; the entry points re-check with the real ld and element size
-  return pcaa_gemm_v2_is_enabled() && K >= 320 && (long)cdiv(M, 256) * 256 * N * 4 < (1L << 32);
+// The 4-wave KC x KC loop's answer (pcaa_gemm_4wave_kernel) for the canonical operands the predicates assume: images with
+// ld = row length on aligned bases, one pass over the K_walked-deep contraction, the plain epilogue; the result [M, ldc]
+// of ``elem`` bytes per element at C.  M need not be a multiple of 256 (round 4: the loop reads the rows past M as zeros
+// and skips them on the way out).   With the entry points' argument checks this states everything the
+// loop asks, so that a shape reported as supported cannot end in PCAA_ERR_LAUNCH.
+static bool v2_kc_takes(int M, int N, long K_walked, int seg_len, const void* C, long ldc, int elem) {
+  GemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.M = M; p.N = N;
+  p.K = (int)(K_walked < (1L << 31) ? K_walked : (1L << 31) - 64 + K_walked % 64);      // (beyond int: the entry points refuse such a K by name)
+  p.seg_len = seg_len;
+  p.k_per_split = p.K;
+  p.nsplit = 1;
+  p.C = const_cast<void*>(C); p.ldc = ldc;
+  return pcaa_gemm_4wave_kernel(p, KC, elem, EPI_PLAIN) == PCAA_GEMM_KERNEL_V2_KC;
 }
+// the output conditions alone -- ldc % 8 == 0, a 16-B aligned C, ceil(M / 256) * 256 * ldc * elem < 4 GiB -- asked at the
+// smallest shape the loop takes.  (Every caller has asked a *_supported predicate first: the lab switch decides there.)
 static bool ragged_out_ok(int M, const void* C, long ldc, int elem) {
-  return (M % 256) == 0 || ((ldc % 8) == 0 && ((uintptr_t)C % 16) == 0 && (long)cdiv(M, 256) * 256 * ldc * elem < (1L << 32));
+  return (M % 256) == 0 || v2_kc_takes(M, 256, 320, 0, C, ldc, elem);
 }
-// (round 5: the 4-wave loops are the only LDS-DMA kernels left -- a contraction of at least five 64-deep steps, three
-// K-long passes for the split operands)
+// (bounded by N columns of 4 bytes; the entry points re-check with the real ld and element size.  A partial last row
+// tile of split operands asks K >= 320 of ONE pass, more than the loop's 3 K >= 320: kept as it was.)
 extern "C" int pcaa_gemm_split3_supported(int M, int N, int K) {
-  return M > 0 && N > 0 && K > 0 && pcaa_gemm_v2_is_enabled() && 3L * K >= 320 &&
-         ((M % 256) == 0 || ragged_m_ok(M, N, K)) && (N % 256) == 0 && (K % 64) == 0;
+  return M > 0 && N > 0 && K > 0 && v2_kc_takes(M, N, 3L * K, K, nullptr, N, 4) && ((M % 256) == 0 || K >= 320);
 }
 
-static int gemm_split3_impl(const void* A, const void* B, int layout, long lda, long ldb, void* C, long ldc, int M, int N,
-                            int K, double* colstats, int nrep, int split_k, long c_split_stride, float out_scale,
-                            void* stream) {
+static int gemm_split3_plan(GemmPlan& pl, const void* A, const void* B, int layout, long lda, long ldb, const void* C,
+                            long ldc, int M, int N, int K, const double* colstats, int nrep, int split_k,
+                            long c_split_stride, float out_scale) {
   PCAA_CHECK_ARG(A && B && C, "pcaa_gemm_split3: null operand");
   PCAA_CHECK_ARG(layout == KC || layout == RC, "pcaa_gemm_split3: bad layout");
   PCAA_CHECK_ARG(pcaa_gemm_split3_supported(M, N, K) && (layout == KC || (M % 256) == 0),
@@ -605,12 +647,14 @@ static int gemm_split3_impl(const void* A, const void* B, int layout, long lda, 
                  "pcaa_gemm_split3: leading dimensions must cover the [hi | lo] images");
   PCAA_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "pcaa_gemm_split3: 16-B aligned operands");
   PCAA_CHECK_ARG(!(colstats && (split_k > 1 || c_split_stride)), "pcaa_gemm_split3: column statistics need a single K pass");
-  GemmParams p;
+  pl.a_dtype = pl.b_dtype = PCAA_BF16; pl.a_layout = pl.b_layout = layout; pl.c_dtype = PCAA_F32;
+  pl.vec = false;
+  GemmParams& p = pl.p;
   memset(&p, 0, sizeof(p));
-  p.A = A; p.B = B; p.C = C;
+  p.A = A; p.B = B; p.C = const_cast<void*>(C);
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.M = M; p.N = N; p.K = 3 * K;
-  p.colstats = colstats; p.nrep = nrep > 0 ? nrep : 1;
+  p.colstats = const_cast<double*>(colstats); p.nrep = nrep > 0 ? nrep : 1;
   p.seg_len = K;
   p.out_scale = out_scale;
   const long half_a = layout == KC ? K : M, half_b = layout == KC ? K : N;
@@ -622,11 +666,27 @@ static int gemm_split3_impl(const void* A, const void* B, int layout, long lda, 
   const int nsplit = gemm_num_splits(PCAA_BF16, 3 * K, split_k, &kps);
   p.k_per_split = kps;
   const long ntiles = cdiv(M, 256) * cdiv(N, 256);
-  if (!pcaa_launch_gemm_bf16_big(p, PCAA_BF16, layout, PCAA_BF16, layout, PCAA_F32, nsplit, as_stream(stream))) {
+  if (!pcaa_plan_gemm_bf16_big(pl, nsplit)) {
     pcaa_set_error("pcaa_gemm_split3: shape not served by the LDS-DMA kernel (ntiles %ld, nsplit %d)", ntiles, nsplit);
     return PCAA_ERR_INVALID_ARG;
   }
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_gemm_split3");
+  return PCAA_OK;
+}
+
+static int gemm_split3_impl(const void* A, const void* B, int layout, long lda, long ldb, void* C, long ldc, int M, int N,
+                            int K, double* colstats, int nrep, int split_k, long c_split_stride, float out_scale,
+                            void* stream) {
+  GemmPlan pl;
+  const int rc = gemm_split3_plan(pl, A, B, layout, lda, ldb, C, ldc, M, N, K, colstats, nrep, split_k, c_split_stride, out_scale);
+  return rc != PCAA_OK ? rc : gemm_launch(pl, "pcaa_gemm_split3", as_stream(stream));
+}
+
+extern "C" int pcaa_gemm_split3_route(const void* A, const void* B, int layout, long lda, long ldb, const void* C, long ldc,
+                                      int M, int N, int K, const double* colstats, int nrep, int split_k,
+                                      long c_split_stride, float out_scale) {
+  GemmPlan pl;
+  const int rc = gemm_split3_plan(pl, A, B, layout, lda, ldb, C, ldc, M, N, K, colstats, nrep, split_k, c_split_stride, out_scale);
+  return rc != PCAA_OK ? -1 : pl.kernel;
 }
 
 extern "C" int pcaa_gemm_split3(const void* A, const void* B, int layout, long lda, long ldb, float* C, long ldc, int M,
@@ -646,8 +706,7 @@ extern "C" int pcaa_gemm_slabs_split3(const void* A, const void* B, int layout, 
 }
 
 extern "C" int pcaa_gemm_dgrad_bn_supported(int M, int N, int K) {
-  return M > 0 && N > 0 && K >= 320 && pcaa_gemm_v2_is_enabled() && ((M % 256) == 0 || ragged_m_ok(M, N, K)) &&
-         (N % 256) == 0 && (K % 64) == 0;
+  return M > 0 && N > 0 && K > 0 && v2_kc_takes(M, N, K, 0, nullptr, N, 4);
 }
 
 extern "C" int pcaa_gemm_dgrad_bn(const void* dy, long lddy, const void* Wt, long ldw, const void* y, void* dz,

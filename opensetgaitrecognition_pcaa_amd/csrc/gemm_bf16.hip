@@ -314,9 +314,6 @@ __device__ __forceinline__ void piece_lane_offsets(long ld, int lane, unsigned (
 // workgroup barrier that leaves vector-memory operations (the next tile's LDS-DMA pieces, this tile's C stores) alone
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// what leaves the kernel
-enum { EPI_PLAIN = 0, EPI_DGRAD_BN = 1, EPI_AFFINE = 3, EPI_POOL1 = 4, EPI_POOL2 = 5, EPI_POOL4 = 6 };
-
 // per-lane element offset of fragment rows [row_base, row_base+32) at k-step 0 (row_base % 32 == 0), 32x32x16 shape
 template <int LAY>
 __device__ __forceinline__ int dma_frag_offset(int row_base, int lane) {
@@ -329,11 +326,9 @@ __device__ __forceinline__ int dma_frag_offset(int row_base, int lane) {
 #include "gemm_v2.h"      // the 4-wave tile loops (namespace v2)
 
 
-// The 4-wave tile loop (gemm_v2.h) serves every KC x KC launch without K splits whose contraction is at least five
-// 64-deep steps long (its ticket hand-off needs four of them); pcaa_gemm_v2_enable(0) declines them all (lab A/B against
-// the register-staged kernel; the fused entry points then report their shapes unsupported).
+// pcaa_gemm_v2_enable(0): the 4-wave tile loops (gemm_v2.h) decline every launch (lab A/B against the register-staged
+// kernel; the fused entry points then report their shapes unsupported).  The rule itself: pcaa_gemm_4wave_kernel below.
 static int g_v2_enabled = -1;
-bool pcaa_gemm_v2_is_enabled();
 static bool v2_enabled() {
   if (g_v2_enabled < 0) {
     const char* e = getenv("PCAA_GEMM_V2");
@@ -341,50 +336,42 @@ static bool v2_enabled() {
   }
   return g_v2_enabled != 0;
 }
+// one launch of a 4-wave loop: its LDS opted into once per instantiation, armed timing events attached to the dispatch
+template <typename Kern>
+bool launch_v2(Kern kern, bool& configured, int id, const GemmParams& p, dim3 grid, hipStream_t s) {
+  if (!configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            v2::LDS_BYTES) != hipSuccess)
+      return false;
+    configured = true;
+  }
+  const PcaaLaunchEvents ev = pcaa_take_launch_events();
+  if (ev.start != nullptr)
+    hipExtLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, ev.start, ev.stop, 0, p);
+  else
+    hipLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, p);
+  g_pcaa_gemm_last_kernel = id;
+  return true;
+}
 template <typename TC, int EPI, bool SPLIT, bool RAG>
 bool launch_v2_rag(const GemmParams& p, dim3 grid, hipStream_t s) {
   static bool configured = false;
-  auto kern = v2::gemm_bf16_v2_kernel<TC, EPI, SPLIT, RAG>;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            v2::LDS_BYTES) != hipSuccess)
-      return false;
-    configured = true;
-  }
-  const PcaaLaunchEvents ev = pcaa_take_launch_events();
-  if (ev.start != nullptr)
-    hipExtLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, ev.start, ev.stop, 0, p);
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, p);
-  return true;
+  return launch_v2(v2::gemm_bf16_v2_kernel<TC, EPI, SPLIT, RAG>, configured, PCAA_GEMM_KERNEL_V2_KC, p, grid, s);
 }
-
+template <typename TC, int EPI, bool SPLIT>      // (RAG: a partial last row tile)
+bool launch_v2_inst(const GemmParams& p, dim3 grid, hipStream_t s) {
+  return (p.M % BM) != 0 ? launch_v2_rag<TC, EPI, SPLIT, true>(p, grid, s) : launch_v2_rag<TC, EPI, SPLIT, false>(p, grid, s);
+}
 template <bool SPLIT>
 bool launch_v2rc(const GemmParams& p, dim3 grid, hipStream_t s) {
   static bool configured = false;
-  auto kern = v2::gemm_bf16_v2rc_kernel<SPLIT>;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            v2::LDS_BYTES) != hipSuccess)
-      return false;
-    configured = true;
-  }
-  const PcaaLaunchEvents ev = pcaa_take_launch_events();
-  if (ev.start != nullptr)
-    hipExtLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, ev.start, ev.stop, 0, p);
-  else
-    hipLaunchKernelGGL(kern, grid, dim3(v2::NT), v2::LDS_BYTES, s, p);
-  return true;
+  return launch_v2(v2::gemm_bf16_v2rc_kernel<SPLIT>, configured, PCAA_GEMM_KERNEL_V2_RC, p, grid, s);
 }
 
-template <typename TC, int EPI, bool SPLIT>
-bool launch_v2_inst(const GemmParams& p, dim3 grid, hipStream_t s) {
-  // a partial last row tile stores (and, fused dgrad, reads y) through 32-bit buffer offsets over the whole matrix; the
-  // epilogues form offsets for every row of the last tile, also those past M, which the buffer's range check only
-  // drops as long as they do not wrap: the bound is on the PADDED row count
-  if ((p.M % BM) != 0 && (long)cdiv(p.M, BM) * BM * p.ldc * (long)sizeof(TC) >= (1L << 32)) return false;
-  return (p.M % BM) != 0 ? launch_v2_rag<TC, EPI, SPLIT, true>(p, grid, s) : launch_v2_rag<TC, EPI, SPLIT, false>(p, grid, s);
-}
+// the instantiations of the KC x KC loop that exist: split operands leave as fp32 through the plain or the fused-dgrad
+// epilogue; plain operands through every epilogue, except that fp32 dz exists for the split operands only
+constexpr bool v2_split_inst(int c_bytes, int epi) { return c_bytes == 4 && (epi == EPI_PLAIN || epi == EPI_DGRAD_BN); }
+constexpr bool v2_plain_inst(int c_bytes, int epi) { return !(epi == EPI_DGRAD_BN && c_bytes == 4); }
 
 // Launches without K splits start one workgroup per CU (a multiple of 8: the XCD-aware tile order) and let them draw
 // their tiles: no dispatch gap between a CU's tiles, and the next tile's first stages are requested before the
@@ -454,50 +441,26 @@ bool launch_dma(const GemmParams& p_in, dim3 grid_in, hipStream_t s) {
     if ((EPI == EPI_PLAIN || EPI == EPI_DGRAD_BN) && p.colstats != nullptr && grid.y == 1)
       p.tail = pcaa_take_bn_tail(p.colstats);
   }
-  // buffer addressing needs each operand below 4 GiB (32-bit offsets); the flat form serves anything larger.  Same-box
-  // A/B (profiles/r02_gemm_lab2.txt): forward / fused dgrad +1..3 %, wgrad (whole stage issued at the top of the step:
-  // 8 pieces x ~7 VALU each in front of the first MFMA) +2.6 / +7.3 / +10.1 % on the three PointNet shapes.
-  const int krows = p.seg_len > 0 ? p.seg_len : p.K;
-  const long a_bytes = (long)(ALAY == KC ? p.M : krows) * p.lda * 2, b_bytes = (long)(BLAY == KC ? p.N : krows) * p.ldb * 2;
-  const bool buf = a_bytes < (1L << 32) && b_bytes < (1L << 32);
   // (advisor, round 3) every path that does not launch hands the tail back: resolve() then runs the stand-alone finalize
   bool ok = false;
-  bool decided = false;
+  const int kernel = pcaa_gemm_4wave_kernel(p, ALAY, (int)sizeof(TC), EPI);
   if constexpr (ALAY == KC && BLAY == KC) {
     // PCAA_GEMM_TICKETS=0: fixed tile shares in the 4-wave loop (A/B of the ticket draw's once-per-tile drain)
     static const bool tickets = [] { const char* e = getenv("PCAA_GEMM_TICKETS"); return !(e != nullptr && e[0] == '0'); }();
     if (!tickets) p.sched = nullptr;
-    const int steps = (p.seg_len > 0 ? 3 * p.seg_len : p.K) / BK;
-    constexpr bool kSplitOk = sizeof(TC) == 4 && (EPI == EPI_PLAIN || EPI == EPI_DGRAD_BN);
-    constexpr bool kPlainOk = !(EPI == EPI_DGRAD_BN && sizeof(TC) == 4);      // fp32 dz exists for the split operands only
-    if (v2_enabled() && grid.z == 1 && grid.y == 1 && !p.split_fast && !p.atomic && p.nsplit <= 1 && p.c_split_stride == 0 &&
-        steps >= 5 && (p.seg_len > 0 ? p.k_per_split == p.K : (p.k_per_split >= p.K)) && (p.ldc % 8) == 0 &&
-        ((uintptr_t)p.C % 16) == 0) {
+    if (kernel == PCAA_GEMM_KERNEL_V2_KC) {
       if (p.seg_len > 0) {
-        if constexpr (kSplitOk) {
-          ok = launch_v2_inst<TC, EPI, true>(p, grid, s);
-          decided = true;
-        }
+        if constexpr (v2_split_inst(sizeof(TC), EPI)) ok = launch_v2_inst<TC, EPI, true>(p, grid, s);
       } else {
-        if constexpr (kPlainOk) {
-          ok = launch_v2_inst<TC, EPI, false>(p, grid, s);
-          decided = true;
-        }
+        if constexpr (v2_plain_inst(sizeof(TC), EPI)) ok = launch_v2_inst<TC, EPI, false>(p, grid, s);
       }
     }
   }
   if constexpr (ALAY == RC && BLAY == RC && EPI == EPI_PLAIN && sizeof(TC) == 4) {
     // the weight gradients (slab split-K or a single K pass, no atomics): the 4-wave loop on the RC images
-    static const bool rc_on = [] { const char* e = getenv("PCAA_GEMM_V2_RC"); return !(e != nullptr && e[0] == '0'); }();
-    if (v2_enabled() && rc_on && !p.atomic && (p.M % BM) == 0 && (p.N % BN) == 0 && (p.k_per_split % BK) == 0 && buf &&
-        (p.ldc % 1) == 0 && p.colstats == nullptr && p.bias == nullptr) {
-      ok = p.seg_len > 0 ? launch_v2rc<true>(p, grid, s) : launch_v2rc<false>(p, grid, s);
-      decided = true;
-    }
+    if (kernel == PCAA_GEMM_KERNEL_V2_RC) ok = p.seg_len > 0 ? launch_v2rc<true>(p, grid, s) : launch_v2rc<false>(p, grid, s);
   }
-  // (anything else -- a contraction shorter than five steps, K splits with atomics, a partial tile the loop cannot take --
-  // is declined: the caller falls back to the register-staged kernel, the fused entry points report the shape unsupported)
-  (void)decided;
+  // (anything else is declined: the fused entry points report the shape unsupported)
   if (!ok) pcaa_rearm_bn_tail(p.tail);
   return ok;
 }
@@ -513,15 +476,67 @@ bool launch(const GemmParams& p, dim3 grid, hipStream_t s) {
     configured = true;
   }
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), LDS_BYTES, s, p);
+  g_pcaa_gemm_last_kernel = PCAA_GEMM_KERNEL_BF16_STAGED;
   return true;
+}
+
+// the register-staged kernel's instantiations: its launcher, or nullptr where there is none
+typedef bool (*staged_launcher_t)(const GemmParams&, dim3, hipStream_t);
+staged_launcher_t staged_launcher(int a_dtype, int a_layout, int b_dtype, int b_layout, int c_dtype) {
+  const bool af = a_dtype == PCAA_F32, bf = b_dtype == PCAA_F32, cf = c_dtype == PCAA_F32;
+  if (a_layout == KC && b_layout == KC) {
+    // bf16 activations x fp32/bf16 weights (PointNet forward / dgrad), fp32 x fp32 (decoder forward)
+    if (!af && bf && !cf) return launch<bf16_t, float, bf16_t, KC, KC>;
+    if (!af && bf && cf) return launch<bf16_t, float, float, KC, KC>;
+    if (!af && !bf && !cf) return launch<bf16_t, bf16_t, bf16_t, KC, KC>;
+    if (!af && !bf && cf) return launch<bf16_t, bf16_t, float, KC, KC>;
+    if (af && bf && cf) return launch<float, float, float, KC, KC>;
+  } else if (a_layout == RC && b_layout == RC) {
+    // wgrad: contraction over rows
+    if (!af && !bf && cf) return launch<bf16_t, bf16_t, float, RC, RC>;
+    if (af && bf && cf) return launch<float, float, float, RC, RC>;
+  } else if (a_layout == KC && b_layout == RC) {
+    // decoder dgrad: dX = dY . W with W stored [out, in]
+    if (af && bf && cf) return launch<float, float, float, KC, RC>;
+  }
+  return nullptr;
 }
 
 }  // namespace
 
+// The 4-wave tile loops (gemm_v2.h), the only LDS-DMA kernels (round 5).  The caller vouches for bf16 (or split-fp16)
+// operands of one layout; everything else the loops ask of a launch is here.
+int pcaa_gemm_4wave_kernel(const GemmParams& p, int layout, int c_bytes, int epi) {
+  if (!v2_enabled() || (p.N % BN) != 0 || (p.K % BK) != 0 || (p.k_per_split % BK) != 0) return -1;      // whole column tiles and K steps
+  if (layout == KC) {
+    // one K pass (no K splits, atomics or slabs) of at least five 64-deep steps: the ticket hand-off needs four of them
+    // (split operands walk K = 3 seg_len); the result on a 16-B aligned base with a leading dimension of whole 8-chunks
+    const int steps = p.K / BK;
+    // a partial last row tile stores (and, fused dgrad, reads y) through 32-bit buffer offsets over the whole matrix; the
+    // epilogues form offsets for every row of the last tile, also those past M, which the buffer's range check only
+    // drops as long as they do not wrap: the bound is on the PADDED row count
+    const bool rows_ok = (p.M % BM) == 0 || (long)cdiv(p.M, BM) * BM * p.ldc * c_bytes < (1L << 32);
+    return (!p.split_fast && !p.atomic && p.nsplit <= 1 && p.c_split_stride == 0 && steps >= 5 &&
+            (p.seg_len > 0 ? p.k_per_split == p.K : (p.k_per_split >= p.K)) && (p.ldc % 8) == 0 && ((uintptr_t)p.C % 16) == 0 &&
+            (p.seg_len > 0 ? v2_split_inst(c_bytes, epi) : v2_plain_inst(c_bytes, epi)) && rows_ok)
+               ? PCAA_GEMM_KERNEL_V2_KC : -1;
+  }
+  // RC x RC -> fp32, plain epilogue (the weight gradients): slab split-K or a single K pass of any length over whole
+  // tiles -- no atomics, bias or column statistics
+  static const bool rc_on = [] { const char* e = getenv("PCAA_GEMM_V2_RC"); return !(e != nullptr && e[0] == '0'); }();
+  // buffer addressing needs each operand below 4 GiB (32-bit offsets); the flat form of the register-staged kernel serves
+  // anything larger.  Same-box A/B (profiles/r02_gemm_lab2.txt): forward / fused dgrad +1..3 %, wgrad (whole stage issued
+  // at the top of the step: 8 pieces x ~7 VALU each in front of the first MFMA) +2.6 / +7.3 / +10.1 % on the three
+  // PointNet shapes.
+  const int krows = p.seg_len > 0 ? p.seg_len : p.K;
+  const bool buf = (long)krows * p.lda * 2 < (1L << 32) && (long)krows * p.ldb * 2 < (1L << 32);
+  return (epi == EPI_PLAIN && c_bytes == 4 && rc_on && !p.atomic && (p.M % BM) == 0 && buf && p.colstats == nullptr &&
+          p.bias == nullptr) ? PCAA_GEMM_KERNEL_V2_RC : -1;
+}
+
 // dgrad + BatchNorm/ELU backward of the layer below (pcaa_gemm_dgrad_bn): whole 256x256 tiles, bf16 KC x KC
 bool pcaa_launch_gemm_dgrad_bn(const GemmParams& p_in, hipStream_t stream) {
   GemmParams p = p_in;
-  if ((p.N % BN) || (p.K % BK)) return false;      // (M: a partial last row tile is the 4-wave loop's; launch_dma refuses it otherwise)
   p.nsplit = 1;
   p.split_fast = 0;
   p.k_per_split = p.K;
@@ -529,20 +544,15 @@ bool pcaa_launch_gemm_dgrad_bn(const GemmParams& p_in, hipStream_t stream) {
   p.c_split_stride = 0;
   const long ntiles = cdiv(p.M, BM) * (p.N / BN);
   if (ntiles >= (1L << 31)) return false;
-  if (p.seg_len > 0) {
-    // split-fp16 operands: K is the contraction length of ONE pass (the kernel walks 3 K); y and dz fp32
-    if (p.ep_y == nullptr) return false;
-    p.k_per_split = p.K;
-    return launch_dma<float, KC, KC, EPI_DGRAD_BN>(p, dim3((unsigned)ntiles, 1, 1), stream);
-  }
   if (p.ep_y == nullptr) return false;
-  return launch_dma<bf16_t, KC, KC, EPI_DGRAD_BN>(p, dim3((unsigned)ntiles, 1, 1), stream);
+  // (split-fp16 operands: y and dz fp32)
+  return p.seg_len > 0 ? launch_dma<float, KC, KC, EPI_DGRAD_BN>(p, dim3((unsigned)ntiles, 1, 1), stream)
+                       : launch_dma<bf16_t, KC, KC, EPI_DGRAD_BN>(p, dim3((unsigned)ntiles, 1, 1), stream);
 }
 
 // product + eval-mode BatchNorm + ELU (pcaa_gemm_affine_elu): whole 256x256 tiles, bf16 KC x KC -> bf16
 bool pcaa_launch_gemm_affine_elu(const GemmParams& p_in, hipStream_t stream) {
   GemmParams p = p_in;
-  if ((p.N % BN) || (p.K % BK)) return false;
   p.nsplit = 1;
   p.split_fast = 0;
   p.k_per_split = p.K;
@@ -561,15 +571,14 @@ bool pcaa_launch_gemm_affine_elu(const GemmParams& p_in, hipStream_t stream) {
   }
 }
 
-bool pcaa_launch_gemm_bf16_big(const GemmParams& p_in, int a_dtype, int a_layout, int b_dtype, int b_layout,
-                               int c_dtype, int nsplit, hipStream_t stream) {
-  GemmParams p = p_in;
+bool pcaa_plan_gemm_bf16_big(GemmPlan& pl, int nsplit) {
+  GemmParams p = pl.p;
   if (p.N < 128) return false;
   if ((p.lda % 8) || (p.ldb % 8) || ((uintptr_t)p.A % 16) || ((uintptr_t)p.B % 16)) return false;
   // a KC operand needs whole 8-chunks along K, an RC operand whole 8-chunks along its rows
-  if ((a_layout == KC || b_layout == KC) && (p.K % 8)) return false;
-  if (a_layout == RC && (p.M % 8)) return false;
-  if (b_layout == RC && (p.N % 8)) return false;
+  if ((pl.a_layout == KC || pl.b_layout == KC) && (p.K % 8)) return false;
+  if (pl.a_layout == RC && (p.M % 8)) return false;
+  if (pl.b_layout == RC && (p.N % 8)) return false;
   const long ntiles = cdiv(p.M, BM) * cdiv(p.N, BN);
   if (ntiles * nsplit >= (1L << 31)) return false;
   p.nsplit = nsplit;
@@ -581,49 +590,37 @@ bool pcaa_launch_gemm_bf16_big(const GemmParams& p_in, int a_dtype, int a_layout
   p.split_fast = (p.c_split_stride != 0 && nsplit >= 8 && nsplit % 8 == 0 && ntiles * nsplit >= 256) ? 1 : 0;
   dim3 grid((unsigned)ntiles, 1, (unsigned)nsplit);
   if (p.split_fast) grid = dim3((unsigned)(ntiles * nsplit), 1, 1);
-  const bool af = a_dtype == PCAA_F32, bf = b_dtype == PCAA_F32, cf = c_dtype == PCAA_F32;
-  // LDS-DMA kernel: bf16 x bf16, whole tiles only
-  // (a partial last row tile: KC x KC without K splits through the 4-wave loop; launch_dma returns false otherwise and
-  // the register-staged kernels below take the shape as before)
-  const bool m_ok = (p.M % BM) == 0 || (a_layout == KC && nsplit == 1 && v2_enabled() && p.K / BK >= 5 && !p.atomic &&
-                                        p.c_split_stride == 0);
-  if (!af && !bf && m_ok && (p.N % BN) == 0 && (p.K % BK) == 0 && (p.k_per_split % BK) == 0 &&
-      a_layout == b_layout) {
-    if (a_layout == KC) {
-      // (declined -- a contraction shorter than five steps, K splits, a partial last row tile it cannot address: the
-      // register-staged kernel below)
-      if (cf ? launch_dma<float, KC, KC, EPI_PLAIN>(p, grid, stream) : launch_dma<bf16_t, KC, KC, EPI_PLAIN>(p, grid, stream))
-        return true;
-    } else if (cf) {
-      // (declined -- atomics, a partial tile, an operand beyond 4 GiB: the register-staged kernel below)
-      if (launch_dma<float, RC, RC, EPI_PLAIN>(p, grid, stream)) return true;
-    }
+  // the 4-wave LDS-DMA loops: bf16 x bf16 of one layout; what they decline -- a contraction shorter than five steps, K
+  // splits with atomics, a partial tile they cannot address, an operand beyond 4 GiB -- is the register-staged kernel's
+  int kernel = -1;
+  if (pl.a_dtype == PCAA_BF16 && pl.b_dtype == PCAA_BF16 && pl.a_layout == pl.b_layout)
+    kernel = pcaa_gemm_4wave_kernel(p, pl.a_layout, pl.c_dtype == PCAA_F32 ? 4 : 2, EPI_PLAIN);
+  if (kernel < 0) {
+    // (split-fp16 operands are served by the LDS-DMA loops only)
+    if (p.seg_len > 0 || staged_launcher(pl.a_dtype, pl.a_layout, pl.b_dtype, pl.b_layout, pl.c_dtype) == nullptr) return false;
+    kernel = PCAA_GEMM_KERNEL_BF16_STAGED;
   }
-  if (p.seg_len > 0) return false;       // split-fp16 operands are served by the LDS-DMA kernel only
-  if (a_layout == KC && b_layout == KC) {
-    // bf16 activations x fp32/bf16 weights (PointNet forward / dgrad), fp32 x fp32 (decoder forward)
-    if (!af && bf && !cf) return launch<bf16_t, float, bf16_t, KC, KC>(p, grid, stream);
-    if (!af && bf && cf) return launch<bf16_t, float, float, KC, KC>(p, grid, stream);
-    if (!af && !bf && !cf) return launch<bf16_t, bf16_t, bf16_t, KC, KC>(p, grid, stream);
-    if (!af && !bf && cf) return launch<bf16_t, bf16_t, float, KC, KC>(p, grid, stream);
-    if (af && bf && cf) return launch<float, float, float, KC, KC>(p, grid, stream);
-    return false;
-  }
-  if (a_layout == RC && b_layout == RC) {
-    // wgrad: contraction over rows
-    if (!af && !bf && cf) return launch<bf16_t, bf16_t, float, RC, RC>(p, grid, stream);
-    if (af && bf && cf) return launch<float, float, float, RC, RC>(p, grid, stream);
-    return false;
-  }
-  if (a_layout == KC && b_layout == RC) {
-    // decoder dgrad: dX = dY . W with W stored [out, in]
-    if (af && bf && cf) return launch<float, float, float, KC, RC>(p, grid, stream);
-    return false;
-  }
-  return false;
+  pl.kernel = kernel;
+  pl.p = p;
+  pl.grid = grid;
+  return true;
 }
 
-bool pcaa_gemm_v2_is_enabled() { return v2_enabled(); }
+bool pcaa_launch_gemm_bf16_big(const GemmPlan& pl, hipStream_t stream) {
+  const GemmParams& p = pl.p;
+  if (pl.kernel == PCAA_GEMM_KERNEL_V2_KC) {
+    if (pl.c_dtype == PCAA_F32 ? launch_dma<float, KC, KC, EPI_PLAIN>(p, pl.grid, stream)
+                               : launch_dma<bf16_t, KC, KC, EPI_PLAIN>(p, pl.grid, stream))
+      return true;
+  } else if (pl.kernel == PCAA_GEMM_KERNEL_V2_RC) {
+    if (launch_dma<float, RC, RC, EPI_PLAIN>(p, pl.grid, stream)) return true;
+  }
+  // The register-staged kernel: as planned, or -- the single case in which the launched kernel differs from the planned
+  // one -- in place of a 4-wave launcher whose hipFuncSetAttribute failed.
+  const staged_launcher_t staged = staged_launcher(pl.a_dtype, pl.a_layout, pl.b_dtype, pl.b_layout, pl.c_dtype);
+  return p.seg_len == 0 && staged != nullptr && staged(p, pl.grid, stream);
+}
+
 extern "C" int pcaa_gemm_v2_enable(int on) {
   g_v2_enabled = on ? 1 : 0;
   return PCAA_OK;

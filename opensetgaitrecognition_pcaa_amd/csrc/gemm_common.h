@@ -68,9 +68,31 @@ __device__ __forceinline__ int block_coords(const GemmParams& p, int nbm, int nb
 struct PcaaLaunchEvents { hipEvent_t start, stop; };
 PcaaLaunchEvents pcaa_take_launch_events();      // returns {nullptr, nullptr} when nothing is armed; disarms
 
-// 256x256-tile bf16 kernel (gemm_bf16.hip).  Returns false if the shape/dtype
-// combination is not served by it (caller falls back to the small-tile kernel).
-bool pcaa_launch_gemm_bf16_big(const GemmParams& p, int a_dtype, int a_layout, int b_dtype, int b_layout,
-                               int c_dtype, int nsplit, hipStream_t stream);
+// what leaves the LDS-DMA kernels (gemm_bf16.hip, gemm_v2.h)
+enum { EPI_PLAIN = 0, EPI_DGRAD_BN = 1, EPI_AFFINE = 3, EPI_POOL1 = 4, EPI_POOL2 = 5, EPI_POOL4 = 6 };
+
+// A planned product launch: made from the call's arguments alone by the plan step (gemm_plan / gemm_split3_plan in
+// gemm.hip: every argument check and every decision, no device memory read, no HIP call), carried out by the launch
+// step, a switch over ``kernel``.  pcaa_gemm_route / pcaa_gemm_split3_route stop after the plan.
+struct GemmPlan {
+  int kernel;      // PCAA_GEMM_KERNEL_*
+  GemmParams p;
+  dim3 grid;
+  int a_dtype, a_layout, b_dtype, b_layout, c_dtype;      // the instantiation
+  bool vec;        // PCAA_GEMM_KERNEL_F32_TILE128: 4-element staging
+};
+// the PCAA_GEMM_KERNEL_* this thread's most recent GEMM launch started (pcaa_gemm_last_kernel); set at the launch sites
+extern thread_local int g_pcaa_gemm_last_kernel;
+
+// gemm_bf16.hip.  THE dispatch rule of the two 4-wave LDS-DMA loops (gemm_v2.h): PCAA_GEMM_KERNEL_V2_KC / _V2_RC, or -1
+// where they decline, for bf16 (or [hi | lo] fp16) operands that both have ``layout``, a result of c_bytes per
+// element and epilogue ``epi``.  Host arithmetic on the arguments only.  launch_dma, the plan step and the
+// *_supported predicates all ask here.
+int pcaa_gemm_4wave_kernel(const GemmParams& p, int layout, int c_bytes, int epi);
+// bf16 math: the 256x256-tile kernels' part of the plan (pl.kernel, pl.grid, pl.p.nsplit / split_fast).  Returns false
+// if the shape/dtype combination is not served by them (the small-tile kernel is next in line).
+bool pcaa_plan_gemm_bf16_big(GemmPlan& pl, int nsplit);
+// launches the planned 4-wave loop or register-staged kernel; false: the launch could not be configured
+bool pcaa_launch_gemm_bf16_big(const GemmPlan& pl, hipStream_t stream);
 bool pcaa_launch_gemm_dgrad_bn(const GemmParams& p, hipStream_t stream);
 bool pcaa_launch_gemm_affine_elu(const GemmParams& p, hipStream_t stream);

@@ -194,6 +194,23 @@ def set_timer(timer):
     TIMER = timer
 
 
+def _timed(key, launch, flops, nbytes):
+    """``launch()``, recorded under ``key`` when a LaunchTimer is installed and wants it.  ``key`` may be a callable
+    (the route query of ops.gemm): it runs only with a timer installed.  Without one this is ``launch()`` and nothing
+    else -- no ctypes call, no event (see _s for what host time per launch costs a step)."""
+    timer = TIMER
+    if timer is None:
+        return launch()
+    if callable(key):
+        key = key()
+    if not timer.wants(key):
+        return launch()
+    ev = _begin_timing(key)
+    launch()
+    ev.end()
+    timer.records.append((key, flops, float(nbytes), ev))
+
+
 class StatsPool:
     """One fp64 buffer for all BatchNorm statistics of a step, cleared by ONE
     fill at the start of the step instead of one per layer and direction."""
@@ -330,44 +347,30 @@ class BnTailBwd:
 
 
 # ------------------------------------------------------------------ GEMM
-_GEMM_V2 = {"on": os.environ.get("PCAA_GEMM_V2", "1") != "0"}
-
-
 def gemm_v2_enable(on=True):
     """Lab switch (pcaa_gemm_v2_enable): with ``on=False`` the 4-wave tile loops (csrc/gemm_v2.h) decline every launch --
     plain products then take the register-staged 256 x 256 kernel, the fused entry points report their shapes unsupported.
     (Rounds 1-4 routed to the 8-wave loop here; round 5 removed it.)"""
-    _GEMM_V2["on"] = bool(on)
     check(_lib.load().pcaa_gemm_v2_enable(int(bool(on))), "pcaa_gemm_v2_enable")
 
 
-_GEMM_V2_RC = os.environ.get("PCAA_GEMM_V2_RC", "1")[:1] != "0"     # read the same way by csrc/gemm_bf16.hip
+# LaunchTimer / PMC key of the kernel a product takes, by the PCAA_GEMM_KERNEL_* that pcaa_gemm_route answers (rocprofv3
+# lists the instantiations as separate kernels; the 4-wave loops are timed kernel-exactly, the rest with stream events)
+_GEMM_KEYS = {_lib.GEMM_KERNEL_F32_TILE128: "gemm_f32_kernel",
+              _lib.GEMM_KERNEL_BF16_SMALL: "gemm_bf16_kernel",
+              _lib.GEMM_KERNEL_BF16_STAGED: "gemm_bf16_big_kernel<{dt},{lay},{lay}>",
+              _lib.GEMM_KERNEL_V2_KC: "gemm_bf16_v2_kernel<{dt},plain>",       # PointNet forward / plain dgrad
+              _lib.GEMM_KERNEL_V2_RC: "gemm_bf16_v2rc_kernel<f32>"}            # the weight gradients
 
 
-def _v2_takes(K, split_k=1, accumulate=False):
-    """the dispatch rule of csrc/gemm_bf16.hip (launch_dma) for bf16 KC x KC operands: the 4-wave loop takes a launch
-    without K splits, atomics or slabs whose contraction is at least five 64-deep steps long (and whose result has a
-    leading dimension that is a multiple of 8 on a 16-B aligned base, which N % 256 == 0 and a torch allocation give)"""
-    return _GEMM_V2["on"] and K // 64 >= 5 and int(split_k) <= 1 and not accumulate
-
-
-def _v2rc_takes(split_k=1, accumulate=False, bias=None, colstats=None):
-    """the same for bf16 RC x RC operands with an fp32 result (whole 256 x 256 tiles, K % 64 == 0): the 4-wave loop takes
-    a single K pass or slabs of any contraction length -- no atomics, no bias, no column statistics"""
-    return _GEMM_V2["on"] and _GEMM_V2_RC and int(split_k) <= 1 and not accumulate and bias is None and colstats is None
-
-
-def _dma_key(out_dtype, layout, v2=False):
-    """LaunchTimer / PMC key of one LDS-DMA GEMM instantiation (rocprofv3 lists them as separate kernels): the 4-wave
-    loops' v2::gemm_bf16_v2_kernel<__bf16, 0, false> = PointNet forward / plain dgrad, v2::gemm_bf16_v2rc_kernel = the
-    weight gradients; anything they decline runs on the register-staged gemm_bf16_big_kernel (timed with stream events)."""
-    dt = 'bf16' if out_dtype == torch.bfloat16 else 'f32'
-    if v2 and layout == KC:
-        return f"gemm_bf16_v2_kernel<{dt},plain>"
-    if v2 and layout == RC and dt == 'f32' and _GEMM_V2["on"] and _GEMM_V2_RC:
-        return "gemm_bf16_v2rc_kernel<f32>"      # the weight gradients on the 4-wave loop (whole 256 x 256 tiles)
-    lay = "KC" if layout == KC else "RC"
-    return f"gemm_bf16_big_kernel<{dt},{lay},{lay}>"
+def _gemm_key(what, *args):
+    """the key of the kernel the library would launch for the arguments of pcaa_gemm_route"""
+    kernel = _lib.load().pcaa_gemm_route(*args)
+    check(int(kernel < 0), what)          # a refusal: raised as the launch would raise it
+    a_dtype, a_layout, b_dtype, b_layout, c_dtype = args[2], args[3], args[6], args[7], args[10]
+    if kernel == _lib.GEMM_KERNEL_BF16_STAGED and not (a_dtype == b_dtype == PCAA_BF16 and a_layout == b_layout):
+        return "gemm_bf16_big_kernel"
+    return _GEMM_KEYS[kernel].format(dt="bf16" if c_dtype == PCAA_BF16 else "f32", lay="KC" if a_layout == KC else "RC")
 
 
 def gemm(A, a_layout, B, b_layout, M, N, K, *, lda=None, ldb=None, out=None, out_dtype=torch.float32,
@@ -402,30 +405,13 @@ def gemm(A, a_layout, B, b_layout, M, N, K, *, lda=None, ldb=None, out=None, out
         _chk(colstats, "gemm.colstats", torch.float64)
         if tuple(colstats.shape) != (NREP, 2, N):
             raise ValueError("gemm: colstats shape")
-    lib = _lib.load()
-    timer = TIMER
-    if timer is not None:
-        if math != PCAA_BF16:
-            key = "gemm_f32_kernel"
-        elif (A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and a_layout == b_layout
-              and (M % 256 == 0 or (a_layout == KC and _v2_takes(K, split_k, accumulate))) and N % 256 == 0 and K % 64 == 0):
-            # same dispatch rule as pcaa_launch_gemm_bf16_big
-            key = _dma_key(out.dtype, a_layout, _v2_takes(K, split_k, accumulate) if a_layout == KC
-                           else _v2rc_takes(split_k, accumulate, bias, colstats))
-        else:
-            key = "gemm_bf16_big_kernel"
-        timer = timer if timer.wants(key) else None
-    if timer is not None:
-        ev = _begin_timing(key)
+    da, db, dc = _dt(A), _dt(B), _dt(out)
+    args = (math, _p(A), da, a_layout, lda, _p(B), db, b_layout, ldb, _p(out), dc, N, M, N, K, _p(bias), _p(colstats), NREP,
+            int(split_k), int(bool(accumulate)))
     if tail is not None:
         tail.arm(colstats)
-    check(lib.pcaa_gemm(math, _p(A), _dt(A), a_layout, lda, _p(B), _dt(B), b_layout, ldb,
-                        _p(out), _dt(out), N, M, N, K, _p(bias), _p(colstats), NREP,
-                        int(split_k), int(bool(accumulate)), _s()), "pcaa_gemm")
-    if timer is not None:
-        ev.end()
-        nbytes = A.numel() * A.element_size() + B.numel() * B.element_size() + out.numel() * out.element_size()
-        timer.records.append((key, 2.0 * M * N * K, float(nbytes), ev))
+    _timed(lambda: _gemm_key("pcaa_gemm", *args, 0), lambda: check(_lib.load().pcaa_gemm(*args, _s()), "pcaa_gemm"), 2.0 * M * N * K,
+           (4 - 2 * da) * M * K + (4 - 2 * db) * N * K + (4 - 2 * dc) * M * N)          # (PCAA_BF16 = 1: 2 bytes, PCAA_F32 = 0: 4)
     if tail is not None:
         tail.resolve(colstats)
     return out
@@ -478,21 +464,11 @@ def gemm_slabs(A, a_layout, B, b_layout, M, N, K, split_k, out=None, accumulate=
         _chk(out, "gemm_slabs.out", torch.float32)
         if out.numel() != M * N:
             raise ValueError("gemm_slabs: out size")
-    timer = TIMER
-    if timer is not None:
-        dma = (math == PCAA_BF16 and A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and a_layout == b_layout
-               and M % 256 == 0 and N % 256 == 0 and K % 64 == 0)
-        # (slabs: the RC x RC loop takes them -- every K range is a multiple of 64 deep; the KC x KC loop takes no slabs)
-        key = _dma_key(torch.float32, a_layout, a_layout == RC) if dma else ("gemm_bf16_big_kernel" if math == PCAA_BF16 else "gemm_f32_kernel")
-        timer = timer if timer.wants(key) else None
-    if timer is not None:
-        ev = _begin_timing(key)
-    check(lib.pcaa_gemm_slabs(math, _p(A), _dt(A), a_layout, A.stride(0), _p(B), _dt(B), b_layout, B.stride(0),
-                              _p(slabs), stride, M, N, K, int(split_k), _s()), "pcaa_gemm_slabs")
-    if timer is not None:
-        ev.end()
-        nbytes = A.numel() * A.element_size() + B.numel() * B.element_size() + ns * stride * 4
-        timer.records.append((key, 2.0 * M * N * K, float(nbytes), ev))
+    da, db = _dt(A), _dt(B)
+    ab = (math, _p(A), da, a_layout, A.stride(0), _p(B), db, b_layout, B.stride(0))
+    _timed(lambda: _gemm_key("pcaa_gemm_slabs", *ab, _p(slabs), PCAA_F32, N, M, N, K, None, None, 0, int(split_k), 0, stride),
+           lambda: check(lib.pcaa_gemm_slabs(*ab, _p(slabs), stride, M, N, K, int(split_k), _s()), "pcaa_gemm_slabs"),
+           2.0 * M * N * K, (4 - 2 * da) * M * K + (4 - 2 * db) * N * K + ns * stride * 4)
     if colstats is not None:
         # reduction fused with the BatchNorm column statistics of the result
         if accumulate:
@@ -562,18 +538,11 @@ def gemm_affine_elu(a, W16, scale, shift, pool_rows=0):
         out = torch.empty((M // pool_rows, N), dtype=torch.float32, device=a.device)
     else:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    timer = TIMER
     # eval-mode epilogues (BatchNorm affine + ELU [+ mean-pool])
-    key = "gemm_bf16_v2_kernel<bf16,affine_elu>"
-    timer = timer if (timer is not None and timer.wants(key)) else None
-    if timer is not None:
-        ev = _begin_timing(key)
-    check(_lib.load().pcaa_gemm_affine_elu(_p(a), a.stride(0), _p(W16), W16.stride(0), _p(out), N, _p(scale),
-                                           _p(shift), M, N, K, int(pool_rows), _s()), "pcaa_gemm_affine_elu")
-    if timer is not None:
-        ev.end()
-        nbytes = 2 * (M * K + N * K) + out.numel() * out.element_size()
-        timer.records.append((key, 2.0 * M * N * K, float(nbytes), ev))
+    _timed("gemm_bf16_v2_kernel<bf16,affine_elu>",
+           lambda: check(_lib.load().pcaa_gemm_affine_elu(_p(a), a.stride(0), _p(W16), W16.stride(0), _p(out), N, _p(scale),
+                                                          _p(shift), M, N, K, int(pool_rows), _s()), "pcaa_gemm_affine_elu"),
+           2.0 * M * N * K, 2 * (M * K + N * K) + out.numel() * out.element_size())
     return out
 
 
@@ -595,22 +564,14 @@ def gemm_dgrad_bn(dy, Wt, y, scale, shift, mean, rstd, tail=None):
         raise ValueError("gemm_dgrad_bn: shape mismatch")
     dz = torch.empty_like(y)
     stats = new_stats(N, dy.device)
-    timer = TIMER
-    # its own instantiation (epilogue carries ELU' + statistics)
-    key = "gemm_bf16_v2_kernel<bf16,dgrad_bn>"
-    timer = timer if (timer is not None and timer.wants(key)) else None
-    if timer is not None:
-        ev = _begin_timing(key)
     if tail is not None:
         tail.arm(stats)
-    check(_lib.load().pcaa_gemm_dgrad_bn(_p(dy), dy.stride(0), _p(Wt), Wt.stride(0), _p(y), _p(dz), dz.stride(0),
-                                         _p(scale), _p(shift), _p(mean), _p(rstd), _p(stats), NREP, M, N, K,
-                                         None, 0, None, _s()),
-          "pcaa_gemm_dgrad_bn")
-    if timer is not None:
-        ev.end()
-        nbytes = 2 * (M * K + N * K + 2 * M * N)
-        timer.records.append((key, 2.0 * M * N * K, float(nbytes), ev))
+    # its own instantiation (epilogue carries ELU' + statistics)
+    _timed("gemm_bf16_v2_kernel<bf16,dgrad_bn>",
+           lambda: check(_lib.load().pcaa_gemm_dgrad_bn(_p(dy), dy.stride(0), _p(Wt), Wt.stride(0), _p(y), _p(dz), dz.stride(0),
+                                                        _p(scale), _p(shift), _p(mean), _p(rstd), _p(stats), NREP, M, N, K,
+                                                        None, 0, None, _s()), "pcaa_gemm_dgrad_bn"),
+           2.0 * M * N * K, 2 * (M * K + N * K + 2 * M * N))
     if tail is not None:
         tail.resolve(stats)
     return dz, stats
@@ -708,18 +669,12 @@ def gemm_split3(A, B, layout, M, N, K, colstats=None, tail=None, out=None):
         raise ValueError(f"gemm_split3: operand shapes {A.shape} {B.shape} do not match M={M} N={N} K={K}")
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    timer = TIMER
-    key = "gemm_bf16_v2_kernel<f32,split3>" if layout == KC else "gemm_bf16_v2rc_kernel<f32,split3>"
-    timer = timer if (timer is not None and timer.wants(key)) else None
-    if timer is not None:
-        ev = _begin_timing(key)
     if tail is not None:
         tail.arm(colstats)
-    check(_lib.load().pcaa_gemm_split3(_p(A.img), _p(B.img), layout, A.img.stride(0), B.img.stride(0), _p(out), N, M, N, K,
-                                       _p(colstats), NREP, 1.0 / (A.scale * B.scale), _s()), "pcaa_gemm_split3")
-    if timer is not None:
-        ev.end()
-        timer.records.append((key, 3 * 2.0 * M * N * K, float(4 * (A.img.numel() // 2 + B.img.numel() // 2 + M * N)), ev))
+    _timed("gemm_bf16_v2_kernel<f32,split3>" if layout == KC else "gemm_bf16_v2rc_kernel<f32,split3>",
+           lambda: check(_lib.load().pcaa_gemm_split3(_p(A.img), _p(B.img), layout, A.img.stride(0), B.img.stride(0), _p(out), N,
+                                                      M, N, K, _p(colstats), NREP, 1.0 / (A.scale * B.scale), _s()), "pcaa_gemm_split3"),
+           3 * 2.0 * M * N * K, 4 * (A.img.numel() // 2 + B.img.numel() // 2 + M * N))
     if tail is not None:
         tail.resolve(colstats)
     return out
@@ -735,16 +690,10 @@ def gemm_slabs_split3(A, B, M, N, K, split_k, out=None):
     slabs = torch.empty(ns * stride, dtype=torch.float32, device=A.device)
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    timer = TIMER
-    key = "gemm_bf16_v2rc_kernel<f32,split3>"
-    timer = timer if (timer is not None and timer.wants(key)) else None
-    if timer is not None:
-        ev = _begin_timing(key)
-    check(lib.pcaa_gemm_slabs_split3(_p(A.img), _p(B.img), RC, A.img.stride(0), B.img.stride(0), _p(slabs), stride, M, N, K,
-                                     int(split_k), 1.0 / (A.scale * B.scale), _s()), "pcaa_gemm_slabs_split3")
-    if timer is not None:
-        ev.end()
-        timer.records.append((key, 3 * 2.0 * M * N * K, float(4 * (A.img.numel() // 2 + B.img.numel() // 2) + ns * stride * 4), ev))
+    _timed("gemm_bf16_v2rc_kernel<f32,split3>",
+           lambda: check(lib.pcaa_gemm_slabs_split3(_p(A.img), _p(B.img), RC, A.img.stride(0), B.img.stride(0), _p(slabs), stride,
+                                                    M, N, K, int(split_k), 1.0 / (A.scale * B.scale), _s()), "pcaa_gemm_slabs_split3"),
+           3 * 2.0 * M * N * K, 4 * (A.img.numel() // 2 + B.img.numel() // 2) + ns * stride * 4)
     check(lib.pcaa_splitk_reduce(_p(slabs), ns, stride, stride, _p(out), 0, _s()), "pcaa_splitk_reduce")
     return out
 
@@ -1152,16 +1101,6 @@ def skinny_supported(M, N, K):
     return bool(_lib.load().pcaa_skinny_supported(int(M), int(N), int(K)))
 
 
-def _skinny_timed(fn, flops, nbytes):
-    timer = TIMER
-    if timer is None or not timer.wants("gemm_skinny_kernel"):
-        return fn()
-    ev = _TorchEvents()
-    fn()
-    ev.end()
-    timer.records.append(("gemm_skinny_kernel", flops, float(nbytes), ev))
-
-
 def _w16_image(W16, W, what):
     """the bf16 image of weight W (pcaa_skinny_linear_*_w16): same shape, contiguous rows, bf16"""
     _chk(W16, what, torch.bfloat16, 2)
@@ -1188,7 +1127,7 @@ def skinny_linear_fwd(x, W, bias, act, exact=False, W16=None):
         Wsrc, fn, wb = _w16_image(W16, W, "skinny_fwd.W16"), lib.pcaa_skinny_linear_fwd_w16, 2
     else:
         Wsrc, fn, wb = W, (lib.pcaa_skinny_linear_fwd_exact if exact else lib.pcaa_skinny_linear_fwd), 4
-    _skinny_timed(lambda: check(fn(_p(x), x.stride(0), _p(Wsrc), Wsrc.stride(0), _p(bias), act,
+    _timed("gemm_skinny_kernel", lambda: check(fn(_p(x), x.stride(0), _p(Wsrc), Wsrc.stride(0), _p(bias), act,
                                    _p(y), _p(ws), ws.numel(), M, N, K, ns, _s()),
                                 "pcaa_skinny_linear_fwd"), 2.0 * M * N * K, wb * N * K + 4 * (M * K + M * N))
     return y
@@ -1222,7 +1161,7 @@ def skinny_linear_dgrad(dz, W, a_prev=None, out=None, accumulate=False, exact=Fa
         Wsrc, fn, wb = _w16_image(W16, W, "skinny_dgrad.W16"), lib.pcaa_skinny_linear_dgrad_w16, 2
     else:
         Wsrc, fn, wb = W, (lib.pcaa_skinny_linear_dgrad_exact if exact else lib.pcaa_skinny_linear_dgrad), 4
-    _skinny_timed(lambda: check(fn(_p(dz), dz.stride(0), _p(Wsrc), Wsrc.stride(0), _p(out),
+    _timed("gemm_skinny_kernel", lambda: check(fn(_p(dz), dz.stride(0), _p(Wsrc), Wsrc.stride(0), _p(out),
                                    _p(a_prev), int(bool(accumulate)), _p(ws), ws.numel(),
                                    M, N, K, ns, _s()),
                                 "pcaa_skinny_linear_dgrad"), 2.0 * M * N * K, wb * N * K + 4 * (M * K + M * N))
@@ -1247,12 +1186,12 @@ def skinny_linear_wgrad(dz, x, out=None, exact=False):
     if out.dtype == torch.bfloat16:       # the gradient as it crosses the wire (bf16 gradient buckets)
         if exact:
             raise ValueError("skinny_linear_wgrad: the exact variant writes fp32")
-        _skinny_timed(lambda: check(lib.pcaa_skinny_linear_wgrad_bf16(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(out), K,
+        _timed("gemm_skinny_kernel", lambda: check(lib.pcaa_skinny_linear_wgrad_bf16(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(out), K,
                                                                       M, N, K, _s()),
                                     "pcaa_skinny_linear_wgrad_bf16"), 2.0 * M * N * K, 2 * N * K + 4 * (M * K + M * N))
         return out
     fn = lib.pcaa_skinny_linear_wgrad_exact if exact else lib.pcaa_skinny_linear_wgrad
-    _skinny_timed(lambda: check(fn(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(out), K, M, N, K, _s()),
+    _timed("gemm_skinny_kernel", lambda: check(fn(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(out), K, M, N, K, _s()),
                                 "pcaa_skinny_linear_wgrad"), 2.0 * M * N * K, 4 * (N * K + M * K + M * N))
     return out
 
@@ -1273,7 +1212,7 @@ def skinny_linear_wgrad_adam_(dz, x, W, exp_avg, exp_avg_sq, beta1, beta2, eps, 
     _chk(coef_dev, "skinny_wgrad_adam.coef", torch.float32)
     lib = _lib.load()
     fn = lib.pcaa_skinny_linear_wgrad_adam_exact if exact else lib.pcaa_skinny_linear_wgrad_adam
-    _skinny_timed(lambda: check(fn(
+    _timed("gemm_skinny_kernel", lambda: check(fn(
         _p(dz), dz.stride(0), _p(x), x.stride(0), _p(W), _p(exp_avg), _p(exp_avg_sq), K, M, N, K, float(beta1),
         float(beta2), float(eps), float(grad_scale), _p(coef_dev), _s()), "pcaa_skinny_linear_wgrad_adam"),
         2.0 * M * N * K, 4 * (6 * N * K + M * K + M * N))
@@ -1306,7 +1245,7 @@ def skinny_linear_wgrad_adam_rows_(dz_all, x_all, m, W, exp_avg, exp_avg_sq, bet
         if tuple(t.shape) != (N, K):
             raise ValueError(f"skinny_linear_wgrad_adam_rows_: {nm} must be [{N},{K}], got {tuple(t.shape)}")
     _chk(coef_dev, "skinny_wgrad_adam_rows.coef", torch.float32)
-    _skinny_timed(lambda: check(_lib.load().pcaa_skinny_linear_wgrad_adam_rows(
+    _timed("gemm_skinny_kernel", lambda: check(_lib.load().pcaa_skinny_linear_wgrad_adam_rows(
         _p(dz_all), dz_all.stride(0), _p(x_all), x_all.stride(0), _p(W), _p(exp_avg), _p(exp_avg_sq), K, int(m), N, K,
         float(beta1), float(beta2), float(eps), float(grad_scale), _p(coef_dev), R, _s()),
         "pcaa_skinny_linear_wgrad_adam_rows"), 2.0 * m * N * K, 4 * (6 * N * K + m * K + m * N))
@@ -1363,7 +1302,7 @@ def skinny_linear_wgrad_adam_t16_(packed, chunks, W, exp_avg, exp_avg_sq, beta1,
                          f"{tuple(packed.shape)} (at most {PACK_MAX_CHUNKS} chunks of {packed_chunk_elems(N, K)} elements)")
     _chk(coef_dev, "skinny_wgrad_adam_t16.coef", torch.float32)
     m = chunks * PACK_ROWS
-    _skinny_timed(lambda: check(_lib.load().pcaa_skinny_linear_wgrad_adam_t16(
+    _timed("gemm_skinny_kernel", lambda: check(_lib.load().pcaa_skinny_linear_wgrad_adam_t16(
         _p(packed), packed.stride(0), chunks, _p(W), _p(exp_avg), _p(exp_avg_sq), K, N, K, float(beta1), float(beta2),
         float(eps), float(grad_scale), _p(coef_dev), _s()), "pcaa_skinny_linear_wgrad_adam_t16"),
         2.0 * m * N * K, 24 * N * K + 2 * m * (N + K))

@@ -421,8 +421,10 @@ def route(math, a_dtype, a_layout, b_dtype, b_layout, c_dtype, M, N, K, lda, ldb
     csrc/gemm_bf16.hip) restated: one name per distinct code path, ``refused/<reason>`` for an argument error.
     ``aligned``: True, or the set of operands ("A", "B", "C") whose base is 16-B aligned (a misaligned one sits one
     element off); ``slabs``: the slab entry points (c_split_stride != 0).  ``split3``: the [hi | lo] fp16 entry points
-    (K is the logical contraction, lda / ldb cover the images).  A restatement reviewed against the C++: it cannot
-    observe which kernel ran."""
+    (K is the logical contraction, lda / ldb cover the images).  A restatement on purpose, and now an observed one: the
+    kernel a name implies (``kernel_id``) is what pcaa_gemm_route / pcaa_gemm_split3_route answer for every case, refusal
+    and grid point (tests/test_gemm_route_cpu.py, no GPU needed) and what pcaa_gemm_last_kernel reports after every launch
+    of tests/test_gemm_branches.py."""
     al = (lambda x: True) if aligned is True else (lambda x: x in aligned)
     if M <= 0 or N <= 0 or K <= 0:
         return "refused/bad_shape"
@@ -515,8 +517,16 @@ def _route_big(a_dtype, a_layout, b_dtype, b_layout, c_dtype, M, N, K, lda, ldb,
     return "bf16_staged/%s,%s,%s,%s,%s" % inst
 
 
+# PCAA_GEMM_KERNEL_* of include/pcaa_hip.h by the first component of a route name
+KERNEL_IDS = {"f32": 0, "bf16_small": 1, "bf16_staged": 2, "v2": 3, "v2rc": 4, "v2_dgrad": 3, "v2_affine": 3, "refused": -1}
+
+
+def kernel_id(route_name):
+    return KERNEL_IDS[route_name.split("/")[0]]
+
+
 def split3_supported(M, N, K, v2_on):
-    """pcaa_gemm_split3_supported (the 4 GiB bound of ragged_m_ok is out of reach at test size)"""
+    """pcaa_gemm_split3_supported (the 4 GiB bound on the padded rows is out of reach at test size)"""
     return M > 0 and N > 0 and K > 0 and v2_on and 3 * K >= 320 and (M % 256 == 0 or K >= 320) and N % 256 == 0 and K % 64 == 0
 
 
@@ -736,10 +746,9 @@ def gemm_cases(n_cu):
     return cs
 
 
-def all_routes(n_cu=256):
-    """every name ``route`` returns over the supported domain, enumerated from the function itself on a grid of its
-    arguments (the conditions of the launchers taken both ways), refusals left out"""
-    names = set()
+def route_grid(n_cu=256):
+    """the grid of ``route``'s arguments that ``all_routes`` walks (the conditions of the launchers taken both ways), as
+    case dicts.  The slab entry points have an fp32 result without bias or statistics: no other slab call exists."""
     g = persistent_grid(1 << 30, n_cu)
     for math in (M_F32, M_BF16):
         for a, b, c in [(x, y, z) for x in (F32, BF16) for y in (F32, BF16) for z in (F32, BF16)]:
@@ -749,15 +758,22 @@ def all_routes(n_cu=256):
                     for sk, acc, slabs in [(1, False, False), (2, False, False), (1, True, False), (2, False, True), (8, False, True)]:
                         for bias in (False, True):
                             for stats, tail in ((False, False), (True, False), (True, True)):
+                                if slabs and (c != F32 or bias or stats):
+                                    continue
                                 for v2 in (True, False):
-                                    names.add(route(math, a, al, b, bl, c, M, N, K, K if al == KC else M, K if bl == KC else N, N, sk,
-                                                    acc, slabs, bias, stats, v2, n_cu, True, tail=tail))
+                                    yield _c("grid", None, M, N, K, math=math, adt=a, bdt=b, cdt=c, alay=al, blay=bl, split_k=sk,
+                                             accumulate=acc, slabs=slabs, bias=bias, colstats=stats, tail=tail, v2_on=v2)
     for lay in (KC, RC):
         for M, N, K in [(256, 256, 128), (300, 256, 320), (256 * (g + 11), 256, 128), (256 * (g + 11) - 100, 256, 320), (2048, 1024, 512)]:
             for sk, slabs in [(1, False), (2, True), (8, True)]:
                 for stats, tail in ((False, False), (True, False), (True, True)):
-                    names.add(route(M_BF16, BF16, lay, BF16, lay, F32, M, N, K, 2 * (K if lay == KC else M), 2 * (K if lay == KC else N),
-                                    N, sk, False, slabs, False, stats, True, n_cu, True, split3=True, tail=tail))
+                    yield _c("grid", None, M, N, K, alay=lay, blay=lay, split3=True, split_k=sk, slabs=slabs, colstats=stats, tail=tail)
+
+
+def all_routes(n_cu=256):
+    """every name ``route`` returns over the supported domain, enumerated from the function itself on ``route_grid``,
+    refusals left out"""
+    names = {case_route(c, n_cu) for c in route_grid(n_cu)}
     return {n for n in names if not n.startswith("refused/")}
 
 
@@ -1041,7 +1057,7 @@ ABI_REFUSALS = [
 ]
 
 # exits that no call of test size reaches (the message fragments of csrc/gemm.hip): the 4 GiB bounds live inside
-# ragged_out_ok / ragged_m_ok and have no message of their own
+# pcaa_gemm_4wave_kernel (asked through ragged_out_ok and the predicates) and have no message of their own
 OUT_OF_REACH = [("pcaa_gemm:", "too many tiles"), ("pcaa_gemm_group_rc_f32:", "too many blocks"), ("pcaa_gemm_split3:", "K too large"),
                 # pcaa_gemm_split3 takes no split count and pcaa_gemm_slabs_split3 no statistics: the impl's check is unreachable
                 ("pcaa_gemm_split3:", "column statistics need a single K pass")]

@@ -2,8 +2,9 @@
 
 References, gates, the route table and the case lists: tests/gemm_ref.py; the gates are shown reference-safe and
 defect-sensitive, and the case lists complete, by tests/test_gemm_gates_cpu.py.  Every case names the route it means to
-reach (``gemm_ref.route`` restates the launchers; it cannot observe which kernel ran -- a carried BatchNorm tail, which
-only the LDS-DMA loops take, is the one thing the library reports back, and is asserted), computes the result, the
+reach (``gemm_ref.route`` restates the launchers; the library reports the kernel it plans -- pcaa_gemm_route, asked
+before every product launch -- and the one the launch started -- pcaa_gemm_last_kernel, asked after it: both must be the
+kernel the route name implies; a carried BatchNorm tail, which only the LDS-DMA loops take, is asserted too), computes the result, the
 fp64 reference of the same stored operands and the gate, asserts |got - want| <= gate for EVERY element and prints the
 worst ratio (pytest -rP).  Operands live inside NaN-filled allocations (leading-dimension padding, the element in front
 of a misaligned base, the memory behind the last row); outputs inside sentinel-filled ones that must come back
@@ -21,7 +22,8 @@ bit-identical outside the logical window.
     test_refusals, test_abi_refusals         one call per PCAA_CHECK_ARG of csrc/gemm.hip (gemm_ref.REFUSALS, ABI_REFUSALS): the
                                              error code, the message, an untouched output
     test_supported_predicates                pcaa_gemm_*_supported against the entry points' verdicts, v2 on and off
-    test_lab_switches_in_a_child_process     PCAA_GEMM_TICKETS=0 (the fixed-share walk) and PCAA_GEMM_V2_RC=0
+    test_lab_switches_in_a_child_process     PCAA_GEMM_TICKETS=0 (the fixed-share walk) and PCAA_GEMM_V2_RC=0; one timed launch
+                                             per event kind of ops.LaunchTimer (TIMED)
 Not covered: operands beyond 4 GiB (flat addressing, the 4 GiB refusals), more than 128 streams, a stream capture as the
 first launch of a device (capture-time slot allocation).
 """
@@ -156,6 +158,19 @@ def launch_product(c, bt, out, stats, lib, ops, tail=None, via_ops=True):
     return rc
 
 
+def planned_kernel(c, bt, out, stats, lib):
+    """pcaa_gemm_route / pcaa_gemm_split3_route for the call launch_product is about to make"""
+    A, B = bt["A"], bt["B"]
+    M, N, K = bt["M"], bt["N"], c["K"]
+    stride = M * N if c["slabs"] else 0
+    if c["split3"]:
+        return lib.pcaa_gemm_split3_route(ptr(A), ptr(B), c["alay"], A.stride(0), B.stride(0), ptr(out.win), N if c["slabs"] else out.ldc,
+                                          M, N, K, ptr(stats), c["nrep"], c["split_k"], stride, 1.0)
+    return lib.pcaa_gemm_route(c["math"], ptr(A), dt(A.dtype), c["alay"], A.stride(0), ptr(B), dt(B.dtype), c["blay"], B.stride(0),
+                               ptr(out.win), dt(c["cdt"]), out.ldc, M, N, K, ptr(bt["bias"]), ptr(stats), c["nrep"], c["split_k"],
+                               int(c["accumulate"]), stride)
+
+
 def new_out(c, bt, ns=1):
     M, N = bt["M"], bt["N"]
     if c["slabs"]:
@@ -188,8 +203,10 @@ def run_product(c, tickets=True, rc_on=True):
             rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
             tail = ops.BnTailFwd(M, None, bn, N)
             taken0 = ops.TAILS["taken"]
+        planned = planned_kernel(c, bt, out, stats, lib)
         rc = launch_product(c, bt, out, stats, lib, ops, tail)
         assert rc == 0, (c["id"], rc, lib.pcaa_last_error())
+        assert lib.pcaa_gemm_last_kernel() == G.kernel_id(route) == planned, (c["id"], route, planned, lib.pcaa_gemm_last_kernel())
         got = out.take()
         for buf in bt["bufs"]:
             assert bool(torch.isnan(buf[-64:].float()).all())
@@ -242,6 +259,7 @@ def run_fused(c):
     A, B = bt["A"], bt["B"]
     if c["epi"] == "affine":
         got = ops.gemm_affine_elu(A, B, bt["scale"], bt["shift"], c["pool_rows"])
+        assert lib.pcaa_gemm_last_kernel() == G.kernel_id(c["route"]), (c["id"], c["route"], lib.pcaa_gemm_last_kernel())
         torch.cuda.synchronize()
         check(c["id"], got, ref["want"], ref["gate"], c["route"])
         return
@@ -262,6 +280,7 @@ def run_fused(c):
     else:
         rc = lib.pcaa_gemm_dgrad_bn(ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(bt["y"]), ptr(dz.win), ld, *sc, None, 0, None, ops._s())
     assert rc == 0, (c["id"], lib.pcaa_last_error())
+    assert lib.pcaa_gemm_last_kernel() == G.kernel_id(c["route"]), (c["id"], c["route"], lib.pcaa_gemm_last_kernel())
     if tail is not None:
         tail.resolve(stats)
     got = dz.take()
@@ -501,13 +520,43 @@ CHILD_IDS = ("v2-tickets-r0-bf16-nobias-stats-tail", "v2-tickets-r77-f32-bias-st
              "v2rc-slabs-one-step-each", "v2rc-split-fast-8")
 
 
+# the smallest shapes that reach each event kind of ops.LaunchTimer: (case, key, kernel-exact events)
+TIMED = [(G._c("timed-v2-kc", "v2/plain/whole/one_tile_each/nobias/nostats/notail", 256, 256, 320, cdt=BF16), "gemm_bf16_v2_kernel<bf16,plain>", True),
+         (G._c("timed-staged", "bf16_staged/bf16,bf16,f32,KC,KC", 256, 256, 64), "gemm_bf16_big_kernel<f32,KC,KC>", False)]
+
+
+def run_timed(c, key, kernel_exact):
+    """one ops.gemm under a LaunchTimer: exactly one record, under the key of the kernel the library names, with a valid,
+    positive time from the right kind of events; the result within its gate as untimed"""
+    lib, ops = _ops()
+    assert G.case_route(c, n_cu()) == c["route"]
+    bt = G.build(c, DEV)
+    p = G.reference(c, bt)
+    out = new_out(c, bt)
+    timer = ops.LaunchTimer()
+    ops.set_timer(timer)
+    try:
+        assert launch_product(c, bt, out, None, lib, ops) == 0
+    finally:
+        ops.set_timer(None)
+    assert lib.pcaa_gemm_last_kernel() == G.kernel_id(c["route"])
+    check(c["id"], out.take(), p["want"], p["gate"], c["route"])
+    assert [r[0] for r in timer.records] == [key], (c["id"], [r[0] for r in timer.records])
+    ev = timer.records[0][3]
+    assert isinstance(ev, ops._KernelEvents if kernel_exact else ops._TorchEvents), (c["id"], type(ev))
+    assert ev.valid() and ev.elapsed_ms() > 0.0, (c["id"], ev.valid())
+    assert timer.summary()[key]["launches"] == 1
+
+
 def child():
     """PCAA_GEMM_TICKETS=0, PCAA_GEMM_V2_RC=0 (both read once per process): the fixed-share walk a declined ticket slot
-    falls back to, and the register-staged kernel under the whole-tile weight gradients"""
+    falls back to, and the register-staged kernel under the whole-tile weight gradients; then the timed launches"""
     assert os.environ["PCAA_GEMM_TICKETS"] == "0" and os.environ["PCAA_GEMM_V2_RC"] == "0"
     for c in CASES:
         if c["id"] in CHILD_IDS:
             run_product(c, tickets=False, rc_on=False)
+    for c, key, kernel_exact in TIMED:
+        run_timed(c, key, kernel_exact)
     res = dict(WORST)
     print("CHILD_RESULT " + json.dumps(res))
 
