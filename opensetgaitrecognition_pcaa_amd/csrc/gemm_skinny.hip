@@ -390,6 +390,161 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict
 // 32-bit element offsets from uniform base pointers (host-checked < 2^31) so loads and stores use
 // the SGPR-base + VGPR-offset form.  Rows m >= M: dz is zeroed after a clamped load, x is only
 // clamped (0 * finite = 0).
+//
+// The four kernels of the family -- plain gradient, fused Adam, fused Adam from gathered rows, fused Adam from packed
+// operands -- are compositions of the pieces below; a kernel spells out only where its dz and x fragments come from.
+
+// The dz panel of one 64-row chunk in LDS: [row fragment i][k-step s][lane], one bf16x8 MFMA operand each (16 KB);
+// the exact variant holds the same as fp32, [i][s][16-B half][lane] (32 KB).  The B operand of a k-step likewise.
+struct f32x8 { float v[8]; };
+template <bool F32> using pan_t = typename std::conditional<F32, f32x4, bf16x8>::type;
+template <bool F32> using bfrag_t = typename std::conditional<F32, f32x8, bf16x8>::type;
+template <bool F32> struct DzPanel { pan_t<F32> f[4][4][F32 ? 2 : 1][64]; };
+
+template <bool F32>
+__device__ __forceinline__ bfrag_t<F32> make_bfrag(const float (&t)[8]) {
+  if constexpr (F32) {
+    f32x8 b;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b.v[e] = t[e];
+    return b;
+  } else {
+    return pack8(t);
+  }
+}
+
+// wave s packs k-step s of all 4 row fragments of the chunk whose first batch row is m0
+template <bool F32>
+__device__ __forceinline__ void pack_dz_panel(DzPanel<F32>& pan, const float* dz, long lddz, int M, int N,
+                                              int n0, int m0, int s, int lane) {
+  const int l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned ncol = (unsigned)min(n0 + 32 * i + l31, N - 1);
+    float t[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int m = m0 + 16 * s + 8 * h + e;
+      const float v = dz[(unsigned)min(m, M - 1) * (unsigned)lddz + ncol];
+      t[e] = m < M ? v : 0.f;                              // rows past M contribute nothing, whatever x holds there
+    }
+    if constexpr (F32) {
+      pan.f[i][s][0][lane] = f32x4{t[0], t[1], t[2], t[3]};
+      pan.f[i][s][1][lane] = f32x4{t[4], t[5], t[6], t[7]};
+    } else {
+      pan.f[i][s][0][lane] = pack8(t);
+    }
+  }
+}
+
+// acc[i] += (row fragment i of the panel) . b over the chunk's 4 k-steps: 16 MFMAs (exact: 128)
+template <bool F32>
+__device__ __forceinline__ void contract16(f32x16 (&acc)[4], const DzPanel<F32>& pan, const bfrag_t<F32> (&b)[4], int lane) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (F32) {
+        const f32x4 lo = pan.f[i][s][0][lane], hi = pan.f[i][s][1][lane];
+        const float a[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        acc[i] = mfma8_f32(a, b[s].v, acc[i]);
+      } else {
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pan.f[i][s][0][lane], b[s], acc[i], 0, 0, 0);
+      }
+    }
+}
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// x operand of the single-chunk kernels: lane (l31, h) reads x[16 s + 8 h + e][kb + 32 j + l31] as dwords, the row
+// clamped to M - 1, the column step j in the (uniform) base pointer
+__device__ __forceinline__ void x_offsets(unsigned (&xoff)[4][8], long ldx, int M, int K, int kb, int lane) {
+  const int l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      xoff[s][e] = (unsigned)min(16 * s + 8 * h + e, M - 1) * (unsigned)ldx + min(kb, K - 32) + l31;
+}
+__device__ __forceinline__ void x_load(float (&br)[4][8], const float* x, const unsigned (&xoff)[4][8]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) br[s][e] = x[xoff[s][e]];
+}
+
+// Accumulator register r of row fragment i is row 32 i + (r & 3) + 8 (r >> 2) of the workgroup's 128 (+ 4 h, which
+// the callers fold into row0); rows at or beyond N exist only where N % 128 != 0 (FULLN = false)
+__device__ __forceinline__ constexpr unsigned tile_row(int i, int r) { return 32 * i + (r & 3) + 8 * (r >> 2); }
+template <bool FULLN>
+__device__ __forceinline__ bool row_live(unsigned row0, unsigned rr, int N) { return FULLN || row0 + rr < (unsigned)N; }
+
+// The fused update's side of a wave: its fragments f = 4 j + i (32 rows x 32 columns each) of W, exp_avg, exp_avg_sq
+// travel through a ring of NB register buffers (48 dwords per lane and fragment), NB - 1 of them in flight ahead of
+// the one being updated; index = fragment number mod NB, static at every call site.
+// The shape of this type is measured, not taste (gfx950 code objects against the hand-written kernels): with the
+// buffers as members, or with one update() over all four row fragments of a column step, the same source costs the
+// JL > 1 full-panel kernels 80 registers (326 -> 406) and the JL = 1 ones a wave per SIMD (224 -> 268).  So the buffers
+// stay arrays of the kernel, held by reference, the offset o0 and its fence stay in the kernel's column loop, and
+// update() takes ONE fragment: as below every instantiation keeps its waves per SIMD, its loads, stores and MFMAs.
+template <int NB, bool FULLN>
+struct AdamRing {
+  static_assert(NB == 2 || NB == 4, "fragment buffers: a ring of 2 or 4 (index = fragment number mod NB, static)");
+  float* W;
+  float* mo;
+  float* vo;
+  unsigned ldw, row0;
+  int N, nfrag;
+  float b1, b2, eps, grad_scale, step_size, inv_bc2_sqrt;
+  float (&pw)[NB][16], (&pm)[NB][16], (&pv)[NB][16];
+
+  __device__ AdamRing(float (&pw_)[NB][16], float (&pm_)[NB][16], float (&pv_)[NB][16], float* W_, float* mo_, float* vo_,
+                      long ldw_, int n0, int jn, int N_, int lane, float b1_, float b2_, float eps_, float grad_scale_,
+                      const float* coef)
+      : W(W_), mo(mo_), vo(vo_), ldw((unsigned)ldw_), row0((unsigned)(n0 + 4 * (lane >> 5))), N(N_), nfrag(4 * jn),
+        b1(b1_), b2(b2_), eps(eps_), grad_scale(grad_scale_), step_size(coef[0]), inv_bc2_sqrt(coef[1]),
+        pw(pw_), pm(pm_), pv(pv_) {}
+  // o0: the wave's element offset of (row0, its first column) in W -- the kernel's, re-read behind its fence
+  __device__ void prime(unsigned o0) {
+#pragma unroll
+    for (int f = 0; f < NB - 1; ++f) fetch(o0, f, f);
+  }
+  __device__ void fetch(unsigned o0, int f, int b) {       // b = f % NB
+    if (f >= nfrag) return;
+    const unsigned base = o0 + 32u * (unsigned)(f >> 2);
+    const int i = f & 3;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const unsigned rr = tile_row(i, r);
+      if (row_live<FULLN>(row0, rr, N)) {
+        const unsigned o = base + rr * ldw;
+        pw[b][r] = W[o]; pm[b][r] = mo[o]; pv[b][r] = vo[o];
+      }
+    }
+  }
+  // row fragment i of column step j: request the fragment NB - 1 ahead, apply Adam to this one, write the three back
+  __device__ void update(unsigned o0, int j, int i, f32x16 acc) {
+    const unsigned base = o0 + 32u * (unsigned)j;
+    const int b = i % NB;
+    fetch(o0, 4 * j + i + NB - 1, (i + NB - 1) % NB);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const unsigned rr = tile_row(i, r);
+      if (row_live<FULLN>(row0, rr, N)) {
+        const unsigned o = base + rr * ldw;
+        adam_update(pw[b][r], pm[b][r], pv[b][r], acc[r] * grad_scale, b1, b2, eps, step_size, inv_bc2_sqrt);
+        W[o] = pw[b][r];
+        mo[o] = pm[b][r];
+        vo[o] = pv[b][r];
+      }
+    }
+  }
+};
+
 // TO = bf16 (the data-parallel step with bf16 gradient buckets: the gradient is produced in the form it crosses the wire
 // in, no fp32 copy and no cast pass): neighbouring lanes exchange one packed pair (DPP) so that every lane stores two
 // adjacent columns of one row as one dword -- 64-B runs per row and half-wave, the other half of the line follows with
@@ -399,84 +554,28 @@ __global__ __launch_bounds__(256) void skinny_wgrad_kernel(const float* __restri
                                                            const float* __restrict__ x, long ldx,
                                                            TO* __restrict__ dW, long lddw, int M, int N,
                                                            int K) {
-  __shared__ __attribute__((aligned(16))) bf16x8 apan[F32 ? 1 : 4][4][64];      // [row fragment i][k-step s][lane]
-  __shared__ __attribute__((aligned(16))) f32x4 apan32[F32 ? 4 : 1][4][2][64];   // exact variant: the same, fp32 (2 x 16 B)
+  __shared__ __attribute__((aligned(16))) DzPanel<F32> apan;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
   const int n0 = blockIdx.y * 128;
   const int kb = (blockIdx.x * 4 + wave) * (32 * JL);
   const int jn = kb < K ? min(JL, (K - kb) / 32) : 0;
-
-  {
-    const int s = wave;                                   // wave w packs k-step w of all 4 fragments
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned ncol = (unsigned)min(n0 + 32 * i + l31, N - 1);
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int m = 16 * s + 8 * h + e;
-        const float v = dz[(unsigned)min(m, M - 1) * (unsigned)lddz + ncol];
-        t[e] = m < M ? v : 0.f;
-      }
-      if constexpr (F32) {
-        apan32[i][s][0][lane] = f32x4{t[0], t[1], t[2], t[3]};
-        apan32[i][s][1][lane] = f32x4{t[4], t[5], t[6], t[7]};
-      } else {
-        apan[i][s][lane] = pack8(t);
-      }
-    }
-  }
+  pack_dz_panel<F32>(apan, dz, lddz, M, N, n0, 0, wave, lane);
   unsigned xoff[4][8];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      xoff[s][e] = (unsigned)min(16 * s + 8 * h + e, M - 1) * (unsigned)ldx + min(kb, K - 32) + l31;
   float br[4][8];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) br[s][e] = x[xoff[s][e]];
+  x_offsets(xoff, ldx, M, K, kb, lane);
+  x_load(br, x, xoff);
   __syncthreads();
 
   const unsigned row0 = (unsigned)(n0 + 4 * h);
   for (int j = 0; j < jn; ++j) {
-    bf16x8 bf[4];
-    float bq[F32 ? 4 : 1][8];
+    bfrag_t<F32> b[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if constexpr (F32) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bq[s][e] = br[s][e];
-      } else {
-        bf[s] = pack8(br[s]);
-      }
-    }
-    {
-      const float* xn = x + 32 * min(j + 1, jn - 1);      // last iteration: harmless re-read
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) br[s][e] = xn[xoff[s][e]];
-    }
+    for (int s = 0; s < 4; ++s) b[s] = make_bfrag<F32>(br[s]);
+    x_load(br, x + 32 * min(j + 1, jn - 1), xoff);         // the next column step; last iteration: harmless re-read
     asm volatile("" ::: "memory");
     f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (F32) {
-          const f32x4 lo = apan32[i][s][0][lane], hi = apan32[i][s][1][lane];
-          const float a[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-          acc[i] = mfma8_f32(a, bq[s], acc[i]);
-        } else {
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(apan[i][s][lane], bf[s], acc[i], 0, 0, 0);
-        }
-      }
+    acc_zero(acc);
+    contract16<F32>(acc, apan, b, lane);
     TO* dj = dW + kb + 32 * j;                             // uniform
     unsigned o0 = row0 * (unsigned)lddw + l31;
     // opaque to the optimiser: LICM otherwise hoists all 64 store offsets (and the 16 LDS
@@ -487,8 +586,8 @@ __global__ __launch_bounds__(256) void skinny_wgrad_kernel(const float* __restri
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-          if (FULLN || row0 + rr < (unsigned)N) dj[o0 + rr * (unsigned)lddw] = acc[i][r];
+          const unsigned rr = tile_row(i, r);
+          if (row_live<FULLN>(row0, rr, N)) dj[o0 + rr * (unsigned)lddw] = acc[i][r];
         }
     } else {
       const bool odd = lane & 1;
@@ -503,8 +602,8 @@ __global__ __launch_bounds__(256) void skinny_wgrad_kernel(const float* __restri
           const uint32_t mine = pk2(acc[i][r], acc[i][r + 1]);
           const uint32_t theirs = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0xB1, 0xF, 0xF, true);
           const uint32_t packed = __builtin_amdgcn_perm(theirs, mine, sel);
-          const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2) + (odd ? 1u : 0u);
-          if (FULLN || row0 + rr < (unsigned)N) dj32[w0 + rr * (unsigned)(lddw >> 1)] = packed;
+          const unsigned rr = tile_row(i, r) + (odd ? 1u : 0u);
+          if (row_live<FULLN>(row0, rr, N)) dj32[w0 + rr * (unsigned)(lddw >> 1)] = packed;
         }
     }
   }
@@ -524,122 +623,33 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_kernel(const float* __r
                                                                 float* __restrict__ vo, long ldw, int M, int N, int K,
                                                                 float b1, float b2, float eps, float grad_scale,
                                                                 const float* __restrict__ coef) {
-  static_assert(NB == 2 || NB == 4, "fragment buffers: a ring of 2 or 4 (index = fragment number mod NB, static)");
-  __shared__ __attribute__((aligned(16))) bf16x8 apan[F32 ? 1 : 4][4][64];      // [row fragment i][k-step s][lane]
-  __shared__ __attribute__((aligned(16))) f32x4 apan32[F32 ? 4 : 1][4][2][64];   // exact variant: the same, fp32
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  const float step_size = coef[0], inv_bc2_sqrt = coef[1];
+  __shared__ __attribute__((aligned(16))) DzPanel<F32> apan;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n0 = blockIdx.y * 128;
   const int kb = (blockIdx.x * 4 + wave) * (32 * JL);
   const int jn = kb < K ? min(JL, (K - kb) / 32) : 0;
-  {
-    const int s = wave;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned ncol = (unsigned)min(n0 + 32 * i + l31, N - 1);
-      float t[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int m = 16 * s + 8 * h + e;
-        const float v = dz[(unsigned)min(m, M - 1) * (unsigned)lddz + ncol];
-        t[e] = m < M ? v : 0.f;
-      }
-      if constexpr (F32) {
-        apan32[i][s][0][lane] = f32x4{t[0], t[1], t[2], t[3]};
-        apan32[i][s][1][lane] = f32x4{t[4], t[5], t[6], t[7]};
-      } else {
-        apan[i][s][lane] = pack8(t);
-      }
-    }
-  }
+  pack_dz_panel<F32>(apan, dz, lddz, M, N, n0, 0, wave, lane);
   unsigned xoff[4][8];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      xoff[s][e] = (unsigned)min(16 * s + 8 * h + e, M - 1) * (unsigned)ldx + min(kb, K - 32) + l31;
   float br[4][8];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) br[s][e] = x[xoff[s][e]];
-
-  // the wave's fragments f = 4 j + i (32 rows x 32 columns each), NB - 1 of them in flight ahead of the update
-  const unsigned row0 = (unsigned)(n0 + 4 * h);
-  unsigned o0 = row0 * (unsigned)ldw + (unsigned)kb + l31;
+  x_offsets(xoff, ldx, M, K, kb, lane);
+  x_load(br, x, xoff);
   float pw[NB][16], pm[NB][16], pv[NB][16];
-  const int nfrag = 4 * jn;
-  auto fetch = [&](int f, int b) {                         // b = f % NB, static at every call site
-    if (f >= nfrag) return;
-    const unsigned base = o0 + 32u * (unsigned)(f >> 2);
-    const int i = f & 3;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-      if (FULLN || row0 + rr < (unsigned)N) {
-        const unsigned o = base + rr * (unsigned)ldw;
-        pw[b][r] = W[o]; pm[b][r] = mo[o]; pv[b][r] = vo[o];
-      }
-    }
-  };
-#pragma unroll
-  for (int f = 0; f < NB - 1; ++f) fetch(f, f);
+  AdamRing<NB, FULLN> ring(pw, pm, pv, W, mo, vo, ldw, n0, jn, N, lane, b1, b2, eps, grad_scale, coef);
+  unsigned o0 = ring.row0 * (unsigned)ldw + (unsigned)kb + (lane & 31);
+  ring.prime(o0);
   __syncthreads();
 
   for (int j = 0; j < jn; ++j) {
-    bf16x8 bf[4];
-    float bq[F32 ? 4 : 1][8];
+    bfrag_t<F32> b[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if constexpr (F32) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bq[s][e] = br[s][e];
-      } else {
-        bf[s] = pack8(br[s]);
-      }
-    }
-    {
-      const float* xn = x + 32 * min(j + 1, jn - 1);
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) br[s][e] = xn[xoff[s][e]];
-    }
+    for (int s = 0; s < 4; ++s) b[s] = make_bfrag<F32>(br[s]);
+    x_load(br, x + 32 * min(j + 1, jn - 1), xoff);         // the next column step; last iteration: harmless re-read
     asm volatile("" : "+v"(o0) : : "memory");              // keeps the 64 row offsets out of registers (see wgrad)
     f32x16 acc[4];
+    acc_zero(acc);
+    contract16<F32>(acc, apan, b, lane);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if constexpr (F32) {
-          const f32x4 lo = apan32[i][s][0][lane], hi = apan32[i][s][1][lane];
-          const float a[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-          acc[i] = mfma8_f32(a, bq[s], acc[i]);
-        } else {
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(apan[i][s][lane], bf[s], acc[i], 0, 0, 0);
-        }
-      }
-    const unsigned base = o0 + 32u * (unsigned)j;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int b = i % NB;
-      fetch(4 * j + i + NB - 1, (i + NB - 1) % NB);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-        if (FULLN || row0 + rr < (unsigned)N) {
-          const unsigned o = base + rr * (unsigned)ldw;
-          adam_update(pw[b][r], pm[b][r], pv[b][r], acc[i][r] * grad_scale, b1, b2, eps, step_size, inv_bc2_sqrt);
-          W[o] = pw[b][r];
-          mo[o] = pm[b][r];
-          vo[o] = pv[b][r];
-        }
-      }
-    }
+    for (int i = 0; i < 4; ++i) ring.update(o0, j, i, acc[i]);
   }
 }
 
@@ -661,30 +671,13 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_rows_kernel(const float
                                                                      float* __restrict__ vo, long ldw, int M, int N, int K,
                                                                      float b1, float b2, float eps, float grad_scale,
                                                                      const float* __restrict__ coef) {
-  static_assert(NB == 2 || NB == 4, "fragment buffers: a ring of 2 or 4");
-  extern __shared__ __attribute__((aligned(16))) bf16x8 apan_rows[];           // [MC][row fragment i][k-step s][lane]
+  extern __shared__ __attribute__((aligned(16))) DzPanel<false> apan_rows[];          // [MC][row fragment i][k-step s][lane]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  const float step_size = coef[0], inv_bc2_sqrt = coef[1];
   const int n0 = blockIdx.y * 128;
   const int kb = (blockIdx.x * 4 + wave) * (32 * JL);
   const int jn = kb < K ? min(JL, (K - kb) / 32) : 0;
-  {
-    const int s = wave;
 #pragma unroll
-    for (int mc = 0; mc < MC; ++mc)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const unsigned ncol = (unsigned)min(n0 + 32 * i + l31, N - 1);
-        float t[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int m = 64 * mc + 16 * s + 8 * h + e;
-          const float v = dz[(unsigned)min(m, M - 1) * (unsigned)lddz + ncol];
-          t[e] = m < M ? v : 0.f;                          // rows past M contribute nothing, whatever x holds there
-        }
-        apan_rows[((mc * 4 + i) * 4 + s) * 64 + lane] = pack8(t);
-      }
-  }
+  for (int mc = 0; mc < MC; ++mc) pack_dz_panel<false>(apan_rows[mc], dz, lddz, M, N, n0, 64 * mc, wave, lane);
   // x[row][col]: row = 64 mc + 16 s + 8 h + e, col = kb + 32 j + l31 -- one vector offset per lane, everything else in
   // the (uniform) scalar offset of a buffer load.  The scalar offset is outside the buffer's range check: the caller
   // allocates x for 64 MC rows (the rows past M hold finite values -- zeros -- and meet zero dz fragments)
@@ -701,35 +694,16 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_rows_kernel(const float
   };
   float br[4][8];
   load_x(br, 0, 0);
-
-  const unsigned row0 = (unsigned)(n0 + 4 * h);
-  unsigned o0 = row0 * (unsigned)ldw + (unsigned)kb + l31;
   float pw[NB][16], pm[NB][16], pv[NB][16];
-  const int nfrag = 4 * jn;
-  auto fetch = [&](int f, int b) {
-    if (f >= nfrag) return;
-    const unsigned base = o0 + 32u * (unsigned)(f >> 2);
-    const int i = f & 3;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-      if (FULLN || row0 + rr < (unsigned)N) {
-        const unsigned o = base + rr * (unsigned)ldw;
-        pw[b][r] = W[o]; pm[b][r] = mo[o]; pv[b][r] = vo[o];
-      }
-    }
-  };
-#pragma unroll
-  for (int f = 0; f < NB - 1; ++f) fetch(f, f);
+  AdamRing<NB, FULLN> ring(pw, pm, pv, W, mo, vo, ldw, n0, jn, N, lane, b1, b2, eps, grad_scale, coef);
+  unsigned o0 = ring.row0 * (unsigned)ldw + (unsigned)kb + (lane & 31);
+  ring.prime(o0);
   __syncthreads();
 
   for (int j = 0; j < jn; ++j) {
-    asm volatile("" : "+v"(o0) : : "memory");
+    asm volatile("" : "+v"(o0) : : "memory");              // keeps the 64 row offsets out of registers (see wgrad)
     f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    acc_zero(acc);
 #pragma unroll
     for (int mc = 0; mc < MC; ++mc) {
       bf16x8 bf[4];
@@ -738,29 +712,16 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_rows_kernel(const float
       // the next chunk's x (behind the last chunk: the first chunk of the next column step; last step: a harmless re-read)
       if (mc + 1 < MC) load_x(br, mc + 1, j);
       else load_x(br, 0, min(j + 1, jn - 1));
+      // contract16, spelled out: called as the function from this unrolled chunk loop the same 16 MFMAs cost the
+      // full-panel JL = 2 / 4 kernels 44-60 registers (MC = 1 .. 4: 264-272 -> 308-332; gfx950 code objects)
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(apan_rows[((mc * 4 + i) * 4 + s) * 64 + lane], bf[s], acc[i], 0, 0, 0);
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(apan_rows[mc].f[i][s][0][lane], bf[s], acc[i], 0, 0, 0);
     }
-    const unsigned base = o0 + 32u * (unsigned)j;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int b = i % NB;
-      fetch(4 * j + i + NB - 1, (i + NB - 1) % NB);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-        if (FULLN || row0 + rr < (unsigned)N) {
-          const unsigned o = base + rr * (unsigned)ldw;
-          adam_update(pw[b][r], pm[b][r], pv[b][r], acc[i][r] * grad_scale, b1, b2, eps, step_size, inv_bc2_sqrt);
-          W[o] = pw[b][r];
-          mo[o] = pm[b][r];
-          vo[o] = pv[b][r];
-        }
-      }
-    }
+    for (int i = 0; i < 4; ++i) ring.update(o0, j, i, acc[i]);
   }
 }
 
@@ -806,10 +767,8 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_t16_kernel(const bf16_t
                                                                     float* __restrict__ vo, long ldw, int N, int K,
                                                                     float b1, float b2, float eps, float grad_scale,
                                                                     const float* __restrict__ coef) {
-  static_assert(NB == 2 || NB == 4, "fragment buffers: a ring of 2 or 4");
-  extern __shared__ __attribute__((aligned(16))) bf16x8 apan_t16[];            // [MC][row fragment i][k-step s][lane]
+  extern __shared__ __attribute__((aligned(16))) DzPanel<false> apan_t16[];          // [MC][row fragment i][k-step s][lane]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  const float step_size = coef[0], inv_bc2_sqrt = coef[1];
   const int n0 = blockIdx.y * 128;
   const int kb = (blockIdx.x * 4 + wave) * (32 * JL);
   const int jn = kb < K ? min(JL, (K - kb) / 32) : 0;
@@ -826,7 +785,7 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_t16_kernel(const bf16_t
         const unsigned ncol = (unsigned)min(n0 + 32 * i + l31, N - 1);
         const unsigned vo_ = ncol * 128u + (unsigned)h * 64u + (unsigned)s * 16u;
         const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rP, vo_, (unsigned)((long)mc * chunk_stride * 2), 0);
-        apan_t16[((mc * 4 + i) * 4 + s) * 64 + lane] = __builtin_bit_cast(bf16x8, v);
+        apan_t16[mc].f[i][s][0][lane] = __builtin_bit_cast(bf16x8, v);
       }
   }
   // x fragments: column N + kb + 32 j + l31 of chunk mc, bytes [64 h + 16 s, + 16)
@@ -839,65 +798,26 @@ __global__ __launch_bounds__(256) void skinny_wgrad_adam_t16_kernel(const bf16_t
   };
   bf16x8 bcur[4], bnxt[4];
   load_x(bcur, 0, 0);
-
-  const unsigned row0 = (unsigned)(n0 + 4 * h);
-  unsigned o0 = row0 * (unsigned)ldw + (unsigned)kb + l31;
   float pw[NB][16], pm[NB][16], pv[NB][16];
-  const int nfrag = 4 * jn;
-  auto fetch = [&](int f, int b) {
-    if (f >= nfrag) return;
-    const unsigned base = o0 + 32u * (unsigned)(f >> 2);
-    const int i = f & 3;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-      if (FULLN || row0 + rr < (unsigned)N) {
-        const unsigned o = base + rr * (unsigned)ldw;
-        pw[b][r] = W[o]; pm[b][r] = mo[o]; pv[b][r] = vo[o];
-      }
-    }
-  };
-#pragma unroll
-  for (int f = 0; f < NB - 1; ++f) fetch(f, f);
+  AdamRing<NB, FULLN> ring(pw, pm, pv, W, mo, vo, ldw, n0, jn, N, lane, b1, b2, eps, grad_scale, coef);
+  unsigned o0 = ring.row0 * (unsigned)ldw + (unsigned)kb + (lane & 31);
+  ring.prime(o0);
   __syncthreads();
 
   for (int j = 0; j < jn; ++j) {
-    asm volatile("" : "+v"(o0) : : "memory");
+    asm volatile("" : "+v"(o0) : : "memory");              // keeps the 64 row offsets out of registers (see wgrad)
     f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    acc_zero(acc);
     for (int mc = 0; mc < MC; ++mc) {
       // the next chunk's x (behind the last chunk: the first chunk of the next column step; last step: a harmless re-read)
       if (mc + 1 < MC) load_x(bnxt, mc + 1, j);
       else load_x(bnxt, 0, min(j + 1, jn - 1));
-      const bf16x8* ap = apan_t16 + (mc * 16) * 64 + lane;
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[(i * 4 + s) * 64], bcur[s], acc[i], 0, 0, 0);
+      contract16<false>(acc, apan_t16[mc], bcur, lane);
 #pragma unroll
       for (int s = 0; s < 4; ++s) bcur[s] = bnxt[s];
     }
-    const unsigned base = o0 + 32u * (unsigned)j;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int b = i % NB;
-      fetch(4 * j + i + NB - 1, (i + NB - 1) % NB);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rr = 32 * i + (r & 3) + 8 * (r >> 2);
-        if (FULLN || row0 + rr < (unsigned)N) {
-          const unsigned o = base + rr * (unsigned)ldw;
-          adam_update(pw[b][r], pm[b][r], pv[b][r], acc[i][r] * grad_scale, b1, b2, eps, step_size, inv_bc2_sqrt);
-          W[o] = pw[b][r];
-          mo[o] = pm[b][r];
-          vo[o] = pv[b][r];
-        }
-      }
-    }
+    for (int i = 0; i < 4; ++i) ring.update(o0, j, i, acc[i]);
   }
 }
 
@@ -1074,30 +994,77 @@ extern "C" int pcaa_skinny_linear_dgrad_exact(const float* dz, long lddz, const 
   return skinny_dgrad_impl(dz, lddz, W, 0, ldw, dx, a_prev, accumulate, ws, ws_floats, M, N, K, nsplit, 1, stream);
 }
 
+// ------------------------------------------------------------------ the weight-gradient family, host side
+// The argument checks the wgrad entry points share, in the order every one of them makes them; `name` is the entry
+// point's, for the message.  ldw: the leading dimension of dW (plain forms: offsets < 2^31) or of W and its moments
+// (fused forms: < 2^30).  rows_need / rows_alloc: the gathered-rows form's whole 64-row chunks of x.
+enum WgradForm { WG_DW, WG_DW_BF16, WG_ADAM, WG_ADAM_ROWS };
+static int wgrad_check_args(const char* name, WgradForm form, bool ptrs, const void* x, const void* out, long lddz, long ldx,
+                            long ldw, int M, int N, int K, int rows_need = 0, int rows_alloc = 0) {
+  const bool rows = form == WG_ADAM_ROWS, fused = form == WG_ADAM || rows;
+  PCAA_CHECK_ARG(ptrs, "%s: null pointer", name);
+  PCAA_CHECK_ARG(M >= 1 && M <= (rows ? 512 : 64) && N >= 1 && K >= 32 && K % 32 == 0,
+                 "%s: unsupported shape M=%d N=%d K=%d%s", name, M, N, K, rows ? " (M <= 512, K % 32 == 0)" : "");
+  PCAA_CHECK_ARG(rows_alloc >= rows_need, "%s: x must be allocated (and finite) for %d rows, got %d", name, rows_need,
+                 rows_alloc);
+  if (form == WG_DW_BF16)
+    PCAA_CHECK_ARG(lddz >= N && ldx >= K && ldw >= K && ldw % 2 == 0 && ((uintptr_t)out % 4) == 0,
+                   "%s: bad leading dimensions / alignment", name);
+  else
+    PCAA_CHECK_ARG(lddz >= N && ldx >= K && ldw >= K, "%s: bad leading dimensions", name);
+  const bool x_ok = rows ? 512L * ldx < (1L << 30) && ((uintptr_t)x % 4) == 0 : (long)M * ldx < (1L << 31);
+  PCAA_CHECK_ARG((long)M * lddz < (1L << 31) && x_ok && (long)N * ldw < (fused ? 1L << 30 : 1L << 31),
+                 "%s: operands beyond 32-bit %soffsets", name, fused ? "" : "element ");
+  return PCAA_OK;
+}
+#define WGRAD_CHECK_ARGS(...)                                    \
+  do {                                                           \
+    const int rc__ = wgrad_check_args(__VA_ARGS__);              \
+    if (rc__ != PCAA_OK) return rc__;                            \
+  } while (0)
+
+// columns per wave = 32 JL: the widest that still gives the chip >= `want` workgroups (every fragment is a full
+// memory round trip for its wave: the 960 -> 1920 layer took 47 us in 30 workgroups of 4 x 4 fragments per wave)
+static int wgrad_cols_per_wave(int N, int K, int want) {
+  auto ntile = [&](int jl) { return cdiv(K, 4 * 32 * jl) * cdiv(N, 128); };
+  return ntile(4) >= want ? 4 : (ntile(2) >= want ? 2 : 1);
+}
+
+// runtime values -> template arguments: f receives them as std::integral_constant
+template <typename F>
+static bool pick_bool(bool v, F f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F>
+static bool pick_jl_full(int jl, bool full, F f) {
+  return pick_bool(full, [&](auto fulln) {
+    return jl == 4   ? f(std::integral_constant<int, 4>{}, fulln)
+           : jl == 2 ? f(std::integral_constant<int, 2>{}, fulln)
+                     : f(std::integral_constant<int, 1>{}, fulln);
+  });
+}
+
+// One launch of the family's grid.  A kernel with a dynamic dz panel (lds > 0) has its LDS limit raised the first time
+// and again whenever a larger panel arrives; false: the limit could not be raised.
+template <auto KERN, int JL, typename... Args>
+static bool launch_wgrad(size_t lds, hipStream_t st, int N, int K, Args... args) {
+  static size_t configured = 0;                           // per kernel: KERN is a template argument
+  if (lds > configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return false;
+    configured = lds;
+  }
+  hipLaunchKernelGGL(KERN, dim3((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128)), dim3(256), lds, st, args...);
+  return true;
+}
+
 static int skinny_wgrad_impl(const float* dz, long lddz, const float* x, long ldx, float* dW, long lddw,
                              int M, int N, int K, int exact, void* stream) {
-  PCAA_CHECK_ARG(dz && x && dW, "pcaa_skinny_linear_wgrad: null pointer");
-  PCAA_CHECK_ARG(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0,
-                 "pcaa_skinny_linear_wgrad: unsupported shape M=%d N=%d K=%d", M, N, K);
-  PCAA_CHECK_ARG(lddz >= N && ldx >= K && lddw >= K, "pcaa_skinny_linear_wgrad: bad leading dimensions");
-  PCAA_CHECK_ARG((long)M * lddz < (1L << 31) && (long)M * ldx < (1L << 31) && (long)N * lddw < (1L << 31),
-                 "pcaa_skinny_linear_wgrad: operands beyond 32-bit element offsets");
-  constexpr int JL = 4;
-  const dim3 grid((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128));
-  if (exact) {
-    if (N % 128 == 0)
-      hipLaunchKernelGGL((skinny_wgrad_kernel<JL, true, float, true>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x,
-                         ldx, dW, lddw, M, N, K);
-    else
-      hipLaunchKernelGGL((skinny_wgrad_kernel<JL, false, float, true>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x,
-                         ldx, dW, lddw, M, N, K);
-  } else if (N % 128 == 0) {
-    hipLaunchKernelGGL((skinny_wgrad_kernel<JL, true>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x, ldx, dW,
-                       lddw, M, N, K);
-  } else {
-    hipLaunchKernelGGL((skinny_wgrad_kernel<JL, false>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x, ldx, dW,
-                       lddw, M, N, K);
-  }
+  WGRAD_CHECK_ARGS("pcaa_skinny_linear_wgrad", WG_DW, dz && x && dW, x, dW, lddz, ldx, lddw, M, N, K);
+  pick_bool(exact, [&](auto ex) {
+    return pick_bool(N % 128 == 0, [&](auto full) {
+      return launch_wgrad<skinny_wgrad_kernel<4, decltype(full)::value, float, decltype(ex)::value>, 4>(0, as_stream(stream), N, K, dz, lddz, x, ldx,
+                                                                                  dW, lddw, M, N, K);
+    });
+  });
   PCAA_RETURN_LAUNCH_STATUS("pcaa_skinny_linear_wgrad");
 }
 
@@ -1112,22 +1079,12 @@ extern "C" int pcaa_skinny_linear_wgrad_exact(const float* dz, long lddz, const 
 
 extern "C" int pcaa_skinny_linear_wgrad_bf16(const float* dz, long lddz, const float* x, long ldx, void* dW_bf16, long lddw,
                                              int M, int N, int K, void* stream) {
-  PCAA_CHECK_ARG(dz && x && dW_bf16, "pcaa_skinny_linear_wgrad_bf16: null pointer");
-  PCAA_CHECK_ARG(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0,
-                 "pcaa_skinny_linear_wgrad_bf16: unsupported shape M=%d N=%d K=%d", M, N, K);
-  PCAA_CHECK_ARG(lddz >= N && ldx >= K && lddw >= K && lddw % 2 == 0 && ((uintptr_t)dW_bf16 % 4) == 0,
-                 "pcaa_skinny_linear_wgrad_bf16: bad leading dimensions / alignment");
-  PCAA_CHECK_ARG((long)M * lddz < (1L << 31) && (long)M * ldx < (1L << 31) && (long)N * lddw < (1L << 31),
-                 "pcaa_skinny_linear_wgrad_bf16: operands beyond 32-bit element offsets");
-  constexpr int JL = 4;
-  const dim3 grid((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128));
+  WGRAD_CHECK_ARGS("pcaa_skinny_linear_wgrad_bf16", WG_DW_BF16, dz && x && dW_bf16, x, dW_bf16, lddz, ldx, lddw, M, N, K);
   bf16_t* out = reinterpret_cast<bf16_t*>(dW_bf16);
-  if (N % 128 == 0)
-    hipLaunchKernelGGL((skinny_wgrad_kernel<JL, true, bf16_t>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x, ldx, out,
-                       lddw, M, N, K);
-  else
-    hipLaunchKernelGGL((skinny_wgrad_kernel<JL, false, bf16_t>), grid, dim3(256), 0, as_stream(stream), dz, lddz, x, ldx, out,
-                       lddw, M, N, K);
+  pick_bool(N % 128 == 0, [&](auto full) {
+    return launch_wgrad<skinny_wgrad_kernel<4, decltype(full)::value, bf16_t>, 4>(0, as_stream(stream), N, K, dz, lddz, x, ldx, out, lddw,
+                                                                       M, N, K);
+  });
   PCAA_RETURN_LAUNCH_STATUS("pcaa_skinny_linear_wgrad_bf16");
 }
 
@@ -1135,12 +1092,8 @@ static int skinny_wgrad_adam_impl(const float* dz, long lddz, const float* x, lo
                                   float* exp_avg, float* exp_avg_sq, long ldw, int M, int N, int K,
                                   float beta1, float beta2, float eps, float grad_scale,
                                   const float* coef_dev, int exact, void* stream) {
-  PCAA_CHECK_ARG(dz && x && W && exp_avg && exp_avg_sq && coef_dev, "pcaa_skinny_linear_wgrad_adam: null pointer");
-  PCAA_CHECK_ARG(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0,
-                 "pcaa_skinny_linear_wgrad_adam: unsupported shape M=%d N=%d K=%d", M, N, K);
-  PCAA_CHECK_ARG(lddz >= N && ldx >= K && ldw >= K, "pcaa_skinny_linear_wgrad_adam: bad leading dimensions");
-  PCAA_CHECK_ARG((long)M * lddz < (1L << 31) && (long)M * ldx < (1L << 31) && (long)N * ldw < (1L << 30),
-                 "pcaa_skinny_linear_wgrad_adam: operands beyond 32-bit offsets");
+  WGRAD_CHECK_ARGS("pcaa_skinny_linear_wgrad_adam", WG_ADAM, dz && x && W && exp_avg && exp_avg_sq && coef_dev, x, W, lddz,
+                   ldx, ldw, M, N, K);
   // (round 6, built and removed: the MFMA operands swapped -- the transposed tile, a lane holding four consecutive columns of
   // ONE row, so that every access to W / exp_avg / exp_avg_sq is 16 B wide, 4 + 4 instructions per fragment and array instead
   // of 16 + 16 -- bit-identical results, 0.99-1.03 ms against 0.79 on the same box: a wave instruction then touches a
@@ -1148,79 +1101,39 @@ static int skinny_wgrad_adam_impl(const float* dz, long lddz, const float* x, lo
   // measured alone on the four wide layers of the bench shape (tools/skinny_lab.py): 0.81 ms fused against 0.97 ms
   // (weight gradient 0.17 + Adam 0.80), 5.0 TB/s on the 7680 -> 15360 layer; a ring of 4 fragment buffers (three
   // fragments in flight) or 8 column steps per wave: 0.83 / 0.88 / 0.86 ms -- not kept
-  // columns per wave = 32 JL: the widest that still gives the chip >= 1024 workgroups (every fragment is a full
-  // memory round trip for its wave: the 960 -> 1920 layer took 47 us in 30 workgroups of 4 x 4 fragments per wave)
   constexpr int NB = 2;
-  auto ntile = [&](int jl) { return cdiv(K, 4 * 32 * jl) * cdiv(N, 128); };
-  const int jl = ntile(4) >= 1024 ? 4 : (ntile(2) >= 1024 ? 2 : 1);
-#define WA_LAUNCH(JL, FULL, EX)                                                                                   \
-  hipLaunchKernelGGL((skinny_wgrad_adam_kernel<JL, FULL, NB, EX>), dim3((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128)), \
-                     dim3(256), 0, as_stream(stream), dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1,  \
-                     beta2, eps, grad_scale, coef_dev)
-#define WA_PICK(EX)                                                                                               \
-  do {                                                                                                            \
-    if (N % 128 == 0) {                                                                                           \
-      if (jl == 4) WA_LAUNCH(4, true, EX); else if (jl == 2) WA_LAUNCH(2, true, EX); else WA_LAUNCH(1, true, EX); \
-    } else {                                                                                                      \
-      if (jl == 4) WA_LAUNCH(4, false, EX); else if (jl == 2) WA_LAUNCH(2, false, EX); else WA_LAUNCH(1, false, EX); \
-    }                                                                                                             \
-  } while (0)
-  if (exact) WA_PICK(true); else WA_PICK(false);
-#undef WA_PICK
-#undef WA_LAUNCH
+  pick_bool(exact, [&](auto ex) {
+    return pick_jl_full(wgrad_cols_per_wave(N, K, 1024), N % 128 == 0, [&](auto jl, auto full) {
+      return launch_wgrad<skinny_wgrad_adam_kernel<decltype(jl)::value, decltype(full)::value, NB, decltype(ex)::value>, decltype(jl)::value>(
+          0, as_stream(stream), N, K, dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale,
+          coef_dev);
+    });
+  });
   PCAA_RETURN_LAUNCH_STATUS("pcaa_skinny_linear_wgrad_adam");
 }
 
 // gathered rows (data parallel): M = world * B <= 512 rows in chunks of 64
-template <int MC>
-static int launch_wgrad_adam_rows(const float* dz, long lddz, const float* x, long ldx, float* W, float* exp_avg,
-                                  float* exp_avg_sq, long ldw, int M, int N, int K, float beta1, float beta2, float eps,
-                                  float grad_scale, const float* coef_dev, hipStream_t st) {
-  constexpr int NB = 2;
-  constexpr size_t lds = (size_t)MC * 4 * 4 * 64 * sizeof(bf16x8);
-  auto ntile = [&](int jl) { return cdiv(K, 4 * 32 * jl) * cdiv(N, 128); };
-  const int jl = ntile(4) >= 1024 ? 4 : (ntile(2) >= 1024 ? 2 : 1);
-  const bool full = N % 128 == 0;
-#define WR_LAUNCH(JL, FULL)                                                                                            \
-  do {                                                                                                                 \
-    auto kern = skinny_wgrad_adam_rows_kernel<JL, FULL, NB, MC>;                                                       \
-    static bool configured = false;                                                                                    \
-    if (!configured) {                                                                                                 \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return 1;                                                                                                      \
-      configured = true;                                                                                               \
-    }                                                                                                                  \
-    hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128)), dim3(256), lds, st, dz, lddz, x, \
-                       ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev);            \
-  } while (0)
-  if (full) { if (jl == 4) WR_LAUNCH(4, true); else if (jl == 2) WR_LAUNCH(2, true); else WR_LAUNCH(1, true); }
-  else { if (jl == 4) WR_LAUNCH(4, false); else if (jl == 2) WR_LAUNCH(2, false); else WR_LAUNCH(1, false); }
-#undef WR_LAUNCH
-  return 0;
-}
-
 extern "C" int pcaa_skinny_linear_wgrad_adam_rows(const float* dz, long lddz, const float* x, long ldx, float* W,
                                                   float* exp_avg, float* exp_avg_sq, long ldw, int M, int N, int K,
                                                   float beta1, float beta2, float eps, float grad_scale,
                                                   const float* coef_dev, int rows_alloc, void* stream) {
-  PCAA_CHECK_ARG(dz && x && W && exp_avg && exp_avg_sq && coef_dev, "pcaa_skinny_linear_wgrad_adam_rows: null pointer");
-  PCAA_CHECK_ARG(M >= 1 && M <= 512 && N >= 1 && K >= 32 && K % 32 == 0,
-                 "pcaa_skinny_linear_wgrad_adam_rows: unsupported shape M=%d N=%d K=%d (M <= 512, K %% 32 == 0)", M, N, K);
-  {
-    const int mc = M <= 64 ? 1 : (M <= 128 ? 2 : (M <= 256 ? 4 : 8));
-    PCAA_CHECK_ARG(rows_alloc >= 64 * mc, "pcaa_skinny_linear_wgrad_adam_rows: x must be allocated (and finite) for %d rows, "
-                   "got %d", 64 * mc, rows_alloc);
-  }
-  PCAA_CHECK_ARG(lddz >= N && ldx >= K && ldw >= K, "pcaa_skinny_linear_wgrad_adam_rows: bad leading dimensions");
-  PCAA_CHECK_ARG((long)M * lddz < (1L << 31) && 512L * ldx < (1L << 30) && (long)N * ldw < (1L << 30) &&
-                 ((uintptr_t)x % 4) == 0, "pcaa_skinny_linear_wgrad_adam_rows: operands beyond 32-bit offsets");
-  hipStream_t st = as_stream(stream);
-  int rc;
-  if (M <= 64) rc = launch_wgrad_adam_rows<1>(dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev, st);
-  else if (M <= 128) rc = launch_wgrad_adam_rows<2>(dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev, st);
-  else if (M <= 256) rc = launch_wgrad_adam_rows<4>(dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev, st);
-  else rc = launch_wgrad_adam_rows<8>(dz, lddz, x, ldx, W, exp_avg, exp_avg_sq, ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev, st);
-  if (rc != 0) {
+  const int mc = M <= 64 ? 1 : (M <= 128 ? 2 : (M <= 256 ? 4 : 8));
+  WGRAD_CHECK_ARGS("pcaa_skinny_linear_wgrad_adam_rows", WG_ADAM_ROWS, dz && x && W && exp_avg && exp_avg_sq && coef_dev, x, W,
+                   lddz, ldx, ldw, M, N, K, 64 * mc, rows_alloc);
+  constexpr int NB = 2;
+  auto launch = [&](auto mcc) {
+    return pick_jl_full(wgrad_cols_per_wave(N, K, 1024), N % 128 == 0, [&](auto jl, auto full) {
+      return launch_wgrad<skinny_wgrad_adam_rows_kernel<decltype(jl)::value, decltype(full)::value, NB, decltype(mcc)::value>, decltype(jl)::value>(
+          (size_t)decltype(mcc)::value * sizeof(DzPanel<false>), as_stream(stream), N, K, dz, lddz, x, ldx, W, exp_avg, exp_avg_sq,
+          ldw, M, N, K, beta1, beta2, eps, grad_scale, coef_dev);
+    });
+  };
+  using std::integral_constant;
+  const bool ok = mc == 1   ? launch(integral_constant<int, 1>{})
+                  : mc == 2 ? launch(integral_constant<int, 2>{})
+                  : mc == 4 ? launch(integral_constant<int, 4>{})
+                            : launch(integral_constant<int, 8>{});
+  if (!ok) {
     pcaa_set_error("pcaa_skinny_linear_wgrad_adam_rows: cannot raise the dynamic LDS limit");
     return PCAA_ERR_LAUNCH;
   }
@@ -1256,37 +1169,6 @@ extern "C" int pcaa_pack_rows_t16(const float* dz, long lddz, int N, const float
   PCAA_RETURN_LAUNCH_STATUS("pcaa_pack_rows_t16");
 }
 
-template <int NB>
-static int launch_wgrad_adam_t16(const bf16_t* P, long chunk_stride, int MC, float* W, float* exp_avg, float* exp_avg_sq,
-                                 long ldw, int N, int K, float beta1, float beta2, float eps, float grad_scale,
-                                 const float* coef_dev, hipStream_t st) {
-  const size_t lds = (size_t)MC * 4 * 4 * 64 * sizeof(bf16x8);
-  auto ntile = [&](int jl) { return cdiv(K, 4 * 32 * jl) * cdiv(N, 128); };
-  // columns per wave (32 JL).  Up to 2 chunks several workgroups share a CU and the single-process rule holds (>= 1024
-  // workgroups); from 4 chunks on the dz panels leave room for ONE workgroup per CU (64-128 KB of LDS), so 256 run at a
-  // time whatever the grid, and every workgroup pays a panel load (16 KB per chunk, from L2) + a barrier before its first
-  // MFMA: the widest JL that still gives every CU >= 1.5 workgroups amortises that prologue over 4 column steps
-  const int want = MC >= 4 ? 384 : 1024;
-  const int jl = ntile(4) >= want ? 4 : (ntile(2) >= want ? 2 : 1);
-  const bool full = N % 128 == 0;
-#define WT_LAUNCH(JL, FULL)                                                                                            \
-  do {                                                                                                                 \
-    auto kern = skinny_wgrad_adam_t16_kernel<JL, FULL, NB>;                                                            \
-    static size_t configured = 0;                                                                                      \
-    if (lds > configured) {                                                                                            \
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return 1;                                                                                                      \
-      configured = lds;                                                                                                \
-    }                                                                                                                  \
-    hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(K, 4 * 32 * JL), (unsigned)cdiv(N, 128)), dim3(256), lds, st, P, chunk_stride, \
-                       MC, W, exp_avg, exp_avg_sq, ldw, N, K, beta1, beta2, eps, grad_scale, coef_dev);                \
-  } while (0)
-  if (full) { if (jl == 4) WT_LAUNCH(4, true); else if (jl == 2) WT_LAUNCH(2, true); else WT_LAUNCH(1, true); }
-  else { if (jl == 4) WT_LAUNCH(4, false); else if (jl == 2) WT_LAUNCH(2, false); else WT_LAUNCH(1, false); }
-#undef WT_LAUNCH
-  return 0;
-}
-
 extern "C" int pcaa_skinny_linear_wgrad_adam_t16(const void* packed_bf16, long chunk_stride, int chunks, float* W,
                                                  float* exp_avg, float* exp_avg_sq, long ldw, int N, int K, float beta1,
                                                  float beta2, float eps, float grad_scale, const float* coef_dev,
@@ -1298,14 +1180,22 @@ extern "C" int pcaa_skinny_linear_wgrad_adam_t16(const void* packed_bf16, long c
                  "pcaa_skinny_linear_wgrad_adam_t16: chunk stride %ld below (N + K) * 64 or misaligned", chunk_stride);
   PCAA_CHECK_ARG(ldw >= K && (long)N * ldw < (1L << 30) && (long)chunks * chunk_stride * 2 < (1L << 31),
                  "pcaa_skinny_linear_wgrad_adam_t16: operands beyond 32-bit offsets");
-  hipStream_t st = as_stream(stream);
   const bf16_t* P = reinterpret_cast<const bf16_t*>(packed_bf16);
+  // columns per wave (32 JL).  Up to 2 chunks several workgroups share a CU and the single-process rule holds (>= 1024
+  // workgroups); from 4 chunks on the dz panels leave room for ONE workgroup per CU (64-128 KB of LDS), so 256 run at a
+  // time whatever the grid, and every workgroup pays a panel load (16 KB per chunk, from L2) + a barrier before its first
+  // MFMA: the widest JL that still gives every CU >= 1.5 workgroups amortises that prologue over 4 column steps
+  const int jl = wgrad_cols_per_wave(N, K, chunks >= 4 ? 384 : 1024);
   // one workgroup per CU once the dz panels of >= 4 chunks fill the LDS: more fragments of W / exp_avg / exp_avg_sq in
-  // flight per wave then replace the second workgroup's (measured in tools/skinny_lab.py)
-  const int rc = chunks >= 4
-      ? launch_wgrad_adam_t16<4>(P, chunk_stride, chunks, W, exp_avg, exp_avg_sq, ldw, N, K, beta1, beta2, eps, grad_scale, coef_dev, st)
-      : launch_wgrad_adam_t16<2>(P, chunk_stride, chunks, W, exp_avg, exp_avg_sq, ldw, N, K, beta1, beta2, eps, grad_scale, coef_dev, st);
-  if (rc != 0) {
+  // flight per wave (NB = 4) then replace the second workgroup's (measured in tools/skinny_lab.py)
+  const bool ok = pick_bool(chunks >= 4, [&](auto deep) {
+    return pick_jl_full(jl, N % 128 == 0, [&](auto jlc, auto full) {
+      return launch_wgrad<skinny_wgrad_adam_t16_kernel<decltype(jlc)::value, decltype(full)::value, decltype(deep)::value ? 4 : 2>, decltype(jlc)::value>(
+          (size_t)chunks * sizeof(DzPanel<false>), as_stream(stream), N, K, P, chunk_stride, chunks, W, exp_avg,
+          exp_avg_sq, ldw, N, K, beta1, beta2, eps, grad_scale, coef_dev);
+    });
+  });
+  if (!ok) {
     pcaa_set_error("pcaa_skinny_linear_wgrad_adam_t16: cannot raise the dynamic LDS limit");
     return PCAA_ERR_LAUNCH;
   }

@@ -1196,6 +1196,16 @@ def skinny_linear_wgrad(dz, x, out=None, exact=False):
     return out
 
 
+def _chk_adam_state(prefix, W, exp_avg, exp_avg_sq, N, K, dim=None, want=None):
+    """The fused updates' (W, exp_avg, exp_avg_sq): contiguous fp32 device tensors of shape [N, K].  ``prefix`` names the
+    wrapper ("skinny_wgrad_adam" for skinny_linear_wgrad_adam_); ``want``: the shape as the wrapper's message spells it."""
+    fn = prefix.replace("skinny_", "skinny_linear_", 1) + "_"
+    for t, nm in ((W, "W"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, prefix + "." + nm, torch.float32, dim)
+        if tuple(t.shape) != (N, K):
+            raise ValueError(f"{fn}: {nm} must be {want or f'[{N},{K}]'}, got {tuple(t.shape)}")
+
+
 def skinny_linear_wgrad_adam_(dz, x, W, exp_avg, exp_avg_sq, beta1, beta2, eps, coef_dev, grad_scale=1.0, exact=False):
     """W[N,K] <- Adam(W, dz[M,N]^T @ x[M,K]) in place, moments too (M <= 64): the weight gradient never reaches HBM.
     ``coef_dev``: the two step-dependent scalars of the optimizer step in progress (StepCount.coef_dev)."""
@@ -1205,10 +1215,7 @@ def skinny_linear_wgrad_adam_(dz, x, W, exp_avg, exp_avg_sq, beta1, beta2, eps, 
     K = x.shape[1]
     if x.shape[0] != M:
         raise ValueError("skinny_linear_wgrad_adam_: shape mismatch")
-    for t, nm in ((W, "W"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, "skinny_wgrad_adam." + nm, torch.float32)
-        if tuple(t.shape) != (N, K):
-            raise ValueError(f"skinny_linear_wgrad_adam_: {nm} must be [{N},{K}], got {tuple(t.shape)}")
+    _chk_adam_state("skinny_wgrad_adam", W, exp_avg, exp_avg_sq, N, K)
     _chk(coef_dev, "skinny_wgrad_adam.coef", torch.float32)
     lib = _lib.load()
     fn = lib.pcaa_skinny_linear_wgrad_adam_exact if exact else lib.pcaa_skinny_linear_wgrad_adam
@@ -1240,10 +1247,7 @@ def skinny_linear_wgrad_adam_rows_(dz_all, x_all, m, W, exp_avg, exp_avg_sq, bet
     need = gathered_rows_alloc(int(m))
     if need is None or x_all.shape[0] != R or R < need:
         raise ValueError(f"skinny_linear_wgrad_adam_rows_: {m} valid rows need buffers of {need} rows, got {R} / {x_all.shape[0]}")
-    for t, nm in ((W, "W"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, "skinny_wgrad_adam_rows." + nm, torch.float32)
-        if tuple(t.shape) != (N, K):
-            raise ValueError(f"skinny_linear_wgrad_adam_rows_: {nm} must be [{N},{K}], got {tuple(t.shape)}")
+    _chk_adam_state("skinny_wgrad_adam_rows", W, exp_avg, exp_avg_sq, N, K)
     _chk(coef_dev, "skinny_wgrad_adam_rows.coef", torch.float32)
     _timed("gemm_skinny_kernel", lambda: check(_lib.load().pcaa_skinny_linear_wgrad_adam_rows(
         _p(dz_all), dz_all.stride(0), _p(x_all), x_all.stride(0), _p(W), _p(exp_avg), _p(exp_avg_sq), K, int(m), N, K,
@@ -1291,11 +1295,9 @@ def skinny_linear_wgrad_adam_t16_(packed, chunks, W, exp_avg, exp_avg_sq, beta1,
             or packed.stride(1) != 1):
         raise TypeError("skinny_linear_wgrad_adam_t16_: packed must be a [chunks, >= (N + K) * 64] bf16 tensor on the HIP "
                         "device with contiguous rows")
-    for t, nm in ((W, "W"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _chk(t, "skinny_wgrad_adam_t16." + nm, torch.float32, 2)
-        if tuple(t.shape) != tuple(W.shape):
-            raise ValueError(f"skinny_linear_wgrad_adam_t16_: {nm} must be {tuple(W.shape)}, got {tuple(t.shape)}")
+    _chk(W, "skinny_wgrad_adam_t16.W", torch.float32, 2)
     N, K = W.shape
+    _chk_adam_state("skinny_wgrad_adam_t16", W, exp_avg, exp_avg_sq, N, K, dim=2, want=tuple(W.shape))
     chunks = int(chunks)
     if not 1 <= chunks <= min(PACK_MAX_CHUNKS, packed.shape[0]) or packed.shape[1] < packed_chunk_elems(N, K):
         raise ValueError(f"skinny_linear_wgrad_adam_t16_: {chunks} chunks of an [{N},{K}] layer do not fit a packed buffer "

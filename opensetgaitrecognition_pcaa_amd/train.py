@@ -220,12 +220,12 @@ class PCAATrainer:
         ``dp_gather`` (round 5; bf16 mode with the fused update): the wide decoder layers exchange their two small
         weight-gradient operands -- dz [B, out] and x [B, in], all-gathered over the ranks -- instead of the gradient
         (4 world B (in + out) bytes against 4 in out: ~10x less on the wire), and every rank forms the GLOBAL gradient
-        inside the fused weight-gradient + Adam kernel (pcaa_skinny_linear_wgrad_adam_rows): the update stays 24 B per
+        inside the fused weight-gradient + Adam kernel: the update stays 24 B per
         parameter and no Adam pass over the decoder follows the exchange.  Mathematically the all-reduce scheme's step
         (sum over ranks of dz_r^T x_r = stacked-rows product).  Round 6: the two operands travel as ONE packed bf16 chunk
         per rank and layer (ops.pack_rows_t16: transposed, 64 batch rows, the rounding the weight-gradient kernels apply
         anyway) -- half the bytes, one all-gather per layer -- and pcaa_skinny_linear_wgrad_adam_t16 contracts over the
-        ranks' chunks.  Applies while world <= 8 and B <= 64 (else the all-reduce scheme runs; ``dp_scheme`` says which).
+        ranks' chunks (round 5's pcaa_skinny_linear_wgrad_adam_rows, from fp32 rows, is no longer on the trainer's path).  Applies while world <= 8 and B <= 64 (else the all-reduce scheme runs; ``dp_scheme`` says which).
         ``emulate_world=W`` (round 6; no process group): this process runs ONE RANK'S PROGRAM of a W-rank job on its own --
         gradient scale 1/W, W * B stacked rows in the gathered update, every collective replaced by a device operation of
         the same bytes on a stream of its own (dist.EmulatedExchange; peers' gathered rows can be staged there).  It

@@ -17,6 +17,17 @@ def _rand(shape, seed, scale=1.0):
     return torch.from_numpy((rng.standard_normal(shape) * scale).astype(np.float32))
 
 
+def _wgrad_cols_per_wave(N, K, want=1024):
+    """gemm_skinny.hip's wgrad_cols_per_wave restated: JL of the fused weight-gradient kernels, the widest 32 JL columns per
+    wave that still leave ``want`` workgroups (1024; the packed kernel 384 from 4 chunks on)."""
+    ntile = lambda jl: -(-K // (128 * jl)) * -(-N // 128)
+    return 4 if ntile(4) >= want else 2 if ntile(2) >= want else 1
+
+
+# (N, K) of the cases that exist to reach JL > 1 (want = 1024); every other case of these tests selects JL = 1
+WGRAD_JL = {(4096, 8192): 2, (4000, 8192): 2, (4096, 16384): 4, (4000, 16384): 4}
+
+
 def _mk(layout, rows, K, seed, dtype):
     """operand with logical shape (rows, K) stored per layout; returns (device tensor, logical fp64)."""
     logical = _rand((rows, K), seed)
@@ -427,11 +438,15 @@ def test_adam_matches_reference_formula():
         assert torch.allclose(pd.cpu(), params["p"], rtol=1e-6, atol=1e-7), s
 
 
-@pytest.mark.parametrize("M,N,K", [(64, 256, 128), (37, 192, 160), (5, 128, 1024), (64, 960, 1920), (16, 4544, 2304)])
+@pytest.mark.parametrize("M,N,K", [(64, 256, 128), (37, 192, 160), (5, 128, 1024), (64, 960, 1920), (16, 4544, 2304),
+                                   (64, 4096, 8192), (37, 4000, 8192), (64, 4096, 16384), (5, 4000, 16384)])
 def test_skinny_wgrad_adam_equals_wgrad_then_adam_bitwise(M, N, K):
     """pcaa_skinny_linear_wgrad_adam == pcaa_skinny_linear_wgrad followed by pcaa_adam_step_dev, bit for bit
-    (parameters and both moments), over three optimizer steps with changing gradients."""
+    (parameters and both moments), over three optimizer steps with changing gradients.  The four largest shapes are
+    the smallest at which the launcher picks 2 and 4 column steps per wave (1024 tiles), with full and partial row
+    panels -- the instantiations the decoder's wide layers run."""
     from opensetgaitrecognition_pcaa_amd.train import StepCount
+    assert _wgrad_cols_per_wave(N, K) == WGRAD_JL.get((N, K), 1)
     W0 = _rand((N, K), 300, 0.05).to(DEV)
     Wa, Wb = W0.clone(), W0.clone()
     ma, va, mb, vb = (torch.zeros_like(W0) for _ in range(4))
@@ -462,14 +477,17 @@ def test_skinny_wgrad_adam_equals_wgrad_then_adam_bitwise(M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 256, 128), (37, 192, 160), (5, 128, 1024), (128, 256, 128), (6, 512, 256), (192, 960, 1920),
-                                   (256, 192, 160), (300, 128, 96), (512, 384, 512), (512, 1920, 960)])
+                                   (256, 192, 160), (300, 128, 96), (512, 384, 512), (512, 1920, 960),
+                                   (64, 4096, 8192), (512, 4000, 16384)])
 def test_skinny_wgrad_adam_rows_gathered_update(M, N, K):
     """Round 5 (dp_gather): the fused weight-gradient + Adam update from the ranks' stacked rows, M = world * B up to
     512.  M <= 64: the bits of the single-process kernel.  Beyond: the gradient it forms is the bf16-operand product with
     fp32 accumulation over ALL rows -- checked through the Adam state it leaves: exp_avg = (1 - beta1) * grad after one step
     from zero moments, against an fp64 product of the rounded operands (1e-5 of the largest entry); the buffers' rows
-    behind M (zeros, as the trainer allocates them) and a NaN-free W outside [N, K] are left alone."""
+    behind M (zeros, as the trainer allocates them) and a NaN-free W outside [N, K] are left alone.  The last two shapes
+    reach 2 and 4 column steps per wave (one chunk, bitwise; eight chunks with a partial row panel)."""
     from opensetgaitrecognition_pcaa_amd.train import StepCount
+    assert _wgrad_cols_per_wave(N, K) == WGRAD_JL.get((N, K), 1)
     R = ops.gathered_rows_alloc(M)
     W0 = _rand((N, K), 400, 0.05).to(DEV)
     dzb = torch.zeros((R, N), device=DEV)
@@ -531,14 +549,18 @@ def test_pack_rows_t16_is_the_transposed_rounded_operand_pair(rows, N, K):
 
 @pytest.mark.parametrize("chunks,rows,N,K", [(1, 64, 256, 128), (1, 37, 192, 160), (2, 64, 256, 128), (3, 16, 130, 96),
                                              (4, 64, 960, 1920), (5, 64, 384, 512), (8, 64, 1920, 960), (8, 40, 128, 1024),
-                                             (8, 64, 3840, 1920)])
+                                             (8, 64, 3840, 1920),
+                                             (2, 64, 4096, 16384), (2, 40, 4000, 8192), (4, 64, 2048, 12288), (8, 40, 2000, 6144)])
 def test_skinny_wgrad_adam_t16_packed_gathered_update(chunks, rows, N, K):
     """Round 6 (the data-parallel decoder update from PACKED gathered operands): W <- Adam(W, s * sum_c dz_c^T x_c) over up
     to 8 chunks of <= 64 rows.  The gradient it forms is the bf16-operand product with fp32 accumulation over all chunks --
     checked through exp_avg = (1 - beta1) * grad after one step from zero moments against an fp64 product of the rounded
     operands (1e-5 of the largest entry), and against the rows kernel of round 5 on the same stacked rows (the same
-    products in another summation order); chunks behind ``chunks`` in the buffer are not read."""
+    products in another summation order); chunks behind ``chunks`` in the buffer are not read.  The last four shapes
+    reach 4 and 2 column steps per wave with the ring of 2 (1024 tiles) and of 4 (from 4 chunks on: 384 tiles)."""
     from opensetgaitrecognition_pcaa_amd.train import StepCount
+    want_jl = {(2, 4096, 16384): 4, (2, 4000, 8192): 2, (4, 2048, 12288): 4, (8, 2000, 6144): 2}
+    assert _wgrad_cols_per_wave(N, K, 384 if chunks >= 4 else 1024) == want_jl.get((chunks, N, K), 1)
     W0 = _rand((N, K), 900, 0.05).to(DEV)
     ce = ops.packed_chunk_elems(N, K)
     packed = torch.full((chunks + 1, ce + 64), float("nan"), dtype=torch.bfloat16, device=DEV)[:, :ce]     # a strided buffer
