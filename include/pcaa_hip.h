@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 21 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 22 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -699,6 +699,29 @@ int pcaa_orced_heads_bwd(const float* x4, const float* eps, const float* logvar,
                          int d_in, int d_lat, void* stream);
 int pcaa_orced_kl(const float* mu, const float* logvar, const float* mu_k, float* loss, float* d_mu,
                   float* d_logvar, float* d_muk, float gscale, int B, int d_lat, void* stream);
+/* ABI 22: OR-CED's triplet term (reference train_ORCED.py:9,30,34: miners.MultiSimilarityMiner(epsilon) feeding
+ * losses.TripletMarginLoss(margin) of pytorch_metric_learning 1.6.0, as restated by orced.multi_similarity_miner /
+ * orced.triplet_margin_loss) in dense form, with e = x / max(|x|, 1e-12), S = e e^T, D[a,j] = |e_a - e_j|:
+ *   P[a,p] = same label, p != a, S[a,p] - epsilon < max over a's negatives of S[a,.]   (no negative: P empty)
+ *   N[a,n] = other label,        S[a,n] + epsilon > min over a's positives of S[a,.]   (no positive: N empty)
+ *   h = D[a,p] - D[a,n] + margin over all (a, p, n) with P[a,p] and N[a,n]
+ *   *loss = sum_{h>0} h / #{h>0}, 0 with a zero gradient where nothing is mined or no hinge is positive
+ *   dx [B,d_lat] (may be NULL) = gscale * dloss/dx, through the normalisation; a pair at D == 0 contributes nothing
+ *   (torch.cdist's backward rule).
+ * x [B,d_lat] fp32 with non-zero rows, labels [B] int64.  Three launches on `stream`, no atomics, no host read: the
+ * same inputs give the same bits.  ws: (B*B + B*d_lat + 4*B) floats of scratch, 8-byte aligned. */
+int pcaa_orced_triplet_supported(int B, int d_lat);
+int pcaa_orced_triplet(const float* x, const long long* labels, float epsilon, float margin, float gscale, float* ws,
+                       float* loss, float* dx, int B, int d_lat, void* stream);
+/* ABI 22: the ensemble open-set rule of inference_ORCED.py:18-132 after its training-set statistics, one wave per
+ * sample.  Per sample: z [n,d_lat] fp32, re [n] fp32, pred [n] int64; per class, fp64: mean_z, sd_z [K,d_lat] (sd_z is the
+ * SQUARE ROOT of the class's std: the reference hands the std to scipy as a variance, :107) and thr_re [K].
+ *   p_k = prod_d Phi(dev/sd) - prod_d Phi(-dev/sd), dev = |z - mean_k|, in fp64 (Phi(t) = erfc(-t / sqrt 2) / 2)
+ *   out [n] = K where p_k > thresholds_g for EVERY k, or (double)re > thr_re[pred] (or pred outside [0, K)); else pred.
+ * p [K,n] fp64 may be NULL. */
+int pcaa_orced_ood(const float* z, const float* re, const long long* pred, const double* mean_z, const double* sd_z,
+                   const double* thr_re, double thresholds_g, long long* out, double* p, int n, int K, int d_lat,
+                   void* stream);
 
 /* ------------------------------------------------------------------ optimizer
  * torch.optim.Adam (no weight decay, no amsgrad; PCAA_ablation.py:820-833) on a

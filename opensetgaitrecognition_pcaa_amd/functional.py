@@ -1230,6 +1230,30 @@ def cg_kl_divergence(mu, logvar, mu_k):
     return _KlFn.apply(mu, logvar, mu_k)
 
 
+class _TripletFn(torch.autograd.Function):
+    """OR-CED's triplet term (MultiSimilarityMiner + TripletMarginLoss, train_ORCED.py:9,30,34) in dense form: loss and
+    the UNSCALED gradient from the one launch sequence (pcaa_orced_triplet), as _KlFn; nothing is read on the host."""
+
+    @staticmethod
+    def forward(ctx, x, labels, epsilon, margin):
+        loss, dx = ops.orced_triplet(x.contiguous().float(), labels.contiguous(), epsilon, margin, gscale=1.0)
+        ctx.save_for_backward(dx)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return dx * g, None, None, None
+
+
+def orced_triplet_loss(x, labels, epsilon=0.1, margin=0.5):
+    """``triplet_margin_loss(x, labels, multi_similarity_miner(x, labels, epsilon), margin)`` of orced.py on the device
+    kernels; ``margin`` defaults to the reference's TRIPLET_MARGIN (train_ORCED.py:324).  Raises on unsupported shapes."""
+    _require_gpu(x, "orced_triplet_loss")
+    return _TripletFn.apply(x, labels, float(epsilon), float(margin))
+
+
 class _CeFn(torch.autograd.Function):
     """torch.nn.functional.cross_entropy (mean) on the device kernel of the PCAA step (pcaa_cross_entropy: loss and
     softmax - onehot gradient in the same launch)."""

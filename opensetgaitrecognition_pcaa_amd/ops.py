@@ -1698,6 +1698,50 @@ def orced_kl(mu, logvar, mu_k, want_loss=True, gscale=None):
     return loss, grads
 
 
+def orced_triplet(x, labels, epsilon, margin, gscale=None):
+    """MultiSimilarityMiner(epsilon) + TripletMarginLoss(margin) of x [B,L] (non-zero rows) / labels [B] int64 in dense
+    form -> (loss scalar, dx [B,L] = gscale * dloss/dx, or None without ``gscale``).  Three launches, no host read."""
+    _chk(x, "orced_triplet.x", torch.float32, 2)
+    _chk(labels, "orced_triplet.labels", torch.int64, 1)
+    B, L = x.shape
+    lib = _lib.load()
+    if labels.shape[0] != B or labels.device != x.device:
+        raise ValueError(f"orced_triplet: labels {tuple(labels.shape)} on {labels.device} for x {tuple(x.shape)} on {x.device}")
+    if not lib.pcaa_orced_triplet_supported(B, L):
+        raise ValueError(f"orced_triplet: unsupported shape B = {B}, L = {L} (pcaa_orced_triplet_supported)")
+    ws = torch.empty((B * B + B * L + 4 * B + 1) // 2, dtype=torch.float64, device=x.device)      # (8-byte aligned)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x) if gscale is not None else None
+    check(lib.pcaa_orced_triplet(_p(x), _p(labels), float(epsilon), float(margin),
+                                 float(gscale if gscale is not None else 0.0), _p(ws), _p(loss), _p(dx), B, L, _s()),
+          "pcaa_orced_triplet")
+    return loss, dx
+
+
+def orced_ood(z, re, pred, mean_z, sd_z, thr_re, thresholds_g, want_p=False):
+    """The ensemble open-set rule after its statistics: z [n,L] fp32, re [n] fp32, pred [n] int64; mean_z, sd_z [K,L] and
+    thr_re [K] fp64 (sd_z: the square root of the class's std) -> out [n] int64 (pred, or K = unknown), and with
+    ``want_p`` the box probabilities p [K,n] fp64."""
+    _chk(z, "orced_ood.z", torch.float32, 2)
+    _chk(re, "orced_ood.re", torch.float32, 1)
+    _chk(pred, "orced_ood.pred", torch.int64, 1)
+    _chk(mean_z, "orced_ood.mean_z", torch.float64, 2)
+    _chk(sd_z, "orced_ood.sd_z", torch.float64, 2)
+    _chk(thr_re, "orced_ood.thr_re", torch.float64, 1)
+    n, L = z.shape
+    K = mean_z.shape[0]
+    if (re.shape[0] != n or pred.shape[0] != n or tuple(mean_z.shape) != (K, L) or tuple(sd_z.shape) != (K, L)
+            or thr_re.shape[0] != K or K < 1 or L < 1
+            or any(t.device != z.device for t in (re, pred, mean_z, sd_z, thr_re))):
+        raise ValueError("orced_ood: shape or device mismatch")
+    out = torch.empty(n, dtype=torch.int64, device=z.device)
+    p = torch.empty((K, n), dtype=torch.float64, device=z.device) if want_p else None
+    if n:
+        check(_lib.load().pcaa_orced_ood(_p(z), _p(re), _p(pred), _p(mean_z), _p(sd_z), _p(thr_re), float(thresholds_g),
+                                         _p(out), _p(p), n, K, L, _s()), "pcaa_orced_ood")
+    return (out, p) if want_p else out
+
+
 # ------------------------------------------------------------------ discriminator
 def _disc_params(m):
     lin = (m.model[0], m.model[2], m.model[4])

@@ -4,16 +4,21 @@
 
 What runs where: the PointNet / temporal-conv trunk of ``ORCEDEncoder``, ``ORCEDDecoder``, the sequence Chamfer loss,
 ``GaussianMeanLearner`` and Adam are the HIP kernels of the PCAA path (through the drop-in modules' autograd
-Functions and a :class:`~.train.FlatBuffer`); since round 3 so are the [B,32]-sized pieces: the three Linear heads with
-the reparametrisation (``pcaa_orced_heads_fwd / _bwd``), cross-entropy (``pcaa_cross_entropy``) and the KL term
-(``pcaa_orced_kl``).  What stays on torch device ops: the normal draw itself (the reference's ``torch.randn_like``) and
-the triplet term (below: parity unpinned).  The open-set test is host numpy / scipy in float64, as in the reference.
+Functions and a :class:`~.train.FlatBuffer`); so are the [B,32]-sized pieces: the three Linear heads with the
+reparametrisation (``pcaa_orced_heads_fwd / _bwd``), cross-entropy (``pcaa_cross_entropy``), the KL term
+(``pcaa_orced_kl``), the triplet term (``pcaa_orced_triplet``: miner, loss and gradient in three launches, no host
+synchronisation) and the open-set rule (``pcaa_orced_ood`` behind :class:`ORCEDScorer`, whose training-set statistics
+are float64 torch device ops computed once).  What stays on torch device ops: the normal draw itself (the reference's
+``torch.randn_like``) and the outer ``normalize`` of the embeddings.  ``compute_prob`` /
+``ORCED_ensemble_ood_detection`` remain as the host numpy / scipy float64 call surface of the reference.
 
 The triplet term restates ``pytorch_metric_learning==1.6.0`` (requirements.txt; NOT installed here, not vendored in
 the reference): ``miners.MultiSimilarityMiner()`` (epsilon 0.1 on cosine similarity) feeding
 ``losses.TripletMarginLoss(margin)`` (Euclidean distance of L2-normalised embeddings, all (anchor, positive,
 negative) combinations of the mined pairs, mean over the non-zero losses).  **Parity unpinned** for these two
-functions: there is nothing in this container to check the restatement against.
+functions: there is nothing in this container to check the restatement against.  ``multi_similarity_miner`` +
+``triplet_margin_loss`` below are that restatement in torch ops; they are the specification of the device kernel
+(``orced_losses(..., triplet="hip")``, the default) and what ``triplet="aten"`` runs.
 """
 import itertools
 import os
@@ -86,9 +91,13 @@ def _predicted(logits):
 # ---------------------------------------------------------------------------------------------------------
 # training loop (train_ORCED.py:21-280)
 # ---------------------------------------------------------------------------------------------------------
-def orced_losses(encoder, decoder, mean_learner, pcs, gt_labels, config, kl_multiplier, chamfer=None):
+def orced_losses(encoder, decoder, mean_learner, pcs, gt_labels, config, kl_multiplier, chamfer=None, triplet="hip"):
     """The loss terms of one OR-CED step (train_ORCED.py:143-176), weighted.  Returns a dict of scalar tensors
-    (``tot`` carries the graph) plus the predicted labels."""
+    (``tot`` carries the graph) plus the predicted labels.  ``triplet``: "hip" = the device kernel (no host
+    synchronisation; raises on a shape ``pcaa_orced_triplet_supported`` refuses), "aten" = the torch restatement
+    (several host synchronisations a step; for A/B runs and unsupported shapes)."""
+    if triplet not in ("hip", "aten"):
+        raise ValueError(f"orced_losses: triplet must be 'hip' or 'aten', got {triplet!r}")
     K = len(config["TRAIN_CLASSES"])
     chamfer = chamfer or SeqChamferLoss()
     logits, sup_fvs, vae_mu, vae_logvar = encoder(pcs)
@@ -97,8 +106,11 @@ def orced_losses(encoder, decoder, mean_learner, pcs, gt_labels, config, kl_mult
     rec = config["REC_W"] * chamfer(rec_pcs, pcs)
     sup = config["CE_W"] * F_hip.cross_entropy_loss(logits, gt_labels)
     nfv = TF.normalize(sup_fvs, p=2, dim=1)
-    trip = config["TRIPLET_W"] * triplet_margin_loss(nfv, gt_labels, multi_similarity_miner(nfv, gt_labels),
-                                                     config["TRIPLET_MARGIN"])
+    if triplet == "hip":
+        trip = config["TRIPLET_W"] * F_hip.orced_triplet_loss(nfv, gt_labels, 0.1, config["TRIPLET_MARGIN"])
+    else:
+        trip = config["TRIPLET_W"] * triplet_margin_loss(nfv, gt_labels, multi_similarity_miner(nfv, gt_labels),
+                                                         config["TRIPLET_MARGIN"])
     kl = config["KL_W"] * CG_kl_divergence(vae_mu, vae_logvar, mu_gts) * kl_multiplier
     preds = _predicted(logits)
     return {"rec": rec, "sup": sup, "trip": trip, "kl": kl, "tot": rec + sup + trip + kl, "preds": preds}
@@ -238,6 +250,80 @@ def ORCED_ensemble_ood_detection(rec_err_tr, f_vecs_tr, thresholds_g, gt_labels,
     return out
 
 
+class ORCEDScorer:
+    """The ensemble open-set rule on the device, the OR-CED counterpart of ``inference.OpenSetScorer``: the training-set
+    statistics are computed ONCE (``fit`` / ``fit_loader``; float64 torch device ops), ``score`` runs encoder -> decoder
+    -> per-sample Chamfer -> ``pcaa_orced_ood`` with nothing copied to the host.  Same rule as
+    ``ORCED_ensemble_ood_detection`` (which recomputes the statistics on the host at every call)."""
+
+    def __init__(self, encoder, decoder, batch_size=64, thresholds_g=0.95):
+        self.encoder, self.decoder = encoder, decoder
+        self.batch_size = int(batch_size)
+        self.thresholds_g = float(thresholds_g)
+        self.chamfer = SeqChamferLoss()
+        self.n_classes = None
+        self.mean_z = self.sd_z = self.thr_re = None
+
+    def _run(self, pcs):
+        logits, sup_fvs, _, _ = self.encoder(pcs)
+        rec_err = self.chamfer(self.decoder(sup_fvs), pcs, avg_out=False)
+        return _predicted(logits), sup_fvs, rec_err
+
+    def fit(self, rec_err_tr, f_vecs_tr, gt_labels, pred_labels):
+        """Class statistics of the training set (inference_ORCED.py:60-110): per class the mean + 2 population std of
+        the reconstruction errors, and mean / population std of the latent vectors of the CORRECTLY predicted samples.
+        Arguments: tensors or arrays, [n], [n,L], [n], [n]; moved to the encoder's device."""
+        dev = next(self.encoder.parameters()).device
+        re = torch.as_tensor(rec_err_tr).to(dev).double()
+        fv = torch.as_tensor(f_vecs_tr).to(dev).double()
+        gt = torch.as_tensor(gt_labels).to(dev).long()
+        pl = torch.as_tensor(pred_labels).to(dev).long()
+        K = int(torch.unique(gt).numel())                      # (the one host read: once per fit)
+        onehot = (gt.unsqueeze(1) == torch.arange(K, device=dev)).double()        # [n,K]: class k is ``gt == k``, k < K
+        own = gt.clamp(0, K - 1)
+        cnt = onehot.sum(0)
+        mean_re = (onehot.t() @ re) / cnt
+        var_re = (onehot.t() @ (re - mean_re[own]) ** 2) / cnt
+        w = onehot * (gt == pl).double().unsqueeze(1)          # correctly predicted samples only
+        cntc = w.sum(0).unsqueeze(1)
+        mean_z = (w.t() @ fv) / cntc
+        var_z = (w.t() @ (fv - mean_z[own]) ** 2) / cntc
+        self.n_classes = K
+        self.mean_z = mean_z.contiguous()
+        # the reference hands the std to scipy as a VARIANCE (np.diag(stds_z[k]), :107): the box test's sd is its root
+        self.sd_z = var_z.sqrt().sqrt().contiguous()
+        self.thr_re = (mean_re + 2 * var_re.sqrt()).contiguous()
+        return self
+
+    @torch.no_grad()
+    def fit_loader(self, loader):
+        """Run the model over ``loader`` ((pcs, gt_labels) batches) and ``fit`` on what it produced."""
+        dev = next(self.encoder.parameters()).device
+        fv, re, pl, gl = [], [], [], []
+        for pcs, gt in loader:
+            p, f, r = self._run(pcs.to(dev))
+            fv.append(f); re.append(r); pl.append(p); gl.append(gt.to(dev))
+        return self.fit(torch.cat(re), torch.cat(fv), torch.cat(gl), torch.cat(pl))
+
+    def decide(self, preds, sup_fv, rec_err):
+        """The rule alone on already computed model outputs (device tensors) -> labels with ``n_classes`` = unknown"""
+        if self.mean_z is None:
+            raise RuntimeError("ORCEDScorer: call fit() or fit_loader() first")
+        from . import ops
+        return ops.orced_ood(sup_fv.contiguous().float(), rec_err.contiguous().float(), preds.contiguous(), self.mean_z,
+                             self.sd_z, self.thr_re, self.thresholds_g)
+
+    @torch.no_grad()
+    def score(self, pcs):
+        """pcs [n,C,T,N] on the device -> (labels_with_unknown [n] int64, preds [n] int64, sup_fv [n,L], rec_err [n]),
+        all on the device; the model runs in chunks of ``batch_size``."""
+        outs = []
+        for i in range(0, pcs.shape[0], self.batch_size):
+            p, f, r = self._run(pcs[i:i + self.batch_size])
+            outs.append((self.decide(p, f, r), p, f, r))
+        return tuple(torch.cat(c) for c in zip(*outs)) if len(outs) != 1 else outs[0]
+
+
 def ORCED_inference_setup(model_name, loaders_batch_size, generate_dataset=True, device=None):
     """(encoder, decoder, mean_learner, cluster_means, train / test / unseen loaders) from the checkpoints of
     ``train_ORCED`` (inference_ORCED.py:135-254)."""
@@ -274,41 +360,29 @@ def ORCED_inference(model_names, generate_dataset=True, device=None):
     out for a like-for-like comparison with the PCAA procedure).  Writes ``ensemble_ood_final_preds_fixed.npy`` /
     ``..._labels_fixed.npy`` under ``figures/<name>/``; returns {name: metrics}.  Not reproduced: the PNG."""
     from sklearn.metrics import f1_score
-    chamfer = SeqChamferLoss()
     dev = torch.device(device or constants.DEVICE)
     results = {}
     for model_name in model_names:
         figures = os.path.join("figures", model_name)
         os.makedirs(figures, exist_ok=True)
         encoder, decoder, _, _, dl_train, dl_test, dl_unseen = ORCED_inference_setup(model_name, 64, generate_dataset, dev)
-
-        def run(pcs):
-            logits, sup_fvs, _, _ = encoder(pcs)
-            rec_err = chamfer(decoder(sup_fvs), pcs, avg_out=False)
-            return _predicted(logits), sup_fvs.cpu().numpy(), rec_err.cpu().numpy()
-
-        fv, re, pl, gl = [], [], [], []
-        with torch.no_grad():
-            for pcs, gt in dl_train:
-                p, f, r = run(pcs.to(dev))
-                fv.append(f); re.append(r); pl.append(p.cpu().numpy()); gl.append(gt.numpy())
-        rec_err_tr, f_vecs_tr = np.concatenate(re), np.concatenate(fv)
-        gt_labels, pred_labels = np.concatenate(gl), np.concatenate(pl)
-        n_labels = len(np.unique(gt_labels))
+        # the training-set statistics once, on the device; every batch then runs model + rule without a host copy
+        scorer = ORCEDScorer(encoder, decoder, batch_size=64, thresholds_g=0.95).fit_loader(dl_train)
+        n_labels = scorer.n_classes
         test_out, test_lab, unseen_out = [], [], []
         with torch.no_grad():
             for pcs, gt in dl_test:
-                p, f, r = run(pcs.to(dev))
                 test_lab.append(gt.numpy())
-                test_out.append(ORCED_ensemble_ood_detection(rec_err_tr, f_vecs_tr, 0.95, gt_labels, pred_labels, p, f, r))
+                test_out.append(scorer.score(pcs.to(dev))[0])
             leave_out = None
             for pcs, gt in dl_unseen:
                 if leave_out is None:
                     leave_out = gt[0].item()
-                p, f, r = run(pcs.to(dev))            # (the draw of eps happens for every batch, as in the reference)
+                out = scorer.score(pcs.to(dev))[0]    # (the draw of eps happens for every batch, as in the reference)
                 if gt[0].item() != leave_out:
-                    unseen_out.append(ORCED_ensemble_ood_detection(rec_err_tr, f_vecs_tr, 0.95, gt_labels,
-                                                                   pred_labels, p, f, r))
+                    unseen_out.append(out)
+        test_out = [t.cpu().numpy() for t in test_out]
+        unseen_out = [t.cpu().numpy() for t in unseen_out]
         test_out = np.concatenate(test_out)
         unseen_out = np.concatenate(unseen_out) if unseen_out else np.zeros(0, dtype=np.int64)
         final_preds = np.concatenate([test_out, unseen_out])
