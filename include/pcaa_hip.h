@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 22 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 23 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -277,6 +277,23 @@ int pcaa_bn_bwd_finalize(const double* stats, int nrep, long count, const float*
                          float* coef, float* dgamma, float* dbeta, int ch, void* stream);
 int pcaa_bn_bwd_dy(const void* dz, const void* y, void* dy, int dtype, const float* coef,
                    long rows, int ch, void* stream);
+/* ABI 23: backward through EVAL-mode BatchNorm + ELU (BatchNorm is the fixed map z = scale*y + shift, scale = gamma*r,
+ * r = 1/sqrt(running_var + eps); y is stored bias-free, so the mean it is centred on is m' = running_mean - bias).
+ * pcaa_bn_eval_moments writes (m', r) as fp32 vectors.  pcaa_bn_eval_act_bwd makes ONE pass over y[rows, ch]:
+ *   g  = (dpool ? dpool[row / group_rows][c] * pool_scale : da[row][c])
+ *   dz = g * ELU'(y*scale + shift);   dy = scale * dz  (y's dtype; dy may alias da);
+ *   stats += { sum dz, sum dz * (y - mean)*rstd }  (fp32 inside a workgroup of 128 rows, fp64 across: [nrep][2][ch],
+ *   zero-initialised);  ch as for pcaa_bn_act_bwd_dz.
+ * pcaa_bn_eval_bwd_finalize: dbeta = sum dz, dgamma = sum dz*xhat, dbias = scale*dbeta -- the bias in front of an
+ * eval-mode BatchNorm has a real gradient -- in fp64 with one rounding; each destination may be NULL. */
+int pcaa_bn_eval_moments(const float* running_mean, const float* running_var, const float* lin_bias,
+                         float eps, float* mean, float* rstd, int ch, void* stream);
+int pcaa_bn_eval_act_bwd(const void* da, const float* dpool, int group_rows, float pool_scale,
+                         const void* y, void* dy, int dtype,
+                         const float* scale, const float* shift, const float* mean, const float* rstd,
+                         double* stats, int nrep, long rows, int ch, void* stream);
+int pcaa_bn_eval_bwd_finalize(const double* stats, int nrep, const float* scale,
+                              float* dgamma, float* dbeta, float* dbias, int ch, void* stream);
 /* The finalize CARRIED BY THE PRODUCER of the statistics (round 3; csrc/bn_tail.h).  pcaa_bn_tail_arm_fwd / _bwd
  * note the arguments of pcaa_bn_finalize / pcaa_bn_bwd_finalize on the calling thread; the NEXT launch on that thread
  * that accumulates into exactly this `stats` buffer and can carry a tail (pcaa_gemm on the LDS-DMA path with colstats,

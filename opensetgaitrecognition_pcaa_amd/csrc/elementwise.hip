@@ -405,6 +405,107 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ stats, int nre
   coef[2 * ch + c] = (float)(-g * c1 + g * c2 * rs * mu);
 }
 
+// ---------------------------------------------------------------- eval-mode BatchNorm + ELU backward, one pass
+// BatchNorm in eval mode is the fixed map z = scale*y + shift (scale = gamma*r, r = 1/sqrt(running_var + eps)), so
+// dy = scale * dz needs no batch statistic: ONE pass over (da, y) writes dy and reduces {sum dz, sum dz*xhat} with
+// xhat = (y - m')*r, m' = running_mean - bias (y is stored bias-free) -- dbeta and dgamma.  Layout and reduction of
+// bn_act_bwd_dz_kernel (thread = channel quad x row lane, 128 rows per workgroup, fp32 per lane, one fp64 atomic per
+// (workgroup, statistic, channel)); a lane's rows go four at a time so their loads are in flight together.
+// dy may alias da (a thread reads exactly the quads it overwrites, before it does): neither is __restrict__.
+__global__ void bn_eval_moments_kernel(const float* __restrict__ rm, const float* __restrict__ rv,
+                                       const float* __restrict__ lin_bias, float eps, float* mean, float* rstd, int ch) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ch) return;
+  mean[c] = rm[c] - (lin_bias ? lin_bias[c] : 0.f);
+  rstd[c] = 1.f / sqrtf(rv[c] + eps);          // (the r of bn_eval_coeffs_kernel)
+}
+
+template <typename T, bool POOL>
+__global__ __launch_bounds__(256) void bn_eval_act_bwd_kernel(const T* da, const float* __restrict__ dpool,
+                                                              unsigned group_rows, float pool_scale,
+                                                              const T* __restrict__ y, T* dy,
+                                                              const float* __restrict__ scale,
+                                                              const float* __restrict__ shift,
+                                                              const float* __restrict__ mean,
+                                                              const float* __restrict__ rstd,
+                                                              double* __restrict__ stats, int nrep, long rows, int ch) {
+  __shared__ f32x4 red[2][256];
+  constexpr int U = 4;
+  const int qpr = ch >> 2;
+  const int rl = 256 / qpr;
+  const int cq = threadIdx.x % qpr, rlane = threadIdx.x / qpr;
+  const int c = cq * 4;
+  const f32x4 sc = load4(scale + c), sh = load4(shift + c), mu = load4(mean + c), rs = load4(rstd + c);
+  const long r0 = (long)blockIdx.x * ROWS_PER_BLOCK;
+  const long r1 = min(rows, r0 + ROWS_PER_BLOCK);
+  // the pooled gradient's group index advances with the rows by constants: no per-quad division (rows < 2^31, host-checked)
+  unsigned grp = 0u, rem = 0u, gstep = 0u, rrem = 0u;
+  if (POOL) {
+    grp = (unsigned)(r0 + rlane) / group_rows;
+    rem = (unsigned)(r0 + rlane) - grp * group_rows;
+    gstep = (unsigned)rl / group_rows;
+    rrem = (unsigned)rl - gstep * group_rows;
+  }
+  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  for (long r = r0 + rlane; r < r1; r += (long)U * rl) {
+    f32x4 yv[U], g[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long rr = r + (long)u * rl;
+      if (rr < r1) {
+        yv[u] = load4(y + rr * ch + c);
+        g[u] = POOL ? load4(dpool + (size_t)grp * ch + c) : load4(da + rr * ch + c);
+      }
+      if (POOL) {
+        rem += rrem;
+        grp += gstep;
+        if (rem >= group_rows) { rem -= group_rows; ++grp; }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long rr = r + (long)u * rl;
+      if (rr >= r1) break;
+      f32x4 gg = g[u];
+      if (POOL) gg *= pool_scale;
+      const f32x4 v = yv[u];
+      f32x4 d;
+      d.x = gg.x * elu_grad_from_pre_t<T>(v.x * sc.x + sh.x);
+      d.y = gg.y * elu_grad_from_pre_t<T>(v.y * sc.y + sh.y);
+      d.z = gg.z * elu_grad_from_pre_t<T>(v.z * sc.z + sh.z);
+      d.w = gg.w * elu_grad_from_pre_t<T>(v.w * sc.w + sh.w);
+      store4(dy + rr * ch + c, sc * d);
+      s1 += d;
+      s2.x += d.x * ((v.x - mu.x) * rs.x);
+      s2.y += d.y * ((v.y - mu.y) * rs.y);
+      s2.z += d.z * ((v.z - mu.z) * rs.z);
+      s2.w += d.w * ((v.w - mu.w) * rs.w);
+    }
+  }
+  red[0][threadIdx.x] = s1;
+  red[1][threadIdx.x] = s2;
+  __syncthreads();
+  for (int o = threadIdx.x; o < 2 * ch; o += 256) {
+    const int stat = o / ch, cc = o - stat * ch;
+    const int q = cc >> 2, e = cc & 3;
+    double v = 0.0;
+    for (int l = 0; l < rl; ++l) v += (double)red[stat][l * qpr + q][e];
+    unsafeAtomicAdd(&stats[((long)(blockIdx.x % nrep) * 2 + stat) * ch + cc], v);
+  }
+}
+
+// dbeta = sum dz, dgamma = sum dz*xhat, dbias = scale * dbeta: fp64 on the fp64 sums, one rounding to fp32
+__global__ void bn_eval_bwd_finalize_kernel(const double* __restrict__ stats, int nrep, const float* __restrict__ scale,
+                                            float* dgamma, float* dbeta, float* dbias, int ch) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ch) return;
+  double s1 = 0.0, s2 = 0.0;
+  replica_sums(stats, nrep, ch, c, s1, s2);
+  if (dbeta) dbeta[c] = (float)s1;
+  if (dgamma) dgamma[c] = (float)s2;
+  if (dbias) dbias[c] = (float)((double)scale[c] * s1);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_dy_kernel(const T* __restrict__ dz, const T* __restrict__ y,
                                                         T* __restrict__ dy, const float* __restrict__ coef,
@@ -894,6 +995,47 @@ extern "C" int pcaa_bn_bwd_finalize(const double* stats, int nrep, long count, c
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
                      stats, nrep, 1.0 / (double)count, gamma, mean, rstd, coef, dgamma, dbeta, ch);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_finalize");
+}
+
+extern "C" int pcaa_bn_eval_moments(const float* running_mean, const float* running_var, const float* lin_bias,
+                                    float eps, float* mean, float* rstd, int ch, void* stream) {
+  PCAA_CHECK_ARG(running_mean && running_var && mean && rstd, "pcaa_bn_eval_moments: null pointer");
+  PCAA_CHECK_ARG(ch >= 1, "pcaa_bn_eval_moments: bad sizes");
+  hipLaunchKernelGGL(bn_eval_moments_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
+                     running_mean, running_var, lin_bias, eps, mean, rstd, ch);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_eval_moments");
+}
+
+extern "C" int pcaa_bn_eval_act_bwd(const void* da, const float* dpool, int group_rows, float pool_scale,
+                                    const void* y, void* dy, int dtype, const float* scale, const float* shift,
+                                    const float* mean, const float* rstd, double* stats, int nrep, long rows, int ch,
+                                    void* stream) {
+  PCAA_CHECK_ARG((da != nullptr) != (dpool != nullptr), "pcaa_bn_eval_act_bwd: exactly one of da / dpool");
+  PCAA_CHECK_ARG(y && dy && scale && shift && mean && rstd && stats, "pcaa_bn_eval_act_bwd: null pointer");
+  PCAA_CHECK_ARG(rows >= 1 && rows < (1L << 31) && nrep >= 1 && ch_ok(ch),
+                 "pcaa_bn_eval_act_bwd: ch/4 must divide 256 (ch=%d), rows < 2^31", ch);
+  PCAA_CHECK_ARG(!dpool || group_rows >= 1, "pcaa_bn_eval_act_bwd: bad group_rows");
+  PCAA_CHECK_ARG(dy != y, "pcaa_bn_eval_act_bwd: dy may alias da, not y");
+  const unsigned grid = (unsigned)cdiv(rows, ROWS_PER_BLOCK);
+  hipStream_t s = as_stream(stream);
+#define LAUNCH_EV(T, POOL)                                                                         \
+  hipLaunchKernelGGL((bn_eval_act_bwd_kernel<T, POOL>), dim3(grid), dim3(256), 0, s, (const T*)da, \
+                     dpool, (unsigned)group_rows, pool_scale, (const T*)y, (T*)dy, scale, shift,   \
+                     mean, rstd, stats, nrep, rows, ch)
+  if (dtype == PCAA_F32) { if (dpool) LAUNCH_EV(float, true); else LAUNCH_EV(float, false); }
+  else if (dtype == PCAA_BF16) { if (dpool) LAUNCH_EV(bf16_t, true); else LAUNCH_EV(bf16_t, false); }
+  else { pcaa_set_error("pcaa_bn_eval_act_bwd: bad dtype"); return PCAA_ERR_INVALID_ARG; }
+#undef LAUNCH_EV
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_eval_act_bwd");
+}
+
+extern "C" int pcaa_bn_eval_bwd_finalize(const double* stats, int nrep, const float* scale, float* dgamma,
+                                         float* dbeta, float* dbias, int ch, void* stream) {
+  PCAA_CHECK_ARG(stats && (scale || !dbias), "pcaa_bn_eval_bwd_finalize: null pointer");
+  PCAA_CHECK_ARG(nrep >= 1 && ch >= 1, "pcaa_bn_eval_bwd_finalize: bad sizes");
+  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
+                     stats, nrep, scale, dgamma, dbeta, dbias, ch);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_eval_bwd_finalize");
 }
 
 // ---------------------------------------------------------------- finalize carried by the producer (bn_tail.h)

@@ -259,11 +259,13 @@ def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None
     return y, scale, shift, mean, rstd, count
 
 
-def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
+def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, want_bwd=False):
     """xp2d: [P, C] fp32.  Returns (output, saves).  If pool_rows>0 the last
     layer's ELU output is mean-pooled over groups of pool_rows rows (fp32
     [P/pool_rows, ch]); else the last activation [P, ch] is returned.
-    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing them."""
+    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing them.
+    ``want_bwd`` (matters in eval mode only): a backward will follow, so every layer keeps what pointnet_backward reads
+    (its pre-BatchNorm ``y``: no fused-epilogue layers, no split images); off, the eval forward is unchanged."""
     if consts is not None and (training or consts.mode != mode):
         raise ValueError("pointnet_forward: consts are eval-mode constants of one precision mode "
                          f"(made for {consts.mode!r}, asked for {mode!r}, training={training})")
@@ -272,7 +274,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
     nl = len(layers)
     # fp16x3 mode: the activations between the layers are [hi | lo] images when every later product is one the
     # LDS-DMA kernel serves (whole 256-tiles); else the layer stack runs in exact fp32
-    split = mode == "fp16x3" and nl > 1 and all(
+    split = mode == "fp16x3" and nl > 1 and (training or not want_bwd) and all(
         ops.gemm_split3_supported(xp2d.shape[0], l.module[0].weight.shape[0], l.module[0].weight.shape[1])
         and l.module[0].weight.shape[1] % 256 == 0 for l in layers[1:])
     for li, layer in enumerate(layers):
@@ -305,7 +307,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None):
                                       (ops.SplitImage.dtype if split else torch.float32))
             continue
         last_pool = li == nl - 1 and pool_rows
-        if (_FUSE_EVAL_EPILOGUE and not training and mode == "bf16" and a.dtype == torch.bfloat16
+        if (_FUSE_EVAL_EPILOGUE and not training and not want_bwd and mode == "bf16" and a.dtype == torch.bfloat16
                 and (not last_pool or pool_rows in (32, 64, 128))
                 and ops.gemm_dgrad_bn_supported(a.shape[0], cout, cin)):
             # eval mode: BatchNorm is a fixed per-channel affine map -> BN + ELU (and the mean over the frame's
@@ -399,7 +401,8 @@ _MOMENT_STATS = os.environ.get("PCAA_MOMENT_STATS", "1") != "0"
 
 def _bn_layer_backward(s, bn, W2d, mode, da=None, dpool=None, group_rows=0, pool_scale=1.0,
                        need_dinput=True, lhs=None, outs=None, below=None, below_W=None, dgrad_fn=None,
-                       below_bn=None, below_outs=None, wgrad_math=PCAA_F32, defer_wgrad=None):
+                       below_bn=None, below_outs=None, wgrad_math=PCAA_F32, defer_wgrad=None, lin_bias=None,
+                       dbias_out=None):
     """Backward of one (linear, BN, ELU) layer.  ``lhs`` is the GEMM's left
     operand ([rows, K]: the input activation or the im2col matrix).  ``outs`` =
     (dW, dgamma, dbeta) destination views (dW PRE-ZEROED: the trainer's flat
@@ -407,12 +410,27 @@ def _bn_layer_backward(s, bn, W2d, mode, da=None, dpool=None, group_rows=0, pool
     above already applied ELU' and reduced the statistics).  ``below``: the saved state of the
     layer that produced ``lhs`` -- if it qualifies, this layer's dgrad is fused with the first
     half of ITS backward and a _FusedGrad is returned as d_lhs.
-    Returns (dW2d, dgamma, dbeta, d_lhs or None)."""
+    An eval-mode save (``s.mean is None``: BatchNorm was the fixed map z = scale*y + shift) takes one pass instead
+    (ops.bn_eval_act_bwd) and the linear bias ``lin_bias`` in front of the BatchNorm has a gradient, dbias = scale*dbeta
+    (written to ``dbias_out`` when given); in train mode dbias is None (analytically zero: the batch mean removes it).
+    Returns (dW2d, dgamma, dbeta, dbias, d_lhs or None)."""
     y = s.y
     rows_local, cout = y.shape
     d_lhs = None
+    dbias = None
     dgrad_done = False
-    if isinstance(da, _FusedGrad):
+    if s.mean is None:
+        # no batch statistic stands between da and dy: dy and the two column sums in ONE pass, then their finalize;
+        # the running statistics are only read, and no collective is issued whatever the SyncBN setting
+        if da is not None and da.dtype != y.dtype:
+            da = da.to(y.dtype)
+        emean, erstd = ops.bn_eval_moments(bn, cout, lin_bias)
+        dy, stats = ops.bn_eval_act_bwd(y, s.scale, s.shift, emean, erstd, da=da, dpool=dpool, group_rows=group_rows,
+                                        pool_scale=pool_scale, out=da)
+        dgamma, dbeta, dbias = ops.bn_eval_bwd_finalize(stats, s.scale, cout, dgamma=outs[1] if outs else None,
+                                                        dbeta=outs[2] if outs else None,
+                                                        dbias=dbias_out if lin_bias is not None else None)
+    elif isinstance(da, _FusedGrad):
         stats = da.stats
         if da.fin is not None:
             coef, dgamma, dbeta = da.fin          # finalized by the launch that produced the statistics
@@ -537,7 +555,7 @@ def _bn_layer_backward(s, bn, W2d, mode, da=None, dpool=None, group_rows=0, pool
         else:
             d_lhs = ops.gemm(dy, KC, W2d, RC, rows_local, K, cout,
                              out_dtype=torch.float32)
-    return dW, dgamma, dbeta, d_lhs
+    return dW, dgamma, dbeta, dbias, d_lhs
 
 
 def _layer_outs(gout, prefix, wname, gname, bname):
@@ -562,7 +580,9 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
         below_bn = layers[li - 1].module[1] if li > 0 else None
         below_outs = _layer_outs(gout, f"{prefix}{li}.", "module.0.weight", "module.1.weight", "module.1.bias") if li > 0 else None
         below_W = None
-        if s.y is None and da is not None and not need_in:
+        bias_out = gout[f"{prefix}{li + 1}.module.0.bias"] if gout is not None else None
+        dbias = None
+        if s.y is None and s.mean is not None and da is not None and not need_in:
             # recompute path of the first layer: two passes over da (one, when the dgrad above already applied
             # ELU' and reduced the statistics), nothing else is read or written
             fused = isinstance(da, _FusedGrad)
@@ -595,18 +615,22 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
                                            dz_is_pre=fused)
             dprev = None
         elif li == len(layers) - 1 and dpool is not None:
-            dW, dg, db, dprev = _bn_layer_backward(s, bn, W2d, mode, dpool=dpool, group_rows=pool_rows,
-                                                   pool_scale=1.0 / pool_rows, need_dinput=need_in, lhs=s.a_in,
-                                                   outs=outs, below=saves[li - 1] if li > 0 else None,
-                                                   below_W=below_W, below_bn=below_bn, below_outs=below_outs)
+            dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, dpool=dpool, group_rows=pool_rows,
+                                                          pool_scale=1.0 / pool_rows, need_dinput=need_in, lhs=s.a_in,
+                                                          outs=outs, below=saves[li - 1] if li > 0 else None,
+                                                          below_W=below_W, below_bn=below_bn, below_outs=below_outs,
+                                                          lin_bias=conv.bias, dbias_out=bias_out)
         else:
-            if s.y is None:      # recompute layer, but the caller wants the gradient w.r.t. the points: rebuild y
+            if s.y is None:
+                # recompute layer, but the caller wants the gradient w.r.t. the points, or the save is an eval-mode one
+                # (which takes the general route): rebuild y from the points
                 s.y = ops.pointnet_in_fwd(s.a_in, W2d, None, da.dtype)
-            dW, dg, db, dprev = _bn_layer_backward(s, bn, W2d, mode, da=da, need_dinput=need_in, lhs=s.a_in,
-                                                   outs=outs, below=saves[li - 1] if li > 0 else None,
-                                                   below_W=below_W, below_bn=below_bn, below_outs=below_outs)
-        # the conv bias gradient is analytically zero (BatchNorm removes the mean)
-        zb = gout[f"{prefix}{li + 1}.module.0.bias"] if gout is not None else torch.zeros_like(conv.bias)
+            dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, da=da, need_dinput=need_in, lhs=s.a_in,
+                                                          outs=outs, below=saves[li - 1] if li > 0 else None,
+                                                          below_W=below_W, below_bn=below_bn, below_outs=below_outs,
+                                                          lin_bias=conv.bias, dbias_out=bias_out)
+        # train mode: the conv bias gradient is analytically zero (BatchNorm removes the mean); eval mode: scale * dbeta
+        zb = dbias if dbias is not None else (bias_out if gout is not None else torch.zeros_like(conv.bias))
         grads.append({"module.0.weight": dW.view_as(conv.weight), "module.0.bias": zb,
                       "module.1.weight": dg, "module.1.bias": db})
         da = dprev
@@ -637,14 +661,19 @@ def _dtc_bf16(mode, kc, nc, adj=False):
     return on and kc >= 128 and kc % 32 == 0 and nc >= 64 and nc % 4 == 0
 
 
-def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0, consts=None):
+def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0, consts=None,
+                want_bwd=False):
     """a2d: [B*T, Cin] fp32 rows (b,t).  Causal dilated conv = (implicit) im2col + contraction.
     ``win_row`` (ops.WindowRows, eval only): a2d is a frame-feature table [table_rows, Cin] instead and sequence b is
     its T rows from win_row[b] on (modulo ``ring_rows`` if > 0).  Only the first layer reads the table: fused, through
     the windowed form of its launch; otherwise the windows are written out with one gather and today's path runs.
-    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing the BatchNorm coefficients."""
+    ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing the BatchNorm coefficients.
+    ``want_bwd`` (matters in eval mode only): a backward will follow, so the fused launch also writes the im2col matrix
+    dtc_backward contracts with; off, the eval forward is unchanged."""
     if consts is not None and training:
         raise ValueError("dtc_forward: consts are eval-mode constants")
+    if win_row is not None and want_bwd:
+        raise ValueError("dtc_forward: the windowed form has no backward")
     saves = []
     a = a2d
     nl = len(layers)
@@ -668,7 +697,7 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
             stats = ops.new_stats(cout, a.device) if training else None
             tail = ops.BnTailFwd(a.shape[0], conv.bias, bn, cout, sync=_sync_fn()) if training else None
             y, col = ops.dtc_conv_fwd(a, prev[0] if prev else None, prev[1] if prev else None, W2d, B, T,
-                                      layer.dilation, stats=stats, want_col=training, tail=tail,
+                                      layer.dilation, stats=stats, want_col=training or want_bwd, tail=tail,
                                       bf16=_dtc_bf16(mode, cin, cout), win_row=win_row if li == 0 else None)
             if training:
                 scale, shift, mean, rstd = tail.out
@@ -742,14 +771,18 @@ def dtc_backward(saves, layers, B, T, d_last=None, dpool=None, need_dx=True, gou
                 return (_FusedGrad(out, stats, fin=btail.out) if sb else out), dy_used
 
             dgrad_fn.forms_dy = s.cout <= 512
+        bias_out = gout[f"{prefix}{li + 1}.conv1d.bias"] if gout is not None else None
         if li == len(layers) - 1 and dpool is not None:
-            dW, dg, db, dcol = _bn_layer_backward(s, bn, W2d, "fp32", dpool=dpool, group_rows=T,
-                                                  pool_scale=1.0 / T, need_dinput=need_in, lhs=s.col, outs=outs,
-                                                  dgrad_fn=dgrad_fn, wgrad_math=wmath, defer_wgrad=defer)
+            dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", dpool=dpool, group_rows=T,
+                                                         pool_scale=1.0 / T, need_dinput=need_in, lhs=s.col, outs=outs,
+                                                         dgrad_fn=dgrad_fn, wgrad_math=wmath, defer_wgrad=defer,
+                                                         lin_bias=conv.bias, dbias_out=bias_out)
         else:
-            dW, dg, db, dcol = _bn_layer_backward(s, bn, W2d, "fp32", da=da, need_dinput=need_in, lhs=s.col,
-                                                  outs=outs, dgrad_fn=dgrad_fn, wgrad_math=wmath, defer_wgrad=defer)
-        zb = gout[f"{prefix}{li + 1}.conv1d.bias"] if gout is not None else torch.zeros_like(conv.bias)
+            dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", da=da, need_dinput=need_in, lhs=s.col,
+                                                         outs=outs, dgrad_fn=dgrad_fn, wgrad_math=wmath,
+                                                         defer_wgrad=defer, lin_bias=conv.bias, dbias_out=bias_out)
+        # (train mode: analytically zero; eval mode: scale * dbeta)
+        zb = dbias if dbias is not None else (bias_out if gout is not None else torch.zeros_like(conv.bias))
         grads.append({"conv1d.weight": dW.view_as(conv.weight), "conv1d.bias": zb,
                       "batch_norm.weight": dg, "batch_norm.bias": db})
         if not need_in:
@@ -941,9 +974,10 @@ def _check_encoder_input(enc, C, N):
                            "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
 
 
-def encoder_forward(enc, x, training, mode=None, gph=None):
+def encoder_forward(enc, x, training, mode=None, gph=None, want_bwd=False):
     """``gph``: optional decoder projection head ``Sequential(Linear(32,64), ELU)`` evaluated in the
-    same launch as the MLP heads (``st.hproj``)."""
+    same launch as the MLP heads (``st.hproj``).  ``want_bwd``: encoder_backward will follow -- in eval mode the two
+    blocks then keep what it reads (pointnet_forward / dtc_forward); a train-mode forward always does."""
     mode = get_precision() if mode is None else mode
     _require_gpu(x, "CGEncoder")
     if x.dim() != 4:
@@ -951,14 +985,15 @@ def encoder_forward(enc, x, training, mode=None, gph=None):
     B, C, T, N = x.shape
     _check_encoder_input(enc, C, N)
     st = EncoderState()
-    st.B, st.C, st.T, st.N, st.mode, st.training = B, C, T, N, mode, training
+    st.B, st.C, st.T, st.N, st.mode, st.training, st.want_bwd = B, C, T, N, mode, training, training or want_bwd
     xp = _point_major(x).view(B * T * N, C)
     st.xp = xp
     mark("enc_fwd.begin")
-    x2, st.pn = pointnet_forward(xp, enc.pc_block.layers(), training, mode, pool_rows=N)   # [B*T, 1024]
+    x2, st.pn = pointnet_forward(xp, enc.pc_block.layers(), training, mode, pool_rows=N, want_bwd=want_bwd)   # [B*T, 1024]
     st.x2 = x2
     mark("enc_fwd.pointnet")
-    x4, st.dtc = dtc_forward(x2, B, T, enc.tc_block.layers(), training, pool_time=True, mode=mode)     # [B, 512]
+    x4, st.dtc = dtc_forward(x2, B, T, enc.tc_block.layers(), training, pool_time=True, mode=mode,
+                             want_bwd=want_bwd)                                                        # [B, 512]
     st.x4 = x4
     mark("enc_fwd.dtc")
     return _encoder_heads(enc, st, x4, gph)
@@ -1031,10 +1066,12 @@ def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, befor
     them, so they must arrive ZEROED (the trainer zeroes its flat buffer once).
     ``gph`` / ``d_hproj`` / ``gph_gout``: the decoder projection head evaluated by encoder_forward(gph=...),
     the gradient w.r.t. its output and optional (dW, db) destinations: its backward runs in the heads'
-    launch; its gradients are returned under "GPH.0.weight" / "GPH.0.bias"."""
-    if not st.training:
-        raise RuntimeError("CGEncoder backward in eval mode is not implemented on the HIP path "
-                           "(the reference only differentiates the train-mode encoder)")
+    launch; its gradients are returned under "GPH.0.weight" / "GPH.0.bias".
+    An eval-mode state (encoder_forward(..., training=False, want_bwd=True)) differentiates the frozen-BatchNorm encoder:
+    the running statistics are read, never written, and the biases in front of the BatchNorms get real gradients."""
+    if not getattr(st, "want_bwd", st.training):
+        raise RuntimeError("encoder_backward: this eval-mode forward kept nothing for a backward -- "
+                           "call encoder_forward(..., want_bwd=True)")
     g = {}
     B, T, N = st.B, st.T, st.N
 
@@ -1120,7 +1157,8 @@ def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, befor
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, x, *params):
-        logits, sup_fv, st = encoder_forward(enc, x, enc.training)
+        # (cg_encoder only comes here when a gradient is wanted)
+        logits, sup_fv, st = encoder_forward(enc, x, enc.training, want_bwd=True)
         ctx.enc, ctx.st = enc, st
         ctx.need_dx = x.requires_grad
         ctx.names = [n for n, _ in enc.named_parameters()]
@@ -1141,18 +1179,24 @@ def cg_encoder(enc, x):
     return logits, sup_fv
 
 
+def _want_bwd(x, params):
+    """the "a backward will follow" switch of an eval-mode forward, decided where autograd's state can still be seen
+    (inside Function.forward grad mode is off): the condition cg_encoder tests"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+
+
 # ---------------------------------------------------------------- encoder trunk (OR-CED baseline, models.py:446-505)
 class _TrunkFn(torch.autograd.Function):
     """PointNetBlock -> mean over the points -> TemporalConvolutionBlock -> mean over time: x [B,C,T,N] -> x4 [B,512],
     the part ORCEDEncoder shares with CGEncoder, on the same kernels (its three Linear heads follow in torch)."""
 
     @staticmethod
-    def forward(ctx, enc, x, *params):
+    def forward(ctx, enc, want_bwd, x, *params):
         B, C, T, N = x.shape
         mode = get_precision()
         xp = _point_major(x).view(B * T * N, C)
-        x2, pn = pointnet_forward(xp, enc.pc_block.layers(), enc.training, mode, pool_rows=N)
-        x4, dtc = dtc_forward(x2, B, T, enc.tc_block.layers(), enc.training, pool_time=True)
+        x2, pn = pointnet_forward(xp, enc.pc_block.layers(), enc.training, mode, pool_rows=N, want_bwd=want_bwd)
+        x4, dtc = dtc_forward(x2, B, T, enc.tc_block.layers(), enc.training, pool_time=True, want_bwd=want_bwd)
         ctx.enc, ctx.pn, ctx.dtc, ctx.shape, ctx.mode, ctx.training = enc, pn, dtc, (B, C, T, N), mode, enc.training
         ctx.names = [n for n, _ in itertools.chain(enc.pc_block.named_parameters(prefix="pc_block"),
                                                    enc.tc_block.named_parameters(prefix="tc_block"))]
@@ -1161,8 +1205,6 @@ class _TrunkFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dx4):
-        if not ctx.training:
-            raise RuntimeError("ORCEDEncoder backward in eval mode is not implemented on the HIP path")
         B, C, T, N = ctx.shape
         enc = ctx.enc
         g = {}
@@ -1174,7 +1216,7 @@ class _TrunkFn(torch.autograd.Function):
         for i, d in enumerate(pg, start=1):
             for k, v in d.items():
                 g[f"pc_block.pointnet{i}.{k}"] = v
-        return (None, None) + tuple(g.get(n) for n in ctx.names)
+        return (None, None, None) + tuple(g.get(n) for n in ctx.names)
 
 
 class _OrcedHeadsFn(torch.autograd.Function):
@@ -1282,16 +1324,16 @@ def encoder_trunk(enc, x):
     if x.dim() != 4 or x.shape[3] != enc.nmax_points:
         raise RuntimeError(f"ORCEDEncoder expects [B,C,T,{enc.nmax_points}], got {tuple(x.shape)}")
     params = list(enc.pc_block.parameters()) + list(enc.tc_block.parameters())
-    return _TrunkFn.apply(enc, x, *params)
+    return _TrunkFn.apply(enc, _want_bwd(x, params), x, *params)
 
 
 # ---------------------------------------------------------------- standalone blocks
 class _PointNetStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layers, training, x, *params):
+    def forward(ctx, layers, training, want_bwd, x, *params):
         B, C, T, N = x.shape
         xp = _point_major(x).view(B * T * N, C)
-        a, saves = pointnet_forward(xp, layers, training, "fp32")
+        a, saves = pointnet_forward(xp, layers, training, "fp32", want_bwd=want_bwd)
         ctx.layers, ctx.saves, ctx.shape = layers, saves, (B, C, T, N)
         ctx.need_dx = x.requires_grad
         ctx.training = training
@@ -1300,8 +1342,6 @@ class _PointNetStackFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        if not ctx.training:
-            raise RuntimeError("PointNet backward in eval mode is not implemented on the HIP path")
         B, C, T, N = ctx.shape
         d = gout.permute(0, 2, 3, 1).contiguous().view(B * T * N, -1)
         grads, dxp = pointnet_backward(ctx.saves, ctx.layers, "fp32", d_last=d, need_dx=ctx.need_dx)
@@ -1309,7 +1349,7 @@ class _PointNetStackFn(torch.autograd.Function):
         for gd in grads:
             flat += [gd["module.0.weight"], gd["module.0.bias"], gd["module.1.weight"], gd["module.1.bias"]]
         dx = dxp.view(B, T, N, C).permute(0, 3, 1, 2) if ctx.need_dx else None
-        return (None, None, dx) + tuple(flat)
+        return (None, None, None, dx) + tuple(flat)
 
 
 def pointnet_stack(x, layers, training):
@@ -1317,30 +1357,28 @@ def pointnet_stack(x, layers, training):
     params = []
     for l in layers:
         params += [l.module[0].weight, l.module[0].bias, l.module[1].weight, l.module[1].bias]
-    return _PointNetStackFn.apply(layers, training, x, *params)
+    return _PointNetStackFn.apply(layers, training, _want_bwd(x, params), x, *params)
 
 
 class _DtcStackFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, layers, training, x, *params):
+    def forward(ctx, layers, training, want_bwd, x, *params):
         B, C, T = x.shape
         a2d = x.permute(0, 2, 1).contiguous().view(B * T, C)
-        a, saves = dtc_forward(a2d, B, T, layers, training, pool_time=False)
+        a, saves = dtc_forward(a2d, B, T, layers, training, pool_time=False, want_bwd=want_bwd)
         ctx.layers, ctx.saves, ctx.shape, ctx.training = layers, saves, (B, C, T), training
         return a.view(B, T, -1).permute(0, 2, 1)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        if not ctx.training:
-            raise RuntimeError("DilTempConv1d backward in eval mode is not implemented on the HIP path")
         B, C, T = ctx.shape
         d = gout.permute(0, 2, 1).contiguous().view(B * T, -1)
         grads, dx2d = dtc_backward(ctx.saves, ctx.layers, B, T, d_last=d, need_dx=True)
         flat = []
         for gd in grads:
             flat += [gd["conv1d.weight"], gd["conv1d.bias"], gd["batch_norm.weight"], gd["batch_norm.bias"]]
-        return (None, None, dx2d.view(B, T, C).permute(0, 2, 1)) + tuple(flat)
+        return (None, None, None, dx2d.view(B, T, C).permute(0, 2, 1)) + tuple(flat)
 
 
 def dtc_stack(x, layers, training):
@@ -1348,7 +1386,7 @@ def dtc_stack(x, layers, training):
     params = []
     for l in layers:
         params += [l.conv1d.weight, l.conv1d.bias, l.batch_norm.weight, l.batch_norm.bias]
-    return _DtcStackFn.apply(layers, training, x.float(), *params)
+    return _DtcStackFn.apply(layers, training, _want_bwd(x, params), x.float(), *params)
 
 
 # ======================================================================
@@ -1526,15 +1564,14 @@ class _GmlFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        if not ctx.training:
-            raise RuntimeError("GaussianMeanLearner backward in eval mode is not implemented on the HIP path")
         m = ctx.gml.model
         dW9, db9, da = linear_act_backward(ctx.a_last, None, m[9], ACT_NONE, gout.contiguous())
         out = []
         for (lin_i, bn_i), s in reversed(list(zip(((0, 1), (3, 4), (6, 7)), ctx.saves))):
             lin, bn = m[lin_i], m[bn_i]
-            dW, dg, db, da = _bn_layer_backward(s, bn, lin.weight, "fp32", da=da, need_dinput=True, lhs=s.a_in)
-            out = [dW, torch.zeros_like(lin.bias), dg, db] + out
+            dW, dg, db, dbias, da = _bn_layer_backward(s, bn, lin.weight, "fp32", da=da, need_dinput=True, lhs=s.a_in,
+                                                       lin_bias=lin.bias)
+            out = [dW, dbias if dbias is not None else torch.zeros_like(lin.bias), dg, db] + out
         return (None, da) + tuple(out) + (dW9, db9)
 
 

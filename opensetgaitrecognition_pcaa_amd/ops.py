@@ -1067,6 +1067,50 @@ def bn_bwd_finalize(stats, count, bn, mean, rstd, ch, dgamma=None, dbeta=None):
     return coef, dgamma, dbeta
 
 
+def bn_eval_moments(bn, ch, lin_bias=None):
+    """eval-mode (mean, rstd) of the bias-free y: running_mean - bias and 1/sqrt(running_var + eps)"""
+    dev = bn.weight.device
+    mean = torch.empty(ch, dtype=torch.float32, device=dev)
+    rstd = torch.empty_like(mean)
+    check(_lib.load().pcaa_bn_eval_moments(_p(bn.running_mean), _p(bn.running_var), _p(lin_bias), bn.eps, _p(mean),
+                                           _p(rstd), ch, _s()), "pcaa_bn_eval_moments")
+    return mean, rstd
+
+
+def bn_eval_act_bwd(y, scale, shift, mean, rstd, *, da=None, dpool=None, group_rows=0, pool_scale=1.0, out=None):
+    """Backward through eval-mode BatchNorm + ELU in one pass: dy = scale * (g * ELU'(scale*y + shift)) (``out`` may be
+    ``da``) and the statistics {sum dz, sum dz*xhat} for bn_eval_bwd_finalize.  -> (dy, stats)"""
+    _chk(y, "bn_eval_act_bwd.y", dim=2)
+    rows, ch = y.shape
+    if da is not None:
+        _chk(da, "bn_eval_act_bwd.da", y.dtype, 2)
+        if da.shape != y.shape:
+            raise ValueError("bn_eval_act_bwd: da shape")
+    else:
+        _chk(dpool, "bn_eval_act_bwd.dpool", torch.float32, 2)
+        if dpool.shape[0] * group_rows != rows or dpool.shape[1] != ch:
+            raise ValueError("bn_eval_act_bwd: dpool shape")
+    dy = out if out is not None else torch.empty_like(y)
+    if dy.shape != y.shape or dy.dtype != y.dtype or not dy.is_contiguous():
+        raise ValueError("bn_eval_act_bwd: out must be contiguous with y's shape and dtype")
+    stats = new_stats(ch, y.device)
+    check(_lib.load().pcaa_bn_eval_act_bwd(_p(da), _p(dpool), int(group_rows), float(pool_scale), _p(y), _p(dy),
+                                           _dt(y), _p(scale), _p(shift), _p(mean), _p(rstd), _p(stats), NREP,
+                                           rows, ch, _s()), "pcaa_bn_eval_act_bwd")
+    return dy, stats
+
+
+def bn_eval_bwd_finalize(stats, scale, ch, dgamma=None, dbeta=None, dbias=None):
+    """-> (dgamma, dbeta, dbias), written into the given destinations where given"""
+    dev = stats.device
+    dgamma = torch.empty(ch, dtype=torch.float32, device=dev) if dgamma is None else dgamma
+    dbeta = torch.empty(ch, dtype=torch.float32, device=dev) if dbeta is None else dbeta
+    dbias = torch.empty(ch, dtype=torch.float32, device=dev) if dbias is None else dbias
+    check(_lib.load().pcaa_bn_eval_bwd_finalize(_p(stats), NREP, _p(scale), _p(dgamma), _p(dbeta), _p(dbias), ch, _s()),
+          "pcaa_bn_eval_bwd_finalize")
+    return dgamma, dbeta, dbias
+
+
 def bn_bwd_dy(dz, y, coef, out=None):
     dy = out if out is not None else torch.empty_like(dz)
     check(_lib.load().pcaa_bn_bwd_dy(_p(dz), _p(y), _p(dy), _dt(y), _p(coef), y.shape[0], y.shape[1], _s()),
