@@ -383,185 +383,231 @@ class _on_wgrad_stream:
         return False
 
 
-# Fusions that have an unfused fallback for the shapes their kernels do not take.  They were A/B-ed through
-# environment switches in round 1 (docs/LAB_LOG.md section 4) and are plain constants now: the product has one path per shape.
-# PointNet weight gradients on the wgrad side stream: measured no change (they fill the chip either way) -> off.
-_BIG_WGRAD_ASIDE = False
-# ... but the split-K slab reductions that follow them (12 us each, three per step, needed only by Adam) do leave it
+# Fusions that have an unfused fallback for the shapes their kernels do not take were A/B-ed through environment switches in round 1
+# (docs/LAB_LOG.md section 4); what was decided is plain code now.  The PointNet weight gradients stay on the main stream (they fill
+# the chip either way), but the split-K slab reductions that follow them (12 us each, three per step, needed only by Adam) leave it
 _REDUCE_ASIDE = os.environ.get("PCAA_REDUCE_ASIDE", "1") != "0"
-_FUSE_DGRAD_BN = True
-# (the same fusion into the dgrad above the FIRST layer -- y rebuilt from the points in the epilogue -- measured slower in
-# round 1: the layer-2 dgrad went 0.195 -> 0.361 ms to save a 0.10 ms statistics pass; it lived in the 8-wave kernel only
-# and was removed with it in round 5)
 # first PointNet layer, bf16 mode: one pass over the incoming gradient instead of two (ops.pointnet_in_bwd_onepass)
 _ONEPASS_IN_BWD = os.environ.get("PCAA_ONEPASS_IN_BWD", "1") != "0"
 # first PointNet layer, forward: BatchNorm statistics from the points' second moments instead of a pass over [P, cout]
 _MOMENT_STATS = os.environ.get("PCAA_MOMENT_STATS", "1") != "0"
 
 
-def _bn_layer_backward(s, bn, W2d, mode, da=None, dpool=None, group_rows=0, pool_scale=1.0,
-                       need_dinput=True, lhs=None, outs=None, below=None, below_W=None, dgrad_fn=None,
-                       below_bn=None, below_outs=None, wgrad_math=PCAA_F32, defer_wgrad=None, lin_bias=None,
-                       dbias_out=None):
-    """Backward of one (linear, BN, ELU) layer.  ``lhs`` is the GEMM's left
-    operand ([rows, K]: the input activation or the im2col matrix).  ``outs`` =
-    (dW, dgamma, dbeta) destination views (dW PRE-ZEROED: the trainer's flat
-    gradient buffer) or None to allocate.  ``da`` may be a _FusedGrad (the dgrad of the layer
-    above already applied ELU' and reduced the statistics).  ``below``: the saved state of the
-    layer that produced ``lhs`` -- if it qualifies, this layer's dgrad is fused with the first
-    half of ITS backward and a _FusedGrad is returned as d_lhs.
-    An eval-mode save (``s.mean is None``: BatchNorm was the fixed map z = scale*y + shift) takes one pass instead
-    (ops.bn_eval_act_bwd) and the linear bias ``lin_bias`` in front of the BatchNorm has a gradient, dbias = scale*dbeta
-    (written to ``dbias_out`` when given); in train mode dbias is None (analytically zero: the batch mean removes it).
-    Returns (dW2d, dgamma, dbeta, dbias, d_lhs or None)."""
+def _bwd_tail(save, bn, outs, ch):
+    """the BatchNorm-backward finalize of ``save``'s layer, for the launch that reduces its statistics to carry"""
+    return ops.BnTailBwd(save.rows, bn, save.mean, save.rstd, ch, dgamma=outs[1] if outs else None,
+                         dbeta=outs[2] if outs else None, sync=_sync_fn())
+
+
+def _fused_coefficients(da, s, bn, outs):
+    """(coef, dgamma, dbeta) behind a _FusedGrad: finalized by the launch that produced the statistics, else (SyncBN) now"""
+    if da.fin is not None:
+        return da.fin
+    _sync_stats(da.stats, 0)
+    return ops.bn_bwd_finalize(da.stats, s.rows, bn, s.mean, s.rstd, s.cout, dgamma=outs[1] if outs else None,
+                               dbeta=outs[2] if outs else None)
+
+
+def _bn_dy(s, bn, da, pool, lhs_split, outs, lin_bias, dbias_out, adjoint_dy=None):
+    """First stage: the gradient w.r.t. the pre-BatchNorm ``s.y``, from ``da`` (tensor or _FusedGrad) or ``pool``, and the
+    BatchNorm gradients.  ``lhs_split``: dy is wanted as a SplitImage; ``adjoint_dy``: the caller's adjoint when it forms dy
+    itself (then d_lhs comes back too).  Returns (dy, dgamma, dbeta, dbias, d_lhs or None)."""
     y = s.y
-    rows_local, cout = y.shape
-    d_lhs = None
-    dbias = None
-    dgrad_done = False
+    dpool, group_rows, pool_scale = pool if pool is not None else (None, 0, 1.0)
+    if isinstance(da, torch.Tensor) and da.dtype != y.dtype:
+        da = da.to(y.dtype)
+    grad = dict(da=da, dpool=dpool, group_rows=group_rows, pool_scale=pool_scale)      # (unused with a _FusedGrad)
+    # ---- eval-mode save: BatchNorm was the fixed map z = scale*y + shift, so no batch statistic stands between da and dy:
+    # dy and the two column sums in ONE pass, then their finalize; the running statistics are only read, and no collective
+    # is issued whatever the SyncBN setting
     if s.mean is None:
-        # no batch statistic stands between da and dy: dy and the two column sums in ONE pass, then their finalize;
-        # the running statistics are only read, and no collective is issued whatever the SyncBN setting
-        if da is not None and da.dtype != y.dtype:
-            da = da.to(y.dtype)
-        emean, erstd = ops.bn_eval_moments(bn, cout, lin_bias)
-        dy, stats = ops.bn_eval_act_bwd(y, s.scale, s.shift, emean, erstd, da=da, dpool=dpool, group_rows=group_rows,
-                                        pool_scale=pool_scale, out=da)
-        dgamma, dbeta, dbias = ops.bn_eval_bwd_finalize(stats, s.scale, cout, dgamma=outs[1] if outs else None,
+        emean, erstd = ops.bn_eval_moments(bn, s.cout, lin_bias)
+        dy, stats = ops.bn_eval_act_bwd(y, s.scale, s.shift, emean, erstd, out=da, **grad)
+        dgamma, dbeta, dbias = ops.bn_eval_bwd_finalize(stats, s.scale, s.cout, dgamma=outs[1] if outs else None,
                                                         dbeta=outs[2] if outs else None,
                                                         dbias=dbias_out if lin_bias is not None else None)
-    elif isinstance(da, _FusedGrad):
-        stats = da.stats
-        if da.fin is not None:
-            coef, dgamma, dbeta = da.fin          # finalized by the launch that produced the statistics
-        else:
-            _sync_stats(stats, 0)
-            coef, dgamma, dbeta = ops.bn_bwd_finalize(stats, s.rows, bn, s.mean, s.rstd, cout,
-                                                      dgamma=outs[1] if outs else None, dbeta=outs[2] if outs else None)
-        if need_dinput and dgrad_fn is not None and getattr(dgrad_fn, "forms_dy", False):
+        return dy, dgamma, dbeta, dbias, None
+    # ---- fused: the dgrad above already applied ELU' and reduced the statistics
+    if isinstance(da, _FusedGrad):
+        coef, dgamma, dbeta = _fused_coefficients(da, s, bn, outs)
+        if adjoint_dy is not None:
             # the adjoint kernel forms dy = c0*dz + c1*y + c2 while it stages its operand and hands it back
             # for the weight gradient: no separate elementwise pass
-            d_lhs, dy = dgrad_fn(None, dz=da.dz, y=y, coef=coef)
-            dgrad_done = True
-        elif isinstance(lhs, ops.SplitImage):
+            d_lhs, dy = adjoint_dy(None, dz=da.dz, y=y, coef=coef)
+            return dy, dgamma, dbeta, None, d_lhs
+        if lhs_split:
             # fp16x3 mode: dz (fp32) came out of the split-operand dgrad's epilogue; dy only feeds the two products below
             dy = ops.bn_bwd_dy_split(da.dz, y, coef)
         else:
             dy = ops.bn_bwd_dy(da.dz, y, coef, out=da.dz)
+        return dy, dgamma, dbeta, None, None
+    # ---- plain: pass 1: statistics only (reads da/dpool and y, writes nothing); pass 2: dy directly, with
+    # dz = da*ELU'(z) recomputed in registers -- dz is never materialised
+    tail = _bwd_tail(s, bn, outs, s.cout)
+    if dpool is not None and s.pool_e is not None:
+        # mean-pooled layer: the statistics follow from the forward's per-group sums, y is not re-read
+        ops.bn_pool_bwd_stats(dpool, s.pool_e, pool_scale, tail=tail)
     else:
-        # pass 1: statistics only (reads da/dpool and y, writes nothing); pass 2: dy directly, with
-        # dz = da*ELU'(z) recomputed in registers -- dz is never materialised
-        if da is not None and da.dtype != y.dtype:
-            da = da.to(y.dtype)
-        pool_e = getattr(s, "pool_e", None)
-        tail = ops.BnTailBwd(s.rows, bn, s.mean, s.rstd, cout, dgamma=outs[1] if outs else None,
-                             dbeta=outs[2] if outs else None, sync=_sync_fn())
-        if dpool is not None and pool_e is not None:
-            # mean-pooled layer: the statistics follow from the forward's per-group sums, y is not re-read
-            ops.bn_pool_bwd_stats(dpool, pool_e, pool_scale, tail=tail)
-        else:
-            ops.bn_act_bwd_stats(y, s.scale, s.shift, s.mean, s.rstd, da=da, dpool=dpool,
-                                 group_rows=group_rows, pool_scale=pool_scale, tail=tail)
-        coef, dgamma, dbeta = tail.out
-        if isinstance(lhs, ops.SplitImage):
-            # fp16x3 mode: dy only feeds the two products below -> written as its [hi | lo] image
-            dy = ops.bn_bwd_dy_fused_split(y, s.scale, s.shift, coef, da=da, dpool=dpool, group_rows=group_rows,
-                                           pool_scale=pool_scale)
-        else:
-            dy = ops.bn_bwd_dy_fused(y, s.scale, s.shift, coef, da=da, dpool=dpool, group_rows=group_rows,
-                                     pool_scale=pool_scale, out=da)
+        ops.bn_act_bwd_stats(y, s.scale, s.shift, s.mean, s.rstd, tail=tail, **grad)
+    coef, dgamma, dbeta = tail.out
+    if lhs_split:
+        # fp16x3 mode: dy only feeds the two products below -> written as its [hi | lo] image
+        dy = ops.bn_bwd_dy_fused_split(y, s.scale, s.shift, coef, **grad)
+    else:
+        dy = ops.bn_bwd_dy_fused(y, s.scale, s.shift, coef, out=da, **grad)
+    return dy, dgamma, dbeta, None, None
+
+
+def _wgrad_route(mode, dy_dtype, lhs_dtype, cout, K, has_col, addrs, deferring, has_out):
+    """Which launch forms dW[cout, K] = dy^T . lhs.  Pure: launches and allocates nothing.  ``dy_dtype``: ops.SplitImage.dtype
+    for a split image; ``has_col``: lhs is an im2col matrix; ``addrs``: base addresses of dy, lhs and, when given, the dW
+    destination; ``deferring``: the caller collects products for a grouped launch; ``has_out``: a dW destination was given."""
+    if dy_dtype == ops.SplitImage.dtype:
+        return "split_slabs"
+    if lhs_dtype == torch.float32 and K <= 8 and not has_col and ops.pointnet_in_ok(K, cout):
+        return "pointnet_in"
+    if (mode == "bf16" and dy_dtype == torch.bfloat16 and lhs_dtype == torch.bfloat16
+            and cout >= 256 and K >= 128 and cout % 8 == 0 and K % 8 == 0):
+        return "bf16"
+    # the grouped launch stages 16-B quads of both operands: cout % 4, K % 4 and 16-B aligned bases (ADVICE round 4:
+    # channel counts outside the product's own, e.g. DilTempConv1d(6, 10), keep the per-layer product)
+    if (deferring and cout % 4 == 0 and K % 4 == 0 and all(a % 16 == 0 for a in addrs)
+            and dy_dtype == torch.float32 and lhs_dtype == torch.float32):
+        return "grouped"
+    return "fp32_aside" if has_out else "fp32_inline"
+
+
+def _wgrad_split_k(route, cout, K, rows):
+    """split-K factor of a weight-gradient route (pure); a split image contracts over 3 * rows: hi.hi + lo.hi + hi.lo"""
+    if route in ("split_slabs", "bf16"):
+        return ops.pick_split_k(cout, K, 3 * rows if route == "split_slabs" else rows, target_blocks=256, bk=64, tile=256)
+    return ops.pick_split_k(cout, K, rows)
+
+
+def _layer_wgrad(dy, lhs, s, mode, dW_out, defer_wgrad):
+    """Second stage: dW[cout, K] = dy^T . lhs (contraction over the rows: both operands row-contiguous).  ``defer_wgrad``: list
+    that takes (dy, lhs, dW, split_k) of a product the caller launches together with its siblings (dtc_backward: grouped)."""
+    rows, cout = s.y.shape
     K = lhs.shape[1]
-    dW_out = outs[0].view(cout, K) if outs else None
-    # dW[cout, K] = dy^T . lhs   (contraction over the rows: both operands row-contiguous)
-    wgrad_bf16 = (mode == "bf16" and dy.dtype == torch.bfloat16 and lhs.dtype == torch.bfloat16
-                  and cout >= 256 and K >= 128 and cout % 8 == 0 and K % 8 == 0)
-    if isinstance(dy, ops.SplitImage):
-        sk = ops.pick_split_k(cout, K, 3 * rows_local, target_blocks=256, bk=64, tile=256)
-        dW = ops.gemm_slabs_split3(dy, lhs, cout, K, rows_local, sk, out=dW_out)
-    elif lhs.dtype == torch.float32 and K <= 8 and s.col is None and ops.pointnet_in_ok(K, cout):
-        dW = ops.pointnet_in_wgrad(dy, lhs, out=dW_out, out_is_zero=True)
-    elif wgrad_bf16:
-        sk = ops.pick_split_k(cout, K, rows_local, target_blocks=256, bk=64, tile=256)
-        with _on_wgrad_stream(dy, lhs) if (_BIG_WGRAD_ASIDE and dW_out is not None) else contextlib.nullcontext():
-            if sk > 1:
-                # the slab sum only feeds the optimizer: off the main stream (joined before the encoder's Adam)
-                dW = ops.gemm_slabs(dy, RC, lhs, RC, cout, K, rows_local, sk, out=dW_out, math=PCAA_BF16,
-                                    reduce_ctx=_on_wgrad_stream if (_REDUCE_ASIDE and dW_out is not None) else None)
-            else:
-                dW = ops.gemm(dy, RC, lhs, RC, cout, K, rows_local, out=dW_out, math=PCAA_BF16)
+    addrs = () if defer_wgrad is None else tuple(t.data_ptr() for t in (dy, lhs, dW_out) if isinstance(t, torch.Tensor))
+    route = _wgrad_route(mode, dy.dtype, lhs.dtype, cout, K, s.col is not None, addrs, defer_wgrad is not None,
+                         dW_out is not None)
+    if route == "pointnet_in":
+        return ops.pointnet_in_wgrad(dy, lhs, out=dW_out, out_is_zero=True)
+    sk = _wgrad_split_k(route, cout, K, rows)
+    if route == "split_slabs":
+        return ops.gemm_slabs_split3(dy, lhs, cout, K, rows, sk, out=dW_out)
+    if route == "bf16":
+        if sk > 1:
+            # the slab sum only feeds the optimizer: off the main stream (joined before the encoder's Adam)
+            return ops.gemm_slabs(dy, RC, lhs, RC, cout, K, rows, sk, out=dW_out, math=PCAA_BF16,
+                                  reduce_ctx=_on_wgrad_stream if (_REDUCE_ASIDE and dW_out is not None) else None)
+        return ops.gemm(dy, RC, lhs, RC, cout, K, rows, out=dW_out, math=PCAA_BF16)
+    if route == "grouped":
+        dW = dW_out if dW_out is not None else torch.zeros((cout, K), dtype=torch.float32, device=dy.device)
+        defer_wgrad.append((dy, lhs, dW, sk))
+        return dW
+    if route == "fp32_aside":
+        with _on_wgrad_stream(dy, lhs):
+            return ops.gemm(dy, RC, lhs, RC, cout, K, rows, out=dW_out, split_k=sk, accumulate=True, math=PCAA_F32)
+    return ops.gemm(dy, RC, lhs, RC, cout, K, rows, out=None, split_k=sk, accumulate=sk > 1, math=PCAA_F32)
+
+
+# The dgrad by the image dy arrives in: (cache of the W^T image the forward made, its maker; dtype of the y below that the fused
+# op -- ELU' and the BatchNorm-backward statistics of the layer below in the epilogue -- takes, its predicate, that op; the plain op)
+_DGRAD_IMAGE = {
+    "split": (_WSPLIT_T_CACHE, lambda W2d: ops.split_f16(W2d, transpose=True), torch.float32,
+              ops.gemm_dgrad_bn_split3_supported, ops.gemm_dgrad_bn_split3,
+              lambda dy, wt, rows, K, cout: ops.gemm_split3(dy, wt, KC, rows, K, cout)),
+    "bf16": (_W16_CACHE, lambda W2d: ops.cast_bf16(W2d, False, True)[1], torch.bfloat16,
+             ops.gemm_dgrad_bn_supported, ops.gemm_dgrad_bn,
+             lambda dy, wt, rows, K, cout: ops.gemm(dy, KC, wt, KC, rows, K, cout, out_dtype=torch.bfloat16,
+                                                    math=PCAA_BF16)),
+}
+
+
+def _dgrad_route(mode, adjoint, forms_dy=False, da_fused=False, dy_dtype=None, rows=0, cout=0, K=0, below_y=None, below_has_mean=False):
+    """Which launch forms d_lhs[rows, K] = dy . W.  Pure: launches and allocates nothing.  ``adjoint``: the caller has an
+    adjoint of its own -- the route is then known before dy is: with ``forms_dy`` it forms dy itself from a _FusedGrad
+    (``da_fused``).  Without one it follows from dy: ``below_y`` is the (shape, dtype) of the stored y of the layer that
+    produced lhs, or None; ``below_has_mean``: that layer's save is a train-mode one."""
+    if adjoint:
+        return "adjoint_dy" if (forms_dy and da_fused) else "adjoint"
+    if dy_dtype == ops.SplitImage.dtype:
+        image = "split"
+    elif mode == "bf16" and dy_dtype == torch.bfloat16 and cout % 8 == 0:
+        image = "bf16"
     else:
-        # (wgrad_math = PCAA_BF16: the temporal block's weight gradients in the bf16 throughput mode -- the fp32 operands
-        # are rounded to bf16 on their way into the fragments of the 256x256-tile kernel; fp32 accumulate)
-        big = wgrad_math == PCAA_BF16 and cout >= 128 and K >= 128 and cout % 8 == 0
-        sk = ops.pick_split_k(cout, K, rows_local, target_blocks=256, bk=64, tile=256) if big else ops.pick_split_k(cout, K, rows_local)
-        wm = PCAA_BF16 if big else PCAA_F32
-        # the grouped launch stages 16-B quads of both operands: cout % 4, K % 4 and 16-B aligned bases (ADVICE round 4:
-        # channel counts outside the product's own, e.g. DilTempConv1d(6, 10), keep the per-layer product below)
-        groupable = (cout % 4 == 0 and K % 4 == 0 and dy.data_ptr() % 16 == 0 and lhs.data_ptr() % 16 == 0
-                     and (dW_out is None or dW_out.data_ptr() % 16 == 0))
-        if (defer_wgrad is not None and not big and groupable and dy.dtype == torch.float32
-                and lhs.dtype == torch.float32):
-            # the caller launches this product together with its siblings (dtc_backward: one grouped launch)
-            dW = dW_out if dW_out is not None else torch.zeros((cout, K), dtype=torch.float32, device=dy.device)
-            defer_wgrad.append((dy, lhs, dW, sk))
-        elif dW_out is not None:
-            with _on_wgrad_stream(dy, lhs):
-                dW = ops.gemm(dy, RC, lhs, RC, cout, K, rows_local, out=dW_out, split_k=sk, accumulate=True, math=wm)
-        else:
-            dW = ops.gemm(dy, RC, lhs, RC, cout, K, rows_local, out=dW_out, split_k=sk, accumulate=sk > 1, math=wm)
-    if dgrad_done:
-        pass
-    elif need_dinput and dgrad_fn is not None:
-        d_lhs = dgrad_fn(dy)              # the caller's own adjoint (temporal block: implicit col2im)
-        if isinstance(d_lhs, tuple):
-            d_lhs = d_lhs[0]
-    elif need_dinput and isinstance(dy, ops.SplitImage):
-        wt_img = _WSPLIT_T_CACHE.pop(W2d.data_ptr(), None)            # [K, 2 cout] image of W^T made by the forward
-        if wt_img is None or tuple(wt_img.shape) != (K, cout):
-            wt_img = ops.split_f16(W2d, transpose=True)
-        if (_FUSE_DGRAD_BN and below is not None and below.y is not None and below.y.dtype == torch.float32
-                and below.mean is not None and tuple(below.y.shape) == (rows_local, K)
-                and ops.gemm_dgrad_bn_split3_supported(rows_local, K, cout)):
-            # as in the bf16 mode: ELU' and the BatchNorm-backward statistics of the layer below in the dgrad's epilogue
-            # (round 3; before, this mode re-read da and y in a statistics pass of its own: 0.6 ms per step)
-            btail = None
-            if below_bn is not None:
-                btail = ops.BnTailBwd(below.rows, below_bn, below.mean, below.rstd, K,
-                                      dgamma=below_outs[1] if below_outs else None,
-                                      dbeta=below_outs[2] if below_outs else None, sync=_sync_fn())
-            d_lhs = _FusedGrad(*ops.gemm_dgrad_bn_split3(dy, wt_img, below.y, below.scale, below.shift, below.mean,
-                                                         below.rstd, tail=btail), fin=btail.out if btail else None)
-        else:
-            d_lhs = ops.gemm_split3(dy, wt_img, KC, rows_local, K, cout)
-    elif need_dinput:
-        if mode == "bf16" and dy.dtype == torch.bfloat16 and cout % 8 == 0:
-            Wt = _W16_CACHE.pop(W2d.data_ptr(), None)      # bf16 [K, cout] made by the forward pass
-            if Wt is None or tuple(Wt.shape) != (K, cout):
-                _, Wt = ops.cast_bf16(W2d, False, True)
-            if (_FUSE_DGRAD_BN and below is not None and below.y is not None and below.y.dtype == torch.bfloat16
-                    and below.mean is not None and tuple(below.y.shape) == (rows_local, K)
-                    and ops.gemm_dgrad_bn_supported(rows_local, K, cout)):
-                # dgrad fused with ELU' and the BatchNorm-backward statistics of the layer below (and, when the caller
-                # handed that layer's BatchNorm over, their finalize)
-                btail = None
-                if below_bn is not None:
-                    btail = ops.BnTailBwd(below.rows, below_bn, below.mean, below.rstd, K,
-                                          dgamma=below_outs[1] if below_outs else None,
-                                          dbeta=below_outs[2] if below_outs else None, sync=_sync_fn())
-                d_lhs = _FusedGrad(*ops.gemm_dgrad_bn(dy, Wt, below.y, below.scale, below.shift, below.mean,
-                                                      below.rstd, tail=btail), fin=btail.out if btail else None)
-            else:
-                d_lhs = ops.gemm(dy, KC, Wt, KC, rows_local, K, cout, out_dtype=torch.bfloat16, math=PCAA_BF16)
-        else:
-            d_lhs = ops.gemm(dy, KC, W2d, RC, rows_local, K, cout,
-                             out_dtype=torch.float32)
+        return "fp32"
+    y_dtype, supported = _DGRAD_IMAGE[image][2:4]
+    if (below_y is not None and below_has_mean and below_y[1] == y_dtype and tuple(below_y[0]) == (rows, K)
+            and supported(rows, K, cout)):
+        return image + "_bn"
+    return image
+
+
+def _layer_dgrad(dy, W2d, s, mode, below, adjoint):
+    """Third stage: d_lhs = dy . W, through ``adjoint`` (the caller's own; temporal block: implicit col2im) if given"""
+    if adjoint is not None:
+        d_lhs = adjoint(dy)
+        return d_lhs[0] if isinstance(d_lhs, tuple) else d_lhs
+    rows, cout = s.y.shape
+    K = W2d.shape[1]
+    bs, below_bn, below_outs = below if below is not None else (None, None, None)
+    below_y = (bs.y.shape, bs.y.dtype) if bs is not None and bs.y is not None else None
+    route = _dgrad_route(mode, False, dy_dtype=dy.dtype, rows=rows, cout=cout, K=K, below_y=below_y,
+                         below_has_mean=bs is not None and bs.mean is not None)
+    if route == "fp32":
+        return ops.gemm(dy, KC, W2d, RC, rows, K, cout, out_dtype=torch.float32)
+    image, _, with_bn = route.partition("_")
+    cache, make, _, _, fused_op, plain_op = _DGRAD_IMAGE[image]
+    wt = cache.pop(W2d.data_ptr(), None)             # the image of W^T [K, cout] made by the forward pass
+    if wt is None or tuple(wt.shape) != (K, cout):
+        wt = make(W2d)
+    if not with_bn:
+        return plain_op(dy, wt, rows, K, cout)
+    btail = _bwd_tail(bs, below_bn, below_outs, K)
+    return _FusedGrad(*fused_op(dy, wt, bs.y, bs.scale, bs.shift, bs.mean, bs.rstd, tail=btail), fin=btail.out)
+
+
+def _bn_layer_backward(s, bn, W2d, mode, lhs, da=None, pool=None, need_dinput=True, outs=None, below=None,
+                       dgrad_fn=None, defer_wgrad=None, lin_bias=None, dbias_out=None):
+    """Backward of one (linear, BN, ELU) layer.  ``lhs`` is the GEMM's left operand ([rows, K]: the input activation or
+    the im2col matrix).  ``outs`` = (dW, dgamma, dbeta) destination views (dW PRE-ZEROED: the trainer's flat gradient
+    buffer) or None to allocate.  ``da`` may be a _FusedGrad (the dgrad of the layer above already applied ELU' and reduced
+    the statistics); ``pool`` = (dpool, group_rows, pool_scale) instead of ``da`` when the layer's output was mean-pooled.
+    ``below`` = (save, bn, outs) of the layer that produced ``lhs`` -- if it qualifies, this layer's dgrad is fused with
+    the first half of ITS backward and a _FusedGrad is returned as d_lhs.
+    With an eval-mode save (``s.mean is None``) the linear bias ``lin_bias`` in front of the BatchNorm has a gradient, dbias =
+    scale*dbeta (written to ``dbias_out`` when given); in train mode dbias is None (analytically zero: the batch mean removes it).
+    Returns (dW2d, dgamma, dbeta, dbias, d_lhs or None)."""
+    # the caller's adjoint, where it forms dy itself, replaces the tail of the first stage; any other route follows from dy
+    forms_dy = need_dinput and dgrad_fn is not None and _dgrad_route(
+        mode, True, getattr(dgrad_fn, "forms_dy", False), s.mean is not None and isinstance(da, _FusedGrad)) == "adjoint_dy"
+    dy, dgamma, dbeta, dbias, d_lhs = _bn_dy(s, bn, da, pool, isinstance(lhs, ops.SplitImage), outs, lin_bias,
+                                             dbias_out, adjoint_dy=dgrad_fn if forms_dy else None)
+    dW = _layer_wgrad(dy, lhs, s, mode, outs[0].view(s.y.shape[1], lhs.shape[1]) if outs else None, defer_wgrad)
+    if need_dinput and d_lhs is None:
+        d_lhs = _layer_dgrad(dy, W2d, s, mode, below, dgrad_fn)
     return dW, dgamma, dbeta, dbias, d_lhs
 
 
-def _layer_outs(gout, prefix, wname, gname, bname):
+_PN_NAMES = ("module.0.weight", "module.0.bias", "module.1.weight", "module.1.bias")
+_DTC_NAMES = ("conv1d.weight", "conv1d.bias", "batch_norm.weight", "batch_norm.bias")
+
+
+def _layer_outs(gout, prefix, names):
+    """-> ((dW, dgamma, dbeta) destinations, linear-bias destination) of the layer whose parameters are ``names``"""
     if gout is None:
-        return None
-    return gout[prefix + wname], gout[prefix + gname], gout[prefix + bname]
+        return None, None
+    return (gout[prefix + names[0]], gout[prefix + names[2]], gout[prefix + names[3]]), gout[prefix + names[1]]
+
+
+def _layer_grads(names, conv, dW, dgamma, dbeta, dbias, bias_out):
+    """one layer's {parameter-name suffix: gradient}.  The linear bias: in train mode its gradient is analytically zero
+    (BatchNorm removes the mean) -- the pre-zeroed destination, or zeros; in eval mode ``dbias`` = scale * dbeta"""
+    zb = dbias if dbias is not None else (bias_out if bias_out is not None else torch.zeros_like(conv.bias))
+    return {names[0]: dW.view_as(conv.weight), names[1]: zb, names[2]: dgamma, names[3]: dbeta}
 
 
 def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0, need_dx=False, gout=None,
@@ -575,71 +621,51 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
         conv, bn = layer.module[0], layer.module[1]
         W2d = conv.weight.view(s.cout, s.cin)
         need_in = li > 0 or need_dx
-        outs = _layer_outs(gout, f"{prefix}{li + 1}.", "module.0.weight", "module.1.weight", "module.1.bias")
-        # the layer below: its BatchNorm and gradient destinations, for the finalize the fused dgrad can carry
-        below_bn = layers[li - 1].module[1] if li > 0 else None
-        below_outs = _layer_outs(gout, f"{prefix}{li}.", "module.0.weight", "module.1.weight", "module.1.bias") if li > 0 else None
-        below_W = None
-        bias_out = gout[f"{prefix}{li + 1}.module.0.bias"] if gout is not None else None
-        dbias = None
+        outs, bias_out = _layer_outs(gout, f"{prefix}{li + 1}.", _PN_NAMES)
         if s.y is None and s.mean is not None and da is not None and not need_in:
             # recompute path of the first layer: two passes over da (one, when the dgrad above already applied
             # ELU' and reduced the statistics), nothing else is read or written
             fused = isinstance(da, _FusedGrad)
-            if fused and da.fin is not None:
-                coef, dg, db = da.fin
-            elif fused:
-                _sync_stats(da.stats, 0)
-                coef, dg, db = ops.bn_bwd_finalize(da.stats, s.rows, bn, s.mean, s.rstd, s.cout,
-                                                   dgamma=outs[1] if outs else None, dbeta=outs[2] if outs else None)
+            dW_out = outs[0].view(s.cout, s.cin) if outs else None
+            if fused:
+                coef, dg, db = _fused_coefficients(da, s, bn, outs)
             else:
-                tail = ops.BnTailBwd(s.rows, bn, s.mean, s.rstd, s.cout, dgamma=outs[1] if outs else None,
-                                     dbeta=outs[2] if outs else None, sync=_sync_fn())
+                tail = _bwd_tail(s, bn, outs, s.cout)
                 if (_ONEPASS_IN_BWD and (da.dtype == torch.bfloat16 or (mode == "fp16x3" and da.dtype == torch.float32))
                         and outs is not None and outs[0].is_contiguous()):
                     # bf16 and fp16x3 modes: statistics and G = dz^T.x from ONE read of da; the weight gradient is then a
                     # combination of G with the points' second moments (exact-fp32 mode keeps the two passes: there
                     # dy is formed per element before the contraction, as the oracle's autograd does)
                     dW = ops.pointnet_in_bwd_onepass(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail,
-                                                     mom=s.mom, out=outs[0].view(s.cout, s.cin))
+                                                     mom=s.mom, out=dW_out)
                     coef, dg, db = tail.out
-                    zb = gout[f"{prefix}{li + 1}.module.0.bias"] if gout is not None else torch.zeros_like(conv.bias)
-                    grads.append({"module.0.weight": dW.view_as(conv.weight), "module.0.bias": zb,
-                                  "module.1.weight": dg, "module.1.bias": db})
+                    grads.append(_layer_grads(_PN_NAMES, conv, dW, dg, db, None, bias_out))
                     da = None
                     continue
                 ops.pointnet_in_bwd_stats(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail=tail)
                 coef, dg, db = tail.out
             dW = ops.pointnet_in_bwd_wgrad(da.dz if fused else da, s.a_in, W2d, s.scale, s.shift, coef,
-                                           out=outs[0].view(s.cout, s.cin) if outs else None, out_is_zero=True,
-                                           dz_is_pre=fused)
-            dprev = None
-        elif li == len(layers) - 1 and dpool is not None:
-            dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, dpool=dpool, group_rows=pool_rows,
-                                                          pool_scale=1.0 / pool_rows, need_dinput=need_in, lhs=s.a_in,
-                                                          outs=outs, below=saves[li - 1] if li > 0 else None,
-                                                          below_W=below_W, below_bn=below_bn, below_outs=below_outs,
-                                                          lin_bias=conv.bias, dbias_out=bias_out)
+                                           out=dW_out, out_is_zero=True, dz_is_pre=fused)
+            dbias = dprev = None
         else:
-            if s.y is None:
+            pooled = li == len(layers) - 1 and dpool is not None
+            if s.y is None and not pooled:
                 # recompute layer, but the caller wants the gradient w.r.t. the points, or the save is an eval-mode one
                 # (which takes the general route): rebuild y from the points
                 s.y = ops.pointnet_in_fwd(s.a_in, W2d, None, da.dtype)
-            dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, da=da, need_dinput=need_in, lhs=s.a_in,
-                                                          outs=outs, below=saves[li - 1] if li > 0 else None,
-                                                          below_W=below_W, below_bn=below_bn, below_outs=below_outs,
+            below = (saves[li - 1], layers[li - 1].module[1],
+                     _layer_outs(gout, f"{prefix}{li}.", _PN_NAMES)[0]) if li > 0 else None
+            dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, s.a_in, da=None if pooled else da,
+                                                          pool=(dpool, pool_rows, 1.0 / pool_rows) if pooled else None,
+                                                          need_dinput=need_in, outs=outs, below=below,
                                                           lin_bias=conv.bias, dbias_out=bias_out)
-        # train mode: the conv bias gradient is analytically zero (BatchNorm removes the mean); eval mode: scale * dbeta
-        zb = dbias if dbias is not None else (bias_out if gout is not None else torch.zeros_like(conv.bias))
-        grads.append({"module.0.weight": dW.view_as(conv.weight), "module.0.bias": zb,
-                      "module.1.weight": dg, "module.1.bias": db})
+        grads.append(_layer_grads(_PN_NAMES, conv, dW, dg, db, dbias, bias_out))
         da = dprev
     grads.reverse()
     return grads, da
 
 
 _FUSE_DTC = True
-_FUSE_DTC_BWD = True
 
 
 # The temporal block's products in the bf16 throughput mode (PCAA_DTC_BF16): "wide" (default) = the bf16 matrix pipe where
@@ -726,44 +752,27 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
     return a, saves
 
 
-# measured (round 4, same box, 2 x 3 windows of 20 steps): N=128 5.64 / 5.56 on, 5.57 / 5.58 off; N=32 2.16 / 2.16 on, 2.13 / 2.09 off -- the
-# 256x256-tile kernel with an atomic epilogue is no better than the exact-fp32 128x128 one on these small products: off
-_DTC_WGRAD_BF16 = os.environ.get("PCAA_DTC_WGRAD_BF16", "0") != "0"
-
-
-# the temporal block's weight gradients: "wg" = one grouped launch on the weight-gradient stream, "main" = on the calling
-# stream, "0" = one launch per layer (rounds 1-3)
-_DTC_WGRAD_GROUP = os.environ.get("PCAA_DTC_WGRAD_GROUP", "wg")
-
-
 def dtc_backward(saves, layers, B, T, d_last=None, dpool=None, need_dx=True, gout=None, prefix="tc_block.dtc", mode="fp32"):
     grads = []
-    wmath = PCAA_BF16 if (mode == "bf16" and _DTC_WGRAD_BF16) else PCAA_F32
-    defer = [] if _DTC_WGRAD_GROUP != "0" else None
+    defer = []
     da = d_last
     for li in range(len(layers) - 1, -1, -1):
         layer, s = layers[li], saves[li]
         conv, bn = layer.conv1d, layer.batch_norm
         W2d = conv.weight.view(s.cout, s.cin * 3)
         need_in = li > 0 or need_dx
-        outs = _layer_outs(gout, f"{prefix}{li + 1}.", "conv1d.weight", "batch_norm.weight", "batch_norm.bias")
-        fused = _FUSE_DTC and _FUSE_DTC_BWD and T <= 32 and s.cin % 4 == 0 and s.cout % 4 == 0
+        outs, bias_out = _layer_outs(gout, f"{prefix}{li + 1}.", _DTC_NAMES)
+        fused = _FUSE_DTC and T <= 32 and s.cin % 4 == 0 and s.cout % 4 == 0
         # the adjoint w.r.t. the layer input in one launch (implicit col2im), with the first half of the
         # BatchNorm+ELU backward of the layer below in its epilogue (dz and the two column sums: that layer then
         # starts at bn_bwd_finalize); else dcol = dy . W, then col2im
         dgrad_fn = None
         if fused:
             sb = saves[li - 1] if (li > 0 and s.cout <= 512 and saves[li - 1].mean is not None) else None
-            sb_bn = layers[li - 1].batch_norm if sb is not None else None
-            sb_outs = _layer_outs(gout, f"{prefix}{li}.", "conv1d.weight", "batch_norm.weight", "batch_norm.bias") \
-                if sb is not None else None
+            btail = _bwd_tail(sb, layers[li - 1].batch_norm, _layer_outs(gout, f"{prefix}{li}.", _DTC_NAMES)[0],
+                              s.cin) if sb is not None else None
 
-            def dgrad_fn(dy, dz=None, y=None, coef=None, W2d=W2d, s=s, sb=sb, sb_bn=sb_bn, sb_outs=sb_outs):
-                btail = None
-                if sb is not None:
-                    btail = ops.BnTailBwd(sb.rows, sb_bn, sb.mean, sb.rstd, s.cin,
-                                          dgamma=sb_outs[1] if sb_outs else None, dbeta=sb_outs[2] if sb_outs else None,
-                                          sync=_sync_fn())
+            def dgrad_fn(dy, dz=None, y=None, coef=None, W2d=W2d, s=s, sb=sb, btail=btail):
                 out, stats, dy_used = ops.dtc_conv_dgrad(
                     dy, W2d, B, T, s.cin, s.dil, dz=dz, y=y, coef=coef, want_dy=dy is None,
                     below=(sb.y, sb.scale, sb.shift, sb.mean, sb.rstd) if sb else None, tail=btail,
@@ -771,20 +780,12 @@ def dtc_backward(saves, layers, B, T, d_last=None, dpool=None, need_dx=True, gou
                 return (_FusedGrad(out, stats, fin=btail.out) if sb else out), dy_used
 
             dgrad_fn.forms_dy = s.cout <= 512
-        bias_out = gout[f"{prefix}{li + 1}.conv1d.bias"] if gout is not None else None
-        if li == len(layers) - 1 and dpool is not None:
-            dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", dpool=dpool, group_rows=T,
-                                                         pool_scale=1.0 / T, need_dinput=need_in, lhs=s.col, outs=outs,
-                                                         dgrad_fn=dgrad_fn, wgrad_math=wmath, defer_wgrad=defer,
-                                                         lin_bias=conv.bias, dbias_out=bias_out)
-        else:
-            dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", da=da, need_dinput=need_in, lhs=s.col,
-                                                         outs=outs, dgrad_fn=dgrad_fn, wgrad_math=wmath,
-                                                         defer_wgrad=defer, lin_bias=conv.bias, dbias_out=bias_out)
-        # (train mode: analytically zero; eval mode: scale * dbeta)
-        zb = dbias if dbias is not None else (bias_out if gout is not None else torch.zeros_like(conv.bias))
-        grads.append({"conv1d.weight": dW.view_as(conv.weight), "conv1d.bias": zb,
-                      "batch_norm.weight": dg, "batch_norm.bias": db})
+        pooled = li == len(layers) - 1 and dpool is not None
+        dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", s.col, da=None if pooled else da,
+                                                     pool=(dpool, T, 1.0 / T) if pooled else None, need_dinput=need_in,
+                                                     outs=outs, dgrad_fn=dgrad_fn, defer_wgrad=defer, lin_bias=conv.bias,
+                                                     dbias_out=bias_out)
+        grads.append(_layer_grads(_DTC_NAMES, conv, dW, dg, db, dbias, bias_out))
         if not need_in:
             da = None
         elif fused:
@@ -794,13 +795,11 @@ def dtc_backward(saves, layers, B, T, d_last=None, dpool=None, need_dx=True, gou
     if defer:
         # the block's weight gradients dW_l = dy_l^T . col_l, all in one launch behind the dgrad chain (round 4: they were
         # six launches of 26-47 us in a chain beside it; measured without them the N = 32 step was 0.17 ms shorter)
+        # (exact fp32: bf16 operands on the 256x256-tile kernel measured no better in round 4 -- N=32 2.16 against 2.11 ms)
         tensors = [t for d in defer for t in d[:3]]
         for k in range(0, len(defer), 8):
-            if _DTC_WGRAD_GROUP == "main":
+            with _on_wgrad_stream(*tensors):
                 ops.gemm_group_rc_f32(defer[k:k + 8])
-            else:
-                with _on_wgrad_stream(*tensors):
-                    ops.gemm_group_rc_f32(defer[k:k + 8])
     grads.reverse()
     return grads, da
 
@@ -1569,8 +1568,7 @@ class _GmlFn(torch.autograd.Function):
         out = []
         for (lin_i, bn_i), s in reversed(list(zip(((0, 1), (3, 4), (6, 7)), ctx.saves))):
             lin, bn = m[lin_i], m[bn_i]
-            dW, dg, db, dbias, da = _bn_layer_backward(s, bn, lin.weight, "fp32", da=da, need_dinput=True, lhs=s.a_in,
-                                                       lin_bias=lin.bias)
+            dW, dg, db, dbias, da = _bn_layer_backward(s, bn, lin.weight, "fp32", s.a_in, da=da, lin_bias=lin.bias)
             out = [dW, dbias if dbias is not None else torch.zeros_like(lin.bias), dg, db] + out
         return (None, da) + tuple(out) + (dW9, db9)
 
