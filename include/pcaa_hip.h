@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 23 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 24 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -526,6 +526,22 @@ int pcaa_skinny_linear_dgrad_w16(const float* dz, long lddz, const void* W16, lo
  * pcaa_dtc_conv_supported: T <= 32, cin % 4 == 0, cout % 16 == 0. */
 int pcaa_dtc_conv_supported(int T, int cin, int cout);
 int pcaa_dtc_conv_ksplit(int B, int cin, int cout);   /* the ksplit to pass: >= cin/256, 8 for few long tiles */
+/* ABI 24: the kernel a temporal-conv call takes, from its shape alone (a host function: no HIP call, works without a GPU).
+ * adjoint: 0 = pcaa_dtc_conv_fwd*, 1 = pcaa_dtc_conv_dgrad*; bf16: the _bf16 entry point; windowed: the _win / _seg forms.
+ * The entry points dispatch on this value.  One workgroup = one sequence (32 output columns fp32, 128 bf16), or two
+ * sequences x 32 or 64 columns (contraction >= 128 channels in whole 32-chunks, >= 64 output channels, ksplit == 1, not
+ * windowed; 64 columns when (B + 1) / 2 * (columns / 64) >= 192 workgroups remain).  PCAA_DTC_PAIR (0, fwd, adj) switches
+ * the two-sequence kernels off per direction.  The limit of 256 (forward) / 512 (adjoint) contraction channels per
+ * workgroup is the one-sequence kernels': a call this function sends to a two-sequence kernel stages its channels in
+ * passes of 256 and is accepted with ksplit == 1 at any width (through ABI 23 the entry points refused those calls before
+ * they looked at the route, so the forward's further passes could not be reached). */
+#define PCAA_DTC_ROUTE_ONE_F32 0
+#define PCAA_DTC_ROUTE_ONE_BF16 1
+#define PCAA_DTC_ROUTE_PAIR32_F32 2
+#define PCAA_DTC_ROUTE_PAIR32_BF16 3
+#define PCAA_DTC_ROUTE_PAIR64_F32 4
+#define PCAA_DTC_ROUTE_PAIR64_BF16 5
+int pcaa_dtc_conv_route(int adjoint, int bf16, int B, int cin, int cout, int ksplit, int windowed);
 int pcaa_dtc_conv_fwd(const float* src, const float* scale, const float* shift, const float* W, float* y,
                       float* col, double* stats, int nrep, int B, int T, int cin, int cout, int dilation,
                       int ksplit, long slab_stride, void* stream);

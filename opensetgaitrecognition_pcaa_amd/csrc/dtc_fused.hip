@@ -317,6 +317,9 @@ __global__ __launch_bounds__(256) void dtc_fwd_bf16_kernel(DtcFwdParams p) {
       }
       *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
     }
+    // cvt8 reads 8 floats from a column that is a multiple of 8: with cr % 8 == 4 a row's last fragment takes in the
+    // row's four pad floats, which meet zero weights -- and 0 x NaN is NaN on the matrix pipe: the pad is zeros
+    for (int r = tid; r < T; r += 256) *reinterpret_cast<f32x4*>(&a_lds[r * AP + cr]) = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;
   }
   // weight chunk: 128 columns x 96 contiguous floats W[n0 + c][(cz0 + c0) * 3 ...], 12 float4 per thread
@@ -588,6 +591,7 @@ __global__ __launch_bounds__(256) void dtc_dgrad_bf16_kernel(DtcDgradParams p, i
       *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
       if (keep) store4(p.dy_out + g, v);
     }
+    for (int r = tid; r < T; r += 256) *reinterpret_cast<f32x4*>(&a_lds[r * AP + cr]) = f32x4{0.f, 0.f, 0.f, 0.f};   // the pad cvt8 reads
     for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;
   }
   // weight chunk: 32 contraction channels co x (128 input channels x 3 taps = 384 contiguous floats)
@@ -1032,15 +1036,33 @@ static int launch_pair(const DtcPairParams& p, hipStream_t s) {
   return 0;
 }
 
+// 64-column workgroups when they still fill the chip (the 256 -> 512 layer's forward: 32 pairs x 8), else 32
+static inline bool pair_wide(int B, int nc) { return (long)((B + 1) / 2) * (nc / 64) >= 192 && nc % 64 == 0; }
+
+// the kernel a call takes (PCAA_DTC_ROUTE_*): the one decision both entry points launch by and pcaa_dtc_conv_route reports.
+// A windowed source always takes the one-sequence kernels (the block's first layer, 1024 -> 16, is theirs anyway)
+static inline int dtc_route(bool adj, bool bf16, int B, int cin, int cout, int ksplit, bool windowed) {
+  const int kc = adj ? cout : cin, nc = adj ? cin : cout;
+  int family = 0;
+  if (!windowed && pair_takes(kc, nc, ksplit, adj)) family = pair_wide(B, nc) ? 2 : 1;
+  return family * 2 + (bf16 ? 1 : 0);
+}
+
 template <bool ADJ>
-static int launch_pair_any(const DtcPairParams& p, bool bf16, hipStream_t s) {
-  // 64-column workgroups when they still fill the chip (the 256 -> 512 layer's forward: 32 pairs x 8), else 32
-  const bool wide = (long)((p.B + 1) / 2) * (p.nc / 64) >= 192 && p.nc % 64 == 0;
-  if (wide) return bf16 ? launch_pair<ADJ, true, 64>(p, s) : launch_pair<ADJ, false, 64>(p, s);
-  return bf16 ? launch_pair<ADJ, true, 32>(p, s) : launch_pair<ADJ, false, 32>(p, s);
+static int launch_pair_route(const DtcPairParams& p, int route, hipStream_t s) {
+  switch (route) {
+    case PCAA_DTC_ROUTE_PAIR64_BF16: return launch_pair<ADJ, true, 64>(p, s);
+    case PCAA_DTC_ROUTE_PAIR64_F32: return launch_pair<ADJ, false, 64>(p, s);
+    case PCAA_DTC_ROUTE_PAIR32_BF16: return launch_pair<ADJ, true, 32>(p, s);
+    default: return launch_pair<ADJ, false, 32>(p, s);
+  }
 }
 
 }  // namespace
+
+extern "C" int pcaa_dtc_conv_route(int adjoint, int bf16, int B, int cin, int cout, int ksplit, int windowed) {
+  return dtc_route(adjoint != 0, bf16 != 0, B, cin, cout, ksplit, windowed != 0);
+}
 
 extern "C" int pcaa_dtc_conv_supported(int T, int cin, int cout) {
   return (T >= 1 && T <= ROWS && cin >= 4 && cin % 4 == 0 && cout >= 16 && cout % 16 == 0) ? 1 : 0;
@@ -1068,16 +1090,17 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
                  ((uintptr_t)shift % 16) == 0)), "pcaa_dtc_conv_fwd: src, W, scale, shift must be 16-B aligned");
   const int chunks = (cin + CC - 1) / CC;
   const int per_z = (chunks + ksplit - 1) / ksplit * CC;
-  PCAA_CHECK_ARG(ksplit <= chunks && per_z <= MAX_CR, "pcaa_dtc_conv_fwd: ksplit must keep <= %d channels per workgroup "
-                 "(pcaa_dtc_conv_ksplit)", MAX_CR);
+  // (the two-sequence kernels stage their contraction channels in passes of PAIR_KC: the limit is the one-sequence kernels')
+  const int route = dtc_route(false, bf16, B, cin, cout, ksplit, win_row != nullptr);
+  PCAA_CHECK_ARG(ksplit <= chunks && (route >= PCAA_DTC_ROUTE_PAIR32_F32 || per_z <= MAX_CR),
+                 "pcaa_dtc_conv_fwd: ksplit must keep <= %d channels per workgroup (pcaa_dtc_conv_ksplit)", MAX_CR);
   PCAA_CHECK_ARG(ksplit == 1 || (stats == nullptr && slab_stride >= (long)B * T * cout),
                  "pcaa_dtc_conv_fwd: ksplit > 1 writes slabs (no statistics): slab_stride >= B*T*cout");
-  // a windowed source always takes the one-sequence kernels (the block's first layer, 1024 -> 16, is theirs anyway)
-  if (win_row == nullptr && pair_takes(cin, cout, ksplit, false)) {
+  if (route >= PCAA_DTC_ROUTE_PAIR32_F32) {
     DtcPairParams pp{src, scale, shift, nullptr, nullptr, nullptr, nullptr, W, y, col, stats, nrep,
                      nullptr, nullptr, nullptr, nullptr, nullptr, B, T, cin, cout, dilation,
                      stats != nullptr ? pcaa_take_bn_tail(stats) : BnTail{}};
-    if (launch_pair_any<false>(pp, bf16, as_stream(stream)) != 0) {
+    if (launch_pair_route<false>(pp, route, as_stream(stream)) != 0) {
       pcaa_rearm_bn_tail(pp.tail);
       pcaa_set_error("pcaa_dtc_conv_fwd: cannot raise the dynamic LDS limit");
       return PCAA_ERR_LAUNCH;
@@ -1086,7 +1109,7 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
   }
   DtcFwdParams p{src, scale, shift, W, y, col, stats, B, T, cin, cout, dilation, nrep, ksplit > 1 ? slab_stride : 0,
                  (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}, win_row, ring_rows, seg};
-  if (bf16) hipLaunchKernelGGL(dtc_fwd_bf16_kernel, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
+  if (route == PCAA_DTC_ROUTE_ONE_BF16) hipLaunchKernelGGL(dtc_fwd_bf16_kernel, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
   else hipLaunchKernelGGL(dtc_fwd_kernel, dim3(B, (cout + 31) / 32, ksplit), dim3(256), 0, as_stream(stream), p);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
 }
@@ -1175,17 +1198,18 @@ static int dtc_conv_dgrad_impl(bool bf16, const float* dy, const float* dz, cons
                  "pcaa_dtc_conv_dgrad: 16-B alignment");
   const int chunks = (cout + CC - 1) / CC;
   const int per_z = (chunks + ksplit - 1) / ksplit * CC;
-  PCAA_CHECK_ARG(ksplit <= chunks && per_z <= DG_MAX_CR, "pcaa_dtc_conv_dgrad: ksplit must keep <= %d channels per "
-                 "workgroup (pcaa_dtc_conv_dgrad_ksplit)", DG_MAX_CR);
+  const int route = dtc_route(true, bf16, B, cin, cout, ksplit, false);
+  PCAA_CHECK_ARG(ksplit <= chunks && (route >= PCAA_DTC_ROUTE_PAIR32_F32 || per_z <= DG_MAX_CR),
+                 "pcaa_dtc_conv_dgrad: ksplit must keep <= %d channels per workgroup (pcaa_dtc_conv_dgrad_ksplit)", DG_MAX_CR);
   PCAA_CHECK_ARG(ksplit == 1 || slab_stride >= (long)B * T * cin, "pcaa_dtc_conv_dgrad: slab_stride >= B*T*cin");
   const bool ep = ep_stats != nullptr;
   PCAA_CHECK_ARG(!ep || (ksplit == 1 && ep_y && ep_scale && ep_shift && ep_mean && ep_rstd && nrep >= 1),
                  "pcaa_dtc_conv_dgrad: the epilogue needs ksplit == 1 and ep_y, ep_scale, ep_shift, ep_mean, ep_rstd");
-  if (pair_takes(cout, cin, ksplit, true)) {
+  if (route >= PCAA_DTC_ROUTE_PAIR32_F32) {
     DtcPairParams pp{dy, nullptr, nullptr, dz, y, coef, dy_out, W, out, nullptr, ep_stats, nrep,
                      ep_y, ep_scale, ep_shift, ep_mean, ep_rstd, B, T, cout, cin, dilation,
                      ep ? pcaa_take_bn_tail(ep_stats) : BnTail{}};
-    if (launch_pair_any<true>(pp, bf16, as_stream(stream)) != 0) {
+    if (launch_pair_route<true>(pp, route, as_stream(stream)) != 0) {
       pcaa_rearm_bn_tail(pp.tail);
       pcaa_set_error("pcaa_dtc_conv_dgrad: cannot raise the dynamic LDS limit");
       return PCAA_ERR_LAUNCH;
@@ -1196,7 +1220,7 @@ static int dtc_conv_dgrad_impl(bool bf16, const float* dy, const float* dz, cons
   DtcDgradParams p{dy, dz, y, coef, dy_out, W, out, ep_y, ep_scale, ep_shift, ep_mean, ep_rstd, ep_stats, nrep,
                    B, T, cin, cout, dilation, ksplit > 1 ? slab_stride : 0,
                    ep ? pcaa_take_bn_tail(ep_stats) : BnTail{}};
-  if (bf16) {
+  if (route == PCAA_DTC_ROUTE_ONE_BF16) {
     const size_t lds16 = (size_t)tile * sizeof(float) + (size_t)NCT * WPH * sizeof(bf16_t) + 16;
     static bool configured16 = false;
     if (!configured16) {
