@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 24 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 25 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -645,6 +645,35 @@ int pcaa_stream_score(const float* logits, const float* sup_fv, const float* mea
 int pcaa_frames_from_raw(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
                          const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
                          float* out, int n_out, int* pick_out, int* err_flag, void* stream);
+/* ABI 25: the same frames without their padding.  A padded frame repeats detections, and in eval mode the per-point
+ * network f is a pure function of the point, so mean over the N padded rows of f(row) = (1/N) sum_i m_i f(p_i) over the
+ * frame's DISTINCT picked detections p_i with multiplicities m_i (pcaa_segment_weighted_mean below pools that way).
+ * Arguments as pcaa_frames_from_raw up to divide_by_std.  Two launches, nothing read back:
+ *  1. u_off [n + 1] int32 = exclusive scan of u_cnt[f] = min(card_f, N), 1 for a frame whose offsets are bad (card < 1,
+ *     card > PCAA_RAW_MAX_CARD, offsets outside [0, P]): a function of offsets alone;
+ *  2. rows [M, C] fp32 and weight [M] fp32: rows u_off[f] .. of frame f are its distinct picked detections in order of
+ *     first occurrence in its pick row, each exactly the value pcaa_frames_from_raw writes for that pick (the same code:
+ *     the mean and std are those of the N padded rows), weight = the multiplicity (integer-valued).  The rows of a frame's
+ *     allotment that its picks leave unused (supplied picks only) and the rows u_off[n] .. M - 1 are zero with weight 0.
+ * A bad frame (the rule of pcaa_frames_from_raw, a supplied pick out of range included) is ONE zero row of weight N, the
+ * rest of its allotment unused, pick_out -1, *err_flag set: pooled, it gives f(0), the padded path's all-zero frame.
+ * For ascending offsets inside [0, P], u_off[n] <= min(P + n, n N); a frame whose rows would pass M (inconsistent
+ * offsets) is not written and sets *err_flag, and pcaa_segment_weighted_mean returns zeros for it.  A frame's rows and
+ * weights depend on its own detections and picks / key only.  1 <= M < 2^31, n * 1024 < 2^31. */
+int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
+                                const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
+                                float* rows, float* weight, int* u_off, long M, int* pick_out, int* err_flag,
+                                void* stream);
+/* ABI 25 (segment_pool.hip): out[f, c] = (1 / N) sum_{r = u_off[f]}^{u_off[f + 1] - 1} weight[r] * v(a[r * lda + c]) for
+ * n frames, a [M, ch] fp32 or bf16 (dtype) with leading dimension lda, out [n, ch] fp32.  v = identity; with scale / shift
+ * [ch] (both or neither) a is a pre-BatchNorm y and v = ELU(a * scale[c] + shift[c]) (fused multiply-add, expm1f).  fp32
+ * accumulation in a fixed order that is a function of the segment alone (four row lanes, each ascending, added in lane
+ * order, one division by N): the result does not depend on n or the grid.  16-byte loads: ch % 8 == 0, lda % 8 == 0,
+ * a / out / scale / shift 16-B aligned.  Segments of any length (0 rows: zeros).  A segment with u_off[f] < 0,
+ * u_off[f + 1] < u_off[f] or u_off[f + 1] > M is written as zeros and sets *err_flag (may be NULL): no fault. */
+int pcaa_segment_weighted_mean(const void* a, int dtype, long lda, const float* weight, const int* u_off, int n, long M,
+                               int ch, int N, const float* scale, const float* shift, float* out, int* err_flag,
+                               void* stream);
 /* The adjoint w.r.t. the layer input in one launch (replaces dcol = dy . W on the im2col layout followed by
  * pcaa_dtc_col2im): da[(b,t)][ci] = sum_{co,tap} dy[b][t+(2-tap)*d][co] * W[co][ci][tap].
  *  - dy given, or formed on load from this layer's dz, y and the coefficients of pcaa_bn_bwd_finalize

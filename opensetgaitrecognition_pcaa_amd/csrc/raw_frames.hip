@@ -70,18 +70,145 @@ __device__ __forceinline__ void zero_frame(float* dst, int NC, bool vec) {
   }
 }
 
+// a frame's offsets are unusable: the first half of the bad-frame rule (the second: a supplied pick outside [0, card))
+__host__ __device__ __forceinline__ bool raw_offsets_bad(long off0, long off1, long P) {
+  const long card = off1 - off0;
+  return off0 < 0 || off1 > P || card < 1 || card > PCAA_RAW_MAX_CARD;
+}
+
+// the LDS of one frame's workgroup
+struct RawShared {
+  double val[PCAA_RAW_MAX_POINTS * RAW_COLS];     // the gathered points, point-major like the output
+  int pick[PCAA_RAW_MAX_POINTS];
+  uint32_t key[PCAA_RAW_MAX_CARD];
+  double red[RAW_WAVES * RAW_COLS];
+  int bad;
+};
+
+// Steps 1 - 3 of the header comment for frame f, shared by every kernel of this file so that they produce the same
+// bits: picks -> sh.pick (and pick_out), gather -> sh.val, mean / denom in every thread's registers.  Returns false
+// for a bad frame: pick_out is -1, *err set, sh.val / mean / denom undefined; the caller writes its zeros.
+template <typename T, int C>
+__device__ __forceinline__ bool raw_frame_prepare(
+    RawShared& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
+    const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
+    int standardize, int divide_by_std, int* __restrict__ pick_out, int* __restrict__ err, int& card_out,
+    double (&mean)[C], double (&denom)[C]) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  const int NC = N * C;
+  const long off0 = offsets[f], off1 = offsets[f + 1];
+  bool bad = raw_offsets_bad(off0, off1, P);      // uniform over the workgroup
+  const int card = bad ? 1 : (int)(off1 - off0);
+  card_out = card;
+  if (tid == 0) sh.bad = 0;
+  __syncthreads();
+
+  if (!bad) {
+    if (pick != nullptr) {
+      bool mine = false;
+      for (int p = tid; p < N; p += RAW_THREADS) {
+        const int i = pick[f * N + p];
+        mine |= i < 0 || i >= card;
+        sh.pick[p] = i;
+      }
+      if (mine) sh.bad = 1;
+    } else {
+      uint32_t s = raw_absorb(raw_absorb(0x9e3779b9u, seed_lo), seed_hi);
+      s = raw_absorb(raw_absorb(s, (uint32_t)frame_key[2 * f]), (uint32_t)frame_key[2 * f + 1]);
+      if (card < N) {
+        for (int p = tid; p < N; p += RAW_THREADS)
+          sh.pick[p] = p < card ? p : (int)(((uint64_t)raw_absorb(s, (uint32_t)p) * (uint64_t)card) >> 32);
+      } else {
+        for (int i = tid; i < card; i += RAW_THREADS) sh.key[i] = raw_absorb(s, (uint32_t)i);
+        __syncthreads();
+        for (int i = tid; i < card; i += RAW_THREADS) {
+          const uint32_t k = sh.key[i];
+          int rank = 0;
+          for (int j = 0; j < card; ++j) {
+            const uint32_t kj = sh.key[j];
+            rank += (kj < k) || (kj == k && j < i);
+          }
+          if (rank < N) sh.pick[rank] = i;
+        }
+      }
+    }
+    __syncthreads();
+    bad = sh.bad != 0;
+  }
+  if (bad) {
+    if (pick_out != nullptr)
+      for (int p = tid; p < N; p += RAW_THREADS) pick_out[f * N + p] = -1;
+    if (err != nullptr && tid == 0) atomicOr(err, 1);
+    return false;
+  }
+  if (pick_out != nullptr)
+    for (int p = tid; p < N; p += RAW_THREADS) pick_out[f * N + p] = sh.pick[p];
+
+  // gather, point-major; the power column to dB
+  const T* src = points + off0 * RAW_COLS;
+  for (int e = tid; e < NC; e += RAW_THREADS) {
+    const int p = e / C, c = e - p * C;
+    double v = (double)src[(long)sh.pick[p] * RAW_COLS + c];
+    if (C == RAW_COLS && c == RAW_COLS - 1) v = 10.0 * log10(v + 1e-8);
+    sh.val[e] = v;
+  }
+  __syncthreads();
+
+#pragma unroll
+  for (int c = 0; c < C; ++c) { mean[c] = 0.0; denom[c] = 1.0; }
+  if (standardize) {
+    double acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 0.0;
+    for (int p = tid; p < N; p += RAW_THREADS) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] += sh.val[p * C + c];
+    }
+    block_sum_cols<C>(acc, sh.red);
+#pragma unroll
+    for (int c = 0; c < C; ++c) mean[c] = acc[c] / (double)N;
+    if (divide_by_std) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] = 0.0;
+      for (int p = tid; p < N; p += RAW_THREADS) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const double d = sh.val[p * C + c] - mean[c];
+          acc[c] += d * d;
+        }
+      }
+      block_sum_cols<C>(acc, sh.red);
+#pragma unroll
+      for (int c = 0; c < C; ++c) denom[c] = sqrt(acc[c] / (double)N) + 1e-8;
+    }
+  }
+  return true;
+}
+
+// step 4 for element e = p * C + c of the frame: centre, scale, round once
+template <int C>
+__device__ __forceinline__ float raw_frame_finish(const RawShared& sh, int e, const double (&mean)[C],
+                                                  const double (&denom)[C], int divide_by_std) {
+#pragma clang fp contract(off)
+  const int c = e % C;
+  double m = mean[0], d = denom[0];
+#pragma unroll
+  for (int k = 1; k < C; ++k) {                   // a select chain: mean / denom stay in registers
+    m = c == k ? mean[k] : m;
+    d = c == k ? denom[k] : d;
+  }
+  double v = sh.val[e] - m;
+  if (divide_by_std) v = v / d;
+  return (float)v;
+}
+
 template <typename T, int C>
 __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
     const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
     float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err) {
-#pragma clang fp contract(off)
-  __shared__ double s_val[PCAA_RAW_MAX_POINTS * RAW_COLS];
-  __shared__ int s_pick[PCAA_RAW_MAX_POINTS];
-  __shared__ uint32_t s_key[PCAA_RAW_MAX_CARD];
-  __shared__ double s_red[RAW_WAVES * RAW_COLS];
-  __shared__ int s_bad;
-
+  __shared__ RawShared sh;
   const int tid = threadIdx.x;
   const long f = blockIdx.x;
   const int NC = N * C;
@@ -91,117 +218,180 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     zero_frame(dst, NC, vec);
     return;
   }
-  const long off0 = offsets[f], off1 = offsets[f + 1];
-  const long card_l = off1 - off0;
-  bool bad = off0 < 0 || off1 > P || card_l < 1 || card_l > PCAA_RAW_MAX_CARD;     // uniform over the workgroup
-  const int card = bad ? 1 : (int)card_l;
-  if (tid == 0) s_bad = 0;
-  __syncthreads();
-
-  if (!bad) {
-    if (pick != nullptr) {
-      bool mine = false;
-      for (int p = tid; p < N; p += RAW_THREADS) {
-        const int i = pick[f * N + p];
-        mine |= i < 0 || i >= card;
-        s_pick[p] = i;
-      }
-      if (mine) s_bad = 1;
-    } else {
-      uint32_t s = raw_absorb(raw_absorb(0x9e3779b9u, seed_lo), seed_hi);
-      s = raw_absorb(raw_absorb(s, (uint32_t)frame_key[2 * f]), (uint32_t)frame_key[2 * f + 1]);
-      if (card < N) {
-        for (int p = tid; p < N; p += RAW_THREADS)
-          s_pick[p] = p < card ? p : (int)(((uint64_t)raw_absorb(s, (uint32_t)p) * (uint64_t)card) >> 32);
-      } else {
-        for (int i = tid; i < card; i += RAW_THREADS) s_key[i] = raw_absorb(s, (uint32_t)i);
-        __syncthreads();
-        for (int i = tid; i < card; i += RAW_THREADS) {
-          const uint32_t k = s_key[i];
-          int rank = 0;
-          for (int j = 0; j < card; ++j) {
-            const uint32_t kj = s_key[j];
-            rank += (kj < k) || (kj == k && j < i);
-          }
-          if (rank < N) s_pick[rank] = i;
-        }
-      }
-    }
-    __syncthreads();
-    bad = s_bad != 0;
-  }
-  if (bad) {
+  double mean[C], denom[C];
+  int card;
+  if (!raw_frame_prepare<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                               divide_by_std, pick_out, err, card, mean, denom)) {
     zero_frame(dst, NC, vec);
-    if (pick_out != nullptr)
-      for (int p = tid; p < N; p += RAW_THREADS) pick_out[f * N + p] = -1;
-    if (err != nullptr && tid == 0) atomicOr(err, 1);
     return;
   }
-  if (pick_out != nullptr)
-    for (int p = tid; p < N; p += RAW_THREADS) pick_out[f * N + p] = s_pick[p];
-
-  // gather, point-major; the power column to dB
-  const T* src = points + off0 * RAW_COLS;
-  for (int e = tid; e < NC; e += RAW_THREADS) {
-    const int p = e / C, c = e - p * C;
-    double v = (double)src[(long)s_pick[p] * RAW_COLS + c];
-    if (C == RAW_COLS && c == RAW_COLS - 1) v = 10.0 * log10(v + 1e-8);
-    s_val[e] = v;
-  }
-  __syncthreads();
-
-  double mean[C], denom[C];
-#pragma unroll
-  for (int c = 0; c < C; ++c) { mean[c] = 0.0; denom[c] = 1.0; }
-  if (standardize) {
-    double acc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0;
-    for (int p = tid; p < N; p += RAW_THREADS) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] += s_val[p * C + c];
-    }
-    block_sum_cols<C>(acc, s_red);
-#pragma unroll
-    for (int c = 0; c < C; ++c) mean[c] = acc[c] / (double)N;
-    if (divide_by_std) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] = 0.0;
-      for (int p = tid; p < N; p += RAW_THREADS) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          const double d = s_val[p * C + c] - mean[c];
-          acc[c] += d * d;
-        }
-      }
-      block_sum_cols<C>(acc, s_red);
-#pragma unroll
-      for (int c = 0; c < C; ++c) denom[c] = sqrt(acc[c] / (double)N) + 1e-8;
-    }
-  }
-
-  // centre, scale, round once, store
-  auto finish = [&](int e) -> float {
-    const int c = e % C;
-    double m = mean[0], d = denom[0];
-#pragma unroll
-    for (int k = 1; k < C; ++k) {                 // a select chain: mean / denom stay in registers
-      m = c == k ? mean[k] : m;
-      d = c == k ? denom[k] : d;
-    }
-    double v = s_val[e] - m;
-    if (divide_by_std) v = v / d;
-    return (float)v;
-  };
   if (vec) {
     for (int e = tid * 4; e < NC; e += RAW_THREADS * 4) {
       f32x4 o;
-      o.x = finish(e); o.y = finish(e + 1); o.z = finish(e + 2); o.w = finish(e + 3);
+      o.x = raw_frame_finish<C>(sh, e, mean, denom, divide_by_std);
+      o.y = raw_frame_finish<C>(sh, e + 1, mean, denom, divide_by_std);
+      o.z = raw_frame_finish<C>(sh, e + 2, mean, denom, divide_by_std);
+      o.w = raw_frame_finish<C>(sh, e + 3, mean, denom, divide_by_std);
       store4(dst + e, o);
     }
   } else {
-    for (int e = tid; e < NC; e += RAW_THREADS) dst[e] = finish(e);
+    for (int e = tid; e < NC; e += RAW_THREADS) dst[e] = raw_frame_finish<C>(sh, e, mean, denom, divide_by_std);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same frames without their padding (pcaa_frames_from_raw_unique): a padded frame repeats detections, and in eval mode
+// the per-point network is a pure function of the point, so mean over the N rows of f(row) = (1/N) sum_i m_i f(p_i) over
+// the DISTINCT picked detections p_i with multiplicities m_i.  Frame f owns u_cnt[f] = min(card, N) rows of a compact
+// [M, C] table from u_off[f] on (a frame whose offsets are bad: one row): u_off depends on the offsets alone.
+
+// u_off[0 .. n] = exclusive scan of u_cnt: one workgroup walks the frames in chunks of its size with a running carry
+constexpr int SCAN_THREADS = 1024;
+__global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(const int* __restrict__ offsets, int n, long P,
+                                                                          int N, int* __restrict__ u_off) {
+  __shared__ int s_wave[SCAN_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;                                  // the same in every thread
+  if (tid == 0) u_off[0] = 0;
+  for (int base = 0; base < n; base += SCAN_THREADS) {
+    const int f = base + tid;
+    int cnt = 0;
+    if (f < n) {
+      const long off0 = offsets[f], off1 = offsets[f + 1];
+      cnt = raw_offsets_bad(off0, off1, P) ? 1 : (int)((off1 - off0) < (long)N ? (off1 - off0) : (long)N);
+    }
+    int incl = cnt;                               // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    __syncthreads();                              // the previous chunk's reads of s_wave are over
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+      const int t = s_wave[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    if (f < n) u_off[f + 1] = carry + before + incl;
+    carry += total;
+  }
+}
+
+constexpr int RAW_PER_THREAD = PCAA_RAW_MAX_POINTS / RAW_THREADS;      // pick positions one thread ranks
+
+template <typename T, int C>
+__global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
+    const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
+    const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
+    float* __restrict__ rows, float* __restrict__ weight, const int* __restrict__ u_off, long M,
+    int* __restrict__ pick_out, int* __restrict__ err) {
+  __shared__ RawShared sh;
+  __shared__ int s_cnt[PCAA_RAW_MAX_CARD];        // by raw index: how often it was picked
+  __shared__ int s_first[PCAA_RAW_MAX_CARD];      // by raw index: the first pick position that holds it
+  __shared__ int s_rank[PCAA_RAW_MAX_POINTS];     // by pick position: distinct detections first seen before it
+  __shared__ int s_wave[RAW_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool vec = (C == 4) && ((uintptr_t)rows % 16 == 0);
+
+  auto zero_rows = [&](long r0, long r1) {        // rows r0 .. r1 - 1: the zero point, weight 0
+    for (long r = r0 + tid; r < r1; r += RAW_THREADS) weight[r] = 0.f;
+    for (long e = r0 * C + tid; e < r1 * C; e += RAW_THREADS) rows[e] = 0.f;
+  };
+
+  if ((long)blockIdx.x >= (long)n) {              // the rows no frame owns: u_off[n] .. M - 1, shared by the tail blocks
+    long r0 = u_off[n];
+    r0 = r0 < 0 ? 0 : (r0 > M ? M : r0);
+    const long nb = (long)gridDim.x - n, b = (long)blockIdx.x - n;
+    const long per = (M - r0 + nb - 1) / nb;
+    const long a = r0 + b * per, z = a + per < M ? a + per : M;
+    if (a < z) zero_rows(a, z);
+    return;
+  }
+  const long f = blockIdx.x;
+  const long u0 = u_off[f], u1 = u_off[f + 1];
+  if (u0 < 0 || u1 <= u0 || u1 > M) {             // the table is too small for this frame (inconsistent offsets)
+    if (err != nullptr && tid == 0) atomicOr(err, 1);
+    return;
+  }
+  double mean[C], denom[C];
+  int card;
+  if (!raw_frame_prepare<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                               divide_by_std, pick_out, err, card, mean, denom)) {
+    zero_rows(u0, u1);                            // one row, the zero point N times: the padded path's all-zero frame
+    __syncthreads();                              // (the weight below is written after the zeros, by the thread that wrote them)
+    if (tid == 0) weight[u0] = (float)N;
+    return;
+  }
+
+  // multiplicities and first occurrences: integer LDS atomics, so the result does not depend on their order
+  for (int i = tid; i < card; i += RAW_THREADS) { s_cnt[i] = 0; s_first[i] = N; }
+  __syncthreads();
+  for (int p = tid; p < N; p += RAW_THREADS) {
+    const int i = sh.pick[p];
+    atomicAdd(&s_cnt[i], 1);
+    atomicMin(&s_first[i], p);
+  }
+  __syncthreads();
+  // rank of every first occurrence: thread t owns positions t * RAW_PER_THREAD .. + RAW_PER_THREAD - 1
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < RAW_PER_THREAD; ++k) {
+    const int p = tid * RAW_PER_THREAD + k;
+    mine += (p < N && s_first[sh.pick[p]] == p) ? 1 : 0;
+  }
+  int incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int before = incl - mine, distinct = 0;
+#pragma unroll
+  for (int w = 0; w < RAW_WAVES; ++w) {
+    const int t = s_wave[w];
+    before += w < wave ? t : 0;
+    distinct += t;
+  }
+#pragma unroll
+  for (int k = 0; k < RAW_PER_THREAD; ++k) {
+    const int p = tid * RAW_PER_THREAD + k;
+    if (p < N) {
+      const bool first = s_first[sh.pick[p]] == p;
+      s_rank[p] = first ? before : -1;
+      before += first ? 1 : 0;
+    }
+  }
+  __syncthreads();
+
+  // distinct <= min(card, N) = u1 - u0: the rows the picks leave unused are zero with weight 0
+  if (vec) {
+    for (int p = tid; p < N; p += RAW_THREADS) {
+      const int r = s_rank[p];
+      if (r < 0) continue;
+      f32x4 o;
+      o.x = raw_frame_finish<C>(sh, p * C, mean, denom, divide_by_std);
+      o.y = raw_frame_finish<C>(sh, p * C + 1, mean, denom, divide_by_std);
+      o.z = raw_frame_finish<C>(sh, p * C + 2, mean, denom, divide_by_std);
+      o.w = raw_frame_finish<C>(sh, p * C + 3, mean, denom, divide_by_std);
+      store4(rows + (u0 + r) * C, o);
+    }
+  } else {
+    for (int e = tid; e < N * C; e += RAW_THREADS) {
+      const int p = e / C, r = s_rank[p];
+      if (r >= 0) rows[(u0 + r) * C + (e - p * C)] = raw_frame_finish<C>(sh, e, mean, denom, divide_by_std);
+    }
+  }
+  for (int p = tid; p < N; p += RAW_THREADS) {
+    const int r = s_rank[p];
+    if (r >= 0) weight[u0 + r] = (float)s_cnt[sh.pick[p]];
+  }
+  zero_rows(u0 + distinct, u1);
 }
 
 template <typename T>
@@ -213,6 +403,23 @@ void launch_frames_from_raw(int C, dim3 grid, hipStream_t st, const T* points, l
   case CC:                                                                                                             \
     hipLaunchKernelGGL((frames_from_raw_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n, pick,   \
                        frame_key, lo, hi, N, standardize, divide_by_std, out, pick_out, err);                          \
+    break;
+  switch (C) {
+    PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
+  }
+#undef PCAA_RAW_CASE
+}
+
+template <typename T>
+void launch_frames_from_raw_unique(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
+                                   const int* pick, const int* frame_key, long seed, int N, int standardize,
+                                   int divide_by_std, float* rows, float* weight, const int* u_off, long M, int* pick_out,
+                                   int* err) {
+  const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
+#define PCAA_RAW_CASE(CC)                                                                                              \
+  case CC:                                                                                                             \
+    hipLaunchKernelGGL((frames_from_raw_unique_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n,  \
+                       pick, frame_key, lo, hi, N, standardize, divide_by_std, rows, weight, u_off, M, pick_out, err); \
     break;
   switch (C) {
     PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
@@ -242,4 +449,35 @@ extern "C" int pcaa_frames_from_raw(const void* points, int points_f64, long P, 
     launch_frames_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n, pick,
                                   frame_key, seed, N, standardize, divide_by_std, out, pick_out, err_flag);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_frames_from_raw");
+}
+
+extern "C" int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, const int* offsets, int n,
+                                           const int* pick, const int* frame_key, long seed, int N, int C,
+                                           int standardize, int divide_by_std, float* rows, float* weight, int* u_off,
+                                           long M, int* pick_out, int* err_flag, void* stream) {
+  PCAA_CHECK_ARG(n >= 0 && M >= 1 && P >= 0 && (long)n * PCAA_RAW_MAX_POINTS < (1L << 31) && M < (1L << 31),
+                 "pcaa_frames_from_raw_unique: needs n >= 0, 1 <= M < 2^31, P >= 0, n * 1024 < 2^31");
+  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
+                 "pcaa_frames_from_raw_unique: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5");
+  PCAA_CHECK_ARG(rows != nullptr && weight != nullptr && u_off != nullptr && ((uintptr_t)rows % 4) == 0 &&
+                     ((uintptr_t)weight % 4) == 0 && ((uintptr_t)u_off % 4) == 0,
+                 "pcaa_frames_from_raw_unique: rows / weight / u_off are null or not 4-B aligned");
+  PCAA_CHECK_ARG(n == 0 || (offsets != nullptr && (points != nullptr || P == 0)),
+                 "pcaa_frames_from_raw_unique: points / offsets are null");
+  PCAA_CHECK_ARG(n == 0 || pick != nullptr || frame_key != nullptr,
+                 "pcaa_frames_from_raw_unique: without picks the frames need their keys (frame_key)");
+  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "pcaa_frames_from_raw_unique: points are misaligned");
+  hipLaunchKernelGGL(raw_unique_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n, P, N, u_off);
+  long tail = cdiv(M, 4096);                      // blocks that zero the rows no frame owns
+  tail = tail < 1 ? 1 : (tail > 64 ? 64 : tail);
+  const dim3 grid((unsigned)(n + tail));
+  if (points_f64)
+    launch_frames_from_raw_unique<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, n,
+                                          pick, frame_key, seed, N, standardize, divide_by_std, rows, weight, u_off, M,
+                                          pick_out, err_flag);
+  else
+    launch_frames_from_raw_unique<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n,
+                                         pick, frame_key, seed, N, standardize, divide_by_std, rows, weight, u_off, M,
+                                         pick_out, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_frames_from_raw_unique");
 }

@@ -259,13 +259,16 @@ def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None
     return y, scale, shift, mean, rstd, count
 
 
-def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, want_bwd=False):
+def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, want_bwd=False, last_pre_bn=False):
     """xp2d: [P, C] fp32.  Returns (output, saves).  If pool_rows>0 the last
     layer's ELU output is mean-pooled over groups of pool_rows rows (fp32
     [P/pool_rows, ch]); else the last activation [P, ch] is returned.
     ``consts`` (eval only): the encoder's EncoderEvalConstants, used instead of recomputing them.
     ``want_bwd`` (matters in eval mode only): a backward will follow, so every layer keeps what pointnet_backward reads
-    (its pre-BatchNorm ``y``: no fused-epilogue layers, no split images); off, the eval forward is unchanged."""
+    (its pre-BatchNorm ``y``: no fused-epilogue layers, no split images); off, the eval forward is unchanged.
+    ``last_pre_bn`` (with pool_rows == 0): where the last layer stores its pre-BatchNorm ``y`` (every route but the
+    fused-epilogue GEMM), return that ``y`` instead of ELU(BN(y)) -- the caller applies ``saves[-1].scale / .shift``
+    itself (encoder_frame_features_ragged: in its pooling pass); ``saves[-1].y`` is None where the epilogue already did."""
     if consts is not None and (training or consts.mode != mode):
         raise ValueError("pointnet_forward: consts are eval-mode constants of one precision mode "
                          f"(made for {consts.mode!r}, asked for {mode!r}, training={training})")
@@ -323,6 +326,8 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, wan
         y, scale, shift, mean, rstd, count = _linear_bn(a, W2d, conv.bias, bn, training, mode, True, consts, conv)
         s = _LayerSave(a, None, y, scale, shift, mean, rstd, count, cin, cout, 0)
         saves.append(s)
+        if li == nl - 1 and last_pre_bn and not pool_rows:
+            return y, saves
         if li == nl - 1 and pool_rows:
             if training:
                 out, s.pool_e = ops.bn_act_meanpool_fwd(y, scale, shift, y.shape[0] // pool_rows, pool_rows, mean, rstd)
@@ -1040,6 +1045,42 @@ def encoder_frame_features(enc, frames, mode=None, consts=None):
     U, N, C = frames.shape
     _check_encoder_input(enc, C, N)
     return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N, consts=consts)
+
+
+def encoder_frame_features_ragged(enc, rows, weight, u_off, n, N, mode=None, consts=None):
+    """``encoder_frame_features`` of n padded frames from their DISTINCT points (``ops.frames_from_raw_unique``): ``rows``
+    [M, C] fp32, ``weight`` fp32 [M] (how often a row's point occurs in its padded frame), ``u_off`` int32 [n + 1] (frame
+    f owns rows ``u_off[f] .. u_off[f + 1] - 1``) -> ([n, 1024] fp32, saves).  In eval mode the per-point network f is a
+    pure function of the point, so the mean over a frame's N padded rows of f(row) is (1 / N) sum_i weight_i f(row_i): the
+    eval PointNet layers run on the M compact rows with no pooling in the last layer, then ``ops.segment_weighted_mean``
+    pools (and applies BatchNorm + ELU itself where the last layer left its pre-BatchNorm y: fp32 and fp16x3 modes).
+    Eval mode and no gradient only: the saves do not serve pointnet_backward."""
+    mode = get_precision() if mode is None else mode
+    _require_gpu(rows, "CGEncoder")
+    if enc.training:
+        raise RuntimeError("encoder_frame_features_ragged: the encoder is in training mode (batch statistics would need "
+                           "weighted moments); call encoder.eval()")
+    if torch.is_grad_enabled() and (rows.requires_grad or any(p.requires_grad for p in enc.parameters())):
+        raise RuntimeError("encoder_frame_features_ragged: forward only -- a backward is wanted (autograd is on and the "
+                           "rows or the encoder's parameters require a gradient); call it under torch.no_grad(), or "
+                           "differentiate encoder_frame_features on the padded frames")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError(f"encoder_frame_features_ragged expects contiguous fp32 rows [M,C], got {tuple(rows.shape)} {rows.dtype}")
+    M, C = rows.shape
+    n, N = int(n), int(N)
+    _check_encoder_input(enc, C, N)
+    if not isinstance(weight, torch.Tensor) or not isinstance(u_off, torch.Tensor) or not weight.is_cuda or not u_off.is_cuda:
+        raise RuntimeError("encoder_frame_features_ragged: weight and u_off must live on the HIP device")
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (M,):
+        raise ValueError(f"encoder_frame_features_ragged: weight must be fp32 [{M}], got {tuple(weight.shape)} {weight.dtype}")
+    if u_off.dtype != torch.int32 or tuple(u_off.shape) != (n + 1,):
+        raise ValueError(f"encoder_frame_features_ragged: u_off must be int32 [{n + 1}], got {tuple(u_off.shape)} {u_off.dtype}")
+    with torch.no_grad():
+        a, saves = pointnet_forward(rows, enc.pc_block.layers(), False, mode, pool_rows=0, consts=consts, last_pre_bn=True)
+        last = saves[-1]
+        if last.y is not None:
+            return ops.segment_weighted_mean(a, weight, u_off, N, last.scale, last.shift), saves
+        return ops.segment_weighted_mean(a, weight, u_off, N), saves
 
 
 def encoder_forward_windows(enc, table, win_row, T, mode=None, consts=None):

@@ -136,6 +136,16 @@ def _upload_keys(serial, first, n, dev):
     return host.to(dev, non_blocking=True)
 
 
+def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, mode=None, consts=None):
+    """raw frames -> their distinct points and multiplicities -> [n, 1024] frame features (the ``dedup_points`` route of
+    the raw entries) -> (features, the PointNet layer records, rows of the compact table)"""
+    n = offsets.numel() - 1
+    rows, weight, u_off = ops.frames_from_raw_unique(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys,
+                                                     err_flag=err_flag)
+    feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, n, N, mode, consts=consts)
+    return feats, saves, rows.shape[0]
+
+
 def _empty_triple(D, dev):
     """(preds, sup_fv, likelihood) of no window at all"""
     return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
@@ -153,6 +163,7 @@ class OpenSetScorer:
         self.threshold = None
         self.last_frames_encoded = None      # unique frames the last deduplicated embed / embed_track encoded (no padding)
         self.last_pointnet_saves = None      # the PointNet layer records of its last chunk (which path ran)
+        self.last_rows_encoded = None        # embed_raw_track(dedup_points=True): rows of the compact tables it ran
         self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
 
     @torch.no_grad()
@@ -237,6 +248,10 @@ class OpenSetScorer:
                 chunk = track[a:b]
             f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, chunk)
             feats.append(f[lo:lo + b - a])
+        return self._score_track_table(feats, U, W, T, hop, dev)
+
+    def _score_track_table(self, feats, U, W, T, hop, dev):
+        """the feature chunks of a track's first U frames -> the triple of its W windows"""
         table = feats[0] if len(feats) == 1 else torch.cat(feats)
         self.last_frames_encoded = U
         starts = hop * np.arange(W, dtype=np.int64)
@@ -246,17 +261,39 @@ class OpenSetScorer:
 
     @torch.no_grad()
     def embed_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None, seed: int = 0,
-                        track_key: int = 0, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True):
+                        track_key: int = 0, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True,
+                        dedup_points: bool = False):
         """``embed_track`` from the radar's detections: ``points`` [P,5] fp32 / fp64 and ``offsets`` int32 [F + 1] on the
         device (``datasets.pack_raw_frames``) -> one ``ops.frames_from_raw`` launch for the whole track (centred, not
         divided by std, as ``generate_splits`` prepares the crops) -> exactly ``embed_track`` on those frames.  ``pick``
         int32 [F, N]: host-drawn picks (``datasets.draw_picks``); None: drawn on the device, frame f under the key
-        ``(track_key, f)`` and ``seed``.  ``raw_err`` (int32 [1], device) is set by a frame that could not be processed."""
+        ``(track_key, f)`` and ``seed``.  ``raw_err`` (int32 [1], device) is set by a frame that could not be processed.
+        ``dedup_points``: the padded frames are never written; every frame's DISTINCT picked detections go through the
+        PointNet block once and are pooled with their multiplicities (``ops.frames_from_raw_unique``,
+        ``functional.encoder_frame_features_ragged``): the same features up to fp32 summation order, from
+        ``sum(min(card, N))`` rows instead of ``F * N``.  ``last_rows_encoded`` is the number of table rows it ran."""
         enc = self.encoder
         N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
         F = _check_raw(points, offsets, pick, N, "embed_raw_track")
         dev = points.device
         keys = _upload_keys(track_key, 0, F, dev) if pick is None and F else None
+        if dedup_points:
+            T, hop = constants.NSTEPS, int(hop)
+            W = window_count(F, T, hop) if drop_last_aligned else (0 if F < T else (F - T) // hop + 1)
+            if W == 0:
+                self.last_frames_encoded = self.last_rows_encoded = 0
+                return _empty_triple(enc.MLP_sup1[0].weight.shape[0], dev)
+            U = (W - 1) * hop + T                                          # frames any window uses
+            step = max(self.batch_size * T, 1)
+            feats, self.last_rows_encoded = [], 0
+            for a in range(0, U, step):
+                b = min(a + step, U)
+                f, self.last_pointnet_saves, M = _ragged_features(
+                    enc, points, offsets[a:b + 1], N, C, None if pick is None else pick[a:b], seed,
+                    None if keys is None else keys[a:b], self.raw_err)
+                self.last_rows_encoded += M
+                feats.append(f)
+            return self._score_track_table(feats, U, W, T, hop, dev)
         frames = ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=self.raw_err)
         return self.embed_track(frames, hop, drop_last_aligned)
 
@@ -505,10 +542,12 @@ class StreamingScorer(_LiveScorer):
     in one batched tick with O(k) state per track."""
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
-                 hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0):
+                 hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0,
+                 dedup_points: bool = False):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         dev = self.means.device
         self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
+        self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
         self.seed, self.serial = int(seed), -1           # push_raw: frame f of the track is drawn under (serial, f)
         self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
         # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
@@ -550,7 +589,9 @@ class StreamingScorer(_LiveScorer):
         (``datasets.pack_raw_frames``), the next n frames of the track -> one ``ops.frames_from_raw`` launch per
         ``max_push`` frames (centred, padded to whole GEMM tiles by the same launch), then what ``push`` does.  ``pick``
         int32 [n, N]: host-drawn picks; None: drawn on the device, frame f of the track under the key ``(serial, f)`` and
-        the constructor's ``seed``.  ``raw_err`` is set by a frame that could not be processed (its frame is zeros)."""
+        the constructor's ``seed``.  ``raw_err`` is set by a frame that could not be processed (its frame is zeros).
+        With the constructor's ``dedup_points`` the padded frames are never written: ``ops.frames_from_raw_unique`` and
+        ``functional.encoder_frame_features_ragged`` give the same frame features from the frames' distinct points."""
         self._check_eval()
         n = _check_raw(points, offsets, pick, self._N, "StreamingScorer.push_raw")
         q = F_hip.frame_pad_quantum(self._N)
@@ -558,6 +599,12 @@ class StreamingScorer(_LiveScorer):
         for a in range(0, n, self.max_push):
             b = min(a + self.max_push, n)
             keys = _upload_keys(self.serial, self.n_frames, b - a, points.device) if pick is None else None
+            if self.dedup_points:
+                feats, self.last_pointnet_saves, _ = _ragged_features(
+                    self.encoder, points, offsets[a:b + 1], self._N, self._C, None if pick is None else pick[a:b],
+                    self.seed, keys, self.raw_err)
+                out.append(self._push_features(feats, b - a))
+                continue
             frames = ops.frames_from_raw(points, offsets[a:b + 1], self._N, self._C, pick=None if pick is None else pick[a:b],
                                          seed=self.seed, frame_key=keys, n_out=b - a + (a - b) % q, err_flag=self.raw_err)
             out.append(self._push_padded(frames, b - a))
@@ -573,6 +620,10 @@ class StreamingScorer(_LiveScorer):
     def _push_padded(self, frames, n):
         """``frames``: on the device, padded to whole tiles, the first ``n`` of them the track's next frames"""
         feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames)
+        return self._push_features(feats, n)
+
+    def _push_features(self, feats, n):
+        """``feats``: the frame features of the track's next ``n`` frames in its first rows"""
         pos = self.n_frames % self.ring_rows
         first = min(n, self.ring_rows - pos)
         self.ring[pos:pos + first].copy_(feats[:first])
@@ -753,9 +804,10 @@ class MultiStreamScorer(_LiveScorer):
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
-                 batch_size: int = 1024, seed: int = 0):
+                 batch_size: int = 1024, seed: int = 0, dedup_points: bool = False):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         self.max_streams, self.batch_size = int(max_streams), int(batch_size)
+        self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
         if self.max_streams < 1 or self.batch_size < 1:
             raise ValueError("MultiStreamScorer: needs max_streams >= 1, batch_size >= 1")
         dev = self.means.device
@@ -830,20 +882,30 @@ class MultiStreamScorer(_LiveScorer):
         them and padded to whole GEMM tiles) and no host work per frame.  ``pick`` int32 [sum(counts), N]: host-drawn picks
         (``datasets.draw_picks``: the reference's draws); None: drawn on the device, frame f of a track under the key
         ``(track_serial[slot], f)`` and the constructor's ``seed`` -- the keys travel in the tick's one pinned upload.
-        ``raw_err`` is set by a frame that could not be processed (it is encoded as zeros)."""
+        ``raw_err`` is set by a frame that could not be processed (it is encoded as zeros).
+        With the constructor's ``dedup_points`` the padded frames are never written: the tick's distinct points go through
+        the PointNet block once (``ops.frames_from_raw_unique``, ``functional.encoder_frame_features_ragged``: three
+        launches in place of one, still none per stream) and give the same frame features up to fp32 summation order."""
         self._check_eval()
         n = _check_raw(points, offsets, pick, self._N, "MultiStreamScorer.push_raw")
-        sids, plan, part, mode = self._begin_tick(sids, counts, n, self._N, "push_raw", pick is None)
+        sids, plan, part, mode = self._begin_tick(sids, counts, n, self._N, "push_raw", pick is None,
+                                                  pad_to=1 if self.dedup_points else None)
         if n == 0:
             return self._empty(plan, self.ring.device)
+        if self.dedup_points:
+            feats, self.last_pointnet_saves, _ = _ragged_features(
+                self.encoder, points, offsets, self._N, self._C, pick, self.seed,
+                part["frame_key"].view(n, 2) if pick is None else None, self.raw_err, mode, self._consts)
+            return self._finish_tick_features(sids, plan, part, mode, feats)
         frames = ops.frames_from_raw(points, offsets, self._N, self._C, pick=pick, seed=self.seed,
                                      frame_key=part["frame_key"].view(n, 2) if pick is None else None,
                                      n_out=plan.dst_row.size, err_flag=self.raw_err)
         return self._finish_tick(sids, plan, part, mode, frames)
 
-    def _begin_tick(self, sids, counts, n, N, what, want_keys):
+    def _begin_tick(self, sids, counts, n, N, what, want_keys, pad_to=None):
         """the arguments of a tick checked, its plan made and (unless the tick is empty) uploaded -> (sids, plan, the
-        plan's parts on the device, precision mode)"""
+        plan's parts on the device, precision mode).  ``pad_to``: frames of the tick's PointNet pass are padded to a
+        multiple of it (default: ``frame_pad_quantum``)."""
         sids = self._slots(sids, what)
         counts = _host_ints(counts)
         if counts is None or counts.size != sids.size:
@@ -854,7 +916,7 @@ class MultiStreamScorer(_LiveScorer):
             raise ValueError(f"MultiStreamScorer.{what}: counts add up to {int(counts.sum())} frames, got {n}")
         dev = self.ring.device
         mode = F_hip.get_precision()
-        q = F_hip.frame_pad_quantum(N, mode)
+        q = F_hip.frame_pad_quantum(N, mode) if pad_to is None else pad_to
         plan = plan_tick(self.n_frames, self.n_windows, sids, counts, self.T, self.hop, self.k, self.ring_rows, q,
                          serials=self.track_serial if want_keys else None)
         if n == 0:
@@ -870,8 +932,12 @@ class MultiStreamScorer(_LiveScorer):
 
     def _finish_tick(self, sids, plan, part, mode, frames):
         """a tick from the point where its frames are on the device and padded to whole tiles"""
-        dev = self.ring.device
         feats, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, frames, mode, consts=self._consts)
+        return self._finish_tick_features(sids, plan, part, mode, feats)
+
+    def _finish_tick_features(self, sids, plan, part, mode, feats):
+        """a tick from the point where its frames' features are on the device, one row per entry of the plan's dst_row"""
+        dev = self.ring.device
         ops.scatter_rows(feats, part["dst_row"], self.ring, err_flag=self.scatter_err)
         self.n_frames[sids], self.n_windows[sids] = plan.n_frames, plan.n_windows
         nw = plan.win_row.size

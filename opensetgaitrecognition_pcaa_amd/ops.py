@@ -1594,6 +1594,100 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     return out
 
 
+UNIQUE_ROW_QUANTUM = 256  # rows of the compact table: whole 256-row GEMM tiles (pcaa_gemm_affine_elu, pcaa_gemm_split3)
+
+
+def unique_table_rows(P, n, N):
+    """M of ``frames_from_raw_unique``: frame f owns min(card_f, N) rows, a bad frame one, so for ascending offsets the
+    frames own at most min(P + n, n N) rows; rounded up to whole GEMM tiles (at least one)."""
+    need = max(min(int(P) + int(n), int(n) * int(N)), 1)
+    return (need + UNIQUE_ROW_QUANTUM - 1) // UNIQUE_ROW_QUANTUM * UNIQUE_ROW_QUANTUM
+
+
+def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
+                           divide_by_std=False, M=None, pick_out=None, err_flag=None):
+    """``frames_from_raw`` without the padding (pcaa_frames_from_raw_unique; arguments as there) -> ``(rows [M, C] fp32,
+    weight [M] fp32, u_off [n + 1] int32)``: rows ``u_off[f] .. u_off[f + 1] - 1`` hold frame f's distinct picked
+    detections in order of first occurrence, each bit-equal to the row ``frames_from_raw`` writes for that pick, ``weight``
+    how often it was picked.  Unused rows of a frame's ``min(card, N)`` and the rows from ``u_off[n]`` on are zero with
+    weight 0; a bad frame is one zero row of weight N and sets ``err_flag``.  ``M`` defaults to ``unique_table_rows``.
+    Two launches (the scan of ``u_off``, the rows); nothing comes back to the host."""
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise TypeError("frames_from_raw_unique.points: expected a float32 or float64 tensor")
+    _chk(points, "frames_from_raw_unique.points", None, 2)
+    _chk(offsets, "frames_from_raw_unique.offsets", torch.int32, 1)
+    N, C, seed = int(N), int(C), int(seed)
+    n = offsets.numel() - 1
+    if points.shape[1] != 5 or n < 0 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
+        raise ValueError(f"frames_from_raw_unique: needs points [P, 5], offsets [n + 1], 1 <= N <= {RAW_MAX_POINTS}, "
+                         f"1 <= C <= 5; got points {tuple(points.shape)}, n={n}, N={N}, C={C}")
+    M = unique_table_rows(points.shape[0], n, N) if M is None else int(M)
+    if not 1 <= M < 2 ** 31 or n * RAW_MAX_POINTS >= 2 ** 31:
+        raise ValueError(f"frames_from_raw_unique: needs 1 <= M < 2^31 and n * {RAW_MAX_POINTS} < 2^31, got M={M}, n={n}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError("frames_from_raw_unique: the seed must fit 64 bits")
+    if pick is not None:
+        _chk(pick, "frames_from_raw_unique.pick", torch.int32, 2)
+        if tuple(pick.shape) != (n, N):
+            raise ValueError(f"frames_from_raw_unique: pick must be [{n}, {N}], got {tuple(pick.shape)}")
+    elif n:
+        if frame_key is None:
+            raise ValueError("frames_from_raw_unique: without picks every frame needs its key (frame_key int32 [n, 2])")
+        _chk(frame_key, "frames_from_raw_unique.frame_key", torch.int32, 2)
+        if tuple(frame_key.shape) != (n, 2):
+            raise ValueError(f"frames_from_raw_unique: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
+    if pick_out is not None:
+        _chk(pick_out, "frames_from_raw_unique.pick_out", torch.int32, 2)
+        if tuple(pick_out.shape) != (n, N):
+            raise ValueError(f"frames_from_raw_unique: pick_out must be [{n}, {N}], got {tuple(pick_out.shape)}")
+    if err_flag is not None:
+        _chk(err_flag, "frames_from_raw_unique.err_flag", torch.int32)
+    dev = points.device
+    rows = torch.empty((M, C), dtype=torch.float32, device=dev)
+    weight = torch.empty(M, dtype=torch.float32, device=dev)
+    u_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique(
+        _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
+        None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+        _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s()), "pcaa_frames_from_raw_unique"),
+        0.0, points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4)
+    return rows, weight, u_off
+
+
+def segment_weighted_mean(a, weight, u_off, N, scale=None, shift=None, err_flag=None):
+    """``out[f] = (1 / N) sum_{r in [u_off[f], u_off[f + 1])} weight[r] * v(a[r])`` (pcaa_segment_weighted_mean): ``a``
+    [M, ch] bf16 or fp32, ``weight`` fp32 [M], ``u_off`` int32 [n + 1] -> fp32 [n, ch].  ``v`` is the identity, or with
+    ``scale`` / ``shift`` fp32 [ch] ``ELU(a * scale + shift)`` (``a`` a pre-BatchNorm y).  fp32 accumulation in a fixed
+    order: a frame's result does not depend on n.  ``ch % 8 == 0``.  A segment outside ``[0, M]`` comes back as zeros and
+    sets ``err_flag`` (int32 [1])."""
+    _chk(a, "segment_weighted_mean.a", None, 2)
+    if a.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"segment_weighted_mean.a: expected float32 or bfloat16, got {a.dtype}")
+    _chk(weight, "segment_weighted_mean.weight", torch.float32, 1)
+    _chk(u_off, "segment_weighted_mean.u_off", torch.int32, 1)
+    M, ch = a.shape
+    n, N = u_off.numel() - 1, int(N)
+    if weight.numel() != M:
+        raise ValueError(f"segment_weighted_mean: weight must be [{M}] (one per row of a), got {tuple(weight.shape)}")
+    if ch < 8 or ch % 8 or n < 0 or N < 1:
+        raise ValueError(f"segment_weighted_mean: needs ch % 8 == 0, u_off [n + 1], N >= 1; got ch={ch}, n={n}, N={N}")
+    if (scale is None) != (shift is None):
+        raise ValueError("segment_weighted_mean: scale and shift come together")
+    if scale is not None:
+        for t, name in ((scale, "scale"), (shift, "shift")):
+            _chk(t, "segment_weighted_mean." + name, torch.float32, 1)
+            if t.numel() != ch:
+                raise ValueError(f"segment_weighted_mean: {name} must be [{ch}], got {tuple(t.shape)}")
+    if err_flag is not None:
+        _chk(err_flag, "segment_weighted_mean.err_flag", torch.int32)
+    out = torch.empty((n, ch), dtype=torch.float32, device=a.device)
+    if n:
+        _timed("segment_weighted_mean_kernel", lambda: check(_lib.load().pcaa_segment_weighted_mean(
+            _p(a), _dt(a), ch, _p(weight), _p(u_off), n, M, ch, N, _p(scale), _p(shift), _p(out), _p(err_flag), _s()),
+            "pcaa_segment_weighted_mean"), 2.0 * M * ch, M * ch * a.element_size() + n * ch * 4)
+    return out
+
+
 def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
                  n_classes, hist_lik, hist_pred):
     """One tick of many live streams in one launch (pcaa_stream_score) -> (preds [nw] int64, lik [nw] f64, votes [n_votes]

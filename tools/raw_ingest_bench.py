@@ -4,6 +4,7 @@
     rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d DIR -- \\
         python tools/raw_ingest_bench.py --trace-segments                                      # a run of its own
     python tools/raw_ingest_bench.py --count-trace DIR [--out profiles/raw_ingest.txt]         # appends the counts
+    python tools/raw_ingest_bench.py --dedup [--out profiles/raw_unique.txt]                   # push_raw padded against dedup_points
 
 N = 128, C = 4, K = 8, bf16 mode, ``hop`` = 6 new frames per stream per tick, every stream warmed until it emits one window
 per tick; raw frames of 3 .. MAX_POINTS detections (both the repeat-pad and the subsample branch at N = 128).  For S in 1, 4,
@@ -15,6 +16,12 @@ per tick; raw frames of 3 .. MAX_POINTS detections (both the repeat-pad and the 
 Alternated in one process: WINDOWS windows of TICKS ticks each; per window the host wall time to a synchronise and the part
 of it spent preparing frames on the host ((a): process_track + cast; (b): pack_raw_frames; (c): nothing), both per tick;
 medians and spreads ((max - min) / median over the windows).
+
+``--dedup`` measures ``dedup_points=True`` (the frames' distinct points through the PointNet block once, pooled with their
+multiplicities) against the padded ``push_raw``, the detections of every tick on the device before the clock starts, the two
+legs alternated in one process as above: ticks at every S, and ``OpenSetScorer.embed_raw_track`` of one track of 1 024 windows;
+N = 128, raw frames of 3 .. 40 and of 3 .. 150 detections, bf16 and fp32.  Next to each time: the rows the PointNet block ran
+(padded: frames x N; dedup: the compact table, and of it the rows that hold a distinct point).
 
 ``--trace-segments`` runs, at every S, TRACE_TICKS ticks of (c), of (b) with the packed detections already on the device
 (as (c)'s frames are: the comparison of what the two entry points launch) and of (b) as timed (pack + two uploads per
@@ -36,7 +43,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from multi_stream_bench import C, K, KVOTE, MARKER, N, STREAMS, TRACE_TICKS, make_encoder, marker  # noqa: E402
-from opensetgaitrecognition_pcaa_amd import constants, datasets, functional as F_hip, inference, synthetic as syn  # noqa: E402
+from opensetgaitrecognition_pcaa_amd import constants, datasets, functional as F_hip, inference, ops, synthetic as syn  # noqa: E402
 
 MAX_POINTS = 200
 LEGS = ("a", "b", "c")
@@ -177,6 +184,111 @@ def count_trace(folder, say):
         + f" -> {'one more at every S' if all(v == 1 for v in extra.values()) else 'NOT one more at every S'}")
 
 
+class DedupBed:
+    """S raw tracks, the detections of every tick staged on the device, a warmed padded and a warmed dedup scorer"""
+
+    def __init__(self, enc, means, S, n_ticks, max_points):
+        T, hop = constants.NSTEPS, constants.CROP_STEP
+        self.S, self.hop = S, hop
+        warm = T + hop * 3
+        tracks = [syn.synthetic_raw_track(1700 + 64 * S + s, warm + hop * n_ticks, max_points=max_points) for s in range(S)]
+        self.multi = {leg: inference.MultiStreamScorer(enc, means, 0.0, KVOTE, K, max_streams=S, seed=S, dedup_points=leg == "u")
+                      for leg in ("p", "u")}
+        self.sids = [self.multi["p"].open() for _ in range(S)]
+        assert [self.multi["u"].open() for _ in range(S)] == self.sids
+        for a in range(0, warm, 32):
+            b = min(a + 32, warm)
+            points, offsets = datasets.pack_raw_frames([fr for t in tracks for fr in t[a:b]], torch.float32)
+            for leg in ("p", "u"):
+                self.multi[leg].push_raw(self.sids, [b - a] * S, points.cuda(), offsets.cuda())
+        self.staged, self.distinct_rows, self.table_rows = [], 0, 0
+        for p in range(warm, warm + hop * n_ticks, hop):
+            raw = [fr for t in tracks for fr in t[p:p + hop]]
+            points, offsets = datasets.pack_raw_frames(raw, torch.float32)
+            self.staged.append((points.cuda(), offsets.cuda()))
+            cards = np.array([len(fr["z_coord"]) for fr in raw])
+            self.distinct_rows += int(np.minimum(cards, N).sum())
+            self.table_rows += ops.unique_table_rows(points.shape[0], len(raw), N)
+        self.n_ticks = n_ticks
+        self.at = {"p": 0, "u": 0}
+        torch.cuda.synchronize()
+
+    def tick(self, leg):
+        points, offsets = self.staged[self.at[leg]]
+        self.at[leg] += 1
+        return self.multi[leg].push_raw(self.sids, [self.hop] * self.S, points, offsets)
+
+
+def _wall(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / reps
+
+
+def _line(say, head, rec):
+    med = {leg: statistics.median(v) for leg, v in rec.items()}
+    for leg, name in (("p", "padded"), ("u", "dedup ")):
+        v = rec[leg]
+        say(f"  {head} {name}: " + " ".join(f"{x:.3f}" for x in v)
+            + f"   median {med[leg]:.3f}  spread {100 * (max(v) - min(v)) / max(med[leg], 1e-9):.1f} %")
+    return med
+
+
+def dedup_legs(args, say):
+    enc, means = make_encoder()
+    hop, T = constants.CROP_STEP, constants.NSTEPS
+    say(f"raw_ingest_bench --dedup: N={N} C={C} K={K}, {torch.cuda.get_device_name(0)}; push_raw with the padded frames "
+        "(padded) against dedup_points=True (dedup), detections on the device before the clock starts; alternated, "
+        f"{args.windows} windows of {args.ticks} ticks, wall ms per tick to a device synchronise; spread = (max - min) / median")
+    say("rows: what the PointNet block ran -- padded: frames x N (to whole tiles); dedup: the compact table "
+        "min(P + n, n N) to whole 256-row tiles, of which 'distinct' hold a point (sum of min(card, N))")
+    for mode in ("bf16", "fp32"):
+        F_hip.set_precision(mode)
+        for max_points in (40, 150):
+            say(f"{mode}, raw frames of 3..{max_points} detections:")
+            for S in STREAMS:
+                n_ticks = 2 + args.windows * args.ticks
+                bed = DedupBed(enc, means, S, n_ticks, max_points)
+                for leg in ("p", "u"):
+                    for _ in range(2):
+                        bed.tick(leg)
+                rec = {"p": [], "u": []}
+                for _ in range(args.windows):
+                    for leg in ("p", "u"):
+                        rec[leg].append(_wall(lambda: bed.tick(leg), args.ticks))
+                for leg in ("p", "u"):
+                    assert bed.multi[leg].scatter_err.item() == 0 and bed.multi[leg].raw_err.item() == 0
+                q = F_hip.frame_pad_quantum(N)
+                padded_rows = -(-S * hop // q) * q * N
+                med = _line(say, f"S={S:<2d}", rec)
+                say(f"  S={S:<2d} rows per tick: padded {padded_rows}, dedup table {bed.table_rows / n_ticks:.0f} (distinct "
+                    f"{bed.distinct_rows / n_ticks:.0f}); rows padded / table {padded_rows * n_ticks / bed.table_rows:.2f}x, "
+                    f"time padded / dedup {med['p'] / med['u']:.2f}x")
+            # one long track: 1 024 windows
+            F = T + hop * 1024
+            raw = syn.synthetic_raw_track(4242, F, max_points=max_points)
+            points, offsets = datasets.pack_raw_frames(raw, torch.float32)
+            points, offsets = points.cuda(), offsets.cuda()
+            sc = inference.OpenSetScorer(enc, means)
+            run = {"p": lambda: sc.embed_raw_track(points, offsets, seed=3), "u": lambda: sc.embed_raw_track(points, offsets, seed=3, dedup_points=True)}
+            for leg in ("p", "u"):
+                run[leg]()
+            table = sc.last_rows_encoded
+            rec = {"p": [], "u": []}
+            for _ in range(args.windows):
+                for leg in ("p", "u"):
+                    rec[leg].append(_wall(run[leg], 3))
+            assert sc.raw_err.item() == 0
+            cards = np.array([len(fr["z_coord"]) for fr in raw])
+            U = sc.last_frames_encoded
+            med = _line(say, f"embed_raw_track, {inference.window_count(F)} windows ({U} frames)", rec)
+            say(f"  embed_raw_track rows: padded {U * N}, dedup table {table} (distinct {int(np.minimum(cards[:U], N).sum())}); "
+                f"rows padded / table {U * N / table:.2f}x, time padded / dedup {med['p'] / med['u']:.2f}x")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
@@ -184,6 +296,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace-segments", action="store_true")
     ap.add_argument("--count-trace", default=None, metavar="DIR")
+    ap.add_argument("--dedup", action="store_true")
     args = ap.parse_args()
     lines = []
 
@@ -201,6 +314,9 @@ def main():
         return write("a")
     if args.trace_segments:
         return trace_segments()
+    if args.dedup:
+        dedup_legs(args, say)
+        return write("w")
     enc, means = make_encoder()
     F_hip.set_precision("bf16")
     hop = constants.CROP_STEP
