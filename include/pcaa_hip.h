@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 25 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 26 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -674,6 +674,23 @@ int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, cons
 int pcaa_segment_weighted_mean(const void* a, int dtype, long lda, const float* weight, const int* u_off, int n, long M,
                                int ch, int N, const float* scale, const float* shift, float* out, int* err_flag,
                                void* stream);
+/* ABI 26 (frame_unique.hip): the same compact table from frames whose padding is already WRITTEN OUT (stored crops,
+ * processed tracks): frames [n, N, C] fp32, contiguous, point-major; 1 <= N <= PCAA_RAW_MAX_POINTS, 1 <= C <= 5,
+ * n * N < 2^31.  Two rows of a frame are the same point iff all their C 32-bit words are equal as BITS (-0.0 != +0.0, two
+ * NaNs are equal iff their payloads are).  u_off [n + 1] int32 = exclusive scan of the number of distinct rows per frame:
+ * two launches whatever n is (a count per frame, one workgroup's scan with a carry), nothing read back.  One workgroup per
+ * frame, the frame in LDS, integer compares only; 16-byte loads for C == 4 on a 16-B aligned base, 4-byte loads else. */
+int pcaa_frames_unique_offsets(const float* frames, int n, int N, int C, int* u_off, void* stream);
+/* ABI 26: the rows of frames a .. b - 1 (0 <= a <= b <= n) of the same frames and u_off, one launch.  With
+ * base = u_off[a], frame f owns rows u_off[f] - base .. u_off[f + 1] - base - 1 of rows [M, C] fp32 / weight [M] fp32: its
+ * distinct rows in order of first occurrence, each bit-equal to the source row, weight = the multiplicity (a frame's
+ * weights add up to N).  Rows u_off[b] - base .. M - 1 are zero with weight 0.  seg_off [b - a + 1] int32 receives the
+ * rebased offsets pcaa_segment_weighted_mean takes (an offset outside [0, M]: -1, a bad segment there).  A frame whose
+ * given segment is not exactly its number of distinct rows inside [0, M] (a u_off from other frames, an M too small)
+ * writes nothing and sets *err_flag (may be NULL); the call still returns 0.  The search runs again here: no scratch is
+ * kept from pcaa_frames_unique_offsets.  1 <= M < 2^31. */
+int pcaa_frames_unique(const float* frames, int n, int N, int C, const int* u_off, int a, int b, float* rows,
+                       float* weight, long M, int* seg_off, int* err_flag, void* stream);
 /* The adjoint w.r.t. the layer input in one launch (replaces dcol = dy . W on the im2col layout followed by
  * pcaa_dtc_col2im): da[(b,t)][ci] = sum_{co,tap} dy[b][t+(2-tap)*d][co] * W[co][ci][tap].
  *  - dy given, or formed on load from this layer's dz, y and the coefficients of pcaa_bn_bwd_finalize

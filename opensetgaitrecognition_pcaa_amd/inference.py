@@ -163,14 +163,24 @@ class OpenSetScorer:
         self.threshold = None
         self.last_frames_encoded = None      # unique frames the last deduplicated embed / embed_track encoded (no padding)
         self.last_pointnet_saves = None      # the PointNet layer records of its last chunk (which path ran)
-        self.last_rows_encoded = None        # embed_raw_track(dedup_points=True): rows of the compact tables it ran
+        self.last_rows_encoded = None        # dedup_points=True: rows of the compact tables the last call ran
         self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
+        self.unique_err = torch.zeros(1, dtype=torch.int32, device=dev)  # set by ops.frames_unique: a segment not its frame's
 
     @torch.no_grad()
-    def embed(self, pcs: torch.Tensor, dedup_frames: bool = False, hop: int = constants.CROP_STEP):
+    def embed(self, pcs: torch.Tensor, dedup_frames: bool = False, hop: int = constants.CROP_STEP,
+              dedup_points: bool = False):
         """pcs [M,C,T,N] on the device -> (preds [M] int64, sup_fv [M,32], likelihood [M] f64).
         ``dedup_frames``: for sequentially ordered crops (cut with ``hop``), encode every frame that consecutive crops
-        share bit for bit once (``_embed_dedup``); same triple, same order, one entry per crop."""
+        share bit for bit once (``_embed_dedup``); same triple, same order, one entry per crop.
+        ``dedup_points``: the stored crops carry their padding written out (``process_track`` repeats detections, every
+        copy bit-equal); every frame's DISTINCT rows go through the PointNet block once and are pooled with their
+        multiplicities (``ops.frames_unique_offsets`` / ``ops.frames_unique``,
+        ``functional.encoder_frame_features_ragged``): the same features up to fp32 summation order.  One small copy to
+        the host per call (the offsets, to plan the chunks); ``last_rows_encoded`` is the number of table rows it ran.
+        The two options multiply."""
+        if dedup_points:
+            return self._embed_points(pcs, hop, dedup_frames)
         if dedup_frames:
             return self._embed_dedup(pcs, hop)
         return self._score(F_hip.encoder_forward(self.encoder, pcs[i:i + self.batch_size], False)[:2]
@@ -185,6 +195,46 @@ class OpenSetScorer:
             fvs.append(sup_fv)
         preds, fvs = torch.cat(preds), torch.cat(fvs)
         return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
+
+    def _unique_features(self, frames):
+        """padded frames [U, N, C] -> the chunks of their [U, 1024] feature table from their distinct rows: one offsets
+        pass, ONE copy of the offsets to the host, chunks of at most the rows a padded chunk runs"""
+        U, N, C = frames.shape
+        u_off = ops.frames_unique_offsets(frames)
+        chunks = ops.plan_unique_chunks(u_off.cpu().numpy(), self.batch_size * constants.NSTEPS * N)
+        feats, self.last_rows_encoded = [], 0
+        for a, b, M in chunks:
+            rows, weight, seg_off = ops.frames_unique(frames, u_off, a, b, M, err_flag=self.unique_err)
+            f, self.last_pointnet_saves = F_hip.encoder_frame_features_ragged(self.encoder, rows, weight, seg_off, b - a, N)
+            self.last_rows_encoded += M
+            feats.append(f)
+        if self.unique_err.item():                     # u_off came from these very frames: an internal inconsistency
+            self.unique_err.zero_()
+            raise RuntimeError("OpenSetScorer: ops.frames_unique met a segment that is not its frame's (unique_err)")
+        return feats
+
+    def _embed_points(self, pcs, hop, dedup_frames):
+        """``embed(dedup_points=True)``: the crops' frames (with ``dedup_frames`` the frames consecutive crops do not
+        share, gathered once) -> their distinct rows through the PointNet block -> windows of the feature table"""
+        if not isinstance(pcs, torch.Tensor) or not pcs.is_cuda:
+            raise RuntimeError("CGEncoder: input must live on the HIP device; this package has no CPU path")
+        if pcs.dim() != 4:
+            raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(pcs.shape)}")
+        M, C, T, N = pcs.shape
+        if M == 0:
+            self.last_rows_encoded = 0
+            return _empty_triple(self.encoder.MLP_sup1[0].weight.shape[0], pcs.device)
+        xp = F_hip._point_major(pcs)                                       # [M, T, N, C] storage
+        if dedup_frames:
+            same = ops.crop_overlap(xp, hop).cpu().numpy() if M > 1 else np.zeros(0, np.int32)
+            frame_src, win_row = plan_frames(same, M, T, hop)
+            frames = ops.gather_frames(xp.view(M * T, N * C), torch.from_numpy(frame_src).to(pcs.device)).view(-1, N, C)
+            self.last_frames_encoded = len(frame_src)
+        else:
+            frames, win_row = xp.view(M * T, N, C), T * np.arange(M, dtype=np.int64)
+        feats = self._unique_features(frames)
+        table = feats[0] if len(feats) == 1 else torch.cat(feats)
+        return self._score_windows(table, ops.WindowRows(win_row, T, table.shape[0], device=pcs.device), T)
 
     def _embed_dedup(self, pcs, hop):
         """overlap mask (one launch, one small copy to the host) -> plan -> unique frames through the PointNet block ->
@@ -217,11 +267,13 @@ class OpenSetScorer:
                            for i in range(0, len(plan), self.batch_size))
 
     @torch.no_grad()
-    def embed_track(self, track: torch.Tensor, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True):
+    def embed_track(self, track: torch.Tensor, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True,
+                    dedup_points: bool = False):
         """track [F,N,C] fp32 on the device (a processed track as the packed store keeps it) -> the triple of ``embed``
         for its ``window_count(F)`` windows of NSTEPS frames, as if ``embed`` had been called on the reference's crops
         of it -- every frame encoded once, no crop ever written out.  ``drop_last_aligned=False`` also takes the
-        aligned last window the reference's rule drops when ``(F - NSTEPS) % hop == 0``."""
+        aligned last window the reference's rule drops when ``(F - NSTEPS) % hop == 0``.  ``dedup_points``: as in
+        ``embed`` -- the distinct rows of every frame once, pooled with their multiplicities."""
         _check_frames(track, "embed_track")
         F, N, C = track.shape
         T, hop = constants.NSTEPS, int(hop)
@@ -229,8 +281,12 @@ class OpenSetScorer:
         dev = track.device
         if W == 0:
             self.last_frames_encoded = 0
+            if dedup_points:
+                self.last_rows_encoded = 0
             return _empty_triple(self.encoder.MLP_sup1[0].weight.shape[0], dev)
         U = (W - 1) * hop + T                                              # frames any window uses
+        if dedup_points:
+            return self._score_track_table(self._unique_features(track[:U]), U, W, T, hop, dev)
         q = F_hip.frame_pad_quantum(N)
         step = max(self.batch_size * T // q, 1) * q
         feats = []
@@ -349,6 +405,7 @@ def naive_sequential_procedure(k, encoder, discriminator_means, *args, **kwargs)
     The REFERENCE's (inference_PCAA.py:117-125), taken when the fourth argument is a path:
     ``naive_sequential_procedure(k, encoder, discriminator_means, figures_folder, model_folder,
     scenarios_list=constants.TRAIN_SCENARIOS, seed=0, unseen_valid_ratio=0.2, force_pc_subsampling=0)``
+    (and the opt-in ``dedup_frames`` / ``dedup_points`` of ``OpenSetScorer.embed``)
     -> ``(out_log, final_preds, final_labels)``: the sequentially ordered TEST / UNSEEN splits are read from the generated
     dataset (packed once into an HBM-resident store), the procedure runs on the device, and ``naive_seq_log_{k}*.json`` is
     written into ``model_folder`` under the reference's three file names.  Not reproduced: the confusion-matrix PNG in
@@ -383,7 +440,7 @@ def _file_suffix(force_pc_subsampling, scenarios_list):
 
 def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_folder, model_folder,
                                       scenarios_list=None, seed=0, unseen_valid_ratio=0.2, force_pc_subsampling=0,
-                                      dedup_frames=False):
+                                      dedup_frames=False, dedup_points=False):
     import json
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
@@ -393,7 +450,7 @@ def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_f
     unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
     preds, labels, _ = naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pcs, known_labels, unseen_pcs,
                                                           unseen_labels, seed=seed, unseen_valid_ratio=unseen_valid_ratio,
-                                                          dedup_frames=dedup_frames)
+                                                          dedup_frames=dedup_frames, dedup_points=dedup_points)
     labels = labels.astype(int)
     out_log = _metrics(k, preds, labels)
     name = f"naive_seq_log_{k}{_file_suffix(force_pc_subsampling, scenarios_list) or ''}.json"    # both given: the plain name
@@ -404,12 +461,13 @@ def _naive_sequential_procedure_files(k, encoder, discriminator_means, figures_f
 
 def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pcs, known_labels, unseen_pcs,
                                        unseen_labels, seed=0, unseen_valid_ratio=0.2, batch_size=1024,
-                                       dedup_frames=False):
+                                       dedup_frames=False, dedup_points=False):
     """The reference's procedure on in-memory, temporally ordered crops: (1) likelihoods of
     known-test and unseen crops, 20 % of the unseen SUBJECTS (rng seed 0) held out to pick the
     threshold; (2) k-window votes on the known test set and on the remaining unseen subjects.
     Returns (open-set predictions, open-set labels, threshold).  ``dedup_frames``: frames that
-    consecutive crops share are encoded once (``OpenSetScorer.embed``)."""
+    consecutive crops share are encoded once; ``dedup_points``: the points that padding repeated
+    inside a frame are encoded once (both: ``OpenSetScorer.embed``)."""
     rng = np.random.default_rng(seed)
     scorer = OpenSetScorer(encoder, discriminator_means, batch_size)
     n_labels = int(len(np.unique(known_labels.cpu().numpy())))
@@ -417,8 +475,8 @@ def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pc
     subjects = np.unique(u_lab)
     val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
     val_mask = np.isin(u_lab, val_subjects)
-    k_preds, _, k_lik = scorer.embed(known_pcs, dedup_frames=dedup_frames)
-    u_preds, _, u_lik = scorer.embed(unseen_pcs, dedup_frames=dedup_frames)
+    k_preds, _, k_lik = scorer.embed(known_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
+    u_preds, _, u_lik = scorer.embed(unseen_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
     vm = torch.from_numpy(val_mask).to(u_lik.device)
     thr = scorer.fit_threshold(k_lik, u_lik[vm])
     preds, labels = [], []
@@ -455,14 +513,16 @@ def _sequential_split_on_device(split, scenarios_list, device):
 
 
 def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None, variation=False,
-                    generate_dataset=True, device=None, dedup_frames=False):
+                    generate_dataset=True, device=None, dedup_frames=False, dedup_points=False):
     """Open-set evaluation driver with the reference's call surface and output files
     (inference_PCAA.py:382-469): for every model and k, the naive sequential procedure on the sequentially
     ordered test / unseen splits; writes ``naive_seq_log_{k}*.json`` (accuracy, F1 micro / macro / weighted),
     ``final_preds_{k}*.npy`` / ``final_labels_{k}*.npy`` and ``naive_seq_log_subsampled{n}.json`` under
     ``models/<name>/``.  Not reproduced: the confusion-matrix PNG (plotting).  The splits are regenerated once per
     call (the reference regenerates them for every (model, k) with identical arguments).  ``dedup_frames`` (opt-in):
-    every frame that consecutive crops of the sequential splits share is encoded once."""
+    every frame that consecutive crops of the sequential splits share is encoded once.  ``dedup_points`` (opt-in): every
+    point that the stored crops' padding repeats inside a frame is encoded once (it pays most with
+    ``force_pc_subsampling``, which pads from fewer points)."""
     import json
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
@@ -483,7 +543,7 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
         for k in ks:
             preds, labels, thr = naive_sequential_procedure(k, enc, means, known_pcs, known_labels, unseen_pcs,
                                                             unseen_labels, seed=0, unseen_valid_ratio=0.2,
-                                                            dedup_frames=dedup_frames)
+                                                            dedup_frames=dedup_frames, dedup_points=dedup_points)
             labels = labels.astype(int)
             metrics = _metrics(k, preds, labels)
             with open(os.path.join(folder, f"naive_seq_log_{k}{suffix}.json"), "w") as f:
@@ -569,7 +629,9 @@ class StreamingScorer(_LiveScorer):
     @torch.no_grad()
     def push(self, frames: torch.Tensor):
         """frames [n,N,C] fp32 on the device, the next n frames of the track -> (preds, sup_fv, likelihood) of the windows
-        they complete (possibly none: empty tensors)."""
+        they complete (possibly none: empty tensors).  No ``dedup_points`` here: the host would have to read the number
+        of distinct rows back before it launches the GEMMs, and a live tick must not wait for the device;
+        ``push_raw`` with the constructor's ``dedup_points`` is the live route (its table is sized from the offsets)."""
         self._check_eval()
         _check_frames(frames, "StreamingScorer.push")
         return self._gather([self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)])
@@ -860,7 +922,9 @@ class MultiStreamScorer(_LiveScorer):
     def push(self, sids, counts, frames: torch.Tensor) -> Tick:
         """``sids``: distinct open slots (host ints); ``counts[i]`` new frames of ``sids[i]`` (0 allowed, at most
         ``max_push``); ``frames`` [sum(counts), N, C] fp32 on the device, concatenated in that order -> the Tick of the
-        windows these frames complete (possibly none: empty tensors, no temporal pass)."""
+        windows these frames complete (possibly none: empty tensors, no temporal pass).  No ``dedup_points`` here: the
+        host would have to read the number of distinct rows back before it launches the GEMMs, and a live tick must not
+        wait for the device; ``push_raw`` with the constructor's ``dedup_points`` is the live route."""
         self._check_eval()
         _check_frames(frames, "MultiStreamScorer.push")
         n, N, C = frames.shape

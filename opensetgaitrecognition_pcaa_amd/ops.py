@@ -1600,8 +1600,7 @@ UNIQUE_ROW_QUANTUM = 256  # rows of the compact table: whole 256-row GEMM tiles 
 def unique_table_rows(P, n, N):
     """M of ``frames_from_raw_unique``: frame f owns min(card_f, N) rows, a bad frame one, so for ascending offsets the
     frames own at most min(P + n, n N) rows; rounded up to whole GEMM tiles (at least one)."""
-    need = max(min(int(P) + int(n), int(n) * int(N)), 1)
-    return (need + UNIQUE_ROW_QUANTUM - 1) // UNIQUE_ROW_QUANTUM * UNIQUE_ROW_QUANTUM
+    return unique_chunk_rows(min(int(P) + int(n), int(n) * int(N)))
 
 
 def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
@@ -1652,6 +1651,94 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
         _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s()), "pcaa_frames_from_raw_unique"),
         0.0, points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4)
     return rows, weight, u_off
+
+
+def _chk_padded_frames(frames, who):
+    """what frames_unique_offsets and frames_unique refuse before any launch -> (n, N, C)"""
+    _chk(frames, who + ".frames", torch.float32, 3)
+    n, N, C = frames.shape
+    if not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5 or n * N >= 2 ** 31:
+        raise ValueError(f"{who}: needs frames [n, N, C] with 1 <= N <= {RAW_MAX_POINTS}, 1 <= C <= 5, n N < 2^31; got "
+                         f"{tuple(frames.shape)}")
+    return n, N, C
+
+
+def frames_unique_offsets(frames):
+    """Padded frames -> where their distinct rows go (pcaa_frames_unique_offsets): ``frames`` fp32 contiguous point-major
+    [n, N, C] -> ``u_off`` int32 [n + 1] on the device, the exclusive scan of the number of distinct rows per frame (rows
+    are equal iff their C words are equal as bits).  Two launches whatever n is; nothing comes back to the host."""
+    n, N, C = _chk_padded_frames(frames, "frames_unique_offsets")
+    u_off = torch.empty(n + 1, dtype=torch.int32, device=frames.device)
+    _timed("frames_unique_count_kernel", lambda: check(_lib.load().pcaa_frames_unique_offsets(
+        _p(frames), n, N, C, _p(u_off), _s()), "pcaa_frames_unique_offsets"), 0.0, n * N * C * 4 + (n + 1) * 8)
+    return u_off
+
+
+def frames_unique(frames, u_off, a=0, b=None, M=None, out=None, err_flag=None):
+    """The compact table of frames ``a .. b - 1`` (pcaa_frames_unique; ``u_off`` from ``frames_unique_offsets`` of the same
+    frames) -> ``(rows [M, C] fp32, weight [M] fp32, seg_off [b - a + 1] int32)``, the contract of
+    ``frames_from_raw_unique``: frame f owns rows ``seg_off[f - a] .. seg_off[f - a + 1] - 1``, its distinct rows in order
+    of first occurrence, bit-equal to the source rows, ``weight`` the multiplicity (a frame's weights add up to N); the
+    rows behind the last frame are zero with weight 0.  ``M`` defaults to the chunk's rows (``unique_chunk_rows``) and must
+    be a multiple of UNIQUE_ROW_QUANTUM; without it (and without ``out``) two entries of ``u_off`` are read back, so a
+    caller that must not wait passes it (``plan_unique_chunks`` gives it).  ``out=(rows, weight)``: the caller's buffers.  A frame whose given segment
+    is not its own (a ``u_off`` of other frames, an ``M`` too small) writes nothing and sets ``err_flag`` (int32 [1])."""
+    n, N, C = _chk_padded_frames(frames, "frames_unique")
+    _chk(u_off, "frames_unique.u_off", torch.int32, 1)
+    a, b = int(a), n if b is None else int(b)
+    if u_off.numel() != n + 1 or not 0 <= a <= b <= n:
+        raise ValueError(f"frames_unique: needs u_off [n + 1 = {n + 1}] and 0 <= a <= b <= n, got u_off "
+                         f"{tuple(u_off.shape)}, a={a}, b={b}")
+    if M is None and out is not None:
+        M = out[0].shape[0]
+    if M is None:
+        lo, hi = u_off[[a, b]].tolist()
+        M = unique_chunk_rows(hi - lo)
+    M = int(M)
+    if not 1 <= M < 2 ** 31 or M % UNIQUE_ROW_QUANTUM:
+        raise ValueError(f"frames_unique: M must be a positive multiple of {UNIQUE_ROW_QUANTUM} below 2^31, got {M}")
+    if err_flag is not None:
+        _chk(err_flag, "frames_unique.err_flag", torch.int32)
+    dev = frames.device
+    if out is None:
+        rows = torch.empty((M, C), dtype=torch.float32, device=dev)
+        weight = torch.empty(M, dtype=torch.float32, device=dev)
+    else:
+        rows, weight = out
+        _chk(rows, "frames_unique.out[0]", torch.float32, 2)
+        _chk(weight, "frames_unique.out[1]", torch.float32, 1)
+        if tuple(rows.shape) != (M, C) or weight.numel() != M:
+            raise ValueError(f"frames_unique: out must be ([{M}, {C}], [{M}]), got {tuple(rows.shape)}, {tuple(weight.shape)}")
+    seg_off = torch.empty(b - a + 1, dtype=torch.int32, device=dev)
+    _timed("frames_unique_kernel", lambda: check(_lib.load().pcaa_frames_unique(
+        _p(frames), n, N, C, _p(u_off), a, b, _p(rows), _p(weight), M, _p(seg_off), _p(err_flag), _s()),
+        "pcaa_frames_unique"), 0.0, (b - a) * N * C * 4 + M * (C + 1) * 4)
+    return rows, weight, seg_off
+
+
+def unique_chunk_rows(need):
+    """rows of a compact table that holds ``need`` distinct rows: whole GEMM tiles, at least one"""
+    return max((int(need) + UNIQUE_ROW_QUANTUM - 1) // UNIQUE_ROW_QUANTUM, 1) * UNIQUE_ROW_QUANTUM
+
+
+def plan_unique_chunks(u_off_host, budget_rows):
+    """Host plan of the chunks of a padding-free pass: ``u_off_host`` [n + 1] (the host copy of ``frames_unique_offsets``),
+    ``budget_rows`` >= the largest frame -> ``[(a, b, M)]``: consecutive frame ranges that cover 0 .. n, each as long as
+    its distinct rows total at most ``budget_rows``; ``M = unique_chunk_rows`` of that total.  n == 0: no chunk."""
+    import numpy as np
+    u = np.asarray(u_off_host, dtype=np.int64).reshape(-1)
+    n, budget = u.size - 1, int(budget_rows)
+    if n < 0 or (n and (u[0] != 0 or (np.diff(u) < 0).any())):
+        raise ValueError("plan_unique_chunks: needs ascending offsets [n + 1] that start at 0")
+    if n and int(np.diff(u).max()) > budget:
+        raise ValueError(f"plan_unique_chunks: a frame of {int(np.diff(u).max())} rows exceeds the budget of {budget}")
+    chunks, a = [], 0
+    while a < n:
+        b = int(np.searchsorted(u, u[a] + budget, side="right")) - 1      # the last b with u[b] - u[a] <= budget
+        b = min(max(b, a + 1), n)
+        chunks.append((a, b, unique_chunk_rows(int(u[b] - u[a]))))
+        a = b
+    return chunks
 
 
 def segment_weighted_mean(a, weight, u_off, N, scale=None, shift=None, err_flag=None):
