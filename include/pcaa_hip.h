@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 26 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 27 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -610,6 +610,16 @@ int pcaa_gather_rows_w4(const void* src, long n_src_rows, long row_words, const 
  * are 16-B aligned, 4-byte copies otherwise. */
 int pcaa_scatter_rows(const void* src, const int* dst_row, long n_rows, long row_words, void* dst, long n_dst_rows,
                       int* err_flag, void* stream);
+/* ABI 27: the adjoint of the row gather (dst[r] = src[idx[r]]), the overlap-add of window gradients into a frame-feature
+ * table: dst[u] = sum_{k = csr_off[u]}^{csr_off[u + 1] - 1} src[csr_idx[k]] for n_dst_rows rows of row_words fp32 words
+ * (csr_off [n_dst_rows + 1], csr_idx [nnz]: device ints; the CSR of idx by destination row).  The sum starts from +0 and
+ * adds the contributors in ascending k in fp32 with plain adds (no contraction, no atomics): the result is a function of
+ * the CSR alone and is reproduced bit for bit by the same loop on the host.  A row without contributors is zero.  An
+ * index outside [0, n_src_rows) is skipped and sets *err_flag (may be NULL); a row whose offsets leave [0, nnz] is
+ * written as zeros and sets it too.  16-byte accesses when row_words % 4 == 0 and src and dst are 16-B aligned, 4-byte
+ * accesses otherwise.  dst may not alias src. */
+int pcaa_gather_sum_rows(const float* src, long n_src_rows, long row_words, const int* csr_off, const int* csr_idx,
+                         long nnz, float* dst, long n_dst_rows, int* err_flag, void* stream);
 /* ABI 19: one tick of a multi-stream scorer in one launch: for the tick's nw windows preds[i] (first maximal softmax
  * probability: the want_preds rule of pcaa_cross_entropy) and lik[i] (the expression of pcaa_joint_likelihood, same bits),
  * and for every window with win_j[i] % k == k - 1 the vote of group win_j[i] / k by the rule of pcaa_kvote, written to
@@ -674,6 +684,26 @@ int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, cons
 int pcaa_segment_weighted_mean(const void* a, int dtype, long lda, const float* weight, const int* u_off, int n, long M,
                                int ch, int N, const float* scale, const float* shift, float* out, int* err_flag,
                                void* stream);
+/* ABI 27 (segment_pool.hip): the adjoint of pcaa_segment_weighted_mean in its (scale, shift) form, and the ragged form of
+ * pcaa_bn_eval_act_bwd's (dpool, y) mode.  For row r of segment f (u_off[f] <= r < u_off[f + 1]) and channel c:
+ *   g = dpool[f, c] * (weight[r] / N),  dz = g * ELU'(y[r, c] * scale[c] + shift[c]),  dy[r, c] = scale[c] * dz
+ * (dy in y's dtype, fp32 or bf16; y and dy [M, ch] with the same leading dimension lda; dpool [n, ch] fp32), and
+ *   stats += { sum_r dz, sum_r dz * (y - mean) * rstd }   ([nrep][2][ch] fp64, ZEROED by the caller)
+ * with (mean, rstd) of pcaa_bn_eval_moments; pcaa_bn_eval_bwd_finalize turns them into dgamma, dbeta and dbias.  The
+ * statistics are summed in fp32 over at most 128 consecutive rows of a segment, then in fp64 (one fp64 atomic per
+ * workgroup, statistic and channel), so their error does not grow with the cardinality.  dy is zero-filled by the call
+ * before its kernel runs: every row that no valid segment owns (the rows from u_off[n] on, the rows of a bad segment)
+ * is zero.  A segment with u_off[f] < 0, u_off[f + 1] < u_off[f] or u_off[f + 1] > M contributes nothing and sets
+ * *err_flag (may be NULL): no fault.  Valid segments must be DISJOINT: validity is checked segment by segment.  With
+ * non-decreasing offsets they are; two valid segments can only share rows behind a segment that runs backwards, which
+ * sets *err_flag -- in such a call the shared rows of dy hold the value of either segment and the statistics count them
+ * once per segment (nothing faults, every other row is as stated); a caller that finds the flag set discards the result.
+ * One workgroup per (segment, 512 channels), 16-byte accesses: ch % 8 == 0, lda % 8 == 0, dpool / y / dy / scale / shift /
+ * mean / rstd 16-B aligned.  dy may not alias y. */
+int pcaa_segment_weighted_mean_bwd(const float* dpool, const void* y, void* dy, int dtype, long lda, const float* weight,
+                                   const int* u_off, int n, long M, int ch, int N, const float* scale,
+                                   const float* shift, const float* mean, const float* rstd, double* stats, int nrep,
+                                   int* err_flag, void* stream);
 /* ABI 26 (frame_unique.hip): the same compact table from frames whose padding is already WRITTEN OUT (stored crops,
  * processed tracks): frames [n, N, C] fp32, contiguous, point-major; 1 <= N <= PCAA_RAW_MAX_POINTS, 1 <= C <= 5,
  * n * N < 2^31.  Two rows of a frame are the same point iff all their C 32-bit words are equal as BITS (-0.0 != +0.0, two

@@ -7,24 +7,23 @@ such (functional.encoder_backward on an eval-mode state: one pass per BatchNorm 
 """
 import torch
 
-from .functional import cross_entropy_loss
+from . import constants
+from .functional import cross_entropy_loss, encode_track_batch, plan_tracks, track_windows
 
 HEADS = ("MLP_sup1", "MLP_head", "MLP_sup2")
 
 
-def finetune_frozen_bn(encoder, pcs, labels, steps, lr, params="heads"):
-    """``steps`` Adam steps (torch.optim.Adam, default betas) on ``cross_entropy_loss(encoder(pcs)[0], labels)`` with the
-    encoder in eval mode.  ``params``: ``"heads"`` updates ``MLP_sup1`` / ``MLP_head`` / ``MLP_sup2`` only (the trunk's
-    parameters receive no gradient and keep their bits), ``"all"`` every parameter -- the biases in front of the
-    BatchNorms included, whose gradients are real in eval mode.  ``pcs`` [B,C,T,N] and ``labels`` [B] live on the device.
-    Returns the per-step losses (floats, the loss BEFORE each update); restores the train / eval mode it found and the
-    parameters' ``requires_grad`` flags."""
+def _chosen(encoder, params, who):
     if params not in ("heads", "all"):
-        raise ValueError(f"finetune_frozen_bn: params must be 'heads' or 'all', got {params!r}")
+        raise ValueError(f"{who}: params must be 'heads' or 'all', got {params!r}")
     if params == "heads":
-        chosen = [p for h in HEADS if hasattr(encoder, h) for p in getattr(encoder, h).parameters()]
-    else:
-        chosen = list(encoder.parameters())
+        return [p for h in HEADS if hasattr(encoder, h) for p in getattr(encoder, h).parameters()]
+    return list(encoder.parameters())
+
+
+def _adam_steps(encoder, chosen, steps, lr, loss_fn):
+    """``steps`` Adam steps on ``loss_fn()`` over ``chosen`` with the encoder in eval mode; the mode and the parameters'
+    ``requires_grad`` flags are restored.  -> the losses before each update"""
     chosen_ids = {id(p) for p in chosen}
     flags = [(p, p.requires_grad) for p in encoder.parameters()]
     was_training = encoder.training
@@ -36,8 +35,7 @@ def finetune_frozen_bn(encoder, pcs, labels, steps, lr, params="heads"):
             p.requires_grad_(id(p) in chosen_ids)
         for _ in range(int(steps)):
             opt.zero_grad(set_to_none=True)
-            logits, _ = encoder(pcs)
-            loss = cross_entropy_loss(logits, labels)
+            loss = loss_fn()
             loss.backward()
             opt.step()
             losses.append(loss.detach())
@@ -46,3 +44,48 @@ def finetune_frozen_bn(encoder, pcs, labels, steps, lr, params="heads"):
             p.requires_grad_(f)
         encoder.train(was_training)
     return [float(l) for l in losses]
+
+
+def finetune_frozen_bn(encoder, pcs, labels, steps, lr, params="heads"):
+    """``steps`` Adam steps (torch.optim.Adam, default betas) on ``cross_entropy_loss(encoder(pcs)[0], labels)`` with the
+    encoder in eval mode.  ``params``: ``"heads"`` updates ``MLP_sup1`` / ``MLP_head`` / ``MLP_sup2`` only (the trunk's
+    parameters receive no gradient and keep their bits), ``"all"`` every parameter -- the biases in front of the
+    BatchNorms included, whose gradients are real in eval mode.  ``pcs`` [B,C,T,N] and ``labels`` [B] live on the device.
+    Returns the per-step losses (floats, the loss BEFORE each update); restores the train / eval mode it found and the
+    parameters' ``requires_grad`` flags."""
+    chosen = _chosen(encoder, params, "finetune_frozen_bn")
+    return _adam_steps(encoder, chosen, steps, lr, lambda: cross_entropy_loss(encoder(pcs)[0], labels))
+
+
+def finetune_frozen_bn_tracks(encoder, tracks, labels, steps, lr, params="heads", hop=None, dedup_points=False):
+    """``finetune_frozen_bn`` on whole walks instead of crops: ``tracks`` is a list of processed tracks [F,N,C] (fp32, on
+    the device), ``labels`` [len(tracks)] one label per walk, repeated over that track's windows (those of
+    ``OpenSetScorer.embed_track``).  The loss is ``cross_entropy_loss`` over all windows of all tracks; every frame goes
+    through the PointNet block once per step instead of once per window it lies in, all walks in one pass
+    (``functional.cg_encoder_tracks``; ``dedup_points``: every frame's distinct detections once, found before the first
+    step; ``hop``: None = CROP_STEP).  Everything else is ``finetune_frozen_bn``'s contract: eval
+    mode, buffers untouched, the mode and the ``requires_grad`` flags restored, the returned floats are the losses before
+    each update.  A track too short for a window raises ValueError.  Each step keeps every track's activations for the
+    backward (see ``cg_encoder_tracks``): the caller bounds the walks."""
+    chosen = _chosen(encoder, params, "finetune_frozen_bn_tracks")
+    tracks = list(tracks)
+    if len(tracks) < 1 or labels.dim() != 1 or labels.numel() != len(tracks):
+        raise ValueError(f"finetune_frozen_bn_tracks: needs at least one track and labels [{len(tracks)}], got "
+                         f"{tuple(labels.shape)}")
+    hop = constants.CROP_STEP if hop is None else int(hop)
+    counts = []
+    for i, t in enumerate(tracks):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"finetune_frozen_bn_tracks: track {i} is not a [F,N,C] tensor")
+        W, _ = track_windows(t.shape[0], constants.NSTEPS, hop)
+        if W == 0:
+            raise ValueError(f"finetune_frozen_bn_tracks: track {i} has {t.shape[0]} frames, too short for a window of "
+                             f"{constants.NSTEPS} (hop {hop})")
+        counts.append(W)
+    win_labels = torch.repeat_interleave(labels, torch.tensor(counts, device=labels.device)).contiguous()
+
+    # the tracks do not change between the steps: their frames are gathered, their windows planned and (dedup_points)
+    # their distinct rows found ONCE -- the host copy of the offsets and the read of the error flag stay out of the loop
+    batch = plan_tracks(encoder, tracks, hop, True, dedup_points, who="finetune_frozen_bn_tracks")
+    return _adam_steps(encoder, chosen, steps, lr,
+                       lambda: cross_entropy_loss(encode_track_batch(encoder, batch)[0], win_labels))

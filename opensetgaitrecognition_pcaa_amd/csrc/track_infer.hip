@@ -6,7 +6,8 @@
 // frame at a time (models.py:82-105, 242-243), so a shared frame needs encoding once.  Here:
 //   * pcaa_crop_overlap    -- which consecutive crops share their overlap bit for bit (the mask the plan is built from);
 //   * pcaa_gather_rows_w4  -- the row gather for frames that are not a multiple of 16 bytes (N = 150, C = 5: 3 000 B);
-//   * pcaa_scatter_rows    -- the inverse of the row gather: a tick's frame features into the rings of many live streams.
+//   * pcaa_scatter_rows    -- the inverse of the row gather: a tick's frame features into the rings of many live streams;
+//   * pcaa_gather_sum_rows -- the adjoint of the row gather: window gradients added up into the frame-feature table.
 // The windowed read of the frame-feature table is an addressing mode of the temporal block's kernels (dtc_fused.hip).
 #include "common.h"
 
@@ -88,6 +89,39 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const V* __restrict__
   }
 }
 
+// dst[u] = sum_{k = csr_off[u]}^{csr_off[u + 1] - 1} src[csr_idx[k]]: the adjoint of the row gather, the overlap-add of the
+// window gradients into the frame-feature table.  One thread per (table row, vector) walks the row's contributors in
+// ascending k and adds them to +0 in fp32: plain adds, no atomics, so the result is a function of the CSR alone.  A row
+// without contributors is zero; an index outside the source is skipped and flagged, and so is a row whose offsets leave
+// [0, nnz] (it is written as zeros).
+template <typename V>
+__global__ __launch_bounds__(256) void gather_sum_rows_kernel(const V* __restrict__ src, long n_src,
+                                                              const int* __restrict__ csr_off,
+                                                              const int* __restrict__ csr_idx, long nnz,
+                                                              V* __restrict__ dst, long n_dst, long row_vec,
+                                                              int* __restrict__ err) {
+#pragma clang fp contract(off)
+  const long total = n_dst * row_vec;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < total; v += (long)gridDim.x * 256) {
+    const long u = v / row_vec, off = v - u * row_vec;
+    long k0 = csr_off[u], k1 = csr_off[u + 1];
+    if (k0 < 0 || k1 < k0 || k1 > nnz) {
+      if (err != nullptr && off == 0) atomicOr(err, 1);
+      k0 = k1 = 0;
+    }
+    V acc = {};
+    for (long k = k0; k < k1; ++k) {
+      const long i = csr_idx[k];
+      if (i < 0 || i >= n_src) {
+        if (err != nullptr && off == 0) atomicOr(err, 1);
+        continue;
+      }
+      acc += src[i * row_vec + off];
+    }
+    dst[v] = acc;
+  }
+}
+
 }  // namespace
 
 extern "C" int pcaa_crop_overlap_vec_bytes(const float* crops, long crop_elems, long frame_elems) {
@@ -141,4 +175,27 @@ extern "C" int pcaa_scatter_rows(const void* src, const int* dst_row, long n_row
                        reinterpret_cast<const uint32_t*>(src), dst_row, n_dst_rows, reinterpret_cast<uint32_t*>(dst), n_rows,
                        row_vec, err_flag);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_scatter_rows");
+}
+
+extern "C" int pcaa_gather_sum_rows(const float* src, long n_src_rows, long row_words, const int* csr_off,
+                                    const int* csr_idx, long nnz, float* dst, long n_dst_rows, int* err_flag,
+                                    void* stream) {
+  PCAA_CHECK_ARG(src && csr_off && dst && (csr_idx || nnz == 0), "pcaa_gather_sum_rows: null pointer");
+  PCAA_CHECK_ARG(n_src_rows >= 1 && n_dst_rows >= 1 && row_words >= 1 && nnz >= 0 && nnz < (1L << 31),
+                 "pcaa_gather_sum_rows: needs n_src_rows, n_dst_rows, row_words >= 1 and 0 <= nnz < 2^31");
+  PCAA_CHECK_ARG(((uintptr_t)src % 4) == 0 && ((uintptr_t)dst % 4) == 0 && ((uintptr_t)csr_off % 4) == 0 &&
+                     ((uintptr_t)csr_idx % 4) == 0, "pcaa_gather_sum_rows: 4-B alignment");
+  PCAA_CHECK_ARG(src != dst, "pcaa_gather_sum_rows: dst may not alias src");
+  const bool v16 = row_words % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
+  const long row_vec = v16 ? row_words / 4 : row_words;
+  const long want = cdiv(n_dst_rows * row_vec, 256);
+  const dim3 grid((unsigned)(want > 4096 ? 4096 : want));
+  if (v16)
+    hipLaunchKernelGGL(gather_sum_rows_kernel<f32x4>, grid, dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const f32x4*>(src), n_src_rows, csr_off, csr_idx, nnz,
+                       reinterpret_cast<f32x4*>(dst), n_dst_rows, row_vec, err_flag);
+  else
+    hipLaunchKernelGGL(gather_sum_rows_kernel<float>, grid, dim3(256), 0, as_stream(stream), src, n_src_rows, csr_off,
+                       csr_idx, nnz, dst, n_dst_rows, row_vec, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_gather_sum_rows");
 }

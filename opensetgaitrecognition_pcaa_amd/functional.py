@@ -23,6 +23,8 @@ import math
 import os
 import itertools
 
+import numpy as np
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -413,6 +415,15 @@ def _fused_coefficients(da, s, bn, outs):
                                dbeta=outs[2] if outs else None)
 
 
+class _RaggedPool:
+    """In the ``group_rows`` place of a ``pool=`` tuple: the pooled groups are the ragged segments ``u_off`` of the rows,
+    row r counted ``weight[r]`` times out of N (ops.segment_weighted_mean) -- eval mode only."""
+    __slots__ = ("weight", "u_off", "N")
+
+    def __init__(self, weight, u_off, N):
+        self.weight, self.u_off, self.N = weight, u_off, int(N)
+
+
 def _bn_dy(s, bn, da, pool, lhs_split, outs, lin_bias, dbias_out, adjoint_dy=None):
     """First stage: the gradient w.r.t. the pre-BatchNorm ``s.y``, from ``da`` (tensor or _FusedGrad) or ``pool``, and the
     BatchNorm gradients.  ``lhs_split``: dy is wanted as a SplitImage; ``adjoint_dy``: the caller's adjoint when it forms dy
@@ -427,11 +438,18 @@ def _bn_dy(s, bn, da, pool, lhs_split, outs, lin_bias, dbias_out, adjoint_dy=Non
     # is issued whatever the SyncBN setting
     if s.mean is None:
         emean, erstd = ops.bn_eval_moments(bn, s.cout, lin_bias)
-        dy, stats = ops.bn_eval_act_bwd(y, s.scale, s.shift, emean, erstd, out=da, **grad)
+        if isinstance(group_rows, _RaggedPool):
+            # the layer's output was pooled over ragged segments with multiplicities (frame_features_ragged)
+            dy, stats = ops.segment_weighted_mean_bwd(dpool, y, group_rows.weight, group_rows.u_off, group_rows.N,
+                                                      s.scale, s.shift, emean, erstd)
+        else:
+            dy, stats = ops.bn_eval_act_bwd(y, s.scale, s.shift, emean, erstd, out=da, **grad)
         dgamma, dbeta, dbias = ops.bn_eval_bwd_finalize(stats, s.scale, s.cout, dgamma=outs[1] if outs else None,
                                                         dbeta=outs[2] if outs else None,
                                                         dbias=dbias_out if lin_bias is not None else None)
         return dy, dgamma, dbeta, dbias, None
+    if isinstance(group_rows, _RaggedPool):
+        raise RuntimeError("a ragged pool is an eval-mode form (train-mode BatchNorm would need weighted batch statistics)")
     # ---- fused: the dgrad above already applied ELU' and reduced the statistics
     if isinstance(da, _FusedGrad):
         coef, dgamma, dbeta = _fused_coefficients(da, s, bn, outs)
@@ -616,9 +634,11 @@ def _layer_grads(names, conv, dW, dgamma, dbeta, dbias, bias_out):
 
 
 def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0, need_dx=False, gout=None,
-                      prefix="pc_block.pointnet"):
+                      prefix="pc_block.pointnet", ragged=None):
     """Returns ({param_name_suffix: grad} per layer list, dx2d or None).  ``gout``:
-    optional {state_dict name: pre-zeroed gradient view} to write into."""
+    optional {state_dict name: pre-zeroed gradient view} to write into.  ``ragged`` (a _RaggedPool, with ``dpool``; eval-mode
+    saves of a ``last_pre_bn`` forward): the last layer was pooled by ops.segment_weighted_mean instead of over groups of
+    ``pool_rows`` rows."""
     grads = []
     da = d_last
     for li in range(len(layers) - 1, -1, -1):
@@ -661,7 +681,8 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
             below = (saves[li - 1], layers[li - 1].module[1],
                      _layer_outs(gout, f"{prefix}{li}.", _PN_NAMES)[0]) if li > 0 else None
             dW, dg, db, dbias, dprev = _bn_layer_backward(s, bn, W2d, mode, s.a_in, da=None if pooled else da,
-                                                          pool=(dpool, pool_rows, 1.0 / pool_rows) if pooled else None,
+                                                          pool=((dpool, ragged, 1.0) if ragged is not None else
+                                                                (dpool, pool_rows, 1.0 / pool_rows)) if pooled else None,
                                                           need_dinput=need_in, outs=outs, below=below,
                                                           lin_bias=conv.bias, dbias_out=bias_out)
         grads.append(_layer_grads(_PN_NAMES, conv, dW, dg, db, dbias, bias_out))
@@ -1112,8 +1133,34 @@ def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, befor
     if not getattr(st, "want_bwd", st.training):
         raise RuntimeError("encoder_backward: this eval-mode forward kept nothing for a backward -- "
                            "call encoder_forward(..., want_bwd=True)")
-    g = {}
     B, T, N = st.B, st.T, st.N
+    g, dx4 = _encoder_heads_backward(enc, st, d_logits, d_supfv, gout, gph, d_hproj, gph_gout)
+    mark("enc_bwd.heads")
+    if after_heads is not None:
+        after_heads()            # trainer hook: the heads' backward is enqueued, the temporal block follows
+    dg, dx2 = dtc_backward(st.dtc, enc.tc_block.layers(), B, T, dpool=dx4, need_dx=True, gout=gout, mode=st.mode)
+    mark("enc_bwd.dtc")
+    for i, d in enumerate(dg, start=1):
+        for k, v in d.items():
+            g[f"tc_block.dtc{i}.{k}"] = v
+    if before_pointnet is not None:
+        before_pointnet()        # trainer hook: everything enqueued so far is the latency-bound part of the backward
+    pg, dxp = pointnet_backward(st.pn, enc.pc_block.layers(), st.mode, dpool=dx2, pool_rows=N, need_dx=need_dx,
+                                gout=gout)
+    for i, d in enumerate(pg, start=1):
+        for k, v in d.items():
+            g[f"pc_block.pointnet{i}.{k}"] = v
+    mark("enc_bwd.pointnet")
+    dx = None
+    if need_dx:
+        dx = dxp.float().view(B, T, N, st.C).permute(0, 3, 1, 2)
+    return g, dx
+
+
+def _encoder_heads_backward(enc, st, d_logits, d_supfv, gout=None, gph=None, d_hproj=None, gph_gout=None):
+    """The MLP heads' part of encoder_backward (arguments as there) -> ({name: grad}, dx4 [B, 512])"""
+    g = {}
+    B = st.B
 
     def dst(name):
         return (gout[name + ".weight"], gout[name + ".bias"]) if gout is not None else (None, None)
@@ -1172,26 +1219,7 @@ def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, befor
         w_o, b_o = dst("MLP_sup1.0")
         dW, db, dx4 = linear_act_backward(st.x4, st.sup_fv, enc.MLP_sup1[0], ACT_ELU, dsup, dW_out=w_o, db_out=b_o)
         g["MLP_sup1.0.weight"], g["MLP_sup1.0.bias"] = dW, db
-    mark("enc_bwd.heads")
-    if after_heads is not None:
-        after_heads()            # trainer hook: the heads' backward is enqueued, the temporal block follows
-    dg, dx2 = dtc_backward(st.dtc, enc.tc_block.layers(), B, T, dpool=dx4, need_dx=True, gout=gout, mode=st.mode)
-    mark("enc_bwd.dtc")
-    for i, d in enumerate(dg, start=1):
-        for k, v in d.items():
-            g[f"tc_block.dtc{i}.{k}"] = v
-    if before_pointnet is not None:
-        before_pointnet()        # trainer hook: everything enqueued so far is the latency-bound part of the backward
-    pg, dxp = pointnet_backward(st.pn, enc.pc_block.layers(), st.mode, dpool=dx2, pool_rows=N, need_dx=need_dx,
-                                gout=gout)
-    for i, d in enumerate(pg, start=1):
-        for k, v in d.items():
-            g[f"pc_block.pointnet{i}.{k}"] = v
-    mark("enc_bwd.pointnet")
-    dx = None
-    if need_dx:
-        dx = dxp.float().view(B, T, N, st.C).permute(0, 3, 1, 2)
-    return g, dx
+    return g, dx4
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -1202,7 +1230,9 @@ class _EncoderFn(torch.autograd.Function):
         ctx.enc, ctx.st = enc, st
         ctx.need_dx = x.requires_grad
         ctx.names = [n for n, _ in enc.named_parameters()]
-        return logits, sup_fv
+        # the state keeps logits and sup_fv for the heads' backward: hand out aliases, or the outputs (whose grad_fn is
+        # this node) and the node (whose state holds them) keep each other, and a step's activations, alive
+        return logits.detach(), sup_fv.detach()
 
     @staticmethod
     @once_differentiable
@@ -1223,6 +1253,312 @@ def _want_bwd(x, params):
     """the "a backward will follow" switch of an eval-mode forward, decided where autograd's state can still be seen
     (inside Function.forward grad mode is off): the condition cg_encoder tests"""
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+
+
+# ---------------------------------------------------------------- the track routes, differentiable in eval mode
+# A deployment's data arrives as tracks: every frame goes through the PointNet block ONCE (frame_features; from its
+# distinct detections with their multiplicities: frame_features_ragged) into a frame-feature table, and the temporal
+# block and the heads read windows of that table (windows_forward).  The three pieces are autograd Functions that chain:
+# the window gradients are overlap-added into the table's gradient (ops.gather_sum_rows), which is the pooled gradient
+# the PointNet backward starts from.  Eval mode only: BatchNorm is the fixed map of its running statistics, which are
+# read and never written.
+def _check_track_eval(enc, who):
+    if enc.training:
+        raise RuntimeError(f"{who}: the encoder is in training mode (batch statistics would need weighted moments); "
+                           "call encoder.eval()")
+
+
+def _pointnet_param_grads(enc, grads):
+    """pointnet_backward's per-layer dicts -> the gradients in the order of enc.pc_block.named_parameters()"""
+    g = {f"pointnet{i}.{k}": v for i, d in enumerate(grads, start=1) for k, v in d.items()}
+    return tuple(g.get(n) for n, _ in enc.pc_block.named_parameters())
+
+
+class _FrameFeaturesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, enc, x, ragged, *params):
+        # (frame_features / frame_features_ragged only come here when a gradient is wanted)
+        mode = get_precision()
+        layers = enc.pc_block.layers()
+        if ragged is None:
+            U, N, C = x.shape
+            out, saves = pointnet_forward(x.view(U * N, C), layers, False, mode, pool_rows=N, want_bwd=True)
+        else:
+            y, saves = pointnet_forward(x, layers, False, mode, pool_rows=0, want_bwd=True, last_pre_bn=True)
+            last = saves[-1]
+            if last.y is None:
+                raise RuntimeError("frame_features_ragged: the last PointNet layer kept no pre-BatchNorm y")
+            out = ops.segment_weighted_mean(y, ragged.weight, ragged.u_off, ragged.N, last.scale, last.shift)
+        ctx.enc, ctx.saves, ctx.mode, ctx.ragged = enc, saves, mode, ragged
+        ctx.x_shape, ctx.need_dx = tuple(x.shape), x.requires_grad
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dfeats):
+        enc, ragged = ctx.enc, ctx.ragged
+        N = ragged.N if ragged is not None else ctx.x_shape[1]
+        grads, dxp = pointnet_backward(ctx.saves, enc.pc_block.layers(), ctx.mode, dpool=dfeats.contiguous(), pool_rows=N,
+                                       need_dx=ctx.need_dx, ragged=ragged)
+        dx = dxp.float().view(ctx.x_shape) if ctx.need_dx else None
+        return (None, dx, None) + _pointnet_param_grads(enc, grads)
+
+
+def frame_features(enc, frames):
+    """Eval-mode PointNet block + mean over the points, frame by frame: point-major ``frames`` [U, N, C] fp32 -> [U, 1024]
+    fp32.  With no gradient wanted this is ``encoder_frame_features`` (same bits); with one (autograd on, ``frames`` or a
+    parameter of the PointNet block requires it) the forward keeps every layer's pre-BatchNorm y and the backward is ``pointnet_backward`` on the
+    eval-mode saves: parameter gradients (the biases in front of the BatchNorms included) and, when ``frames`` requires
+    it, the gradient w.r.t. the frames.  No BatchNorm buffer is written.  Raises in training mode."""
+    _check_track_eval(enc, "frame_features")
+    if not _want_bwd(frames, enc.pc_block.parameters()):
+        return encoder_frame_features(enc, frames)[0]
+    _require_gpu(frames, "CGEncoder")
+    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
+        raise ValueError(f"frame_features expects contiguous fp32 [U,N,C], got {tuple(frames.shape)} {frames.dtype}")
+    _check_encoder_input(enc, frames.shape[2], frames.shape[1])
+    return _FrameFeaturesFn.apply(enc, frames, None, *enc.pc_block.parameters())
+
+
+def frame_features_ragged(enc, rows, weight, u_off, n, N):
+    """``frame_features`` of n padded frames from their DISTINCT points (arguments of ``encoder_frame_features_ragged``):
+    ``rows`` [M, C] fp32, ``weight`` fp32 [M], ``u_off`` int32 [n + 1] -> [n, 1024] fp32.  With no gradient wanted this is
+    ``encoder_frame_features_ragged`` (same bits).  With one, the PointNet layers run on the M compact rows and keep their
+    pre-BatchNorm y, ``ops.segment_weighted_mean`` pools; the backward starts with its adjoint
+    (``ops.segment_weighted_mean_bwd``: dy of the last layer and its BatchNorm statistics in one pass over the M rows) and
+    continues as ``pointnet_backward`` does on M rows.  ``rows.requires_grad`` gives ``rows.grad``: ONE value per distinct
+    detection -- the sum of the padded route's gradients over the copies of that point.  Raises in training mode."""
+    _check_track_eval(enc, "frame_features_ragged")
+    if not _want_bwd(rows, enc.pc_block.parameters()):
+        with torch.no_grad():
+            return encoder_frame_features_ragged(enc, rows, weight, u_off, n, N)[0]
+    _require_gpu(rows, "CGEncoder")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError(f"frame_features_ragged expects contiguous fp32 rows [M,C], got {tuple(rows.shape)} {rows.dtype}")
+    M, C = rows.shape
+    n, N = int(n), int(N)
+    _check_encoder_input(enc, C, N)
+    if not isinstance(weight, torch.Tensor) or not isinstance(u_off, torch.Tensor) or not weight.is_cuda or not u_off.is_cuda:
+        raise RuntimeError("frame_features_ragged: weight and u_off must live on the HIP device")
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (M,):
+        raise ValueError(f"frame_features_ragged: weight must be fp32 [{M}], got {tuple(weight.shape)} {weight.dtype}")
+    if u_off.dtype != torch.int32 or tuple(u_off.shape) != (n + 1,):
+        raise ValueError(f"frame_features_ragged: u_off must be int32 [{n + 1}], got {tuple(u_off.shape)} {u_off.dtype}")
+    return _FrameFeaturesFn.apply(enc, rows, _RaggedPool(weight, u_off, N), *enc.pc_block.parameters())
+
+
+class _WindowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, enc, table, win_row, T, *params):
+        # (windows_forward only comes here when a gradient is wanted)
+        mode = get_precision()
+        B = len(win_row)
+        st = EncoderState()
+        st.B, st.T, st.mode, st.training, st.want_bwd = B, T, mode, False, True
+        a = ops.gather_frames(table, win_row.row_index())                       # the windows, written out: [B*T, 1024]
+        x4, st.dtc = dtc_forward(a, B, T, enc.tc_block.layers(), False, pool_time=True, mode=mode, want_bwd=True)
+        st.x4 = x4
+        logits, sup_fv, _ = _encoder_heads(enc, st, x4)
+        ctx.enc, ctx.st, ctx.need_dtable = enc, st, table.requires_grad
+        ctx.csr = None
+        if ctx.need_dtable:
+            # the plan transposed on the host, uploaded once
+            off, idx = win_row.csr()
+            ctx.csr = (torch.from_numpy(off).to(table.device), torch.from_numpy(idx).to(table.device))
+        return logits.detach(), sup_fv.detach()            # aliases: see _EncoderFn.forward
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_logits, d_supfv):
+        enc, st = ctx.enc, ctx.st
+        g, dx4 = _encoder_heads_backward(enc, st, d_logits, d_supfv)
+        dg, da = dtc_backward(st.dtc, enc.tc_block.layers(), st.B, st.T, dpool=dx4, need_dx=ctx.need_dtable, mode=st.mode)
+        for i, d in enumerate(dg, start=1):
+            for k, v in d.items():
+                g[f"tc_block.dtc{i}.{k}"] = v
+        dtable = ops.gather_sum_rows(da.contiguous(), *ctx.csr) if ctx.need_dtable else None
+        return (None, dtable, None, None) + tuple(g.get(n) for n, _ in enc.named_parameters())
+
+
+def windows_forward(enc, table, win_row, T):
+    """Eval-mode temporal block, mean over T and heads on windows of a frame-feature table [table_rows, 1024] fp32
+    (``win_row``: an ops.WindowRows -- flat, ring or segmented rings) -> (logits, sup_fv).  With no gradient wanted this is
+    ``encoder_forward_windows`` (same bits: the first layer reads the table through its windowed launch).  With one, the
+    windows are written out with one gather (``ops.gather_frames(table, win_row.row_index())``) and go the eval-backward
+    route of the materialised crops; the backward runs the heads, ``dtc_backward`` and, when ``table`` requires a
+    gradient, the overlap-add of the window gradients into the table's (``ops.gather_sum_rows``: fixed order, no atomics).
+    Raises in training mode."""
+    _check_track_eval(enc, "windows_forward")
+    _require_gpu(table, "CGEncoder")
+    if not _want_bwd(table, enc.parameters()):
+        return encoder_forward_windows(enc, table, win_row, T)[:2]
+    if table.dim() != 2 or table.dtype != torch.float32 or not table.is_contiguous():
+        raise ValueError(f"windows_forward expects a contiguous fp32 table [rows, ch], got {tuple(table.shape)} {table.dtype}")
+    if win_row.T != T or win_row.table_rows != table.shape[0] or len(win_row) < 1:
+        raise ValueError("windows_forward: win_row does not describe at least one window of T rows of this table")
+    return _WindowsFn.apply(enc, table, win_row, int(T), *enc.parameters())
+
+
+def track_windows(n_frames, T, hop, drop_last_aligned=True):
+    """-> (W, U): the windows of a track of ``n_frames`` frames (the reference's ``crop_with_step`` rule, which drops the
+    last aligned window when ``(n_frames - T) % hop == 0``; ``drop_last_aligned=False`` keeps it) and the frames they use"""
+    n_frames, T, hop = int(n_frames), int(T), int(hop)
+    if not 1 <= hop:
+        raise ValueError(f"track_windows: hop must be >= 1, got {hop}")
+    W = len(range(0, n_frames - T, hop)) if drop_last_aligned else (0 if n_frames < T else (n_frames - T) // hop + 1)
+    return W, ((W - 1) * hop + T if W else 0)
+
+
+class TrackBatch:
+    """What ``plan_tracks`` derives from tracks that do not change between calls, so that a loop over the same tracks
+    (adapt.finetune_frozen_bn_tracks) does it once: the frames any window uses (``frames`` [U, N, C]; ``spare``: the
+    tensor they are the first U frames of), with ``dedup_points`` their compact table (``rows`` [M, C], ``weight`` [M],
+    ``u_off`` [U + 1]), and the windows' plan (an ops.WindowRows over the U table rows)."""
+    __slots__ = ("frames", "spare", "U", "N", "rows", "weight", "u_off", "plan", "T")
+
+
+def plan_tracks(enc, tracks, hop=None, drop_last_aligned=True, dedup_points=False, who="cg_encoder_tracks"):
+    """-> the TrackBatch of a list of processed tracks [F_i, N, C] (arguments of ``cg_encoder_tracks``).  With
+    ``dedup_points`` this is where the distinct rows are found (``ops.frames_unique_offsets`` / ``ops.frames_unique``: the one
+    host copy of the offsets and the read of the error flag); nothing here is differentiated."""
+    from . import constants
+    tracks = list(tracks)
+    if not tracks:
+        raise ValueError(f"{who}: no track")
+    T, hop = constants.NSTEPS, constants.CROP_STEP if hop is None else int(hop)
+    used, starts, base = [], [], 0
+    for i, track in enumerate(tracks):
+        _require_gpu(track, "CGEncoder")
+        if track.dim() != 3 or track.dtype != torch.float32 or not track.is_contiguous():
+            raise ValueError(f"{who} expects contiguous fp32 [F,N,C], got {tuple(track.shape)} {track.dtype}")
+        F, N, C = track.shape
+        _check_encoder_input(enc, C, N)
+        W, U = track_windows(F, T, hop, drop_last_aligned)
+        if W == 0:
+            raise ValueError(f"{who}: track {i} of {F} frames has no window of {T} frames (hop {hop})")
+        used.append(U)
+        starts.append(base + hop * np.arange(W, dtype=np.int64))
+        base += U
+    if dedup_points and torch.is_grad_enabled() and any(t.requires_grad for t in tracks):
+        raise RuntimeError(f"{who}: with dedup_points the padded frames have no gradient of their own (a repeated "
+                           "detection is one row); call it without dedup_points, or differentiate frame_features_ragged "
+                           "for one gradient per distinct detection")
+    tb = TrackBatch()
+    tb.U, tb.N, tb.T = base, tracks[0].shape[1], T
+    tb.spare = tracks[0] if len(tracks) == 1 else torch.cat([t[:u] for t, u in zip(tracks, used)])
+    tb.frames = tb.spare[:base]
+    tb.rows = tb.weight = tb.u_off = None
+    if dedup_points:
+        with torch.no_grad():
+            u_off = ops.frames_unique_offsets(tb.frames)
+            err = torch.zeros(1, dtype=torch.int32, device=tb.frames.device)
+            M = ops.unique_chunk_rows(int(u_off.cpu()[-1]))                    # the one host copy
+            tb.rows, tb.weight, tb.u_off = ops.frames_unique(tb.frames, u_off, 0, base, M, err_flag=err)
+        if err.item():
+            raise RuntimeError(f"{who}: ops.frames_unique met a segment that is not its frame's")
+    tb.plan = ops.WindowRows(np.concatenate(starts), T, base, device=tb.frames.device)
+    return tb
+
+
+def encode_track_batch(enc, tb):
+    """A planned batch of tracks through the eval-mode encoder -> (logits [W, K], sup_fv [W, 32]): ``cg_encoder_tracks``
+    behind its plan.  Launches only: no host copy, no read of a device flag."""
+    _check_track_eval(enc, "cg_encoder_tracks")
+    if tb.rows is not None:
+        table = frame_features_ragged(enc, tb.rows, tb.weight, tb.u_off, tb.U, tb.N)
+    elif _want_bwd(tb.frames, enc.pc_block.parameters()):
+        table = frame_features(enc, tb.frames)
+    else:
+        # no gradient: whole GEMM row tiles, the way OpenSetScorer.embed_track pads a chunk (neighbouring frames of the
+        # track where it has them, zeros otherwise; the extra frames' features are dropped)
+        pad = (-tb.U) % frame_pad_quantum(tb.N)
+        if pad and tb.U + pad <= tb.spare.shape[0]:
+            chunk = tb.spare[:tb.U + pad]
+        elif pad:
+            chunk = torch.cat([tb.frames, tb.frames.new_zeros((pad,) + tuple(tb.frames.shape[1:]))])
+        else:
+            chunk = tb.frames
+        table = frame_features(enc, chunk)[:tb.U]
+    return windows_forward(enc, table, tb.plan, tb.T)
+
+
+def cg_encoder_tracks(enc, tracks, hop=None, drop_last_aligned=True, dedup_points=False, who="cg_encoder_tracks"):
+    """The eval-mode encoder on the windows of processed tracks, differentiable: ``tracks`` is a list of [F_i, N, C] fp32
+    device tensors -> (logits [W, K], sup_fv [W, 32]) for their W = sum W_i windows of NSTEPS frames, track after track --
+    the windows ``OpenSetScorer.embed_track`` scores (``inference.window_count``; track i's windows use its first
+    ``U_i = (W_i - 1) * hop + NSTEPS`` frames).  Every frame goes through the PointNet block once and no crop is written
+    out; the tracks share ONE PointNet pass and ONE temporal pass (one frame-feature table, a window never leaves its
+    track's rows), so the launches do not grow with the number of tracks.  ``dedup_points``: every frame's DISTINCT rows
+    once, pooled with their multiplicities (``ops.frames_unique_offsets`` / ``ops.frames_unique``: one host copy of the
+    offsets, the table rounded to 256-row tiles).  ``hop``: None = CROP_STEP.  A caller that passes the same tracks again
+    and again plans them once (``plan_tracks``) and calls ``encode_track_batch``.
+
+    With a gradient wanted (autograd on; a parameter or a track requires it) nothing is chunked and the backward reads what
+    the forward kept -- the caller bounds the tracks.  Kept per point row (sum U_i * N rows, with ``dedup_points`` the
+    distinct rows): the pre-BatchNorm y of PointNet layers 2-4 and the three activations between the layers (layer 1's y
+    is recomputed from the points), 4 608 values = 18 KB in fp32 mode, 9 KB in bf16 mode.  Kept per window: its NSTEPS rows
+    of the table written out (120 KB), the six temporal layers' im2col matrices (3 * (1024 + 16 + 32 + 64 + 128 + 256)
+    values per step: 534 KB) and their pre-BatchNorm y (118 KB), all fp32.  A track's ``requires_grad`` is served without
+    ``dedup_points``; with it this raises -- ``frame_features_ragged`` gives the gradient per distinct detection.  Raises
+    in training mode and (ValueError) for a track too short for a window.  No BatchNorm buffer is written."""
+    _check_track_eval(enc, who)
+    return encode_track_batch(enc, plan_tracks(enc, tracks, hop, drop_last_aligned, dedup_points, who))
+
+
+def cg_encoder_track(enc, track, hop=None, drop_last_aligned=True, dedup_points=False):
+    """``cg_encoder_tracks`` of one processed track [F, N, C] -> (logits [W, K], sup_fv [W, 32]).  With no gradient wanted
+    the outputs are the bits ``OpenSetScorer.embed_track`` scores.  ``hop``: None = CROP_STEP.  Memory kept for a backward:
+    see ``cg_encoder_tracks``."""
+    return cg_encoder_tracks(enc, [track], hop, drop_last_aligned, dedup_points, who="cg_encoder_track")
+
+
+def cg_encoder_raw_track(enc, points, offsets, pick=None, seed=0, track_key=0, hop=None, drop_last_aligned=True,
+                         dedup_points=False):
+    """``cg_encoder_track`` from the radar's detections (arguments of ``OpenSetScorer.embed_raw_track``): ``points`` [P, 5]
+    fp32 / fp64 and ``offsets`` int32 [F + 1] on the device -> ``ops.frames_from_raw`` (centred, not divided by std) -> the
+    track route; ``dedup_points``: ``ops.frames_from_raw_unique`` -> ``frame_features_ragged``, the padded frames never
+    written.  ``pick`` int32 [F, N]: host-drawn picks; None: drawn on the device, frame f under the key ``(track_key, f)``
+    and ``seed``.  Parameter gradients only: the frame preparation (centring, dB) is not differentiated, and
+    ``points.requires_grad`` raises.  Memory kept for the backward: as ``cg_encoder_tracks``.  A frame that could not be
+    processed (``ops.frames_from_raw``'s rule) raises."""
+    from . import constants
+    _check_track_eval(enc, "cg_encoder_raw_track")
+    for t, name in ((points, "points"), (offsets, "offsets")) + (((pick, "pick"),) if pick is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"cg_encoder_raw_track: {name} must live on the HIP device; this package has no CPU path")
+    if points.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("cg_encoder_raw_track: no gradient w.r.t. the raw detections (the frame preparation is not "
+                           "differentiated); detach the points")
+    N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
+    if offsets.dim() != 1 or offsets.dtype != torch.int32 or offsets.numel() < 1:
+        raise ValueError(f"cg_encoder_raw_track expects offsets int32 [F + 1], got {tuple(offsets.shape)} {offsets.dtype}")
+    F = offsets.numel() - 1
+    T, hop = constants.NSTEPS, constants.CROP_STEP if hop is None else int(hop)
+    W, U = track_windows(F, T, hop, drop_last_aligned)
+    if W == 0:
+        raise ValueError(f"cg_encoder_raw_track: a track of {F} frames has no window of {T} frames (hop {hop})")
+    dev = points.device
+    keys = None
+    if pick is None:
+        k = np.empty((F, 2), dtype=np.int32)
+        k[:, 0] = np.int64(track_key).astype(np.int32)
+        k[:, 1] = np.arange(F, dtype=np.int64).astype(np.int32)
+        keys = torch.from_numpy(k).to(dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.no_grad():
+        if dedup_points:
+            rows, weight, u_off = ops.frames_from_raw_unique(
+                points, offsets[:U + 1].contiguous(), N, C, pick=None if pick is None else pick[:U].contiguous(), seed=seed,
+                frame_key=None if keys is None else keys[:U].contiguous(), err_flag=err)
+        else:
+            frames = ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=err)
+    if err.item():
+        raise RuntimeError("cg_encoder_raw_track: a frame could not be processed (ops.frames_from_raw's rule)")
+    if not dedup_points:
+        return cg_encoder_track(enc, frames, hop, drop_last_aligned)
+    table = frame_features_ragged(enc, rows, weight, u_off, U, N)
+    plan = ops.WindowRows(hop * np.arange(W, dtype=np.int64), T, table.shape[0], device=dev)
+    return windows_forward(enc, table, plan, T)
 
 
 # ---------------------------------------------------------------- encoder trunk (OR-CED baseline, models.py:446-505)

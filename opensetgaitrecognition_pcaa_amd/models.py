@@ -132,6 +132,11 @@ class CGEncoder(torch.nn.Module):
     def forward(self, x):
         return F_hip.cg_encoder(self, x)
 
+    def forward_track(self, track, hop=None, drop_last_aligned=True, dedup_points=False):
+        """forward on the windows of a processed track [F,N,C] (eval mode, differentiable; ``hop``: None = CROP_STEP):
+        functional.cg_encoder_track"""
+        return F_hip.cg_encoder_track(self, track, hop, drop_last_aligned, dedup_points)
+
 
 class CGDecoder(torch.nn.Module):
     """forward(z[B,input_dim]) -> [B,C,T,N]; bn1..bn4 are registered (they are

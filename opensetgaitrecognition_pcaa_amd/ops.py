@@ -1450,6 +1450,37 @@ def gather_frames(src, idx):
     return gather_rows(src, idx) if row_bytes % 16 == 0 else gather_rows_w4(src, idx)
 
 
+def gather_sum_rows(src, csr_off, csr_idx, out=None, err_flag=None):
+    """The adjoint of ``gather_frames``: ``dst[u] = sum_{k in [csr_off[u], csr_off[u + 1])} src[csr_idx[k]]`` in ascending k,
+    fp32, plain adds from +0 (pcaa_gather_sum_rows: no atomics, reproducible bit for bit on the host).  ``src`` fp32
+    [n_src, ...] contiguous, ``csr_off`` int32 [n_dst + 1] and ``csr_idx`` int32 [nnz] on the device (``WindowRows.csr()``
+    builds them on the host).  A row without contributors is zero; an index outside ``[0, n_src)`` is skipped and sets
+    ``err_flag`` (int32 [1]).  -> fp32 [n_dst, ...]"""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.is_contiguous() and src.dim() >= 2
+            and src.dtype == torch.float32):
+        raise RuntimeError("gather_sum_rows: src must be a contiguous float32 tensor of rows on the HIP device (this "
+                           "package has no CPU path)")
+    _chk(csr_off, "gather_sum_rows.csr_off", torch.int32, 1)
+    _chk(csr_idx, "gather_sum_rows.csr_idx", torch.int32, 1)
+    n_dst, nnz = csr_off.numel() - 1, csr_idx.numel()
+    row_words = src[0].numel() if src.shape[0] else int(torch.Size(src.shape[1:]).numel())
+    if n_dst < 0 or row_words < 1 or src.shape[0] < 1:
+        raise ValueError(f"gather_sum_rows: needs csr_off [n_dst + 1] and at least one source row of at least one word; got "
+                         f"csr_off {tuple(csr_off.shape)}, src {tuple(src.shape)}")
+    shape = (n_dst,) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("gather_sum_rows: out does not match")
+    if err_flag is not None:
+        _chk(err_flag, "gather_sum_rows.err_flag", torch.int32)
+    if n_dst:
+        _timed("gather_sum_rows_kernel", lambda: check(_lib.load().pcaa_gather_sum_rows(
+            _p(src), src.shape[0], row_words, _p(csr_off), _p(csr_idx) if nnz else None, nnz, _p(out), n_dst,
+            _p(err_flag), _s()), "pcaa_gather_sum_rows"), float(nnz * row_words), (nnz + n_dst) * row_words * 4)
+    return out
+
+
 def crop_overlap_vec_bytes(crops):
     """16 or 4: the load width pcaa_crop_overlap takes for this tensor."""
     _chk(crops, "crop_overlap.crops", torch.float32, 4)
@@ -1516,6 +1547,26 @@ class WindowRows:
         ring = self.ring_rows or self.table_rows or 1
         off = start % ring
         return (start - off + (off + t[None, :]) % ring).reshape(-1).contiguous()
+
+    def row_index_host(self):
+        """``row_index()`` from the host copy of the plan: numpy int64 [B*T], no device work"""
+        import numpy as np
+        t = np.arange(self.T, dtype=np.int64)
+        start = self.host[:, None]
+        ring = self.ring_rows or self.table_rows or 1
+        off = start % ring
+        return (start - off + (off + t[None, :]) % ring).reshape(-1)
+
+    def csr(self):
+        """The plan transposed, for ``gather_sum_rows`` (the adjoint of ``gather_frames(table, row_index())``): numpy
+        ``(csr_off int32 [table_rows + 1], csr_idx int32 [B*T])`` -- table row u receives the window rows
+        ``csr_idx[csr_off[u] : csr_off[u + 1]]`` (row ``b * T + t`` of the materialised windows), in ascending order."""
+        import numpy as np
+        idx = self.row_index_host()
+        order = np.argsort(idx, kind="stable")
+        off = np.zeros(self.table_rows + 1, dtype=np.int64)
+        np.cumsum(np.bincount(idx, minlength=self.table_rows), out=off[1:])
+        return off.astype(np.int32), order.astype(np.int32)
 
 
 def scatter_rows(src, dst_row, dst, err_flag=None):
@@ -1773,6 +1824,57 @@ def segment_weighted_mean(a, weight, u_off, N, scale=None, shift=None, err_flag=
             _p(a), _dt(a), ch, _p(weight), _p(u_off), n, M, ch, N, _p(scale), _p(shift), _p(out), _p(err_flag), _s()),
             "pcaa_segment_weighted_mean"), 2.0 * M * ch, M * ch * a.element_size() + n * ch * 4)
     return out
+
+
+def segment_weighted_mean_bwd(dpool, y, weight, u_off, N, scale, shift, mean, rstd, out=None, err_flag=None):
+    """Backward of ``segment_weighted_mean(y, weight, u_off, N, scale, shift)`` w.r.t. the pre-BatchNorm ``y``
+    (pcaa_segment_weighted_mean_bwd): for row r of segment f ``dy[r] = scale * dpool[f] * (weight[r] / N) * ELU'(y[r] *
+    scale + shift)`` in y's dtype, and the statistics {sum dz, sum dz*xhat} for bn_eval_bwd_finalize (``mean``, ``rstd``
+    from bn_eval_moments).  ``dpool`` fp32 [n, ch], ``y`` [M, ch] bf16 or fp32 (a column view with a leading dimension
+    that is a multiple of 8 is taken as is; ``out`` then needs the same strides).  Rows that no valid segment owns come
+    out as zeros; a segment outside ``[0, M]`` contributes nothing and sets ``err_flag`` (int32 [1]).  Valid segments must be
+    disjoint (non-decreasing offsets are; an overlap needs a segment that runs backwards, which sets the flag: discard the
+    result then).  -> (dy, stats)"""
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dim() == 2 and y.stride(1) == 1):
+        raise RuntimeError("segment_weighted_mean_bwd.y: must be a 2-D tensor on the HIP device with unit column stride "
+                           "(this package has no CPU path)")
+    if y.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"segment_weighted_mean_bwd.y: expected float32 or bfloat16, got {y.dtype}")
+    M, ch = y.shape
+    lda = y.stride(0) if M > 1 else ch
+    _chk(dpool, "segment_weighted_mean_bwd.dpool", torch.float32, 2)
+    _chk(weight, "segment_weighted_mean_bwd.weight", torch.float32, 1)
+    _chk(u_off, "segment_weighted_mean_bwd.u_off", torch.int32, 1)
+    n, N = u_off.numel() - 1, int(N)
+    if weight.numel() != M:
+        raise ValueError(f"segment_weighted_mean_bwd: weight must be [{M}] (one per row of y), got {tuple(weight.shape)}")
+    if ch < 8 or ch % 8 or n < 0 or N < 1 or lda < ch or lda % 8:
+        raise ValueError(f"segment_weighted_mean_bwd: needs ch % 8 == 0, a leading dimension >= ch that is a multiple of 8, "
+                         f"u_off [n + 1], N >= 1; got ch={ch}, lda={lda}, n={n}, N={N}")
+    if tuple(dpool.shape) != (n, ch):
+        raise ValueError(f"segment_weighted_mean_bwd: dpool must be [{n}, {ch}], got {tuple(dpool.shape)}")
+    for t, name in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (rstd, "rstd")):
+        _chk(t, "segment_weighted_mean_bwd." + name, torch.float32, 1)
+        if t.numel() != ch:
+            raise ValueError(f"segment_weighted_mean_bwd: {name} must be [{ch}], got {tuple(t.shape)}")
+    if err_flag is not None:
+        _chk(err_flag, "segment_weighted_mean_bwd.err_flag", torch.int32)
+    if out is None:
+        dy = torch.empty_like(y) if y.is_contiguous() else torch.empty_strided((M, ch), (lda, 1), dtype=y.dtype, device=y.device)
+    else:
+        dy = out
+        if not (isinstance(dy, torch.Tensor) and dy.is_cuda and dy.shape == y.shape and dy.dtype == y.dtype
+                and dy.stride(1) == 1 and (M <= 1 or dy.stride(0) == lda)):
+            raise ValueError("segment_weighted_mean_bwd: out must have y's shape, dtype and strides")
+    stats = new_stats(ch, y.device)
+    if n:
+        _timed("segment_weighted_mean_bwd_kernel", lambda: check(_lib.load().pcaa_segment_weighted_mean_bwd(
+            _p(dpool), _p(y), _p(dy), _dt(y), lda, _p(weight), _p(u_off), n, M, ch, N, _p(scale), _p(shift), _p(mean),
+            _p(rstd), _p(stats), NREP, _p(err_flag), _s()), "pcaa_segment_weighted_mean_bwd"),
+            8.0 * M * ch, 3 * M * ch * y.element_size() + n * ch * 4)
+    else:
+        dy.zero_()
+    return dy, stats
 
 
 def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
