@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 27 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 28 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -277,6 +277,27 @@ int pcaa_bn_bwd_finalize(const double* stats, int nrep, long count, const float*
                          float* coef, float* dgamma, float* dbeta, int ch, void* stream);
 int pcaa_bn_bwd_dy(const void* dz, const void* y, void* dy, int dtype, const float* coef,
                    long rows, int ch, void* stream);
+/* ABI 28: the streaming route of the element-wise passes (csrc/ew_stream.h: persistent grid, 16 bytes per lane, a ring
+ * of row-loads per lane).  Every element it writes is bit-identical to the classic grid-stride kernel's.  A launcher
+ * takes it when pcaa_ew_route answers "stream": the pass is one of those ported (PCAA_EW_ACT_FWD: pcaa_bn_act_fwd,
+ * for ch >= 1024 only -- narrower rows measured inside the classic route's spread; PCAA_EW_BWD_DY: pcaa_bn_bwd_dy, in
+ * place or not), dtype is PCAA_BF16, ch % 8 == 0 with ch / 8 dividing 256, the tensors are 16-byte aligned
+ * (aligned != 0), and the switch is on.  Everything else -- fp32, the split images, a ragged ch, the other passes --
+ * answers "classic".  A pure host function: no HIP call, works without a GPU.
+ * The switch: the environment's PCAA_EW_STREAM=0 (read once, at the first decision) or pcaa_ew_stream_set(0) turn the
+ * route off; pcaa_ew_stream_set returns the previous setting. */
+#define PCAA_EW_ACT_FWD 0
+#define PCAA_EW_BWD_DY 1
+#define PCAA_EW_BWD_DY_FUSED 2
+#define PCAA_EW_MEANPOOL 3
+#define PCAA_EW_IN_BWD 4
+#define PCAA_EW_IN_APPLY 5
+const char* pcaa_ew_route(int pass, int dtype, long rows, int ch, int aligned);
+/* the stream kernel's geometry for a pass (0 for a pass that has none): workgroups per CU of its persistent grid (the
+ * grid is that times the CU count, at most one workgroup per trip of 256 / (ch/8) rows) and rows a lane keeps ahead */
+int pcaa_ew_wgs_per_cu(int pass);
+int pcaa_ew_ring_depth(int pass);
+int pcaa_ew_stream_set(int on);
 /* ABI 23: backward through EVAL-mode BatchNorm + ELU (BatchNorm is the fixed map z = scale*y + shift, scale = gamma*r,
  * r = 1/sqrt(running_var + eps); y is stored bias-free, so the mean it is centred on is m' = running_mean - bias).
  * pcaa_bn_eval_moments writes (m', r) as fp32 vectors.  pcaa_bn_eval_act_bwd makes ONE pass over y[rows, ch]:

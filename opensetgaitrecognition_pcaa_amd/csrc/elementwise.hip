@@ -5,8 +5,11 @@
 // registers and leave through one fp64 atomic per channel per workgroup.
 #include <stdarg.h>
 
+#include <stdlib.h>
+
 #include "common.h"
 #include "bn_tail.h"
+#include "ew_stream.h"
 
 // ---------------------------------------------------------------- error string
 static thread_local char g_err[512] = "";
@@ -748,7 +751,56 @@ inline int col_invariant_grid(long nquads, int qpr) {
   return (int)g;
 }
 
+// PCAA_EW_STREAM=0 keeps every pass on the classic grid-stride kernels (the same-box A/B and the bitwise tests);
+// read once, pcaa_ew_stream_set overrides it
+int g_ew_stream = -1;
+inline bool ew_stream_on() {
+  if (g_ew_stream < 0) {
+    const char* e = getenv("PCAA_EW_STREAM");
+    g_ew_stream = (e && e[0] == '0' && e[1] == 0) ? 0 : 1;
+  }
+  return g_ew_stream != 0;
+}
+// the launchers' decision, from the arguments alone: the passes that won at kernel level (profiles/ew_stream.txt),
+// bf16 storage, a channel count the skeleton's lane mapping takes, 16-byte aligned tensors
+inline bool ew_route_stream(int pass, int dtype, long rows, int ch, bool aligned16) {
+  if (!ew_stream_on() || dtype != PCAA_BF16 || rows < 1 || !aligned16 || !ew::ch_ok(ch)) return false;
+  // bn_act_fwd at [245760, 512] came out inside the classic route's own spread (90.4 against 92.8 us, spread 7.2), at
+  // [245760, 1024] it wins (173.7 against 193.0): rows of 1024 channels and more stream, narrower ones stay classic
+  if (pass == PCAA_EW_ACT_FWD) return ch >= 1024;
+  return pass == PCAA_EW_BWD_DY;
+}
+inline bool aligned16(const void* a, const void* b, const void* c) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 }  // namespace
+
+int ew::cu_count() {
+  static int n = 0;
+  if (n <= 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        n <= 0)
+      n = 256;
+  }
+  return n;
+}
+
+extern "C" const char* pcaa_ew_route(int pass, int dtype, long rows, int ch, int aligned) {
+  return ew_route_stream(pass, dtype, rows, ch, aligned != 0) ? "stream" : "classic";
+}
+extern "C" int pcaa_ew_wgs_per_cu(int pass) {
+  return pass == PCAA_EW_ACT_FWD ? ew::ActFwdPolicy::K : pass == PCAA_EW_BWD_DY ? ew::BwdDyPolicy::K : 0;
+}
+extern "C" int pcaa_ew_ring_depth(int pass) {
+  return pass == PCAA_EW_ACT_FWD ? ew::ActFwdPolicy::R : pass == PCAA_EW_BWD_DY ? ew::BwdDyPolicy::R : 0;
+}
+extern "C" int pcaa_ew_stream_set(int on) {
+  const int was = ew_stream_on() ? 1 : 0;
+  g_ew_stream = on ? 1 : 0;
+  return was;
+}
 
 // ---------------------------------------------------------------- C ABI
 extern "C" int pcaa_bn_finalize(const double* stats, int nrep, long count, const float* lin_bias,
@@ -781,6 +833,11 @@ extern "C" int pcaa_bn_act_fwd(const void* y, void* a, int dtype, const float* s
   PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_act_fwd: ch must be a multiple of 4");
   const long nq = rows * (ch >> 2);
   PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_act_fwd: tensor too large for 32-bit quad indices");
+  if (ew_route_stream(PCAA_EW_ACT_FWD, dtype, rows, ch, aligned16(y, a, nullptr))) {
+    ew::launch<1, ew::ActFwdPolicy>((const bf16_t*)y, nullptr, (bf16_t*)a, ew::ActFwd{scale, shift}, rows, ch,
+                                    as_stream(stream));
+    PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_fwd");
+  }
   const int grid = col_invariant_grid(nq, ch >> 2);
   if (dtype == PCAA_F32)
     hipLaunchKernelGGL(bn_act_fwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream),
@@ -1098,6 +1155,12 @@ extern "C" int pcaa_bn_bwd_dy(const void* dz, const void* y, void* dy, int dtype
   PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_bwd_dy: ch must be a multiple of 4");
   const long nq = rows * (ch >> 2);
   PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_bwd_dy: tensor too large for 32-bit quad indices");
+  if (ew_route_stream(PCAA_EW_BWD_DY, dtype, rows, ch, aligned16(dz, y, dy))) {
+    // dy may be dz (ew_stream.h: aliasing)
+    ew::launch<2, ew::BwdDyPolicy>((const bf16_t*)y, (const bf16_t*)dz, (bf16_t*)dy, ew::BwdDy{coef}, rows, ch,
+                                   as_stream(stream));
+    PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy");
+  }
   const int grid = col_invariant_grid(nq, ch >> 2);
   if (dtype == PCAA_F32)
     hipLaunchKernelGGL(bn_bwd_dy_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float*)dz,

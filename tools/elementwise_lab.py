@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The HBM-bound passes of the PointNet block alone on the GPU: ms and TB/s of the bytes each moves, at the bench
 shape.  python tools/elementwise_lab.py        (profiles/r03_elementwise_unroll_lab.txt is this lab on a scratch build
-whose column-invariant kernels took 1 / 2 / 4 / 8 quads per thread and trip; the switch was not kept)"""
+whose column-invariant kernels took 1 / 2 / 4 / 8 quads per thread and trip; the switch was not kept)
+python tools/elementwise_lab.py --routes    the passes with a streaming kernel, both routes alternating, 9 rounds
+(profiles/ew_stream.txt)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,6 +23,51 @@ def timed(fn, reps=10):
     ts.sort()
     return ts[len(ts) // 2]
 
+
+def routes_ab(rounds=9):
+    """the passes that have a streaming kernel (csrc/ew_stream.h), stream and classic alternating on this box"""
+    from opensetgaitrecognition_pcaa_amd import _lib
+    lib = _lib.load()
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    print(f"# {rounds} rounds, stream and classic alternating; us: median (min-max); a pass ships on the stream route only")
+    print("# if its median beats the classic median by more than the classic route's own min-max spread")
+    for ch in (512, 1024):
+        y = (torch.randn(P, ch, device=dev) * 0.7).bfloat16()
+        sc = torch.rand(ch, device=dev) + 0.5
+        sh = torch.randn(ch, device=dev) * 0.1
+        coef = torch.randn(3, ch, device=dev) * 0.3
+        coef[0] = 0.5                                            # the in-place iteration stays bounded
+        dz = (torch.randn(P, ch, device=dev) * 0.1).bfloat16()
+        out = torch.empty_like(y)
+        nb = P * ch * 2
+        passes = [("bn_act_fwd", 2, lambda: ops.bn_act_fwd(y, sc, sh)),
+                  ("bn_bwd_dy (out of place)", 3, lambda: ops.bn_bwd_dy(dz, y, coef, out=out)),
+                  ("bn_bwd_dy (in place)", 3, lambda: ops.bn_bwd_dy(dz, y, coef, out=dz))]
+        for name, nt, fn in passes:
+            ts = {0: [], 1: []}
+            for on in (1, 0):
+                lib.pcaa_ew_stream_set(on); fn(); fn()
+            torch.cuda.synchronize()
+            for _ in range(rounds):
+                for on in (1, 0):
+                    lib.pcaa_ew_stream_set(on)
+                    ts[on].append(once(fn))
+            lib.pcaa_ew_stream_set(1)
+            st = {on: (sorted(v)[len(v) // 2], min(v), max(v)) for on, v in ts.items()}
+            wins = st[0][0] - st[1][0] > st[0][2] - st[0][1]
+            print(f"[{ch}] {name:26s} stream {st[1][0]:7.1f} ({st[1][1]:6.1f}-{st[1][2]:6.1f}) {nt * nb / st[1][0] / 1e6:5.2f} TB/s | "
+                  f"classic {st[0][0]:7.1f} ({st[0][1]:6.1f}-{st[0][2]:6.1f}) {nt * nb / st[0][0] / 1e6:5.2f} TB/s | "
+                  f"{'stream wins' if wins else 'inside the spread: stays classic'}")
+
+
+if "--routes" in sys.argv:
+    routes_ab()
+    sys.exit(0)
 
 for ch in (512, 1024):
     y = (torch.randn(P, ch, device=dev) * 0.7).bfloat16()
