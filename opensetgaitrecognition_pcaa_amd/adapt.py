@@ -7,8 +7,7 @@ such (functional.encoder_backward on an eval-mode state: one pass per BatchNorm 
 """
 import torch
 
-from . import constants
-from .functional import cross_entropy_loss, encode_track_batch, plan_tracks, track_windows
+from .functional import cross_entropy_loss, encode_track_batch, plan_tracks
 
 HEADS = ("MLP_sup1", "MLP_head", "MLP_sup2")
 
@@ -72,20 +71,9 @@ def finetune_frozen_bn_tracks(encoder, tracks, labels, steps, lr, params="heads"
     if len(tracks) < 1 or labels.dim() != 1 or labels.numel() != len(tracks):
         raise ValueError(f"finetune_frozen_bn_tracks: needs at least one track and labels [{len(tracks)}], got "
                          f"{tuple(labels.shape)}")
-    hop = constants.CROP_STEP if hop is None else int(hop)
-    counts = []
-    for i, t in enumerate(tracks):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"finetune_frozen_bn_tracks: track {i} is not a [F,N,C] tensor")
-        W, _ = track_windows(t.shape[0], constants.NSTEPS, hop)
-        if W == 0:
-            raise ValueError(f"finetune_frozen_bn_tracks: track {i} has {t.shape[0]} frames, too short for a window of "
-                             f"{constants.NSTEPS} (hop {hop})")
-        counts.append(W)
-    win_labels = torch.repeat_interleave(labels, torch.tensor(counts, device=labels.device)).contiguous()
-
-    # the tracks do not change between the steps: their frames are gathered, their windows planned and (dedup_points)
-    # their distinct rows found ONCE -- the host copy of the offsets and the read of the error flag stay out of the loop
+    # the tracks do not change between the steps: their frames are checked and gathered, their windows planned (a track too
+    # short for one: ValueError) and (dedup_points) their distinct rows found ONCE, host copy and flag read outside the loop
     batch = plan_tracks(encoder, tracks, hop, True, dedup_points, who="finetune_frozen_bn_tracks")
+    win_labels = torch.repeat_interleave(labels, torch.tensor(batch.counts, device=labels.device)).contiguous()
     return _adam_steps(encoder, chosen, steps, lr,
                        lambda: cross_entropy_loss(encode_track_batch(encoder, batch)[0], win_labels))

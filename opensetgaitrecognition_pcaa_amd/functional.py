@@ -28,7 +28,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import frame_table, ops
 from ._lib import ACT_ELU, ACT_NONE, KC, PCAA_BF16, PCAA_F32, RC
 
 _W16_CACHE = {}           # weight data_ptr -> transposed bf16 shadow made in the forward pass of this step
@@ -999,14 +999,24 @@ def _check_encoder_input(enc, C, N):
                            "(the reference's AvgPool2d((1,nmax_points)) would emit >1 column)")
 
 
+def _check_encoder_frames(enc, frames, who):
+    """point-major frames [n,N,C] on the device (frame_table.check_frames, none empty) of the shape ``enc`` was built for"""
+    frame_table.check_frames(frames, who, empty_ok=False)
+    _check_encoder_input(enc, frames.shape[2], frames.shape[1])
+
+
+def _check_encoder_ragged(enc, rows, weight, u_off, n, N, who):
+    """a compact table (frame_table.check_ragged) of the shape ``enc`` was built for"""
+    _, C = frame_table.check_ragged(rows, weight, u_off, n, N, who)
+    _check_encoder_input(enc, C, int(N))
+
+
 def encoder_forward(enc, x, training, mode=None, gph=None, want_bwd=False):
     """``gph``: optional decoder projection head ``Sequential(Linear(32,64), ELU)`` evaluated in the
     same launch as the MLP heads (``st.hproj``).  ``want_bwd``: encoder_backward will follow -- in eval mode the two
     blocks then keep what it reads (pointnet_forward / dtc_forward); a train-mode forward always does."""
     mode = get_precision() if mode is None else mode
-    _require_gpu(x, "CGEncoder")
-    if x.dim() != 4:
-        raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(x.shape)}")
+    frame_table.check_crops(x, "CGEncoder", empty_ok=False)
     B, C, T, N = x.shape
     _check_encoder_input(enc, C, N)
     st = EncoderState()
@@ -1060,11 +1070,8 @@ def encoder_frame_features(enc, frames, mode=None, consts=None):
     lets overlapping crops share them.  ``consts``: ``encoder_eval_constants(enc, mode)`` of a frozen encoder (same bits,
     the constants are not recomputed); None: they are computed in this call."""
     mode = get_precision() if mode is None else mode
-    _require_gpu(frames, "CGEncoder")
-    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
-        raise ValueError(f"encoder_frame_features expects contiguous fp32 [U,N,C], got {tuple(frames.shape)} {frames.dtype}")
+    _check_encoder_frames(enc, frames, "encoder_frame_features")
     U, N, C = frames.shape
-    _check_encoder_input(enc, C, N)
     return pointnet_forward(frames.view(U * N, C), enc.pc_block.layers(), False, mode, pool_rows=N, consts=consts)
 
 
@@ -1077,25 +1084,13 @@ def encoder_frame_features_ragged(enc, rows, weight, u_off, n, N, mode=None, con
     pools (and applies BatchNorm + ELU itself where the last layer left its pre-BatchNorm y: fp32 and fp16x3 modes).
     Eval mode and no gradient only: the saves do not serve pointnet_backward."""
     mode = get_precision() if mode is None else mode
-    _require_gpu(rows, "CGEncoder")
-    if enc.training:
-        raise RuntimeError("encoder_frame_features_ragged: the encoder is in training mode (batch statistics would need "
-                           "weighted moments); call encoder.eval()")
+    _check_track_eval(enc, "encoder_frame_features_ragged")
+    _check_encoder_ragged(enc, rows, weight, u_off, n, N, "encoder_frame_features_ragged")
     if torch.is_grad_enabled() and (rows.requires_grad or any(p.requires_grad for p in enc.parameters())):
         raise RuntimeError("encoder_frame_features_ragged: forward only -- a backward is wanted (autograd is on and the "
                            "rows or the encoder's parameters require a gradient); call it under torch.no_grad(), or "
                            "differentiate encoder_frame_features on the padded frames")
-    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
-        raise ValueError(f"encoder_frame_features_ragged expects contiguous fp32 rows [M,C], got {tuple(rows.shape)} {rows.dtype}")
-    M, C = rows.shape
-    n, N = int(n), int(N)
-    _check_encoder_input(enc, C, N)
-    if not isinstance(weight, torch.Tensor) or not isinstance(u_off, torch.Tensor) or not weight.is_cuda or not u_off.is_cuda:
-        raise RuntimeError("encoder_frame_features_ragged: weight and u_off must live on the HIP device")
-    if weight.dtype != torch.float32 or tuple(weight.shape) != (M,):
-        raise ValueError(f"encoder_frame_features_ragged: weight must be fp32 [{M}], got {tuple(weight.shape)} {weight.dtype}")
-    if u_off.dtype != torch.int32 or tuple(u_off.shape) != (n + 1,):
-        raise ValueError(f"encoder_frame_features_ragged: u_off must be int32 [{n + 1}], got {tuple(u_off.shape)} {u_off.dtype}")
+    N = int(N)
     with torch.no_grad():
         a, saves = pointnet_forward(rows, enc.pc_block.layers(), False, mode, pool_rows=0, consts=consts, last_pre_bn=True)
         last = saves[-1]
@@ -1261,7 +1256,8 @@ def _want_bwd(x, params):
 # block and the heads read windows of that table (windows_forward).  The three pieces are autograd Functions that chain:
 # the window gradients are overlap-added into the table's gradient (ops.gather_sum_rows), which is the pooled gradient
 # the PointNet backward starts from.  Eval mode only: BatchNorm is the fixed map of its running statistics, which are
-# read and never written.
+# read and never written.  The host-side rules (which windows a track has, where they start in the table, the padding
+# of a chunk to whole GEMM row tiles, the refusals, the raw-detection step) are frame_table.py's, shared with the scorers.
 def _check_track_eval(enc, who):
     if enc.training:
         raise RuntimeError(f"{who}: the encoder is in training mode (batch statistics would need weighted moments); "
@@ -1313,10 +1309,7 @@ def frame_features(enc, frames):
     _check_track_eval(enc, "frame_features")
     if not _want_bwd(frames, enc.pc_block.parameters()):
         return encoder_frame_features(enc, frames)[0]
-    _require_gpu(frames, "CGEncoder")
-    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
-        raise ValueError(f"frame_features expects contiguous fp32 [U,N,C], got {tuple(frames.shape)} {frames.dtype}")
-    _check_encoder_input(enc, frames.shape[2], frames.shape[1])
+    _check_encoder_frames(enc, frames, "frame_features")         # (without a gradient encoder_frame_features checks)
     return _FrameFeaturesFn.apply(enc, frames, None, *enc.pc_block.parameters())
 
 
@@ -1332,19 +1325,8 @@ def frame_features_ragged(enc, rows, weight, u_off, n, N):
     if not _want_bwd(rows, enc.pc_block.parameters()):
         with torch.no_grad():
             return encoder_frame_features_ragged(enc, rows, weight, u_off, n, N)[0]
-    _require_gpu(rows, "CGEncoder")
-    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
-        raise ValueError(f"frame_features_ragged expects contiguous fp32 rows [M,C], got {tuple(rows.shape)} {rows.dtype}")
-    M, C = rows.shape
-    n, N = int(n), int(N)
-    _check_encoder_input(enc, C, N)
-    if not isinstance(weight, torch.Tensor) or not isinstance(u_off, torch.Tensor) or not weight.is_cuda or not u_off.is_cuda:
-        raise RuntimeError("frame_features_ragged: weight and u_off must live on the HIP device")
-    if weight.dtype != torch.float32 or tuple(weight.shape) != (M,):
-        raise ValueError(f"frame_features_ragged: weight must be fp32 [{M}], got {tuple(weight.shape)} {weight.dtype}")
-    if u_off.dtype != torch.int32 or tuple(u_off.shape) != (n + 1,):
-        raise ValueError(f"frame_features_ragged: u_off must be int32 [{n + 1}], got {tuple(u_off.shape)} {u_off.dtype}")
-    return _FrameFeaturesFn.apply(enc, rows, _RaggedPool(weight, u_off, N), *enc.pc_block.parameters())
+    _check_encoder_ragged(enc, rows, weight, u_off, n, N, "frame_features_ragged")   # (without: the call above checks)
+    return _FrameFeaturesFn.apply(enc, rows, _RaggedPool(weight, u_off, int(N)), *enc.pc_block.parameters())
 
 
 class _WindowsFn(torch.autograd.Function):
@@ -1399,22 +1381,15 @@ def windows_forward(enc, table, win_row, T):
     return _WindowsFn.apply(enc, table, win_row, int(T), *enc.parameters())
 
 
-def track_windows(n_frames, T, hop, drop_last_aligned=True):
-    """-> (W, U): the windows of a track of ``n_frames`` frames (the reference's ``crop_with_step`` rule, which drops the
-    last aligned window when ``(n_frames - T) % hop == 0``; ``drop_last_aligned=False`` keeps it) and the frames they use"""
-    n_frames, T, hop = int(n_frames), int(T), int(hop)
-    if not 1 <= hop:
-        raise ValueError(f"track_windows: hop must be >= 1, got {hop}")
-    W = len(range(0, n_frames - T, hop)) if drop_last_aligned else (0 if n_frames < T else (n_frames - T) // hop + 1)
-    return W, ((W - 1) * hop + T if W else 0)
+track_windows = frame_table.track_windows      # (n_frames, T, hop, drop_last_aligned=True) -> (W, U): kept under this name
 
 
 class TrackBatch:
     """What ``plan_tracks`` derives from tracks that do not change between calls, so that a loop over the same tracks
     (adapt.finetune_frozen_bn_tracks) does it once: the frames any window uses (``frames`` [U, N, C]; ``spare``: the
     tensor they are the first U frames of), with ``dedup_points`` their compact table (``rows`` [M, C], ``weight`` [M],
-    ``u_off`` [U + 1]), and the windows' plan (an ops.WindowRows over the U table rows)."""
-    __slots__ = ("frames", "spare", "U", "N", "rows", "weight", "u_off", "plan", "T")
+    ``u_off`` [U + 1]), the windows' plan (an ops.WindowRows over the U table rows), each track's windows (``counts``)."""
+    __slots__ = ("frames", "spare", "U", "N", "rows", "weight", "u_off", "plan", "T", "counts")
 
 
 def plan_tracks(enc, tracks, hop=None, drop_last_aligned=True, dedup_points=False, who="cg_encoder_tracks"):
@@ -1426,37 +1401,27 @@ def plan_tracks(enc, tracks, hop=None, drop_last_aligned=True, dedup_points=Fals
     if not tracks:
         raise ValueError(f"{who}: no track")
     T, hop = constants.NSTEPS, constants.CROP_STEP if hop is None else int(hop)
-    used, starts, base = [], [], 0
-    for i, track in enumerate(tracks):
-        _require_gpu(track, "CGEncoder")
-        if track.dim() != 3 or track.dtype != torch.float32 or not track.is_contiguous():
-            raise ValueError(f"{who} expects contiguous fp32 [F,N,C], got {tuple(track.shape)} {track.dtype}")
-        F, N, C = track.shape
-        _check_encoder_input(enc, C, N)
-        W, U = track_windows(F, T, hop, drop_last_aligned)
-        if W == 0:
-            raise ValueError(f"{who}: track {i} of {F} frames has no window of {T} frames (hop {hop})")
-        used.append(U)
-        starts.append(base + hop * np.arange(W, dtype=np.int64))
-        base += U
+    for track in tracks:
+        _check_encoder_frames(enc, track, who)
+    wp = frame_table.plan_track_windows([t.shape[0] for t in tracks], T, hop, drop_last_aligned, who)
     if dedup_points and torch.is_grad_enabled() and any(t.requires_grad for t in tracks):
         raise RuntimeError(f"{who}: with dedup_points the padded frames have no gradient of their own (a repeated "
                            "detection is one row); call it without dedup_points, or differentiate frame_features_ragged "
                            "for one gradient per distinct detection")
     tb = TrackBatch()
-    tb.U, tb.N, tb.T = base, tracks[0].shape[1], T
-    tb.spare = tracks[0] if len(tracks) == 1 else torch.cat([t[:u] for t, u in zip(tracks, used)])
-    tb.frames = tb.spare[:base]
+    tb.U, tb.N, tb.T, tb.counts = wp.U, tracks[0].shape[1], T, wp.counts
+    tb.spare = tracks[0] if len(tracks) == 1 else torch.cat([t[:u] for t, u in zip(tracks, wp.used)])
+    tb.frames = tb.spare[:tb.U]
     tb.rows = tb.weight = tb.u_off = None
     if dedup_points:
         with torch.no_grad():
             u_off = ops.frames_unique_offsets(tb.frames)
             err = torch.zeros(1, dtype=torch.int32, device=tb.frames.device)
             M = ops.unique_chunk_rows(int(u_off.cpu()[-1]))                    # the one host copy
-            tb.rows, tb.weight, tb.u_off = ops.frames_unique(tb.frames, u_off, 0, base, M, err_flag=err)
+            tb.rows, tb.weight, tb.u_off = ops.frames_unique(tb.frames, u_off, 0, tb.U, M, err_flag=err)
         if err.item():
             raise RuntimeError(f"{who}: ops.frames_unique met a segment that is not its frame's")
-    tb.plan = ops.WindowRows(np.concatenate(starts), T, base, device=tb.frames.device)
+    tb.plan = ops.WindowRows(wp.starts, T, tb.U, device=tb.frames.device)
     return tb
 
 
@@ -1469,16 +1434,8 @@ def encode_track_batch(enc, tb):
     elif _want_bwd(tb.frames, enc.pc_block.parameters()):
         table = frame_features(enc, tb.frames)
     else:
-        # no gradient: whole GEMM row tiles, the way OpenSetScorer.embed_track pads a chunk (neighbouring frames of the
-        # track where it has them, zeros otherwise; the extra frames' features are dropped)
-        pad = (-tb.U) % frame_pad_quantum(tb.N)
-        if pad and tb.U + pad <= tb.spare.shape[0]:
-            chunk = tb.spare[:tb.U + pad]
-        elif pad:
-            chunk = torch.cat([tb.frames, tb.frames.new_zeros((pad,) + tuple(tb.frames.shape[1:]))])
-        else:
-            chunk = tb.frames
-        table = frame_features(enc, chunk)[:tb.U]
+        # no gradient: whole GEMM row tiles (frame_table.pad_chunk); the extra frames' features are dropped
+        table = frame_features(enc, frame_table.pad_chunk(tb.spare, 0, tb.U, frame_pad_quantum(tb.N))[0])[:tb.U]
     return windows_forward(enc, table, tb.plan, tb.T)
 
 
@@ -1523,42 +1480,25 @@ def cg_encoder_raw_track(enc, points, offsets, pick=None, seed=0, track_key=0, h
     processed (``ops.frames_from_raw``'s rule) raises."""
     from . import constants
     _check_track_eval(enc, "cg_encoder_raw_track")
-    for t, name in ((points, "points"), (offsets, "offsets")) + (((pick, "pick"),) if pick is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError(f"cg_encoder_raw_track: {name} must live on the HIP device; this package has no CPU path")
+    N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
+    F = frame_table.check_raw(points, offsets, pick, N, "cg_encoder_raw_track")
     if points.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("cg_encoder_raw_track: no gradient w.r.t. the raw detections (the frame preparation is not "
                            "differentiated); detach the points")
-    N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
-    if offsets.dim() != 1 or offsets.dtype != torch.int32 or offsets.numel() < 1:
-        raise ValueError(f"cg_encoder_raw_track expects offsets int32 [F + 1], got {tuple(offsets.shape)} {offsets.dtype}")
-    F = offsets.numel() - 1
     T, hop = constants.NSTEPS, constants.CROP_STEP if hop is None else int(hop)
-    W, U = track_windows(F, T, hop, drop_last_aligned)
-    if W == 0:
-        raise ValueError(f"cg_encoder_raw_track: a track of {F} frames has no window of {T} frames (hop {hop})")
+    wp = frame_table.plan_track_windows([F], T, hop, drop_last_aligned, "cg_encoder_raw_track")
     dev = points.device
-    keys = None
-    if pick is None:
-        k = np.empty((F, 2), dtype=np.int32)
-        k[:, 0] = np.int64(track_key).astype(np.int32)
-        k[:, 1] = np.arange(F, dtype=np.int64).astype(np.int32)
-        keys = torch.from_numpy(k).to(dev)
+    keys = frame_table.frame_keys(track_key, 0, F, dev) if pick is None else None
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.no_grad():
-        if dedup_points:
-            rows, weight, u_off = ops.frames_from_raw_unique(
-                points, offsets[:U + 1].contiguous(), N, C, pick=None if pick is None else pick[:U].contiguous(), seed=seed,
-                frame_key=None if keys is None else keys[:U].contiguous(), err_flag=err)
-        else:
-            frames = ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=err)
+    with torch.no_grad():              # dedup_points: the frames any window uses; without: all (cg_encoder_track cuts)
+        raw = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err, 0, wp.U if dedup_points else None,
+                                     dedup_points)
     if err.item():
         raise RuntimeError("cg_encoder_raw_track: a frame could not be processed (ops.frames_from_raw's rule)")
     if not dedup_points:
-        return cg_encoder_track(enc, frames, hop, drop_last_aligned)
-    table = frame_features_ragged(enc, rows, weight, u_off, U, N)
-    plan = ops.WindowRows(hop * np.arange(W, dtype=np.int64), T, table.shape[0], device=dev)
-    return windows_forward(enc, table, plan, T)
+        return cg_encoder_track(enc, raw, hop, drop_last_aligned)
+    table = frame_features_ragged(enc, *raw, wp.U, N)
+    return windows_forward(enc, table, ops.WindowRows(wp.starts, T, table.shape[0], device=dev), T)
 
 
 # ---------------------------------------------------------------- encoder trunk (OR-CED baseline, models.py:446-505)

@@ -16,7 +16,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib, constants
+from . import _lib, constants, frame_table
 from . import functional as F_hip
 from . import ops
 from ._lib import check
@@ -78,8 +78,8 @@ def youden_threshold(known_mask: np.ndarray, scores: np.ndarray) -> float:
 def window_count(n_frames, T=constants.NSTEPS, hop=constants.CROP_STEP):
     """Number of crops the reference cuts out of a processed track of ``n_frames`` frames (its ``crop_with_step``,
     datasets.py:16-25, 297-302): one per start in ``arange(n_frames - T, step=hop)``.  The rule drops the last aligned
-    window when ``(n_frames - T) % hop == 0`` and gives none for ``n_frames == T``."""
-    return len(np.arange(int(n_frames) - int(T), step=int(hop)))
+    window when ``(n_frames - T) % hop == 0`` and gives none for ``n_frames == T`` (``frame_table.track_windows``)."""
+    return frame_table.track_windows(n_frames, T, hop)[0]
 
 
 def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
@@ -104,45 +104,11 @@ def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
     return first_t + within, win_row
 
 
-def _check_frames(frames, who):
-    """what every entry point that takes frames refuses: a host tensor, anything but contiguous fp32 [n,N,C]"""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        raise RuntimeError(f"{who}: frames must live on the HIP device; this package has no CPU path")
-    if frames.dim() != 3 or frames.dtype != torch.float32 or not frames.is_contiguous():
-        raise ValueError(f"{who} expects contiguous fp32 [n,N,C], got {tuple(frames.shape)} {frames.dtype}")
-
-
-def _check_raw(points, offsets, pick, N, who):
-    """what every entry point that takes raw detections refuses before it touches its state -> the number of frames"""
-    for t, name in ((points, "points"), (offsets, "offsets")) + (((pick, "pick"),) if pick is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError(f"{who}: {name} must live on the HIP device; this package has no CPU path")
-    if points.dim() != 2 or points.shape[1] != 5 or points.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{who} expects points fp32 or fp64 [P,5], got {tuple(points.shape)} {points.dtype}")
-    if offsets.dim() != 1 or offsets.dtype != torch.int32 or offsets.numel() < 1:
-        raise ValueError(f"{who} expects offsets int32 [n + 1], got {tuple(offsets.shape)} {offsets.dtype}")
-    n = offsets.numel() - 1
-    if pick is not None and (pick.dtype != torch.int32 or tuple(pick.shape) != (n, N)):
-        raise ValueError(f"{who} expects pick int32 [{n}, {N}], got {tuple(pick.shape)} {pick.dtype}")
-    return n
-
-
-def _upload_keys(serial, first, n, dev):
-    """the keys (track serial, frame index) of frames first .. first + n - 1 of one track: int32 [n, 2], one pinned copy"""
-    host = torch.empty((n, 2), dtype=torch.int32, pin_memory=True)
-    k = host.numpy()
-    k[:, 0] = np.int64(serial).astype(np.int32)
-    k[:, 1] = (np.arange(n, dtype=np.int64) + int(first)).astype(np.int32)
-    return host.to(dev, non_blocking=True)
-
-
-def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, mode=None, consts=None):
-    """raw frames -> their distinct points and multiplicities -> [n, 1024] frame features (the ``dedup_points`` route of
-    the raw entries) -> (features, the PointNet layer records, rows of the compact table)"""
-    n = offsets.numel() - 1
-    rows, weight, u_off = ops.frames_from_raw_unique(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys,
-                                                     err_flag=err_flag)
-    feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, n, N, mode, consts=consts)
+def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None):
+    """raw frames (``b``: frames a .. b - 1 of them) -> their distinct points and multiplicities -> (their [n, 1024] frame
+    features, the PointNet layer records, rows of the compact table): the ``dedup_points`` route of the raw entries"""
+    rows, weight, u_off = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a, b, dedup_points=True)
+    feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, u_off.numel() - 1, N, mode, consts=consts)
     return feats, saves, rows.shape[0]
 
 
@@ -172,17 +138,15 @@ class OpenSetScorer:
               dedup_points: bool = False):
         """pcs [M,C,T,N] on the device -> (preds [M] int64, sup_fv [M,32], likelihood [M] f64).
         ``dedup_frames``: for sequentially ordered crops (cut with ``hop``), encode every frame that consecutive crops
-        share bit for bit once (``_embed_dedup``); same triple, same order, one entry per crop.
+        share bit for bit once (``_embed_frames``); same triple, same order, one entry per crop.
         ``dedup_points``: the stored crops carry their padding written out (``process_track`` repeats detections, every
         copy bit-equal); every frame's DISTINCT rows go through the PointNet block once and are pooled with their
         multiplicities (``ops.frames_unique_offsets`` / ``ops.frames_unique``,
         ``functional.encoder_frame_features_ragged``): the same features up to fp32 summation order.  One small copy to
         the host per call (the offsets, to plan the chunks); ``last_rows_encoded`` is the number of table rows it ran.
         The two options multiply."""
-        if dedup_points:
-            return self._embed_points(pcs, hop, dedup_frames)
-        if dedup_frames:
-            return self._embed_dedup(pcs, hop)
+        if dedup_points or dedup_frames:
+            return self._embed_frames(pcs, hop, dedup_frames, dedup_points)
         return self._score(F_hip.encoder_forward(self.encoder, pcs[i:i + self.batch_size], False)[:2]
                            for i in range(0, pcs.shape[0], self.batch_size))
 
@@ -201,64 +165,56 @@ class OpenSetScorer:
         pass, ONE copy of the offsets to the host, chunks of at most the rows a padded chunk runs"""
         U, N, C = frames.shape
         u_off = ops.frames_unique_offsets(frames)
-        chunks = ops.plan_unique_chunks(u_off.cpu().numpy(), self.batch_size * constants.NSTEPS * N)
-        feats, self.last_rows_encoded = [], 0
-        for a, b, M in chunks:
+
+        def chunk(a, b, M):
             rows, weight, seg_off = ops.frames_unique(frames, u_off, a, b, M, err_flag=self.unique_err)
-            f, self.last_pointnet_saves = F_hip.encoder_frame_features_ragged(self.encoder, rows, weight, seg_off, b - a, N)
-            self.last_rows_encoded += M
-            feats.append(f)
+            return F_hip.encoder_frame_features_ragged(self.encoder, rows, weight, seg_off, b - a, N) + (M,)
+        feats = self._chunk_features(ops.plan_unique_chunks(u_off.cpu().numpy(), self.batch_size * constants.NSTEPS * N), chunk)
         if self.unique_err.item():                     # u_off came from these very frames: an internal inconsistency
             self.unique_err.zero_()
             raise RuntimeError("OpenSetScorer: ops.frames_unique met a segment that is not its frame's (unique_err)")
         return feats
 
-    def _embed_points(self, pcs, hop, dedup_frames):
-        """``embed(dedup_points=True)``: the crops' frames (with ``dedup_frames`` the frames consecutive crops do not
-        share, gathered once) -> their distinct rows through the PointNet block -> windows of the feature table"""
-        if not isinstance(pcs, torch.Tensor) or not pcs.is_cuda:
-            raise RuntimeError("CGEncoder: input must live on the HIP device; this package has no CPU path")
-        if pcs.dim() != 4:
-            raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(pcs.shape)}")
+    def _chunk_features(self, chunks, features):
+        """``dedup_points``: ``features(*chunk)`` -> (its frames' features, the PointNet records, its compact table's rows),
+        chunk after chunk -> the chunks of the feature table; counts ``last_rows_encoded``"""
+        feats, self.last_rows_encoded = [], 0
+        for chunk in chunks:
+            f, self.last_pointnet_saves, M = features(*chunk)
+            self.last_rows_encoded += M
+            feats.append(f)
+        return feats
+
+    def _embed_frames(self, pcs, hop, dedup_frames, dedup_points):
+        """``embed`` with an option: the crops' frames -- with ``dedup_frames`` those that consecutive crops do not share
+        (overlap mask: one launch, one small copy to the host; ``plan_frames``), gathered once -- through the PointNet block,
+        with ``dedup_points`` their distinct rows only -> windows of the feature table through the temporal block and heads"""
+        frame_table.check_crops(pcs, "CGEncoder", empty_ok=dedup_points)
         M, C, T, N = pcs.shape
         if M == 0:
             self.last_rows_encoded = 0
             return _empty_triple(self.encoder.MLP_sup1[0].weight.shape[0], pcs.device)
         xp = F_hip._point_major(pcs)                                       # [M, T, N, C] storage
+        frames, win_row = xp.view(M * T, N * C), T * np.arange(M, dtype=np.int64)
         if dedup_frames:
             same = ops.crop_overlap(xp, hop).cpu().numpy() if M > 1 else np.zeros(0, np.int32)
             frame_src, win_row = plan_frames(same, M, T, hop)
-            frames = ops.gather_frames(xp.view(M * T, N * C), torch.from_numpy(frame_src).to(pcs.device)).view(-1, N, C)
             self.last_frames_encoded = len(frame_src)
+        if dedup_points:
+            if dedup_frames:
+                frames = ops.gather_frames(frames, torch.from_numpy(frame_src).to(pcs.device))
+            feats = self._unique_features(frames.view(-1, N, C))
         else:
-            frames, win_row = xp.view(M * T, N, C), T * np.arange(M, dtype=np.int64)
-        feats = self._unique_features(frames)
-        table = feats[0] if len(feats) == 1 else torch.cat(feats)
-        return self._score_windows(table, ops.WindowRows(win_row, T, table.shape[0], device=pcs.device), T)
-
-    def _embed_dedup(self, pcs, hop):
-        """overlap mask (one launch, one small copy to the host) -> plan -> unique frames through the PointNet block ->
-        windows of the frame-feature table through the temporal block and the heads"""
-        F_hip._require_gpu(pcs, "CGEncoder")
-        if pcs.dim() != 4:
-            raise ValueError(f"CGEncoder expects [B,C,T,N], got {tuple(pcs.shape)}")
-        M, C, T, N = pcs.shape
-        xp = F_hip._point_major(pcs)                                       # [M, T, N, C] storage
-        same = ops.crop_overlap(xp, hop).cpu().numpy() if M > 1 else np.zeros(0, np.int32)
-        frame_src, win_row = plan_frames(same, M, T, hop)
-        frames = xp.view(M * T, N * C)
-        U = len(frame_src)
-        q = F_hip.frame_pad_quantum(N)
-        padded = np.concatenate([frame_src, np.zeros((-U) % q, np.int64)])     # whole GEMM row tiles; features dropped
-        idx = torch.from_numpy(padded).to(pcs.device)
-        step = max(self.batch_size * T // q, 1) * q
-        feats = []
-        for a in range(0, len(padded), step):
-            rows = ops.gather_frames(frames, idx[a:a + step].contiguous())
-            f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, rows.view(-1, N, C))
-            feats.append(f)
-        table = feats[0] if len(feats) == 1 else torch.cat(feats)
-        self.last_frames_encoded = U
+            # the index form of frame_table.pad_chunk: whole GEMM row tiles, the padding gathers frame 0; features dropped
+            q = F_hip.frame_pad_quantum(N)
+            idx = torch.from_numpy(np.concatenate([frame_src, np.zeros((-len(frame_src)) % q, np.int64)])).to(pcs.device)
+            step = max(self.batch_size * T // q, 1) * q
+            feats = []
+            for a in range(0, idx.numel(), step):
+                rows = ops.gather_frames(frames, idx[a:a + step].contiguous())
+                f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, rows.view(-1, N, C))
+                feats.append(f)
+        table = frame_table.join_rows(feats)
         return self._score_windows(table, ops.WindowRows(win_row, T, table.shape[0], device=pcs.device), T)
 
     def _score_windows(self, table, plan, T):
@@ -274,46 +230,37 @@ class OpenSetScorer:
         of it -- every frame encoded once, no crop ever written out.  ``drop_last_aligned=False`` also takes the
         aligned last window the reference's rule drops when ``(F - NSTEPS) % hop == 0``.  ``dedup_points``: as in
         ``embed`` -- the distinct rows of every frame once, pooled with their multiplicities."""
-        _check_frames(track, "embed_track")
+        frame_table.check_frames(track, "embed_track")
         F, N, C = track.shape
+
+        def features(U):
+            if dedup_points:
+                return self._unique_features(track[:U])
+            q = F_hip.frame_pad_quantum(N)
+            step = max(self.batch_size * constants.NSTEPS // q, 1) * q
+            feats = []
+            for a in range(0, U, step):
+                b = min(a + step, U)
+                chunk, lo = frame_table.pad_chunk(track, a, b, q)          # whole GEMM row tiles
+                f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, chunk)
+                feats.append(f[lo:lo + b - a])
+            return feats
+        return self._score_track(F, hop, drop_last_aligned, dedup_points, track.device, features)
+
+    def _score_track(self, F, hop, drop_last_aligned, dedup_points, dev, features):
+        """a track of F frames -> the triple of its windows; ``features(U)``: the chunks of the feature table of its first
+        U frames, the frames any window uses"""
         T, hop = constants.NSTEPS, int(hop)
-        W = window_count(F, T, hop) if drop_last_aligned else (0 if F < T else (F - T) // hop + 1)
-        dev = track.device
+        plan = frame_table.plan_track_windows([F], T, hop, drop_last_aligned, allow_empty=True)
+        W, self.last_frames_encoded = plan.counts[0], plan.U
         if W == 0:
-            self.last_frames_encoded = 0
             if dedup_points:
                 self.last_rows_encoded = 0
             return _empty_triple(self.encoder.MLP_sup1[0].weight.shape[0], dev)
-        U = (W - 1) * hop + T                                              # frames any window uses
-        if dedup_points:
-            return self._score_track_table(self._unique_features(track[:U]), U, W, T, hop, dev)
-        q = F_hip.frame_pad_quantum(N)
-        step = max(self.batch_size * T // q, 1) * q
-        feats = []
-        for a in range(0, U, step):
-            b = min(a + step, U)
-            pad = (a - b) % q              # whole GEMM row tiles: neighbouring frames of the track where it has them (a
-            lo = 0                         # view), zeros otherwise; the extra frames' features are dropped
-            if pad and b + pad <= F:
-                chunk = track[a:b + pad]
-            elif pad and a >= pad:
-                chunk, lo = track[a - pad:b], pad
-            elif pad:
-                chunk = torch.cat([track[a:b], track.new_zeros((pad, N, C))])
-            else:
-                chunk = track[a:b]
-            f, self.last_pointnet_saves = F_hip.encoder_frame_features(self.encoder, chunk)
-            feats.append(f[lo:lo + b - a])
-        return self._score_track_table(feats, U, W, T, hop, dev)
-
-    def _score_track_table(self, feats, U, W, T, hop, dev):
-        """the feature chunks of a track's first U frames -> the triple of its W windows"""
-        table = feats[0] if len(feats) == 1 else torch.cat(feats)
-        self.last_frames_encoded = U
-        starts = hop * np.arange(W, dtype=np.int64)
-        plan = ops.WindowRows(starts, T, table.shape[0], device=dev,
+        table = frame_table.join_rows(features(plan.U))
+        rows = ops.WindowRows(plan.starts, T, table.shape[0], device=dev,
                               dev=torch.arange(0, W * hop, hop, dtype=torch.int32, device=dev))
-        return self._score_windows(table, plan, T)
+        return self._score_windows(table, rows, T)
 
     @torch.no_grad()
     def embed_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None, seed: int = 0,
@@ -330,28 +277,17 @@ class OpenSetScorer:
         ``sum(min(card, N))`` rows instead of ``F * N``.  ``last_rows_encoded`` is the number of table rows it ran."""
         enc = self.encoder
         N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
-        F = _check_raw(points, offsets, pick, N, "embed_raw_track")
-        dev = points.device
-        keys = _upload_keys(track_key, 0, F, dev) if pick is None and F else None
-        if dedup_points:
-            T, hop = constants.NSTEPS, int(hop)
-            W = window_count(F, T, hop) if drop_last_aligned else (0 if F < T else (F - T) // hop + 1)
-            if W == 0:
-                self.last_frames_encoded = self.last_rows_encoded = 0
-                return _empty_triple(enc.MLP_sup1[0].weight.shape[0], dev)
-            U = (W - 1) * hop + T                                          # frames any window uses
-            step = max(self.batch_size * T, 1)
-            feats, self.last_rows_encoded = [], 0
-            for a in range(0, U, step):
-                b = min(a + step, U)
-                f, self.last_pointnet_saves, M = _ragged_features(
-                    enc, points, offsets[a:b + 1], N, C, None if pick is None else pick[a:b], seed,
-                    None if keys is None else keys[a:b], self.raw_err)
-                self.last_rows_encoded += M
-                feats.append(f)
-            return self._score_track_table(feats, U, W, T, hop, dev)
-        frames = ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=self.raw_err)
-        return self.embed_track(frames, hop, drop_last_aligned)
+        F = frame_table.check_raw(points, offsets, pick, N, "embed_raw_track")
+        keys = frame_table.frame_keys(track_key, 0, F, points.device) if pick is None and F else None
+        if not dedup_points:
+            frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err)
+            return self.embed_track(frames, hop, drop_last_aligned)
+        step = max(self.batch_size * constants.NSTEPS, 1)
+
+        def features(U):
+            return self._chunk_features(((a, min(a + step, U)) for a in range(0, U, step)), lambda a, b: _ragged_features(
+                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b))
+        return self._score_track(F, hop, drop_last_aligned, True, points.device, features)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
         """ROC-optimal (Youden J) separation of known-test vs held-out-unseen likelihoods
@@ -613,7 +549,7 @@ class StreamingScorer(_LiveScorer):
         # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
         # once, long enough that the windows of any one push are a contiguous slice of it (no upload per push)
         self._period = self.ring_rows // np.gcd(self.ring_rows, self.hop)
-        self._max_win = self.max_push // self.hop + 1
+        self._max_win = frame_table.eager_window_count(self.T + self.max_push, self.T, self.hop)    # of one push
         self._starts = (np.arange(self._period + self._max_win, dtype=np.int64) * self.hop) % self.ring_rows
         self._starts_dev = torch.from_numpy(self._starts.astype(np.int32)).to(dev)
         self.reset()
@@ -633,7 +569,7 @@ class StreamingScorer(_LiveScorer):
         of distinct rows back before it launches the GEMMs, and a live tick must not wait for the device;
         ``push_raw`` with the constructor's ``dedup_points`` is the live route (its table is sized from the offsets)."""
         self._check_eval()
-        _check_frames(frames, "StreamingScorer.push")
+        frame_table.check_frames(frames, "StreamingScorer.push")
         return self._gather([self._push(frames[a:a + self.max_push]) for a in range(0, frames.shape[0], self.max_push)])
 
     def _gather(self, out):
@@ -655,28 +591,24 @@ class StreamingScorer(_LiveScorer):
         With the constructor's ``dedup_points`` the padded frames are never written: ``ops.frames_from_raw_unique`` and
         ``functional.encoder_frame_features_ragged`` give the same frame features from the frames' distinct points."""
         self._check_eval()
-        n = _check_raw(points, offsets, pick, self._N, "StreamingScorer.push_raw")
+        n = frame_table.check_raw(points, offsets, pick, self._N, "StreamingScorer.push_raw")
         q = F_hip.frame_pad_quantum(self._N)
+        keys = frame_table.frame_keys(self.serial, self.n_frames, n, points.device) if pick is None and n else None
+        raw = (points, offsets, self._N, self._C, pick, self.seed, keys, self.raw_err)
         out = []
         for a in range(0, n, self.max_push):
             b = min(a + self.max_push, n)
-            keys = _upload_keys(self.serial, self.n_frames, b - a, points.device) if pick is None else None
             if self.dedup_points:
-                feats, self.last_pointnet_saves, _ = _ragged_features(
-                    self.encoder, points, offsets[a:b + 1], self._N, self._C, None if pick is None else pick[a:b],
-                    self.seed, keys, self.raw_err)
+                feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, a, b)
                 out.append(self._push_features(feats, b - a))
-                continue
-            frames = ops.frames_from_raw(points, offsets[a:b + 1], self._N, self._C, pick=None if pick is None else pick[a:b],
-                                         seed=self.seed, frame_key=keys, n_out=b - a + (a - b) % q, err_flag=self.raw_err)
-            out.append(self._push_padded(frames, b - a))
+            else:
+                out.append(self._push_padded(frame_table.raw_frames(*raw, a, b, n_out=b - a + (a - b) % q), b - a))
         return self._gather(out)
 
     def _push(self, frames):
-        n, N, C = frames.shape
-        q = F_hip.frame_pad_quantum(N)
-        if n % q:                                   # whole GEMM row tiles in bf16 mode; the padding's features are dropped
-            frames = torch.cat([frames, frames.new_zeros(((-n) % q, N, C))])
+        n, q = frames.shape[0], F_hip.frame_pad_quantum(frames.shape[1])
+        if n % q:                  # whole GEMM row tiles in bf16 mode; a push has no neighbours: zeros, features dropped
+            frames = frame_table.pad_chunk(frames, 0, n, q)[0]
         return self._push_padded(frames, n)
 
     def _push_padded(self, frames, n):
@@ -692,7 +624,7 @@ class StreamingScorer(_LiveScorer):
         if first < n:                               # the push wraps: second write from row 0
             self.ring[:n - first].copy_(feats[first:n])
         self.n_frames += n
-        done = 0 if self.n_frames < self.T else (self.n_frames - self.T) // self.hop + 1
+        done = frame_table.eager_window_count(self.n_frames, self.T, self.hop)
         j0, nw = self.n_windows, done - self.n_windows
         if nw == 0:
             return None
@@ -729,7 +661,7 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1,
     ``n_frames`` / ``n_windows``: per SLOT, the frames pushed and the windows emitted so far; ``sids``: the distinct slots
     this tick feeds, ``counts[i]`` new frames of ``sids[i]`` (0 allowed), the frames concatenated in that order.  Slot s
     owns rows ``s * ring_rows .. (s + 1) * ring_rows - 1`` of the feature table, frame f of its track lives in row
-    ``s * ring_rows + f % ring_rows``; a stream with n frames has ``0 if n < T else (n - T) // hop + 1`` windows, window j
+    ``s * ring_rows + f % ring_rows``; a stream with n frames has ``frame_table.eager_window_count(n, T, hop)`` windows, window j
     starts at frame ``j * hop``; group ``j // k`` is voted on by the window with ``j % k == k - 1``.  Returns a TickPlan:
 
     * ``dst_row`` int32 [P]: the table row of every frame; P = the frames padded up to a multiple of ``pad_to``, the
@@ -781,7 +713,7 @@ def plan_tick(n_frames, n_windows, sids, counts, T, hop, k, ring_rows, pad_to=1,
                              "overwrite frames its own windows still read)")
         nf0, w0 = n_frames[sids], n_windows[sids]
         nf1 = nf0 + counts
-        done = np.where(nf1 < T, 0, (nf1 - T) // hop + 1)
+        done = frame_table.eager_window_count(nf1, T, hop)
         nwin = done - w0
         if nwin.min() < 0:
             raise ValueError("plan_tick: a stream has emitted more windows than its frames hold")
@@ -926,7 +858,7 @@ class MultiStreamScorer(_LiveScorer):
         host would have to read the number of distinct rows back before it launches the GEMMs, and a live tick must not
         wait for the device; ``push_raw`` with the constructor's ``dedup_points`` is the live route."""
         self._check_eval()
-        _check_frames(frames, "MultiStreamScorer.push")
+        frame_table.check_frames(frames, "MultiStreamScorer.push")
         n, N, C = frames.shape
         sids, plan, part, mode = self._begin_tick(sids, counts, n, N, "push", False)
         if n == 0:
@@ -951,20 +883,17 @@ class MultiStreamScorer(_LiveScorer):
         the PointNet block once (``ops.frames_from_raw_unique``, ``functional.encoder_frame_features_ragged``: three
         launches in place of one, still none per stream) and give the same frame features up to fp32 summation order."""
         self._check_eval()
-        n = _check_raw(points, offsets, pick, self._N, "MultiStreamScorer.push_raw")
+        n = frame_table.check_raw(points, offsets, pick, self._N, "MultiStreamScorer.push_raw")
         sids, plan, part, mode = self._begin_tick(sids, counts, n, self._N, "push_raw", pick is None,
                                                   pad_to=1 if self.dedup_points else None)
         if n == 0:
             return self._empty(plan, self.ring.device)
+        raw = (points, offsets, self._N, self._C, pick, self.seed, part["frame_key"].view(n, 2) if pick is None else None,
+               self.raw_err)
         if self.dedup_points:
-            feats, self.last_pointnet_saves, _ = _ragged_features(
-                self.encoder, points, offsets, self._N, self._C, pick, self.seed,
-                part["frame_key"].view(n, 2) if pick is None else None, self.raw_err, mode, self._consts)
+            feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, mode=mode, consts=self._consts)
             return self._finish_tick_features(sids, plan, part, mode, feats)
-        frames = ops.frames_from_raw(points, offsets, self._N, self._C, pick=pick, seed=self.seed,
-                                     frame_key=part["frame_key"].view(n, 2) if pick is None else None,
-                                     n_out=plan.dst_row.size, err_flag=self.raw_err)
-        return self._finish_tick(sids, plan, part, mode, frames)
+        return self._finish_tick(sids, plan, part, mode, frame_table.raw_frames(*raw, n_out=plan.dst_row.size))
 
     def _begin_tick(self, sids, counts, n, N, what, want_keys, pad_to=None):
         """the arguments of a tick checked, its plan made and (unless the tick is empty) uploaded -> (sids, plan, the
@@ -1009,15 +938,11 @@ class MultiStreamScorer(_LiveScorer):
             return self._empty(plan, dev)
         rows = ops.WindowRows(plan.win_row, self.T, self.ring.shape[0], self.ring_rows, dev=part["win_row"],
                               segments=self.max_streams)
-        logits, fvs = [], []
-        for i in range(0, nw, self.batch_size):
-            lg, fv, _ = F_hip.encoder_forward_windows(self.encoder, self.ring, rows.slice(i, i + self.batch_size) if
-                                                      nw > self.batch_size else rows, self.T, mode, consts=self._consts)
-            logits.append(lg)
-            fvs.append(fv)
-        logits = logits[0] if len(logits) == 1 else torch.cat(logits)
-        sup_fv = (fvs[0] if len(fvs) == 1 else torch.cat(fvs)).contiguous()
+        out = [F_hip.encoder_forward_windows(self.encoder, self.ring, rows.slice(i, i + self.batch_size) if
+                                             nw > self.batch_size else rows, self.T, mode, consts=self._consts)[:2]
+               for i in range(0, nw, self.batch_size)]
+        logits, sup_fv = (frame_table.join_rows(part).contiguous() for part in zip(*out))
         preds, lik, votes = ops.stream_score(
-            logits.contiguous(), sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
+            logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
             plan.vote_group.size, self.threshold, self.k, self.n_labels, self.n_classes, self.hist_lik, self.hist_pred)
         return _tick(plan, preds, sup_fv, lik, votes)
