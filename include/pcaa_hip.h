@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PCAA_ABI_VERSION 28 /* pcaa_abi_version() of a library built from this header */
+#define PCAA_ABI_VERSION 29 /* pcaa_abi_version() of a library built from this header */
 
 #define PCAA_OK 0
 #define PCAA_ERR_INVALID_ARG 1
@@ -38,6 +38,7 @@ extern "C" {
 #define PCAA_F32 0
 #define PCAA_BF16 1
 #define PCAA_SPLIT_F16 2 /* the [hi | lo] 16-bit image of an fp32 tensor (pcaa_gemm_split3): accepted where a call says so */
+#define PCAA_FP8_E4M3 3 /* OCP e4m3fn bytes (not fnuz), no scale: pcaa_gemm_fp8_affine_elu and pcaa_pointnet_in_apply only */
 
 /* operand storage order for pcaa_gemm */
 #define PCAA_LAYOUT_KC 0 /* contraction index contiguous: A[m*ld + k], B[n*ld + k] */
@@ -143,6 +144,29 @@ int pcaa_gemm_slabs(int math,
 int pcaa_gemm_affine_elu(const void* A, long lda, const void* W, long ldw, void* out, long ldo,
                          const float* scale, const float* shift, int M, int N, int K, int pool_rows,
                          void* stream);
+/* ABI 29: the same eval-mode layer on the block-scaled fp8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, e4m3 x e4m3, every
+ * e8m0 block scale 1.0, fp32 accumulate) -- a deployment precision of the scorers, never of training.
+ * Contract:
+ *   weights   pcaa_quantize_weight_fp8: fp32 W[R,C] (dense) -> W8[R,C] e4m3 and s[R] fp32.  Per row: absmax = f 2^E
+ *             with f in [0.5, 1) gives s = 2^(E-8) (E is held at >= -118 so that s stays a normal fp32; a zero or
+ *             non-finite absmax gives s = 1), W8 = e4m3fn_rne(W / s), |W / s| < 256.  The caller folds s into the
+ *             layer's BatchNorm scale: scale8 = scale * s (exact, a power of two); shift is unchanged.
+ *   values    e4m3fn_rne(clamp(v, -448, 448)), NaN stays NaN; the clamp is arithmetic, no mode bit of the convert.
+ *   product   A8[M,K] . W8[N,K]^T, both contraction-contiguous e4m3 bytes.
+ *   epilogue  ELU(scale8[n] * acc + shift[n]) as pcaa_gemm_affine_elu computes it, stored as
+ *               pool_rows == 0: out_dtype PCAA_FP8_E4M3 (the next layer's operand) or PCAA_BF16, [M, ldo];
+ *               pool_rows in {32, 64, 128}: out_dtype PCAA_F32, the mean over groups of pool_rows rows, [M / pool_rows, ldo]
+ *               (M a multiple of pool_rows).
+ * Shapes (pcaa_gemm_fp8_supported): N a multiple of 256, K a multiple of 128 and at least 128 (the four-stage ring is
+ * filled stage by stage, so one 128-wide step is enough), M > 0: rows past M of a partial last row tile read as zeros
+ * and are not stored.  lda, ldw multiples of 16 that cover K and stay below 2^23; A8, W8, out, scale8, shift 16-B
+ * aligned (a pooled fp32 out: 4-B), ldo >= N and, unpooled, ldo * element size a multiple of 16.  Operands of any
+ * total size: every tile addresses its own 256 rows. */
+int pcaa_quantize_weight_fp8(const float* W, void* W8, float* s, int R, int C, void* stream);
+int pcaa_gemm_fp8_supported(int M, int N, int K);
+int pcaa_gemm_fp8_affine_elu(const void* A8, long lda, const void* W8, long ldw, void* out, int out_dtype, long ldo,
+                             const float* scale8, const float* shift, int M, int N, int K, int pool_rows,
+                             void* stream);
 int pcaa_gemm_dgrad_bn_supported(int M, int N, int K);
 int pcaa_gemm_dgrad_bn(const void* dy, long lddy, const void* Wt, long ldw, const void* y, void* dz, long ld,
                        const float* scale, const float* shift, const float* mean, const float* rstd,
@@ -187,6 +211,8 @@ int pcaa_pointnet_in_wgrad(const void* dy, int dy_dtype, const float* x, int C, 
  * pcaa_bn_finalize, then  a = ELU((x.W^T)*scale + shift).  Backward, two passes over the incoming
  * gradient da only: statistics {sum dz, sum dz*yhat} with dz = da*ELU'(z) (then
  * pcaa_bn_bwd_finalize), and  dW += dy^T.x  with dy = coef0*dz + coef1*y + coef2 formed in registers. */
+/* a_dtype: PCAA_F32, PCAA_BF16, PCAA_SPLIT_F16 or (ABI 29) PCAA_FP8_E4M3 -- the same arithmetic, the activation stored
+ * as e4m3fn_rne(clamp(a, -448, 448)) bytes [P, cout], the operand of pcaa_gemm_fp8_affine_elu. */
 int pcaa_pointnet_in_apply(const float* x, int C, const float* W, const float* scale, const float* shift,
                            void* a, int a_dtype, long P, int cout, void* stream);
 int pcaa_pointnet_in_bwd_stats(const void* da, int dtype, const float* x, int C, const float* W,

@@ -45,7 +45,7 @@ __device__ __forceinline__ float elu_grad_from_pre(float z) { return z > 0.f ? 1
 // to 8 mantissa bits anyway; the fp32 parity path keeps expm1f / expf.  With libm exp the
 // bf16 elementwise passes were VALU-bound, not HBM-bound.
 template <typename T> __device__ __forceinline__ float elu_t(float z) {
-  if constexpr (sizeof(T) == 2) return z > 0.f ? z : __expf(z) - 1.f;
+  if constexpr (sizeof(T) <= 2) return z > 0.f ? z : __expf(z) - 1.f;
   else return elu_f(z);
 }
 template <typename T> __device__ __forceinline__ float elu_grad_from_pre_t(float z) {
@@ -112,6 +112,20 @@ __device__ __forceinline__ void store4_split(split_t* img, size_t row, unsigned 
   *reinterpret_cast<split_x4*>(p) = hi;
   *reinterpret_cast<split_x4*>(p + ch) = lo;
 }
+// ---------------------------------------------------------------- e4m3 storage (PCAA_FP8_E4M3)
+// OCP e4m3fn bytes of the eval-mode fp8 PointNet route (gemm_fp8.hip): e4m3fn_rne(clamp(v, -448, 448)), NaN stays NaN.
+// The clamp is arithmetic: whether the convert instruction saturates depends on a mode bit this code does not own.
+struct fp8_t { unsigned char bits; };
+__device__ __forceinline__ float fp8_clamp(float v) {
+  const float c = fminf(fmaxf(v, -448.f), 448.f);      // (fminf / fmaxf drop a NaN operand: put it back)
+  return v != v ? v : c;
+}
+__device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
+  int r = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(a), fp8_clamp(b), 0, false);
+  r = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(c), fp8_clamp(d), r, true);
+  return (unsigned)r;
+}
+__device__ __forceinline__ void store4(fp8_t* p, f32x4 v) { *reinterpret_cast<unsigned*>(p) = pack4_e4m3(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ float load1(const float* p) { return *p; }
 __device__ __forceinline__ float load1(const bf16_t* p) { return (float)*p; }
 __device__ __forceinline__ void store1(float* p, float v) { *p = v; }

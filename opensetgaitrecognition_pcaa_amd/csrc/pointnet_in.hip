@@ -598,6 +598,8 @@ extern "C" int pcaa_pointnet_in_apply(const float* x, int C, const float* W, con
     LAUNCH_CP(pointnet_in_apply_kernel, float, x, C, W, scale, shift, (float*)a, P, cout);
   else if (a_dtype == PCAA_BF16)
     LAUNCH_CP(pointnet_in_apply_kernel, bf16_t, x, C, W, scale, shift, (bf16_t*)a, P, cout);
+  else if (a_dtype == PCAA_FP8_E4M3)      // the bf16 kernels' arithmetic, stored as e4m3 bytes (common.h, store4(fp8_t*))
+    LAUNCH_CP(pointnet_in_apply_kernel, fp8_t, x, C, W, scale, shift, (fp8_t*)a, P, cout);
   else if (a_dtype == PCAA_SPLIT_F16) {
     // fp32 arithmetic, the activation written as its [hi | lo] bf16 image [P, 2 cout]
     if (C <= 4)

@@ -69,6 +69,38 @@ def get_precision() -> str:
     return _PRECISION["mode"]
 
 
+# How the eval-mode PointNet layers 2-4 multiply in bf16 mode: "bf16" (default) or "fp8" -- e4m3 operands on the block-scaled
+# MFMA (ops.gemm_fp8_affine_elu; the numerics contract is in include/pcaa_hip.h and DESIGN.md section 4).  A switch beside
+# the precision mode, read at each call like it; honoured exactly where the fused bf16 epilogue route runs (_fp8_route),
+# ignored everywhere else: training, a forward that keeps what a backward reads, fp32 and fp16x3 modes, unsupported shapes.
+_EVAL_POINTNET = {"kind": "bf16"}
+
+
+def _check_eval_pointnet(kind):
+    if kind not in ("bf16", "fp8"):
+        raise ValueError("eval_pointnet kind must be 'bf16' or 'fp8'")
+    return kind
+
+
+def set_eval_pointnet(kind: str):
+    _EVAL_POINTNET["kind"] = _check_eval_pointnet(kind)
+
+
+def get_eval_pointnet() -> str:
+    return _EVAL_POINTNET["kind"]
+
+
+@contextlib.contextmanager
+def eval_pointnet(kind):
+    """``with eval_pointnet("fp8"):`` -- the kind inside the block, the previous one restored after it"""
+    prev = _EVAL_POINTNET["kind"]
+    _EVAL_POINTNET["kind"] = _check_eval_pointnet(kind)
+    try:
+        yield
+    finally:
+        _EVAL_POINTNET["kind"] = prev
+
+
 def set_sync_bn_group(group):
     """``None`` (per-rank BatchNorm statistics, stock DDP semantics) or a
     torch.distributed process group over which the fp64 batch statistics are
@@ -161,17 +193,20 @@ class EncoderEvalConstants:
     """What an eval-mode forward derives from a FROZEN encoder alone, computed once by the kernels that compute it in every
     forward otherwise (same bits): the folded BatchNorm coefficients ``(scale, shift)`` of the ten BatchNorm layers and, in
     bf16 mode, the bf16 images of the weights of PointNet layers 2-4.  It records what it was made from -- the encoder, the
-    precision mode, and ``_version`` and storage address of every parameter and buffer -- and ``valid_for`` compares that,
-    so a holder notices ``load_state_dict``, an optimizer step, a move to another dtype or device, or a mode switch.  (The
+    precision mode, the eval-PointNet kind, and ``_version`` and storage address of every parameter and buffer -- and
+    ``valid_for`` compares that, so a holder notices ``load_state_dict``, an optimizer step, a move to another dtype or
+    device, a mode switch or ``set_eval_pointnet``.  Made under kind "fp8" (bf16 mode) it also holds ``w8``: the e4m3
+    image and the folded coefficient ``scale * s`` of PointNet layers 2-4 (ops.quantize_weight_fp8).  (The
     tensors are the ones the encoder had when this was made: a Parameter OBJECT swapped for another is only noticed
     through ``encoder_eval_constants`` being called again.)  Never shared between encoders."""
-    __slots__ = ("mode", "bn", "w16", "enc_id", "tensors", "stamp")
+    __slots__ = ("mode", "kind", "bn", "w16", "w8", "enc_id", "tensors", "stamp")
 
     def _stamp(self):
         return [(t._version, t.data_ptr()) for t in self.tensors]
 
     def valid_for(self, enc, mode):
-        return id(enc) == self.enc_id and mode == self.mode and self._stamp() == self.stamp
+        return (id(enc) == self.enc_id and mode == self.mode and self.kind == get_eval_pointnet()
+                and self._stamp() == self.stamp)
 
 
 def encoder_eval_constants(enc, mode=None):
@@ -182,7 +217,7 @@ def encoder_eval_constants(enc, mode=None):
     if enc.training:
         raise RuntimeError("encoder_eval_constants: the encoder is in training mode (its BatchNorm uses batch statistics)")
     c = EncoderEvalConstants()
-    c.mode, c.bn, c.w16, c.enc_id = mode, {}, {}, id(enc)
+    c.mode, c.kind, c.bn, c.w16, c.w8, c.enc_id = mode, get_eval_pointnet(), {}, {}, {}, id(enc)
     c.tensors = list(itertools.chain(enc.parameters(), enc.buffers()))
     c.stamp = c._stamp()
     with torch.no_grad():
@@ -192,6 +227,8 @@ def encoder_eval_constants(enc, mode=None):
             c.bn[id(bn)] = ops.bn_eval_coeffs(bn, cout, conv.bias)
             if mode == "bf16" and li > 0 and cin % 8 == 0:
                 c.w16[id(conv)] = ops.cast_bf16(conv.weight.view(cout, cin), True, False)[0]
+                if c.kind == "fp8":
+                    c.w8[id(conv)] = _quantize_layer(conv.weight.view(cout, cin), c.bn[id(bn)][0])
         for layer in enc.tc_block.layers():
             c.bn[id(layer.batch_norm)] = ops.bn_eval_coeffs(layer.batch_norm, layer.conv1d.weight.shape[0], layer.conv1d.bias)
     return c
@@ -209,6 +246,33 @@ def _eval_w16(consts, conv, W2d):
     if consts is not None:
         return consts.w16[id(conv)]
     return ops.cast_bf16(W2d, True, False)[0]
+
+
+def _quantize_layer(W2d, scale):
+    """(W8, scale8) of one eval-mode PointNet layer: the e4m3 image and the BatchNorm scale with the rows' weight scales
+    folded in (a power of two each: the product is exact)"""
+    W8, s = ops.quantize_weight_fp8(W2d)
+    return W8, scale * s
+
+
+def _eval_w8(consts, conv, W2d, scale):
+    """(W8, scale8) from the frozen constants where they hold them (made under kind "fp8"), else quantised now"""
+    if consts is not None and id(conv) in consts.w8:
+        return consts.w8[id(conv)]
+    return _quantize_layer(W2d, scale)
+
+
+def _fp8_route(layers, rows, training, mode, pool_rows, want_bwd):
+    """whether this eval-mode forward runs layers 2-4 on the fp8 MFMA: the kind asks for it, the call is one the fused bf16
+    epilogue route serves (bf16 mode, no training, nothing kept for a backward), the first layer is the recompute layer
+    (it writes the e4m3 operand) and every later layer has a shape pcaa_gemm_fp8_affine_elu takes -- all or none"""
+    if not (_EVAL_POINTNET["kind"] == "fp8" and _FUSE_EVAL_EPILOGUE and not training and not want_bwd and mode == "bf16"
+            and pool_rows in (0, 32, 64, 128) and len(layers) > 1 and (not pool_rows or rows % pool_rows == 0)):
+        return False
+    w0 = layers[0].module[0].weight
+    if not (w0.shape[1] <= 8 and ops.pointnet_in_ok(w0.shape[1], w0.shape[0])):
+        return False
+    return all(ops.gemm_fp8_supported(rows, l.module[0].weight.shape[0], l.module[0].weight.shape[1]) for l in layers[1:])
 
 
 def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None, conv=None):
@@ -277,6 +341,7 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, wan
     saves = []
     a = xp2d
     nl = len(layers)
+    fp8 = xp2d.dtype == torch.float32 and _fp8_route(layers, xp2d.shape[0], training, mode, pool_rows, want_bwd)
     # fp16x3 mode: the activations between the layers are [hi | lo] images when every later product is one the
     # LDS-DMA kernel serves (whole 256-tiles); else the layer stack runs in exact fp32
     split = mode == "fp16x3" and nl > 1 and (training or not want_bwd) and all(
@@ -308,10 +373,20 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, wan
                 mean = rstd = None
                 count = rows
             saves.append(_LayerSave(a, None, None, scale, shift, mean, rstd, count, cin, cout, 0, mom=mom))
-            a = ops.pointnet_in_apply(a, W2d, scale, shift, torch.bfloat16 if mode == "bf16" else
-                                      (ops.SplitImage.dtype if split else torch.float32))
+            a = ops.pointnet_in_apply(a, W2d, scale, shift, ops.FP8 if fp8 else (torch.bfloat16 if mode == "bf16" else
+                                      (ops.SplitImage.dtype if split else torch.float32)))
             continue
         last_pool = li == nl - 1 and pool_rows
+        if fp8:
+            # as the fused bf16 route below, on e4m3 operands: layers 2 and 3 hand on e4m3, the last one bf16 rows (the
+            # ragged route's segment_weighted_mean reads them) or the fp32 mean over the frame's points
+            scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
+            W8, scale8 = _eval_w8(consts, conv, W2d, scale)
+            saves.append(_LayerSave(a, None, None, scale, shift, None, None, a.shape[0], cin, cout, 0))
+            if li == nl - 1:
+                return ops.gemm_fp8_affine_elu(a, W8, scale8, shift, pool_rows, None if pool_rows else torch.bfloat16), saves
+            a = ops.gemm_fp8_affine_elu(a, W8, scale8, shift)
+            continue
         if (_FUSE_EVAL_EPILOGUE and not training and not want_bwd and mode == "bf16" and a.dtype == torch.bfloat16
                 and (not last_pool or pool_rows in (32, 64, 128))
                 and ops.gemm_dgrad_bn_supported(a.shape[0], cout, cin)):

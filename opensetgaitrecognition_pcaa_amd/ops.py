@@ -550,6 +550,53 @@ def gemm_dgrad_bn_supported(M, N, K):
     return bool(_lib.load().pcaa_gemm_dgrad_bn_supported(int(M), int(N), int(K)))
 
 
+# ---------------------------------------------------------------- eval-mode PointNet layers in fp8 (csrc/gemm_fp8.hip)
+PCAA_FP8_E4M3 = 3
+FP8 = torch.float8_e4m3fn      # OCP e4m3fn; the tensors only carry the bytes -- no ATen arithmetic runs on them
+
+
+def quantize_weight_fp8(W2d):
+    """fp32 W [R, C] -> (W8 e4m3 [R, C], s fp32 [R]): per row s = 2^(E-8) with absmax = f 2^E, f in [0.5, 1) (1 for a zero
+    or non-finite row), W8 = e4m3fn_rne(W / s).  The caller folds s into the layer's BatchNorm scale."""
+    _chk(W2d, "quantize_weight_fp8.W", torch.float32, 2)
+    R, C = W2d.shape
+    W8 = torch.empty((R, C), dtype=torch.uint8, device=W2d.device)
+    s = torch.empty((R,), dtype=torch.float32, device=W2d.device)
+    check(_lib.load().pcaa_quantize_weight_fp8(_p(W2d), _p(W8), _p(s), R, C, _s()), "pcaa_quantize_weight_fp8")
+    return W8.view(FP8), s
+
+
+def gemm_fp8_supported(M, N, K):
+    return bool(_lib.load().pcaa_gemm_fp8_supported(int(M), int(N), int(K)))
+
+
+def gemm_fp8_affine_elu(a8, W8, scale8, shift, pool_rows=0, out_dtype=None):
+    """ELU(scale8 * (a8[M,K] @ W8[N,K]^T) + shift) on the block-scaled fp8 MFMA, e4m3 operands, fp32 accumulation:
+    e4m3 (default) or bf16 [M, N]; with pool_rows in {32, 64, 128} the fp32 mean over groups of pool_rows rows
+    [M / pool_rows, N].  scale8 = scale * s of quantize_weight_fp8; shapes as gemm_fp8_supported."""
+    _chk(a8, "gemm_fp8_affine_elu.a8", FP8, 2)
+    _chk(W8, "gemm_fp8_affine_elu.W8", FP8, 2)
+    _chk(scale8, "gemm_fp8_affine_elu.scale8", torch.float32)
+    _chk(shift, "gemm_fp8_affine_elu.shift", torch.float32)
+    M, K = a8.shape
+    N = W8.shape[0]
+    if out_dtype is None:
+        out_dtype = torch.float32 if pool_rows else FP8
+    if (W8.shape[1] != K or scale8.numel() != N or shift.numel() != N or not gemm_fp8_supported(M, N, K)
+            or pool_rows not in (0, 32, 64, 128) or (pool_rows and M % pool_rows)):
+        raise ValueError(f"gemm_fp8_affine_elu: unsupported shapes a8 {tuple(a8.shape)} W8 {tuple(W8.shape)} pool {pool_rows}")
+    if out_dtype not in ((torch.float32,) if pool_rows else (FP8, torch.bfloat16)):
+        raise TypeError(f"gemm_fp8_affine_elu: out_dtype {out_dtype} with pool_rows {pool_rows}")
+    out = torch.empty((M // pool_rows if pool_rows else M, N), dtype=out_dtype, device=a8.device)
+    code = PCAA_FP8_E4M3 if out_dtype == FP8 else _dt(out)
+    _timed("gemm_fp8_kernel<affine_elu>",
+           lambda: check(_lib.load().pcaa_gemm_fp8_affine_elu(_p(a8), a8.stride(0), _p(W8), W8.stride(0), _p(out), code, N,
+                                                              _p(scale8), _p(shift), M, N, K, int(pool_rows), _s()),
+                         "pcaa_gemm_fp8_affine_elu"),
+           2.0 * M * N * K, M * K + N * K + out.numel() * out.element_size())
+    return out
+
+
 def gemm_dgrad_bn(dy, Wt, y, scale, shift, mean, rstd, tail=None):
     """dz[M,N] = (dy[M,K] @ Wt[N,K]^T) * ELU'(y*scale+shift) plus the BatchNorm-backward statistics of
     the layer that owns y -- the dgrad of the layer above fused with the first half of this layer's
@@ -821,7 +868,8 @@ def pointnet_in_apply(x2d, W2d, scale, shift, out_dtype):
                                                  cout, _s()), "pcaa_pointnet_in_apply(split)")
         return a
     a = torch.empty((P, cout), dtype=out_dtype, device=x2d.device)
-    check(_lib.load().pcaa_pointnet_in_apply(_p(x2d), C, _p(W2d), _p(scale), _p(shift), _p(a), _dt(a), P, cout, _s()),
+    code = PCAA_FP8_E4M3 if out_dtype == FP8 else _dt(a)      # (e4m3: the operand of gemm_fp8_affine_elu)
+    check(_lib.load().pcaa_pointnet_in_apply(_p(x2d), C, _p(W2d), _p(scale), _p(shift), _p(a), code, P, cout, _s()),
           "pcaa_pointnet_in_apply")
     return a
 
