@@ -59,6 +59,23 @@ def zero_slices(dec_start, total, world, chunks, rank):
             for c in range(chunks)]
 
 
+def subtract_ranges(lo, hi, covered):
+    """[lo, hi) minus the ``covered`` [a, b) ranges (in any order; they may overlap, touch or lie outside) as sorted
+    disjoint non-empty [(a, b)]: what of a region of the flat buffer no other exchange or update has taken."""
+    left, a = [], lo
+    for clo, chi in sorted(covered):
+        if clo >= hi:
+            break
+        if chi <= clo:
+            continue
+        if clo > a:
+            left.append((a, clo))
+        a = max(a, chi)
+    if a < hi:
+        left.append((a, hi))
+    return left
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # The step's exchanges behind one small interface, so that a one-GPU box can run ONE RANK'S PROGRAM OF A WORLD OF W
 # (round 6: no multi-GPU node has been available in any round).

@@ -1190,7 +1190,7 @@ def encoder_forward_windows(enc, table, win_row, T, mode=None, consts=None):
     return _encoder_heads(enc, st, x4)
 
 
-def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, before_pointnet=None,
+def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None,
                      gph=None, d_hproj=None, gph_gout=None, after_heads=None):
     """Returns ({state_dict-style name: grad}, dx [B,C,T,N] view or None).
     ``gout``: optional {name: gradient view}; split-K products accumulate into
@@ -1213,8 +1213,6 @@ def encoder_backward(enc, st, d_logits, d_supfv, need_dx=False, gout=None, befor
     for i, d in enumerate(dg, start=1):
         for k, v in d.items():
             g[f"tc_block.dtc{i}.{k}"] = v
-    if before_pointnet is not None:
-        before_pointnet()        # trainer hook: everything enqueued so far is the latency-bound part of the backward
     pg, dxp = pointnet_backward(st.pn, enc.pc_block.layers(), st.mode, dpool=dx2, pool_rows=N, need_dx=need_dx,
                                 gout=gout)
     for i, d in enumerate(pg, start=1):

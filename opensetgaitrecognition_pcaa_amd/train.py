@@ -13,10 +13,12 @@ RCCL all-reduce per optimiser under data parallelism) and runs one step as a
 fixed sequence of HIP launches on the current stream with NO host
 synchronisation: losses stay on the device until the caller reads them.
 """
+import collections
+import functools
 import itertools
-import math
 import os
 import pickle
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -35,9 +37,13 @@ _ALIGN = 64  # floats; keeps every parameter view 256-B aligned inside the flat 
 _SIDE_STREAMS = {}
 
 
-# where the decoder's side-stream update is enqueued: "dec_bwd" (right after the decoder backward), "heads" (after the MLP
-# heads' backward launch), "pointnet" (before the PointNet backward); re-measured each time the kernels around it change
-_SIDE_ADAM_AT = os.environ.get("PCAA_SIDE_ADAM_AT", "dec_bwd")
+def _round_up(n, multiple):
+    return (n + multiple - 1) // multiple * multiple
+
+
+def _is_wide_weight(named_param):
+    """a decoder parameter the fused weight-gradient + Adam kernels can take: a weight behind the first layer"""
+    return not (named_param[0].startswith("G.dense1.") or named_param[0].endswith(".bias"))
 
 
 def _side_streams(device):
@@ -50,16 +56,36 @@ def _side_streams(device):
         # forced 1-rank RCCL): the critic branch sharing the weight-gradient stream 5.74 | 6.50, sharing the Adam stream
         # (both idle while the critic runs) 5.72 | 6.38, separate streams 5.67 | 6.10 -- although a data-parallel process
         # then has five streams (RCCL brings its own) on the device's four hardware queues and rocprofv3 shows the
-        # critic on the main stream's queue.  PCAA_STREAM_LAYOUT keeps the other two selectable for re-measurement.
-        side, small = torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)
-        layout = os.environ.get("PCAA_STREAM_LAYOUT", "separate")
-        if layout == "critic_on_wgrad":
-            _SIDE_STREAMS[key] = (side, small, small)
-        elif layout == "critic_on_side":
-            _SIDE_STREAMS[key] = (side, side, small)
-        else:
-            _SIDE_STREAMS[key] = (side, small, torch.cuda.Stream(device=device))
+        # critic on the main stream's queue.
+        _SIDE_STREAMS[key] = tuple(torch.cuda.Stream(device=device) for _ in range(3))
     return _SIDE_STREAMS[key]
+
+
+# What a step of ``B`` rows in precision ``mode`` does with the decoder's gradients, decided once and from plain
+# values: ``exchange`` (a process group or an emulated world is there), ``world``, the constructor's ``force_collectives``
+# / ``dp_zero`` / ``dp_gather`` / ``fused_decoder_update``, whether the side streams and a decoder exist.  ->
+#   scheme      "none" (single process) | "allreduce" | "gather" (packed operands all-gathered, the _t16 update) | "zero"
+#               (reduce-scatter, sharded Adam, all-gather).  dp_gather runs as "allreduce" beyond ops.PACK_MAX_CHUNKS
+#               ranks or ops.PACK_ROWS batch rows, outside the bf16 mode and without the fused update; dp_zero needs the
+#               side stream its Adam runs on, and a decoder
+#   collective  the step issues collectives: more than one rank, a forced 1-rank group or the emulation of a world
+#   fused       single process: the wide layers' weight gradients go straight into Adam (wgrad+Adam kernels) ...
+#   exact       ... in their fp32-product form (the parity modes "fp32" / "fp16x3")
+#   early       the side-stream update of the decoder launches right after the decoder backward
+#   buckets     one all-reduce per decoder layer, issued from the wgrad stream during the decoder backward
+StepPlan = collections.namedtuple("StepPlan", "scheme collective fused exact early buckets")
+
+
+def step_plan(exchange, world, force_collectives, dp_zero, dp_gather, fused_decoder_update, side_streams, decoder, mode, B):
+    """-> the StepPlan of a step of ``B`` rows in precision ``mode`` (the fields: see above)"""
+    collective = bool(exchange and (world > 1 or force_collectives))
+    zero = bool(dp_zero and exchange and decoder and collective and side_streams)
+    gather = bool(collective and dp_gather and not zero and mode == "bf16" and fused_decoder_update and side_streams
+                  and world <= ops.PACK_MAX_CHUNKS and B <= ops.PACK_ROWS)
+    exact = mode in ("fp32", "fp16x3")
+    fused = bool(decoder and fused_decoder_update and not collective and side_streams and (mode == "bf16" or exact))
+    return StepPlan("zero" if zero else "gather" if gather else "allreduce" if collective else "none", collective,
+                    fused, fused and exact, bool(side_streams and not zero), bool(collective and side_streams and not zero))
 
 
 class StepCount:
@@ -113,12 +139,12 @@ class FlatBuffer:
             n = int(torch.Size(padded_shapes[name]).numel()) if name in padded_shapes else p.numel()
             self.sizes.append(n)
             self.params.append(p)
-            total += (n + _ALIGN - 1) // _ALIGN * _ALIGN
+            total += _round_up(n, _ALIGN)
         if tail_multiple is not None:
             # (start_name, multiple): zero tail padding so that the region from that parameter to the end of the
             # buffer splits evenly (sharded optimizer: world x chunks x 64-float pieces)
             start = self.offsets[self.names.index(tail_multiple[0])]
-            total = start + (total - start + tail_multiple[1] - 1) // tail_multiple[1] * tail_multiple[1]
+            total = start + _round_up(total - start, tail_multiple[1])
         self.total = total
         self.p = torch.zeros(total, dtype=torch.float32, device=device)
         self.g = torch.zeros(total, dtype=torch.float32, device=device)
@@ -267,8 +293,7 @@ class PCAATrainer:
         self._gather_bufs = {}          # (layer, world) -> (gathered packed chunks [world, (N + K) * 64] bf16, own chunk)
         self._force_collectives = bool(force_collectives)
         self.fused_decoder_update = bool(fused_decoder_update)
-        # the parity modes too (fp32-product kernels); tests that read the decoder's weight gradients pass False
-        self.fused_exact = bool(fused_decoder_update)
+        self._side = self._aux = self._wg = None       # the side streams (finalize)
         if grad_compress not in (None, "bf16"):
             raise ValueError("grad_compress must be None or 'bf16'")
         self.grad_compress = grad_compress
@@ -355,8 +380,7 @@ class PCAATrainer:
         # weight-gradient + Adam kernels what is left for the plain Adam pass is one contiguous range
         if self.decoder is not None:
             dec_named = [("G." + n, p) for n, p in self.decoder.named_parameters() if n.startswith("dense")]
-            is_small = lambda n: n.startswith("G.dense1.") or n.endswith(".bias")
-            g_named += [(n, p) for n, p in dec_named if is_small(n)] + [(n, p) for n, p in dec_named if not is_small(n)]
+            g_named += sorted(dec_named, key=_is_wide_weight)          # (stable: the module's order inside each group)
         # Decoder widths that are not multiples of 64 (N=150, the reference's default: 1125 ... 18000) keep the
         # weight-streaming kernels away -- rows of 1125 floats are not even 16-B aligned.  The weights are then
         # STORED zero-padded to multiples of 64 in both dimensions and the decoder runs in the padded widths
@@ -365,28 +389,24 @@ class PCAATrainer:
         # modules expose are bit-for-bit what an unpadded run of the same kernels would hold.
         pads = {}
         if self.decoder is not None:
-            r64 = lambda v: (v + 63) // 64 * 64
             lins = self.decoder.dense_layers()
             if any(l.weight.shape[0] % 64 for l in lins):
                 for i, l in enumerate(lins, start=1):
                     n_out, n_in = l.weight.shape
-                    kp = n_in if i == 1 else r64(n_in)             # the first layer's input is the latent itself
-                    pads[f"G.dense{i}.weight"] = (r64(n_out), kp)
-                    pads[f"G.dense{i}.bias"] = (r64(n_out),)
+                    kp = n_in if i == 1 else _round_up(n_in, 64)   # the first layer's input is the latent itself
+                    pads[f"G.dense{i}.weight"] = (_round_up(n_out, 64), kp)
+                    pads[f"G.dense{i}.bias"] = (_round_up(n_out, 64),)
         # Data-parallel with a sharded decoder optimizer (PCAA_DP_ZERO=1, ZeRO-1 style): the decoder gradients are
         # reduce-SCATTERED, every rank runs Adam on its 1/world slice only (the 0.78 ms, 4.4 GB update shrinks by the
         # world size) and the updated parameters are all-gathered -- the same bytes on the wire as the all-reduce.
-        self._zero = self._dp_zero_arg and self.pg is not None
+        self._zero = self._dp_zero_arg and self.pg is not None and self.decoder is not None
         self._zero_chunks = 4
         tail = None
-        if self.decoder is None:
-            self._zero = False
         if self._zero:
             first_dec = next(n for n, _ in g_named if n.startswith("G."))
             tail = (first_dec, pdist.zero_tail_multiple(self.world, self._zero_chunks, _ALIGN))
         self.flat_g = FlatBuffer(g_named, self.device, padded_shapes=pads, tail_multiple=tail)
         if pads:
-            from types import SimpleNamespace
             self.decoder._pcaa_pad = [
                 SimpleNamespace(weight=self.flat_g.padded[f"G.dense{i}.weight"][0],
                                 bias=self.flat_g.padded[f"G.dense{i}.bias"][0])
@@ -420,9 +440,6 @@ class PCAATrainer:
                    if nm.startswith("E.MLP_head.") or nm.startswith("E.MLP_sup2.")]
         assert sup_idx == list(range(sup_idx[0], sup_idx[-1] + 1)) and sup_idx[-1] == n_enc - 1
         self._sup_range = (self.flat_g.offsets[sup_idx[0]], enc_end)
-        # projection-head + decoder gradients (>98 % of the bytes) are complete before the encoder
-        # backward starts: their all-reduce is issued asynchronously and overlaps it
-        self._tail_region = self.flat_g.g[enc_end:]
         # The decoder's parameters (98 % of optimizer_G's bytes: a 0.8 ms HBM-bound Adam pass) are
         # final once its backward -- and, data-parallel, the all-reduce of that region -- is done,
         # long before the encoder backward ends.  Their Adam update runs on a side stream beside the
@@ -439,7 +456,7 @@ class PCAATrainer:
                 k = fg.names.index(nm)
                 o, n = fg.offsets[k], fg.sizes[k]
                 shp = tuple(fg.padded[nm][0].shape) if nm in fg.padded else tuple(fg.params[k].shape)
-                self._dec_fused[i] = (o, (o + n + _ALIGN - 1) // _ALIGN * _ALIGN,      # up to the next parameter's offset
+                self._dec_fused[i] = (o, _round_up(o + n, _ALIGN),      # up to the next parameter's offset
                                       fg.p[o:o + n].view(shp), fg.m[o:o + n].view(shp), fg.v[o:o + n].view(shp))
         # layer -> [bf16 image of the weight, the version pair it stands for]: kept by the fused update, streamed by the
         # decoder's forward / dgrad of single-process bf16 steps (_refresh_w16)
@@ -537,33 +554,42 @@ class PCAATrainer:
         self.comm[kind + "_bytes"] = self.comm.get(kind + "_bytes", 0) + int(nbytes)
 
     def _allreduce(self, t, async_op=False):
-        if self._collective() and t.numel():
-            in_dec = (t.data_ptr() >= self.flat_g.g.data_ptr() + 4 * self._dec_start
-                      and t.data_ptr() < self.flat_g.g.data_ptr() + 4 * self.flat_g.total)
-            off = (t.data_ptr() - self.flat_g.g.data_ptr()) // 4 if in_dec else -1
-            # a bucket whose weight gradient exists ONLY as the bf16 wire image (_g16_direct) must take the compressed
-            # path whatever its size: its fp32 range was never written
-            if self.grad_compress == "bf16" and in_dec and (t.numel() >= self._COMPRESS_MIN or off in self._g16_direct):
-                # decoder gradient bucket: round to bf16 once, sum on the wire in bf16, widen back into the fp32
-                # gradient buffer when the consumer waits for it
-                g16 = self._g16[off:off + t.numel()]
-                if off not in self._g16_direct:          # else: the weight-gradient kernel wrote the bf16 image itself
-                    g16.copy_(t)
-                self._count(2 * t.numel())
-                work = self._xchg.all_reduce(g16, async_op=async_op)
-                if not async_op:
-                    t.copy_(g16)
-                    return None
-                return _CompressedWork(work, t, g16)
-            assert off not in self._g16_direct, "a bf16-direct gradient bucket reached the fp32 all-reduce"
-            self._count(t.numel() * t.element_size())
-            return self._xchg.all_reduce(t, async_op=async_op)
-        return None
+        """all-reduce of a tensor that is no part of ``flat_g.g`` (the critic's gradients); like _allreduce_g for the steps
+        that issue collectives: the caller asks the step's plan"""
+        if not t.numel():
+            return None
+        self._count(t.numel() * t.element_size())
+        return self._xchg.all_reduce(t, async_op=async_op)
 
-    def _collective(self):
-        """whether this trainer's steps issue collectives (a group of more than one rank, a forced 1-rank group, or the
-        emulation of a world)"""
-        return self._xchg is not None and (self.world > 1 or self._force_collectives)
+    def _allreduce_g(self, lo, hi, async_op=False):
+        """all-reduce of the gradient bucket ``flat_g.g[lo:hi]``"""
+        if hi <= lo:
+            return None
+        t = self.flat_g.g[lo:hi]
+        # a bucket whose weight gradient exists ONLY as the bf16 wire image (_g16_direct) must take the compressed
+        # path whatever its size: its fp32 range was never written
+        if (self.grad_compress == "bf16" and self._dec_start <= lo < self.flat_g.total
+                and (hi - lo >= self._COMPRESS_MIN or lo in self._g16_direct)):
+            # decoder gradient bucket: round to bf16 once, sum on the wire in bf16, widen back into the fp32
+            # gradient buffer when the consumer waits for it
+            g16 = self._g16[lo:hi]
+            if lo not in self._g16_direct:          # else: the weight-gradient kernel wrote the bf16 image itself
+                g16.copy_(t)
+            self._count(2 * (hi - lo))
+            work = self._xchg.all_reduce(g16, async_op=async_op)
+            if not async_op:
+                t.copy_(g16)
+                return None
+            return _CompressedWork(work, t, g16)
+        assert lo not in self._g16_direct, "a bf16-direct gradient bucket reached the fp32 all-reduce"
+        self._count(4 * (hi - lo))
+        return self._xchg.all_reduce(t, async_op=async_op)
+
+    def _plan(self, mode, B, exchange=None):
+        """step_plan() of this trainer for a step of ``B`` rows in ``mode`` (``exchange=False``: seen as a single process)"""
+        return step_plan(self._xchg is not None if exchange is None else exchange, self.world, self._force_collectives,
+                         self._dp_zero_arg, self._dp_gather, self.fused_decoder_update, self._side is not None,
+                         self.decoder is not None, mode, B)
 
     def _advance_g(self, supervise):
         """Begin optimizer_G's next step: the main count always, the supervised-only parameters' count on
@@ -590,7 +616,7 @@ class PCAATrainer:
             fg.adam(lr, b1, b2, grad_scale=gs, lo=a, hi=b, advance=False, count=fg.sup_count)
         fg.adam(lr, b1, b2, grad_scale=gs, lo=b, hi=hi, advance=False, max_blocks=max_blocks)
 
-    def _w16_active(self, mode, B, collective):
+    def _w16_active(self, mode, B, exchange=None):
         """the layers whose weight a fused wgrad+Adam kernel will update in a step of this kind (the only updater that keeps
         the bf16 image): layer -> (W, m, v) views"""
         # PCAA_DEC_W16=1 turns the images on.  Off by default: measured (round 4, same box) the forward / dgrad kernels drop
@@ -598,12 +624,14 @@ class PCAATrainer:
         # from inside the update kernel (64-B partial lines from different CUs) that kernel went 1.06 -> 2.1 ms, as a cast
         # pass behind it the extra 0.9 GB of side-stream traffic: step 5.39-5.44 -> 5.48-5.53 ms, N=256 11.9-12.0 -> 12.3-12.6
         # (profiles/r04_ab_dec_w16.txt).  The step is short of HBM bandwidth, not of decoder time.
-        if (self.decoder is None or not self.fused_decoder_update or collective or self._side is None or mode != "bf16"
-                or os.environ.get("PCAA_DEC_W16", "0") != "1"):
-            return {}
-        return {i: t for i, t in self._dec_fused.items() if F_hip._skinny(mode, B, t[2].shape[0], t[2].shape[1])}
+        active = {}
+        if os.environ.get("PCAA_DEC_W16", "0") == "1" and mode == "bf16" and self._plan(mode, B, exchange).fused:
+            for i, t in self._dec_fused.items():
+                if F_hip._skinny(mode, B, t[2].shape[0], t[2].shape[1]):
+                    active[i] = t
+        return active
 
-    def _refresh_w16(self, mode, B, collective):
+    def _refresh_w16(self, mode, B, exchange=None):
         """{layer: bf16 image of its weight} for a step of this kind (functional.decoder_forward / _backward stream the
         images instead of the fp32 matrices: half the bytes, same rounding, same result).  An image stands for the
         (flat-buffer, module-parameter) version pair it was built or last updated under: anything that writes the weights
@@ -613,7 +641,7 @@ class PCAATrainer:
         if self.decoder is None:
             return images
         params = self.decoder.dense_layers()
-        active = self._w16_active(mode, B, collective)
+        active = self._w16_active(mode, B, exchange)
         for i, t in self._dec_fused.items():
             if i not in active:
                 if i in self._dec_w16:
@@ -651,434 +679,450 @@ class PCAATrainer:
             self.finalize()
         if self.discriminator_means is None and self.variant != "v1":
             raise RuntimeError("prior means not set: call sample_prior_means() / set_prior_means()")
-        cfg = self.cfg
         B = pcs.shape[0]
         mode = self.precision or F_hip.get_precision()
-        enc, dec = self.encoder, self.decoder
-        gs = 1.0 / self.world
+        plan = self._plan(mode, B)
+        # what this step accumulates on its way to Adam (dropped with the step):
+        #   updates        {layer: callback(dz2, x)} of the layers whose weight gradient a fused kernel forms and consumes
+        #   fused_ranges   their [lo, hi) ranges of flat_g: no gradient exists there
+        #   direct_ranges  the ranges whose gradient exists only as the bf16 wire image
+        #   deferred       the fused update launches, run by the side stream once the decoder backward is enqueued
+        #   early_buckets  (lo, hi, work) of the per-layer all-reduces issued during the decoder backward, in issue order
+        #   pending        (lo, hi, work) of everything the plain Adam pass has to wait for, in issue order
+        #   dec_grads      where the decoder backward writes its gradients
+        #   scatter / gathers  the sharded optimizer's reduce-scatter and all-gather works
+        #   joined / done  events: the critic branch is enqueued / the side stream's decoder update is
+        s = SimpleNamespace(scheme=plan.scheme, plan=plan, mode=mode, B=B, supervise=supervise, gs=1.0 / self.world, w16={},
+                            updates=None, fused_ranges=[], direct_ranges=[], deferred=[], early_buckets=[], pending=[],
+                            dec_grads=self._dec_grads, scatter=[], gathers=[], joined=None, done=None)
+        self._begin_step()
+        # (1) encoder forward (train-mode BatchNorm)
+        # (the decoder projection head rides in the launch of the MLP heads)
+        logits, sup_fv, st = F_hip.encoder_forward(self.encoder, pcs, True, mode, gph=self.decoder_projection_head)
+        F_hip.mark("heads_fwd")
+        # (2) cross-entropy, its gradient and the predicted labels in one launch
+        sup_loss, dlogits, preds = ops.cross_entropy(logits, gt, want_loss=True, want_grad=supervise,
+                                                     grad_scale=1.0, want_preds=True, err_flag=self._err)
+        # (3) D-step and the adversarial term of the G-step, beside (4)
+        d_losses, loss_g, dsup = self._critic(s, gt, z0, alphas, sup_fv)
+        if self.variant == "v3":
+            rec_loss = None
+            self._backward_v3(s, st, dlogits, dsup)
+        else:
+            self.dp_scheme = s.scheme
+            # (4) G-step forward: decoder + Chamfer (+ fused gradient)
+            hproj = st.hproj if self.decoder_projection_head is not None else sup_fv
+            s.w16 = self._refresh_w16(mode, B)
+            rec, acts = F_hip.decoder_forward(self.decoder, hproj, mode, images=s.w16)
+            F_hip.mark("dec_fwd")
+            inv_bt = 1.0 / (B * self.T)
+            frame_loss, drec = ops.chamfer(rec.view(B, self.C, self.T, self.N), pcs, want_grad=True, grad_scale=inv_bt)
+            rec_loss = ops.total(frame_loss, inv_bt)
+            F_hip.mark("chamfer")
+            # (5) G-step backward (the adversarial gradient w.r.t. sup_fvs seeds the accumulation), exchange, update, join
+            F_hip.set_wgrad_stream(self._wg)
+            try:
+                dsup, dh = self._decoder_backward(s, acts, drec, dsup)
+                F_hip.mark("dec_bwd")
+                after_heads = self._exchange_and_update_decoder(s)
+                gv = self.flat_g.grad_views
+                F_hip.encoder_backward(self.encoder, st, dlogits if supervise else None, dsup, gout=self._enc_grads,
+                                       after_heads=after_heads, gph=self.decoder_projection_head, d_hproj=dh,
+                                       gph_gout=(gv["GPH.0.weight"], gv["GPH.0.bias"]) if dh is not None else None)
+            finally:
+                F_hip.set_wgrad_stream(None)
+            self._update_encoder_and_join(s)
+            F_hip.mark("adam+join")
+            # SyncBN's statistics all-reduces (functional._sync_stats) belong to the step's exchanges too
+            self.comm["collectives"] += F_hip._SYNC_BN.get("collectives", 0)
+            self.comm["payload_bytes"] += F_hip._SYNC_BN.get("payload_bytes", 0)
+        tot = (loss_g if rec_loss is None else rec_loss + loss_g) + (sup_loss if supervise else 0.0)
+        return {"d_loss": d_losses[0], "gp": d_losses[1], "rec_loss": rec_loss, "loss_g": loss_g,
+                "sup_loss": sup_loss, "tot_loss": tot, "preds": preds, "out_labels": logits, "sup_fvs": sup_fv}
+
+    def _begin_step(self):
         ops.set_stats_pool(self._stats_pool)
         self._stats_pool.begin()
         self._enc_region.zero_()
         self.comm = {"collectives": 0, "payload_bytes": 0}
         F_hip._SYNC_BN["collectives"] = F_hip._SYNC_BN["payload_bytes"] = 0
-        step_events = self._step_events = [] if self.time_comm else None
-        F_hip._SYNC_BN["events"] = step_events if self._sync_bn_group is not None else None
+        self._step_events = [] if self.time_comm else None
+        F_hip._SYNC_BN["events"] = self._step_events if self._sync_bn_group is not None else None
 
-        # (1) encoder forward (train-mode BatchNorm)
-        # (the decoder projection head rides in the launch of the MLP heads)
-        logits, sup_fv, st = F_hip.encoder_forward(enc, pcs, True, mode, gph=self.decoder_projection_head)
-        F_hip.mark("heads_fwd")
-        # (2) cross-entropy, its gradient and the predicted labels in one launch
-        sup_loss, dlogits, preds = ops.cross_entropy(logits, gt, want_loss=True, want_grad=supervise,
-                                                     grad_scale=1.0, want_preds=True, err_flag=self._err)
-        # (3) D-step: prior sample, WGAN-GP loss + closed-form gradients, Adam; then the adversarial
-        # term of the G-step with the UPDATED critic.  ~10 launches of one wave per batch row: they run
-        # on a second stream beside the HBM-bound decoder forward / Chamfer / decoder backward, which do
-        # not depend on the critic, and join where the adversarial gradient enters the G backward.
+    def _timing_event(self, on=True):      # ``on``: one end of a ``time_comm`` pair, on the current stream; else None
+        if not on:
+            return None
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+
+    def _timing_pair(self, ev0):           # closes the pair ``ev0`` opened (no-op for None)
+        if ev0 is not None:
+            self._step_events.append((ev0, self._timing_event()))
+
+    # ---- (3) the critic
+    # D-step: prior sample, WGAN-GP loss + closed-form gradients, Adam; then the adversarial term of the G-step with the
+    # UPDATED critic.  ~10 launches of one wave per batch row: they run on a second stream beside the HBM-bound decoder
+    # forward / Chamfer / decoder backward, which do not depend on the critic, and join (``s.joined``) where the
+    # adversarial gradient enters the G backward.  -> (losses [2], loss_g [], dsup [B, L])
+    def _critic(self, s, gt, z0, alphas, sup_fv):
+        """the critic branch on its stream -> (losses [2], loss_g [], dsup [B, L]); records ``s.joined``"""
+        if self._aux is None:
+            return self._critic_branch(s, gt, z0, alphas, sup_fv, (None, None, None))
+        fork = torch.cuda.Event()
+        fork.record(ops.current_stream())
+        # The three results the main stream consumes are allocated HERE, from the main stream's pool, and written on the
+        # aux stream: a tensor allocated on the aux stream and handed to the main one (record_stream(main)) costs an
+        # event record ON THE MAIN STREAM when it is freed -- four of them were 18 us of the 40 us step boundary
+        # (round 6, probe: 40.1 -> 21.6 us without them).  This way the records fall on the aux stream.
+        outs = (torch.empty(2, dtype=torch.float32, device=self.device), torch.empty((), dtype=torch.float32, device=self.device),
+                torch.empty_like(sup_fv))
+        for t in outs:
+            t.record_stream(self._aux)
+        with ops.on_stream(self._aux):
+            self._aux.wait_event(fork)
+            res = self._critic_branch(s, gt, z0, alphas, sup_fv, outs)
+            s.joined = torch.cuda.Event()
+            s.joined.record(self._aux)
+        return res
+
+    def _critic_branch(self, s, gt, z0, alphas, sup_fv, outs):
+        """``outs``: (losses [2], loss_g [], dsup [B, L]) destinations allocated by the caller, or Nones"""
+        cfg, al = self.cfg, alphas.reshape(-1).contiguous()
         adv = float(cfg["ADV_WEIGHT"])
-
-        def critic_branch(outs=(None, None, None)):
-            """``outs``: (losses [2], loss_g [], dsup [B, L]) destinations allocated by the caller"""
-            if self.variant == "v1":
-                # centroids from the mean learner (train-mode BatchNorm over the batch's one-hots, :170)
-                _, oh = ops.prior_sample(z0, self._zero_means, gt, self.K)
-                if self.learn_centroids:
-                    for n, p in self.mean_learner.named_parameters():
-                        p.grad = self.flat_d.grad_views["ML." + n]
-                    self.flat_d.g[:self._ml_end].zero_()
-                    mus = self.mean_learner(oh)
-                    z = z0 + mus.detach()
-                    dl, _, dz = ops.disc_wgan_gp(z, sup_fv, oh, alphas.reshape(-1).contiguous(), self._d_params,
-                                                 cfg["GP_WEIGHT"], grads_out=self._d_grads, want_dz=True, losses_out=outs[0])
-                    mus.backward(dz)
-                else:
-                    with torch.no_grad():
-                        z = z0 + self.mean_learner(oh)
-                    dl, _ = ops.disc_wgan_gp(z, sup_fv, oh, alphas.reshape(-1).contiguous(), self._d_params,
-                                             cfg["GP_WEIGHT"], grads_out=self._d_grads, losses_out=outs[0])
+        if self.variant != "v1":
+            z, oh = ops.prior_sample(z0, self.discriminator_means, gt, self.K)
+        else:
+            # centroids from the mean learner (train-mode BatchNorm over the batch's one-hots, :170)
+            _, oh = ops.prior_sample(z0, self._zero_means, gt, self.K)
+            if self.learn_centroids:
+                for n, p in self.mean_learner.named_parameters():
+                    p.grad = self.flat_d.grad_views["ML." + n]
+                self.flat_d.g[:self._ml_end].zero_()
+                mus = self.mean_learner(oh)
+                z = z0 + mus.detach()
             else:
-                z, oh = ops.prior_sample(z0, self.discriminator_means, gt, self.K)
-                dl, _ = ops.disc_wgan_gp(z, sup_fv, oh, alphas.reshape(-1).contiguous(), self._d_params,
-                                         cfg["GP_WEIGHT"], grads_out=self._d_grads, losses_out=outs[0])
+                with torch.no_grad():
+                    z = z0 + self.mean_learner(oh)
+        res = ops.disc_wgan_gp(z, sup_fv, oh, al, self._d_params, cfg["GP_WEIGHT"], grads_out=self._d_grads,
+                               want_dz=self.learn_centroids, losses_out=outs[0])
+        if self.learn_centroids:
+            mus.backward(res[2])
+        if s.plan.collective:
             self._allreduce(self.flat_d.g)
-            self.flat_d.adam(cfg["LR"], cfg["B1"], cfg["B2"], grad_scale=gs)
-            synth = ops.disc_forward(sup_fv, oh, self._d_params)
-            lg = ops.total(synth, -adv / B, out=outs[1])
-            gout = torch.full((B,), -adv / B, dtype=torch.float32, device=self.device)
-            ds, _, _ = ops.disc_backward(sup_fv, oh, self._d_params, gout, want_dx=True, want_params=False, dx_out=outs[2])
-            return dl, lg, ds
+        self.flat_d.adam(cfg["LR"], cfg["B1"], cfg["B2"], grad_scale=s.gs)
+        synth = ops.disc_forward(sup_fv, oh, self._d_params)
+        lg = ops.total(synth, -adv / s.B, out=outs[1])
+        gout = torch.full((s.B,), -adv / s.B, dtype=torch.float32, device=self.device)
+        ds, _, _ = ops.disc_backward(sup_fv, oh, self._d_params, gout, want_dx=True, want_params=False, dx_out=outs[2])
+        return res[0], lg, ds
 
-        joined = None
-        if self._aux is not None:
-            main = ops.current_stream()
-            fork = torch.cuda.Event()
-            fork.record(main)
-            # The three results the main stream consumes are allocated HERE, from the main stream's pool, and written on the
-            # aux stream: a tensor allocated on the aux stream and handed to the main one (record_stream(main)) costs an
-            # event record ON THE MAIN STREAM when it is freed -- four of them were 18 us of the 40 us step boundary
-            # (round 6, probe: 40.1 -> 21.6 us without them).  This way the records fall on the aux stream.
-            outs = (torch.empty(2, dtype=torch.float32, device=self.device), torch.empty((), dtype=torch.float32, device=self.device),
-                    torch.empty_like(sup_fv))
-            for t in outs:
-                t.record_stream(self._aux)
-            with ops.on_stream(self._aux):
-                self._aux.wait_event(fork)
-                d_losses, loss_g, dsup = critic_branch(outs)
-                joined = torch.cuda.Event()
-                joined.record(self._aux)
-        else:
-            d_losses, loss_g, dsup = critic_branch()
-
-        if self.variant == "v3":
-            # no decoder, no reconstruction term: tot = loss_g (+ sup_loss) (PCAA_ablation.py:621-645)
-            if joined is not None:
-                ops.current_stream().wait_event(joined)
-            F_hip.set_wgrad_stream(self._wg)
-            try:
-                F_hip.encoder_backward(enc, st, dlogits if supervise else None, dsup, gout=self._enc_grads)
-            finally:
-                F_hip.set_wgrad_stream(None)
-            if self._wg is not None:
-                ops.current_stream().wait_stream(self._wg)
-            self._allreduce(self.flat_g.g)
-            self._advance_g(supervise)
-            self._adam_g(0, self.flat_g.total, supervise, gs)
-            tot = loss_g + (sup_loss if supervise else 0.0)
-            return {"d_loss": d_losses[0], "gp": d_losses[1], "rec_loss": None, "loss_g": loss_g,
-                    "sup_loss": sup_loss, "tot_loss": tot, "preds": preds, "out_labels": logits, "sup_fvs": sup_fv}
-
-        # (4) G-step forward: decoder + Chamfer (+ fused gradient)
-        hproj = st.hproj if self.decoder_projection_head is not None else sup_fv
-        w16 = self._refresh_w16(mode, B, self._collective())
-        rec, acts = F_hip.decoder_forward(dec, hproj, mode, images=w16)
-        F_hip.mark("dec_fwd")
-        rec4 = rec.view(B, self.C, self.T, self.N)
-        inv_bt = 1.0 / (B * self.T)
-        frame_loss, drec = ops.chamfer(rec4, pcs, want_grad=True, grad_scale=inv_bt)
-        rec_loss = ops.total(frame_loss, inv_bt)
-
-        F_hip.mark("chamfer")
-        # (5) G-step backward (the adversarial gradient w.r.t. sup_fvs seeds the accumulation)
+    def _backward_v3(self, s, st, dlogits, dsup):
+        """variant 3's G-step: no decoder, no reconstruction term: tot = loss_g (+ sup_loss) (PCAA_ablation.py:621-645)"""
+        if s.joined is not None:
+            ops.current_stream().wait_event(s.joined)
         F_hip.set_wgrad_stream(self._wg)
-        if joined is not None and self.decoder_projection_head is None:
-            ops.current_stream().wait_event(joined)
-            joined = None
-        dh = None
-        collective = self._collective()
-        # Data-parallel: a decoder layer's gradient goes onto the wire as soon as it exists.  The backward
-        # produces the 118 M-parameter output layer FIRST (75 % of all gradient bytes), a quarter of a millisecond
-        # before the decoder backward is over: its all-reduce is issued from the wgrad stream right behind its
-        # weight / bias gradient kernels, the later (smaller) layers follow the same way, and the small rest
-        # (first layer, whose bias gradient is on the main stream) goes out after the decoder backward.
-        early_buckets = []                         # (lo, hi, work) in flat_g coordinates, in issue order
-        layer_hook = None
-        zero = self._zero and collective and self._side is not None
-        if zero:
-            pass
-        elif collective and self._wg is not None:
-            fg = self.flat_g
-
-            def layer_hook(layer):
-                if layer < 2:
-                    return
-                lo = fg.offsets[fg.names.index(f"G.dense{layer}.weight")]
-                nxt = f"G.dense{layer + 1}.weight"
-                hi = fg.offsets[fg.names.index(nxt)] if nxt in fg.names else fg.total
-                # ordered behind this layer's dW / db kernels, whichever stream the layer's path put them on
-                self._wg.wait_stream(ops.current_stream())
-                with ops.on_stream(self._wg):
-                    early_buckets.append((lo, hi, self._allreduce(fg.g[lo:hi], async_op=True)))
-
-        # Single process: the wide decoder layers' weight gradients go straight into Adam (one kernel per layer forms
-        # dW in registers and updates W / exp_avg / exp_avg_sq in place: 24 B per parameter instead of 4 + 28).  The
-        # backward only notes each layer's operands; the kernels run on the Adam side stream once the decoder backward
-        # -- whose dgrads read the weights they overwrite -- is enqueued (measured, same box, ms/step: unfused 6.27-6.30
-        # | behind each layer's own dgrad 6.13-6.18, the decoder backward section 276 -> 634 us | here 6.12-6.14).
-        updates, fused_ranges, deferred = None, [], []
-        exact_dec = mode in ("fp32", "fp16x3")      # the parity modes: the same fused kernels with fp32 products
-        if (self.fused_decoder_update and not collective and self._side is not None
-                and (mode == "bf16" or (self.fused_exact and exact_dec))):
-            for layer, (lo, hi, Wv, mv, vv) in self._dec_fused.items():
-                if F_hip._skinny(mode, B, Wv.shape[0], Wv.shape[1]) or F_hip._skinny_exact(mode, B, Wv.shape[0], Wv.shape[1]):
-                    updates = updates or {}
-                    updates[layer] = lambda dz2, x, t=(Wv, mv, vv, w16.get(layer)): deferred.append((dz2, x) + t + (None,))
-                    fused_ranges.append((lo, hi))
-        # Data parallel, dp_gather: the same fused update from the ranks' stacked rows.  A layer's callback runs where the
-        # backward has just formed dz2: the operands are packed and their all-gather goes out from there (the collective's own
-        # stream picks up behind what is enqueued here; this stream does not wait) and the update kernel follows on the Adam
-        # side stream once it is back -- no gradient bucket, no all-reduce, no separate Adam pass for these layers.
-        # (round 6: the operands travel PACKED -- one transposed bf16 chunk of 64 batch rows per rank and layer, ops.pack_rows_t16
-        # -- half the bytes, one all-gather per layer instead of two, and 16-B fragment loads in the update kernel)
-        gather = (collective and self._dp_gather and not zero and mode == "bf16" and self.fused_decoder_update
-                  and self._side is not None and self.world <= ops.PACK_MAX_CHUNKS and B <= ops.PACK_ROWS)
-        self.dp_scheme = "zero" if zero else ("gather" if gather else ("allreduce" if collective else "none"))
-        if gather:
-            def gather_update(layer, Wv, mv, vv):
-                def cb(dz2, x):
-                    key = (layer, self.world)
-                    if key not in self._gather_bufs:
-                        ce = ops.packed_chunk_elems(Wv.shape[0], Wv.shape[1])
-                        self._gather_bufs[key] = (torch.zeros((self.world, ce), dtype=torch.bfloat16, device=self.device),
-                                                  torch.empty(ce, dtype=torch.bfloat16, device=self.device))
-                    packed_all, own = self._gather_bufs[key]
-                    dzc, xc = (dz2 if dz2.stride(1) == 1 else dz2.contiguous()), (x if x.stride(1) == 1 else x.contiguous())
-                    self._count(2 * packed_all.numel(), "gather")
-
-                    def send():
-                        ops.pack_rows_t16(dzc, xc, out=own)
-                        # (flat views: gloo's all-gather wants output and input of the same rank)
-                        return self._xchg.all_gather_into_tensor(packed_all.view(-1), own, async_op=True, tag=layer)
-                    if self._wg is not None:
-                        # pack + all-gather leave from the weight-gradient stream (behind dz2, which this stream has just
-                        # formed): the main stream goes straight on to the layer's dgrad
-                        self._wg.wait_stream(ops.current_stream())
-                        with ops.on_stream(self._wg):
-                            dzc.record_stream(self._wg)
-                            xc.record_stream(self._wg)
-                            work = send()
-                    else:
-                        work = send()
-                    deferred.append((packed_all, None, Wv, mv, vv, None, [work]))
-                return cb
-
-            for layer, (lo, hi, Wv, mv, vv) in self._dec_fused.items():
-                if F_hip._skinny(mode, B, Wv.shape[0], Wv.shape[1]):
-                    updates = updates or {}
-                    updates[layer] = gather_update(layer, Wv, mv, vv)
-                    fused_ranges.append((lo, hi))
-            if layer_hook is not None:
-                # the per-layer gradient buckets only for what the gathered update does not take
-                plain_hook, taken = layer_hook, set(updates or {})
-
-                def layer_hook(layer):
-                    if layer not in taken:
-                        plain_hook(layer)
-        if not set(w16) <= set(updates or {}):
-            # an image is only current if THIS step's update of its weight rewrites it
-            raise RuntimeError("PCAATrainer: a bf16 weight image is in use for a layer whose update is not fused")
-        dec_grads = self._dec_grads
-        self._g16_direct = set()
-        if collective and layer_hook is not None and self.grad_compress == "bf16" and mode == "bf16":
-            dec_grads = dict(dec_grads)
-            for layer, (lo, view16) in self._dec_grads16.items():
-                if updates and layer in updates:
-                    continue                     # (dp_gather: no gradient of this layer exists in any form)
-                # same size rule as _allreduce's compressed path: one predicate decides both
-                if F_hip._skinny(mode, B, view16.shape[0], view16.shape[1]) and view16.numel() >= self._COMPRESS_MIN:
-                    dec_grads[f"dense{layer}.weight"] = view16
-                    self._g16_direct.add(lo)
-        # [lo, hi) ranges of flat_g.g that hold NO gradient after this step: the fused weight-gradient + Adam kernels and
-        # the bf16-direct wire images never write the fp32 gradient there (round-2 advisor finding: a consumer of
-        # grad_views -- clipping, norm logging -- must skip them or construct the trainer with fused_decoder_update=False)
-        self.gradless_ranges = sorted(fused_ranges) + sorted(
-            (lo, lo + v.numel()) for lo, v in (self._dec_grads16.values() if self._g16_direct else ()) if lo in self._g16_direct)
-        if self.decoder_projection_head is not None:
-            # the head's own backward (dh -> dsup, dW, db) runs inside the heads' backward launch below
-            _, dh = F_hip.decoder_backward(dec, acts, drec, need_dz=True, grads_out=dec_grads, mode=mode,
-                                           after_layer=layer_hook, updates=updates, images=w16)
-            if joined is not None:
-                ops.current_stream().wait_event(joined)
-        else:
-            _, dsup = F_hip.decoder_backward(dec, acts, drec, need_dz=True, grads_out=dec_grads, dz_init=dsup,
-                                             mode=mode, after_layer=layer_hook, updates=updates, images=w16)
-        # The decoder's gradients are final here (the projection head's follow with the encoder's: its backward
-        # runs in the MLP heads' launch).  Data-parallel: their all-reduce goes out now, in a few chunks (the
-        # collectives of one communicator run in order), so that the side-stream Adam of chunk i overlaps the
-        # all-reduce of chunk i+1 instead of waiting for all 628 MB.
-        F_hip.mark("dec_bwd")
-        pending = []                               # (lo, hi, work) in flat_g coordinates
-        zero_gather = []
-        if zero:
-            import torch.distributed as dist
-            fg, n = self.flat_g, self._zero_len
-            if self._wg is not None:
-                ops.current_stream().wait_stream(self._wg)   # the decoder's dW/db were written on that stream
-            scatter = []
-            z16 = self.grad_compress == "bf16"
-            for c in range(self._zero_chunks):
-                lo = self._dec_start + c * n
-                if z16:
-                    # bf16 buckets (round 4): the chunk is rounded once, summed on the wire in bf16, and this rank's
-                    # reduced slice goes to Adam as it came off the wire (adam_step_dev_g16_) -- the gradient half of
-                    # the exchange moves half the bytes; the updated parameters are gathered in fp32 as before
-                    g16 = self._g16[lo:lo + n]
-                    g16.copy_(fg.g[lo:lo + n])
-                    self._count(2 * n, "scatter")
-                    scatter.append(dist.reduce_scatter_tensor(self._zero_g16[c], g16, group=self.pg, async_op=True))
-                else:
-                    self._count(4 * n, "scatter")
-                    scatter.append(dist.reduce_scatter_tensor(self._zero_g[c], fg.g[lo:lo + n], group=self.pg, async_op=True))
-            self._advance_g(supervise)
-
-            def launch_zero_adam():
-                ready = torch.cuda.Event()
-                ready.record(ops.current_stream())
-                with ops.on_stream(self._side):
-                    self._side.wait_event(ready)
-                    for c in range(self._zero_chunks):
-                        lo, hi = self._zero_slices[c][2:]                   # this rank's slice of chunk c
-                        scatter[c].wait()
-                        if z16:
-                            ops.adam_step_dev_g16_(fg.p[lo:hi], self._zero_g16[c], fg.m[lo:hi], fg.v[lo:hi], cfg["B1"],
-                                                   cfg["B2"], 1e-8, fg.coef_dev, gs, self._side_adam_blocks)
-                        else:
-                            ops.adam_step_dev_(fg.p[lo:hi], self._zero_g[c], fg.m[lo:hi], fg.v[lo:hi], cfg["B1"], cfg["B2"],
-                                               1e-8, fg.coef_dev, gs, self._side_adam_blocks)
-                        self._zero_p[c].copy_(fg.p[lo:hi])
-                        self._count(4 * n, "gather")
-                        zero_gather.append(dist.all_gather_into_tensor(
-                            fg.p[self._dec_start + c * n:self._dec_start + (c + 1) * n], self._zero_p[c],
-                            group=self.pg, async_op=True))
-        elif gather or early_buckets:
-            # The wide layers are on the wire already, as gathered operands (no gradient exists) or as per-layer buckets.
-            # What is left of the decoder region -- its first layer and the biases in front of the wide weights
-            # (finalize), a wide layer neither scheme took, tail padding -- is the region MINUS those ranges, computed
-            # as such (round-5 advisor finding: the two branches this replaces each assumed which ranges the other
-            # scheme had covered): a few small all-reduces, issued once the wgrad stream's products are in.
-            covered = sorted(fused_ranges + [(lo, hi) for lo, hi, _ in early_buckets])
-            residual, a = [], self._dec_start
-            for lo, hi in covered + [(self.flat_g.total, self.flat_g.total)]:
-                if lo > a:
-                    residual.append((a, lo))
-                a = max(a, hi)
-            if residual and self._wg is not None:
-                ops.current_stream().wait_stream(self._wg)
-            pending = early_buckets + [(lo, hi, self._allreduce(self.flat_g.g[lo:hi], async_op=True)) for lo, hi in residual]
-            # (issue order = the order the collectives of one communicator complete in)
-        else:
-            bounds = [self._dec_start]
-            if collective and self._wg is not None:
-                ops.current_stream().wait_stream(self._wg)   # the decoder's dW/db were written on that stream
-            nchunk = self._dp_chunks if collective else 1
-            dec_n = self.flat_g.total - self._dec_start
-            for i in range(1, nchunk + 1):
-                b = self._dec_start + (dec_n * i // nchunk) // _ALIGN * _ALIGN if i < nchunk else self.flat_g.total
-                if b > bounds[-1]:
-                    bounds.append(b)
-            for lo, hi in zip(bounds[:-1], bounds[1:]):
-                pending.append((lo, hi, self._allreduce(self.flat_g.g[lo:hi], async_op=True)))
-        early = self._side is not None
-        hook = hook_heads = None
-        done = []
-        if zero:
-            early = False
-            hook_heads = launch_zero_adam          # beside the temporal block's backward, like the replicated update
-        if early:
-            self._advance_g(supervise)
-
-            def launch_side_adam():
-                ready = torch.cuda.Event()
-                ready.record(ops.current_stream())
-                with ops.on_stream(self._side):
-                    self._side.wait_event(ready)        # everything enqueued on the main stream so far
-                    if self._wg is not None:
-                        self._side.wait_stream(self._wg)   # ... and the decoder weight gradients on the wgrad stream
-                    for dz2, x, Wv, mv, vv, w16, works in deferred:
-                        dz2.record_stream(self._side)
-                        if x is not None:
-                            x.record_stream(self._side)
-                        if works is not None:
-                            for wk in works:
-                                wk.wait()               # this stream waits for the all-gather of THIS layer only
-                            ops.skinny_linear_wgrad_adam_t16_(dz2, self.world, Wv, mv, vv, *self.betas_g(), 1e-8,
-                                                              self.flat_g.coef_dev, gs)      # (dz2: the gathered packed chunks)
-                            continue
-                        ops.skinny_linear_wgrad_adam_(dz2, x, Wv, mv, vv, *self.betas_g(), 1e-8, self.flat_g.coef_dev, gs,
-                                                      exact=exact_dec)
-                        if w16 is not None:
-                            # the image follows its weight on this stream (a coalesced 6 B/param pass; written from inside
-                            # the update kernel -- 64-B partial lines from different CUs -- it doubled that kernel's time)
-                            ops.cast_bf16(Wv, want_transposed=False, out=w16)
-                    for lo, hi, work in pending:
-                        if hi <= self._dec_start:
-                            continue                    # the projection-head slice is updated on the main stream
-                        g16 = None
-                        if isinstance(work, _CompressedWork) and (lo % 4 == 0):
-                            work.wait(widen=False)      # Adam reads the reduced bf16 bucket as it came off the wire
-                            work.done = True
-                            g16 = self._g16
-                        elif work is not None:
-                            work.wait()                 # side stream waits for THIS chunk's all-reduce only
-                        # what the fused kernels did not take: [lo, hi) minus their ranges
-                        a = max(lo, self._dec_start)
-                        for flo, fhi in sorted(fused_ranges) + [(hi, hi)]:
-                            if flo > a:
-                                self.flat_g.adam(cfg["LR"], cfg["B1"], cfg["B2"], grad_scale=gs, lo=a, hi=min(flo, hi),
-                                                 advance=False, max_blocks=self._side_adam_blocks, g16=g16)
-                            a = max(a, fhi)
-                            if a >= hi:
-                                break
-                    ev = torch.cuda.Event()
-                    ev.record(self._side)
-                    done.append(ev)
-
-            # right after the decoder backward, i.e. beside the heads' and the temporal block's backward (measured
-            # against "after the heads' launch" 6.576 | 6.621 and "beside the PointNet backward GEMMs" 6.90 ms/step)
-            at = _SIDE_ADAM_AT
-            if at == "pointnet":
-                hook = launch_side_adam
-            elif at == "heads":
-                hook_heads = launch_side_adam
-            else:
-                launch_side_adam()
         try:
-            gv = self.flat_g.grad_views
-            F_hip.encoder_backward(enc, st, dlogits if supervise else None, dsup, gout=self._enc_grads,
-                                   before_pointnet=hook, after_heads=hook_heads,
-                                   gph=self.decoder_projection_head, d_hproj=dh,
-                                   gph_gout=(gv["GPH.0.weight"], gv["GPH.0.bias"]) if dh is not None else None)
+            F_hip.encoder_backward(self.encoder, st, dlogits if s.supervise else None, dsup, gout=self._enc_grads)
         finally:
             F_hip.set_wgrad_stream(None)
         if self._wg is not None:
+            ops.current_stream().wait_stream(self._wg)
+        if s.plan.collective:
+            self._allreduce_g(0, self.flat_g.total)
+        self._advance_g(s.supervise)
+        self._adam_g(0, self.flat_g.total, s.supervise, s.gs)
+
+    # ---- (5) decoder backward, exchange, update, join: what the schemes share
+    def _decoder_backward(self, s, acts, drec, dsup):
+        """the scheme installs its callbacks, then the decoder backward runs -> (dsup, dh)"""
+        gph = self.decoder_projection_head is not None
+        if s.joined is not None and not gph:
+            ops.current_stream().wait_event(s.joined)
+            s.joined = None
+        self._g16_direct = set()
+        after_layer = None
+        if s.scheme == "none":
+            self._none_install(s)
+        elif s.scheme == "allreduce":
+            after_layer = self._allreduce_install(s)
+        elif s.scheme == "gather":
+            after_layer = self._gather_install(s)
+        # [lo, hi) ranges of flat_g.g that hold NO gradient after this step: the fused weight-gradient + Adam kernels and
+        # the bf16-direct wire images never write the fp32 gradient there (round-2 advisor finding: a consumer of
+        # grad_views -- clipping, norm logging -- must skip them or construct the trainer with fused_decoder_update=False)
+        self.gradless_ranges = sorted(s.fused_ranges) + sorted(s.direct_ranges)
+        # with a projection head dz is the gradient w.r.t. ITS output: the head's own backward (dh -> dsup, dW, db) runs
+        # inside the heads' backward launch; without one the adversarial gradient seeds the accumulation
+        _, dz = F_hip.decoder_backward(self.decoder, acts, drec, need_dz=True, grads_out=s.dec_grads, mode=s.mode,
+                                       dz_init=None if gph else dsup, after_layer=after_layer, updates=s.updates, images=s.w16)
+        if s.joined is not None:
+            ops.current_stream().wait_event(s.joined)
+        return (dsup, dz) if gph else (dz, None)
+
+    # The decoder's gradients are final here (the projection head's follow with the encoder's: its backward runs in the
+    # MLP heads' launch): the scheme issues what is left of its exchange, and the decoder's update starts on the side
+    # stream.  -> the callback the encoder backward runs once the heads' launch is enqueued, or None.
+    def _exchange_and_update_decoder(self, s):
+        """what is left of the scheme's exchange, then the decoder's update -> encoder_backward's after_heads hook, or None"""
+        if s.scheme == "zero":
+            self._zero_issue(s)
+            return functools.partial(self._zero_adam, s)       # beside the temporal block's backward
+        if s.scheme == "none":
+            s.pending = [(self._dec_start, self.flat_g.total, None)]      # no exchange: the region is ready for Adam as it is
+        elif s.scheme == "allreduce":
+            self._allreduce_issue(s)
+        else:
+            self._allreduce_rest(s)
+        if s.plan.early:
+            # right after the decoder backward, i.e. beside the heads' and the temporal block's backward (measured
+            # against "after the heads' launch" 6.576 | 6.621 and "beside the PointNet backward GEMMs" 6.90 ms/step)
+            self._advance_g(s.supervise)
+            self._side_adam(s)
+
+    # Data-parallel: a decoder layer's gradient goes onto the wire as soon as it exists.  The backward
+    # produces the 118 M-parameter output layer FIRST (75 % of all gradient bytes), a quarter of a millisecond
+    # before the decoder backward is over: its all-reduce is issued from the wgrad stream right behind its
+    # weight / bias gradient kernels, the later (smaller) layers follow the same way, and the small rest
+    # (first layer, whose bias gradient is on the main stream) goes out after the decoder backward.
+    # ``taken``: the layers another exchange covers.
+    def _bucket_hook(self, s, taken, layer):
+        """decoder_backward's after_layer hook: the layer's bucket, unless another exchange has ``taken`` the layer"""
+        if layer < 2 or layer in taken:
+            return
+        fg = self.flat_g
+        lo = fg.offsets[fg.names.index(f"G.dense{layer}.weight")]
+        nxt = f"G.dense{layer + 1}.weight"
+        hi = fg.offsets[fg.names.index(nxt)] if nxt in fg.names else fg.total
+        # ordered behind this layer's dW / db kernels, whichever stream the layer's path put them on
+        self._wg.wait_stream(ops.current_stream())
+        with ops.on_stream(self._wg):
+            s.early_buckets.append((lo, hi, self._allreduce_g(lo, hi, async_op=True)))
+
+    # The wide layers are on the wire already, as gathered operands (no gradient exists) or as per-layer buckets.
+    # What is left of the decoder region -- its first layer and the biases in front of the wide weights (finalize), a
+    # wide layer neither scheme took, tail padding -- is the region MINUS those ranges, computed as such (round-5
+    # advisor finding: the two branches this replaces each assumed which ranges the other scheme had covered): a few
+    # small all-reduces, issued once the wgrad stream's products are in.
+    def _allreduce_rest(self, s):
+        """all-reduces of the decoder region minus what is fused or already on the wire"""
+        covered = list(s.fused_ranges)
+        for lo, hi, _ in s.early_buckets:
+            covered.append((lo, hi))
+        residual = pdist.subtract_ranges(self._dec_start, self.flat_g.total, covered)
+        if residual:
+            ops.current_stream().wait_stream(self._wg)
+        s.pending = list(s.early_buckets)       # (issue order = the order the collectives of one communicator complete in)
+        for lo, hi in residual:
+            s.pending.append((lo, hi, self._allreduce_g(lo, hi, async_op=True)))
+
+    def _side_adam(self, s):
+        """the decoder's update on the Adam side stream: the fused updates, then Adam over what is left; records ``s.done``"""
+        cfg = self.cfg
+        ready = torch.cuda.Event()
+        ready.record(ops.current_stream())
+        with ops.on_stream(self._side):
+            self._side.wait_event(ready)        # everything enqueued on the main stream so far
+            self._side.wait_stream(self._wg)    # ... and the decoder weight gradients on the wgrad stream
+            for update in s.deferred:
+                update()
+            for lo, hi, work in s.pending:
+                if hi <= self._dec_start:
+                    continue                    # the projection-head slice is updated on the main stream
+                g16 = None
+                if isinstance(work, _CompressedWork) and (lo % 4 == 0):
+                    work.wait(widen=False)      # Adam reads the reduced bf16 bucket as it came off the wire
+                    work.done = True
+                    g16 = self._g16
+                elif work is not None:
+                    work.wait()                 # side stream waits for THIS chunk's all-reduce only
+                for a, b in pdist.subtract_ranges(max(lo, self._dec_start), hi, s.fused_ranges):
+                    self.flat_g.adam(cfg["LR"], cfg["B1"], cfg["B2"], grad_scale=s.gs, lo=a, hi=b, advance=False,
+                                     max_blocks=self._side_adam_blocks, g16=g16)
+            s.done = torch.cuda.Event()
+            s.done.record(self._side)
+
+    def _update_encoder_and_join(self, s):
+        """all-reduce of the encoder's and heads' gradients, their Adam, the join with the decoder's exchange and update"""
+        if self._wg is not None:
             ops.current_stream().wait_stream(self._wg)       # its products feed the all-reduce / Adam below
-        ev_c0 = None
-        if self.time_comm and collective:
-            ev_c0 = torch.cuda.Event(enable_timing=True)
-            ev_c0.record()
-        self._allreduce(self.flat_g.g[:self._dec_start])      # encoder + projection head
-        for _, _, work in pending:
+        timed = self.time_comm and s.plan.collective
+        ev0 = self._timing_event(timed)
+        if s.plan.collective:
+            self._allreduce_g(0, self._dec_start)             # encoder + projection head
+        for _, _, work in s.pending:
             if work is not None:
                 work.wait()         # stream-side wait, no host block
-        if ev_c0 is not None:
-            ev_c1 = torch.cuda.Event(enable_timing=True)
-            ev_c1.record()
-            step_events.append((ev_c0, ev_c1))
-        if zero:
-            self._adam_g(0, self._dec_start, supervise, gs)
-            if ev_c0 is not None:
-                ev_g0 = torch.cuda.Event(enable_timing=True)
-                ev_g0.record()
-            for work in zero_gather:
-                work.wait()                                      # next forward reads the gathered decoder
-            if ev_c0 is not None:
-                ev_g1 = torch.cuda.Event(enable_timing=True)
-                ev_g1.record()
-                step_events.append((ev_g0, ev_g1))
-        elif early:
-            self._adam_g(0, self._dec_start, supervise, gs)
-            ev_j0 = None
-            if ev_c0 is not None:
-                # the join with the side stream is where the main stream pays for a LATE exchange of the gathered-operand
-                # scheme (its all-gathers are waited for on the side stream only) -- and, in every scheme, for what of the
-                # decoder update did not fit beside the backward: timed in all of them, so the legs compare like with like
-                ev_j0 = torch.cuda.Event(enable_timing=True)
-                ev_j0.record()
-            ops.current_stream().wait_event(done[0])      # next forward reads the updated decoder
-            if ev_j0 is not None:
-                ev_j1 = torch.cuda.Event(enable_timing=True)
-                ev_j1.record()
-                step_events.append((ev_j0, ev_j1))
+        self._timing_pair(ev0)
+        if s.scheme != "zero" and not s.plan.early:           # no side stream: the decoder's Adam runs here too
+            self._advance_g(s.supervise)
+            self._adam_g(0, self.flat_g.total, s.supervise, s.gs)
+            return
+        self._adam_g(0, self._dec_start, s.supervise, s.gs)
+        # the join with the side stream is where the main stream pays for a LATE exchange of the gathered-operand
+        # scheme (its all-gathers are waited for on the side stream only) -- and, in every scheme, for what of the
+        # decoder update did not fit beside the backward: timed in all of them, so the legs compare like with like
+        ev0 = self._timing_event(timed)
+        if s.scheme == "zero":
+            self._zero_join(s)
         else:
-            self._advance_g(supervise)
-            self._adam_g(0, self.flat_g.total, supervise, gs)
+            ops.current_stream().wait_event(s.done)       # next forward reads the updated decoder
+        self._timing_pair(ev0)
 
-        F_hip.mark("adam+join")
-        # SyncBN's statistics all-reduces (functional._sync_stats) belong to the step's exchanges too
-        self.comm["collectives"] += F_hip._SYNC_BN.get("collectives", 0)
-        self.comm["payload_bytes"] += F_hip._SYNC_BN.get("payload_bytes", 0)
-        tot = rec_loss + loss_g + (sup_loss if supervise else 0.0)
-        return {"d_loss": d_losses[0], "gp": d_losses[1], "rec_loss": rec_loss, "loss_g": loss_g,
-                "sup_loss": sup_loss, "tot_loss": tot, "preds": preds, "out_labels": logits, "sup_fvs": sup_fv}
+    # ---- scheme "none": single process
+    # Single process: the wide decoder layers' weight gradients go straight into Adam (one kernel per layer forms
+    # dW in registers and updates W / exp_avg / exp_avg_sq in place: 24 B per parameter instead of 4 + 28).  The
+    # backward only notes each layer's operands; the kernels run on the Adam side stream once the decoder backward
+    # -- whose dgrads read the weights they overwrite -- is enqueued (measured, same box, ms/step: unfused 6.27-6.30
+    # | behind each layer's own dgrad 6.13-6.18, the decoder backward section 276 -> 634 us | here 6.12-6.14).
+    def _none_install(self, s):
+        """the deferred fused wgrad+Adam updates, and the bf16 weight images they keep"""
+        if s.plan.fused:
+            for layer, (lo, hi, Wv, mv, vv) in self._dec_fused.items():
+                if F_hip._skinny(s.mode, s.B, Wv.shape[0], Wv.shape[1]) or F_hip._skinny_exact(s.mode, s.B, Wv.shape[0], Wv.shape[1]):
+                    s.updates = s.updates or {}
+                    s.updates[layer] = functools.partial(self._none_defer, s, Wv, mv, vv, s.w16.get(layer))
+                    s.fused_ranges.append((lo, hi))
+        if not set(s.w16) <= set(s.updates or {}):
+            # an image is only current if THIS step's update of its weight rewrites it
+            raise RuntimeError("PCAATrainer: a bf16 weight image is in use for a layer whose update is not fused")
+
+    def _none_defer(self, s, Wv, mv, vv, w16, dz2, x):
+        s.deferred.append(functools.partial(self._none_update, s, dz2, x, Wv, mv, vv, w16))
+
+    def _none_update(self, s, dz2, x, Wv, mv, vv, w16):
+        dz2.record_stream(self._side)
+        x.record_stream(self._side)
+        ops.skinny_linear_wgrad_adam_(dz2, x, Wv, mv, vv, *self.betas_g(), 1e-8, self.flat_g.coef_dev, s.gs, exact=s.plan.exact)
+        if w16 is not None:
+            # the image follows its weight on this stream (a coalesced 6 B/param pass; written from inside
+            # the update kernel -- 64-B partial lines from different CUs -- it doubled that kernel's time)
+            ops.cast_bf16(Wv, want_transposed=False, out=w16)
+
+    # ---- scheme "allreduce"
+    # Per-layer buckets (-> the decoder backward's after_layer hook) when there is a wgrad stream to issue them from;
+    # with bf16 buckets in the bf16 mode the wide layers' weight gradients are then produced as bf16 straight into the
+    # wire image.
+    def _allreduce_install(self, s):
+        """-> decoder_backward's after_layer hook (None without a wgrad stream)"""
+        if not s.plan.buckets:
+            return None
+        # (only this scheme has bf16-direct views: _dec_grads16 has the layers and shapes of _dec_fused and the rule below
+        # is _gather_install's _skinny predicate, so the gathered update takes every layer that would qualify)
+        if self.grad_compress == "bf16" and s.mode == "bf16":
+            s.dec_grads = dict(s.dec_grads)
+            for layer, (lo, view16) in self._dec_grads16.items():
+                # same size rule as _allreduce_g's compressed path: one predicate decides both
+                if F_hip._skinny(s.mode, s.B, view16.shape[0], view16.shape[1]) and view16.numel() >= self._COMPRESS_MIN:
+                    s.dec_grads[f"dense{layer}.weight"] = view16
+                    self._g16_direct.add(lo)
+                    s.direct_ranges.append((lo, lo + view16.numel()))
+        return functools.partial(self._bucket_hook, s, ())
+
+    # With per-layer buckets: the rest of the region.  Without a wgrad stream: the whole region after the decoder
+    # backward, in a few chunks (the collectives of one communicator run in order), so that the side-stream Adam of
+    # chunk i overlaps the all-reduce of chunk i+1 instead of waiting for all 628 MB.
+    def _allreduce_issue(self, s):
+        """the residual buckets, or the whole region in ``_dp_chunks`` pieces"""
+        if s.plan.buckets:       # (the hook has issued a bucket: the decoder has wide layers behind its first)
+            self._allreduce_rest(s)
+            return
+        bounds, dec_n = [self._dec_start], self.flat_g.total - self._dec_start
+        for i in range(1, self._dp_chunks + 1):
+            b = self.flat_g.total
+            if i < self._dp_chunks:
+                b = self._dec_start + (dec_n * i // self._dp_chunks) // _ALIGN * _ALIGN
+            if b > bounds[-1]:
+                bounds.append(b)
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            s.pending.append((lo, hi, self._allreduce_g(lo, hi, async_op=True)))
+
+    # ---- scheme "gather"
+    # dp_gather: the single-process fused update from the ranks' stacked rows.  A layer's callback (_gather_send)
+    # runs where the backward has just formed dz2: the operands are packed and their all-gather goes out from there and
+    # the update kernel follows on the Adam side stream once it is back -- no gradient bucket, no all-reduce, no separate
+    # Adam pass for these layers.  (round 6: the operands travel PACKED -- one transposed bf16 chunk of 64 batch rows per
+    # rank and layer, ops.pack_rows_t16 -- half the bytes, one all-gather per layer instead of two, and 16-B fragment loads
+    # in the update kernel.)  -> the per-layer bucket hook for the layers the gathered update does not take.
+    def _gather_install(self, s):
+        """-> decoder_backward's after_layer hook: buckets for the layers the gathered update does not take"""
+        s.updates = {}
+        for layer, (lo, hi, Wv, mv, vv) in self._dec_fused.items():
+            if F_hip._skinny(s.mode, s.B, Wv.shape[0], Wv.shape[1]):
+                s.updates[layer] = functools.partial(self._gather_send, s, layer, Wv, mv, vv)
+                s.fused_ranges.append((lo, hi))
+        return functools.partial(self._bucket_hook, s, set(s.updates))
+
+    def _gather_send(self, s, layer, Wv, mv, vv, dz2, x):
+        key = (layer, self.world)
+        if key not in self._gather_bufs:
+            ce = ops.packed_chunk_elems(Wv.shape[0], Wv.shape[1])
+            self._gather_bufs[key] = (torch.zeros((self.world, ce), dtype=torch.bfloat16, device=self.device),
+                                      torch.empty(ce, dtype=torch.bfloat16, device=self.device))
+        packed_all, own = self._gather_bufs[key]
+        dzc, xc = (dz2 if dz2.is_contiguous() else dz2.contiguous()), (x if x.is_contiguous() else x.contiguous())
+        self._count(2 * packed_all.numel(), "gather")
+        # pack + all-gather leave from the weight-gradient stream (behind dz2, which this stream has just formed; the
+        # collective's own stream picks up behind what is enqueued there): the main stream goes straight on to the
+        # layer's dgrad
+        self._wg.wait_stream(ops.current_stream())
+        with ops.on_stream(self._wg):
+            dzc.record_stream(self._wg)
+            xc.record_stream(self._wg)
+            ops.pack_rows_t16(dzc, xc, out=own)
+            # (flat views: gloo's all-gather wants output and input of the same rank)
+            work = self._xchg.all_gather_into_tensor(packed_all.view(-1), own, async_op=True, tag=layer)
+        s.deferred.append(functools.partial(self._gather_update, s, packed_all, work, Wv, mv, vv))
+
+    def _gather_update(self, s, packed_all, work, Wv, mv, vv):
+        packed_all.record_stream(self._side)
+        work.wait()               # the side stream waits for the all-gather of THIS layer only
+        ops.skinny_linear_wgrad_adam_t16_(packed_all, self.world, Wv, mv, vv, *self.betas_g(), 1e-8, self.flat_g.coef_dev, s.gs)
+
+    # ---- scheme "zero": sharded decoder optimizer
+    def _zero_issue(self, s):
+        """reduce-scatter of the decoder region in ``_zero_chunks`` pieces, issued after the decoder backward"""
+        import torch.distributed as dist
+        fg, n = self.flat_g, self._zero_len
+        ops.current_stream().wait_stream(self._wg)       # the decoder's dW/db were written on that stream
+        for c in range(self._zero_chunks):
+            lo = self._dec_start + c * n
+            src, dst = fg.g[lo:lo + n], self._zero_g[c]
+            if self.grad_compress == "bf16":
+                # bf16 buckets (round 4): the chunk is rounded once, summed on the wire in bf16, and this rank's
+                # reduced slice goes to Adam as it came off the wire (adam_step_dev_g16_) -- the gradient half of
+                # the exchange moves half the bytes; the updated parameters are gathered in fp32 as before
+                src, dst = self._g16[lo:lo + n], self._zero_g16[c]
+                src.copy_(fg.g[lo:lo + n])
+            self._count(src.element_size() * n, "scatter")
+            s.scatter.append(dist.reduce_scatter_tensor(dst, src, group=self.pg, async_op=True))
+        self._advance_g(s.supervise)
+
+    def _zero_adam(self, s):
+        """on the side stream, per chunk: wait for its reduce-scatter, Adam on this rank's slice, all-gather of the slices"""
+        import torch.distributed as dist
+        cfg, fg, n = self.cfg, self.flat_g, self._zero_len
+        adam, grads = ops.adam_step_dev_, self._zero_g
+        if self.grad_compress == "bf16":
+            adam, grads = ops.adam_step_dev_g16_, self._zero_g16          # the reduced slice as it came off the wire
+        ready = torch.cuda.Event()
+        ready.record(ops.current_stream())
+        with ops.on_stream(self._side):
+            self._side.wait_event(ready)
+            for c in range(self._zero_chunks):
+                lo, hi = self._zero_slices[c][2:]                   # this rank's slice of chunk c
+                s.scatter[c].wait()
+                adam(fg.p[lo:hi], grads[c], fg.m[lo:hi], fg.v[lo:hi], cfg["B1"], cfg["B2"], 1e-8, fg.coef_dev, s.gs,
+                     self._side_adam_blocks)
+                self._zero_p[c].copy_(fg.p[lo:hi])
+                self._count(4 * n, "gather")
+                s.gathers.append(dist.all_gather_into_tensor(
+                    fg.p[self._dec_start + c * n:self._dec_start + (c + 1) * n], self._zero_p[c],
+                    group=self.pg, async_op=True))
+
+    def _zero_join(self, s):
+        for work in s.gathers:
+            work.wait()                                      # next forward reads the gathered decoder
 
     def exposed_comm_us(self):
         """Microseconds per recorded step (``time_comm``) the main stream spent waiting for exchanges: the sum over the
@@ -1130,7 +1174,7 @@ class PCAATrainer:
             for dst, src in zip(static, (pcs, gt, z0, alphas)):
                 dst.copy_(src)
             steps0 = (self.flat_g.step, self.flat_d.step)
-            self._refresh_w16(self.precision or F_hip.get_precision(), pcs.shape[0], False)      # not inside the capture
+            self._refresh_w16(self.precision or F_hip.get_precision(), pcs.shape[0], exchange=False)      # not inside the capture
             graph = torch.cuda.CUDAGraph()
             torch.cuda.synchronize(self.device)
             # capture records the launches without running them: parameters, Adam state, BatchNorm
@@ -1148,7 +1192,7 @@ class PCAATrainer:
                 dst.copy_(src, non_blocking=True)
         # the replay streams the bf16 weight images the capture saw: rebuild them (eagerly, before the replay) if the
         # weights were written from outside since
-        self._refresh_w16(self.precision or F_hip.get_precision(), pcs.shape[0], False)
+        self._refresh_w16(self.precision or F_hip.get_precision(), pcs.shape[0], exchange=False)
         self.flat_g.step += 1
         self.flat_d.step += 1
         if supervise:

@@ -147,6 +147,29 @@ def test_emulated_allreduce_scheme_keeps_the_single_process_step():
     assert (err > 0.5e-4).double().mean().item() <= 5e-3
 
 
+def test_gather_callback_packs_column_slices_of_wider_buffers():
+    """The gathered-operand scheme's per-layer callback with dz2 / x that are column slices of wider buffers (unit stride
+    along the row, not contiguous): it packs contiguous copies -- ops.pack_rows_t16 takes nothing else -- so the rank's
+    own chunk is bit for bit the pack of the copies."""
+    from types import SimpleNamespace
+    B, N, C, K = 4, 32, 4, 8
+    tr = _trainer(B, N, C, K, 2)
+    layer = min(tr._dec_fused)
+    Wv, mv, vv = tr._dec_fused[layer][2:]
+    n_out, n_in = Wv.shape
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    dz2 = torch.randn((B, n_out + 24), generator=gen).to(DEV)[:, 8:8 + n_out]
+    x = torch.randn((B, n_in + 24), generator=gen).to(DEV)[:, 16:16 + n_in]
+    for t in (dz2, x):
+        assert t.stride(1) == 1 and not t.is_contiguous()
+    step = SimpleNamespace(deferred=[])
+    tr._gather_send(step, layer, Wv, mv, vv, dz2, x)
+    torch.cuda.synchronize()
+    packed_all, own = tr._gather_bufs[(layer, 2)]
+    assert torch.equal(own, ops.pack_rows_t16(dz2.contiguous(), x.contiguous()))
+    assert torch.equal(packed_all[0], own) and len(step.deferred) == 1
+
+
 def _free_port():
     import socket
     s = socket.socket()

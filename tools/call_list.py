@@ -1,8 +1,18 @@
-"""The library calls of one step, in order: ``python tools/call_list.py fp32|bf16|fp16x3|eval|score|live|tracks`` prints,
-for every pcaa_* call, the entry point, its integer and float arguments and the ordinal (by first appearance) of the
+"""The library calls of one step, in order: ``python tools/call_list.py fp32|bf16|fp16x3|train|eval|score|live|tracks``
+prints, for every pcaa_* call, the entry point, its integer and float arguments and the ordinal (by first appearance) of the
 stream it went to.  Pointers are not recorded, so two trees that launch the same work print the same list -- the check of
 a refactor of the Python layer.  ``fp32`` / ``bf16`` / ``fp16x3``: one eager PCAATrainer step at B=4, N=32, C=4, K=4;
 ``eval``: one eval-mode encoder_forward(want_bwd=True) + encoder_backward(need_dx=True).
+
+Between the calls stands the synchronisation skeleton, in program order and with the same stream ordinals:
+``Stream.wait_stream`` / ``Stream.wait_event`` / ``Event.record`` / ``Tensor.record_stream`` (events by ordinal of first
+appearance) and every collective (``all_reduce`` / ``all_gather_into_tensor`` / ``reduce_scatter_tensor`` of
+torch.distributed and of an emulated exchange: element count, dtype, issuing stream) with the ``wait()`` of its work --
+a dropped or moved wait is the difference a list of kernels alone cannot show.
+
+``train``: every branch of ``PCAATrainer._step`` at the same shape (``train()``), each case under a ``--`` heading and
+followed by the sha256 of the last step's losses and of ``flat_g.p`` / ``flat_d.p`` (two runs of one tree print the same
+hashes; the one output that differed between two runs of a tree has a ``~out`` line).
 
 ``score`` / ``live`` / ``tracks``: the inference and track routes at N=32, C=4, K=4, in fp32 and then in bf16 mode, every
 case under a ``--`` heading and followed by the sha256 of every tensor it returned (equal bits are part of the same diff;
@@ -16,12 +26,13 @@ import hashlib
 import os
 import re
 import sys
+import tempfile
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from opensetgaitrecognition_pcaa_amd import _lib, adapt, constants, datasets, functional as F, inference, models  # noqa: E402
+from opensetgaitrecognition_pcaa_amd import _lib, adapt, constants, datasets, functional as F, inference, models, ops  # noqa: E402
 from opensetgaitrecognition_pcaa_amd import synthetic as syn  # noqa: E402
 from opensetgaitrecognition_pcaa_amd.train import PCAATrainer  # noqa: E402
 from oracle import pcaa_oracle as O  # noqa: E402
@@ -33,7 +44,7 @@ N, C, K, HOP = 32, 4, 4, 6
 
 class Recorder:
     def __init__(self, lib):
-        self.lib, self.calls, self.streams = lib, [], {}
+        self.lib, self.calls, self.streams, self.exchanges = lib, [], {}, 0
         with open(_lib.HEADER) as f:           # the entry points whose last parameter is the stream
             self.streamed = set(re.findall(r"\b(pcaa_\w+)\s*\([^)]*\bstream\s*\)", f.read()))
 
@@ -49,18 +60,78 @@ class Recorder:
             return fn(*args)
         return call
 
-    def case(self, title, fn, exact=None):
+    def stream(self, st=None):
+        """the ordinal of a torch stream (default: the current one), shared with the library calls'"""
+        return self.streams.setdefault(ops._s() if st is None else st.cuda_stream, len(self.streams))
+
+    def hook_sync(self):
+        """record the synchronisation skeleton from here on: wraps the Python-level stream / event / tensor methods and
+        torch.distributed's collectives (an emulated exchange: ``hook_exchange``)"""
+        import torch.distributed as dist
+        events, nested = {}, []
+
+        def ev(e):
+            return events.setdefault(id(e), (len(events), e))[0]       # (the entry keeps the event, hence its id, alive)
+
+        def wrap(cls, name, line):
+            fn = getattr(cls, name)
+
+            def method(obj, *a):
+                if not nested:                 # torch implements wait_stream as record + wait_event: one line, not three
+                    self.calls.append(line(obj, *a))
+                nested.append(name)
+                try:
+                    return fn(obj, *a)
+                finally:
+                    nested.pop()
+            setattr(cls, name, method)
+
+        wrap(torch.cuda.Stream, "wait_stream", lambda s, o: f"Stream.wait_stream stream {self.stream(s)} for stream {self.stream(o)}")
+        wrap(torch.cuda.Stream, "wait_event", lambda s, e: f"Stream.wait_event stream {self.stream(s)} event {ev(e)}")
+        wrap(torch.cuda.Event, "record", lambda e, s=None: f"Event.record event {ev(e)} stream {self.stream(s)}")
+        wrap(torch.Tensor, "record_stream", lambda t, s: f"Tensor.record_stream {t.numel()} {t.dtype} stream {self.stream(s)}")
+        for name in ("all_reduce", "all_gather_into_tensor", "reduce_scatter_tensor"):
+            setattr(dist, name, self._collective(name, getattr(dist, name)))
+
+    def hook_exchange(self, xchg):
+        """an emulated exchange issues no torch.distributed call: its two collectives are wrapped on the object"""
+        if xchg is not None and xchg.emulated:
+            for name in ("all_reduce", "all_gather_into_tensor"):
+                setattr(xchg, name, self._collective(name, getattr(xchg, name)))
+
+    def _collective(self, name, fn):
+        rec = self
+
+        class Work:
+            def __init__(self, work, idx):
+                self.work, self.idx = work, idx
+
+            def wait(self, *a, **k):
+                rec.calls.append(f"wait of exchange {self.idx} stream {rec.stream()}")
+                return self.work.wait(*a, **k)
+
+        def call(*a, **k):
+            self.exchanges += 1
+            tensors = [t for t in a if isinstance(t, torch.Tensor)]
+            self.calls.append(f"{name} exchange {self.exchanges} {[t.numel() for t in tensors]} {tensors[0].dtype} "
+                              f"async_op={bool(k.get('async_op', False))} stream {self.stream()}")
+            work = fn(*a, **k)
+            return None if work is None else Work(work, self.exchanges)
+        return call
+
+    def case(self, title, fn, exact=None, loose=()):
         """one case of the route modes: its heading, its calls, then the hashes of what it returned.  ``exact``: only the
         first so many outputs have reproducible bits; the others (weight gradients, which the GEMMs accumulate with
         floating-point atomics in an order that varies from run to run, and what is computed from them) get a ``~out``
-        line with their norm instead -- ``grep -v '~out'`` leaves the part of a list that two runs must share"""
+        line with their norm instead -- ``grep -v '~out'`` leaves the part of a list that two runs must share.  ``loose``:
+        single outputs, by index, that get a ``~out`` line"""
         self.calls.append(f"-- {title}")
         out = fn()
         for i, t in enumerate(out if isinstance(out, (tuple, list)) else (out,)):
             if isinstance(t, torch.Tensor):
                 t = t.detach().cpu().numpy()
             arr = np.ascontiguousarray(t)
-            if exact is None or i < exact:
+            if (exact is None or i < exact) and i not in loose:
                 self.calls.append(f"   out[{i}] {arr.dtype} {list(arr.shape)} sha256 {hashlib.sha256(arr.tobytes()).hexdigest()}")
             else:
                 self.calls.append(f"   ~out[{i}] {arr.dtype} {list(arr.shape)} l2 {np.linalg.norm(arr.astype(np.float64)):.6e}")
@@ -226,6 +297,74 @@ def tracks(rec, means):
         rec.case(f"finetune_frozen_bn_tracks {list(lengths)} 2 steps params=all {_flags(dedup_points=dp)}", finetune, exact=1)
 
 
+LOSSES = ("d_loss", "gp", "rec_loss", "loss_g", "sup_loss", "tot_loss")
+
+
+def _train_inputs(n, seed=1):
+    return (syn.synthetic_pcs(4, constants.NSTEPS, n, C, seed=seed).to(DEV).permute(0, 3, 1, 2),
+            syn.synthetic_labels(4, K, seed=seed + 1).to(DEV), syn.synthetic_z0(4, 32, seed=seed + 2).to(DEV),
+            syn.synthetic_alphas(4, seed=seed + 3).to(DEV))
+
+
+def _train_case(rec, title, steps=(True,), n=N, precision="bf16", variant="v4", graphed=False, time_comm=False, loose=(), **kw):
+    """``steps``: the ``supervise`` flag of each step of the case; ``loose``: see Recorder.case"""
+    def run():
+        cfg = dict(constants.CONFIG, NMAX=n, TRAIN_CLASSES=list(range(K)), BATCH_SIZE=4)
+        tr = PCAATrainer(cfg, device=DEV, precision=precision, variant=variant, **kw)
+        for i, m in enumerate(tr.modules().values()):
+            syn.deterministic_fill_(m, 30 + i)
+        if variant != "v1":
+            tr.set_prior_means(O.sample_distant_points(32, K, 10, 10).float())
+        tr.finalize()
+        tr.train()
+        tr.time_comm = time_comm
+        rec.hook_exchange(tr._xchg)
+        for i, supervise in enumerate(steps):
+            rec.calls.append(f"   step {i} supervise={supervise}")
+            if graphed:
+                out = tr.step_graphed(*_train_inputs(n), supervise=supervise, warmup=1)
+            else:
+                out = tr.step(*_train_inputs(n), supervise=supervise)
+        torch.cuda.synchronize()
+        rec.calls.append(f"   dp_scheme {tr.dp_scheme} comm {sorted(tr.comm.items())} gradless {tr.gradless_ranges}")
+        losses = torch.stack([torch.as_tensor(out[k] if out[k] is not None else 0.0).float().reshape(()).cpu() for k in LOSSES])
+        return losses, tr.flat_g.p, tr.flat_d.p
+    rec.case(title, run, loose=loose)
+
+
+def train(rec):
+    import torch.distributed as dist
+    _train_case(rec, "v4 bf16: supervised, unsupervised, supervised", steps=(True, False, True))
+    _train_case(rec, "v4 bf16 fused_decoder_update=False", fused_decoder_update=False)
+    os.environ["PCAA_DEC_W16"] = "1"
+    _train_case(rec, "v4 bf16 PCAA_DEC_W16=1, two steps", steps=(True, True))
+    del os.environ["PCAA_DEC_W16"]
+    _train_case(rec, "v4 bf16 step_graphed: eager warm-up, capture", steps=(True, True), graphed=True)
+    _train_case(rec, "base bf16", variant="base")
+    _train_case(rec, "v1 bf16", variant="v1")
+    _train_case(rec, "v1 bf16 learn_centroids=True", variant="v1", learn_centroids=True)
+    _train_case(rec, "v3 bf16", variant="v3")
+    _train_case(rec, "v4 bf16 N=50: padded decoder", n=50)
+    _train_case(rec, "emulate_world=2 all-reduce fp32 buckets", emulate_world=2)
+    _train_case(rec, "emulate_world=2 all-reduce bf16 buckets", emulate_world=2, grad_compress="bf16")
+    _train_case(rec, "emulate_world=2 dp_gather", emulate_world=2, dp_gather=True)
+    _train_case(rec, "emulate_world=8 dp_gather", emulate_world=8, dp_gather=True)
+    _train_case(rec, "emulate_world=8 dp_gather time_comm", emulate_world=8, dp_gather=True, time_comm=True)
+    # every output of every case is hashed: two runs of one tree return the same bits, parameters after three steps included
+    # -- but for flat_g.p of the one fp32-mode case, whose fp32 products accumulate with atomics in a varying order
+    _train_case(rec, "emulate_world=2 dp_gather fp32: falls back to all-reduce", emulate_world=2, dp_gather=True,
+                precision="fp32", loose=(1,))
+    # the sharded optimizer wants a process group: one rank, the transport of tests/test_dp_rehearsal.py
+    with tempfile.TemporaryDirectory() as tmp:
+        dist.init_process_group("gloo", init_method=f"file://{tmp}/store", rank=0, world_size=1)
+        for compress in (None, "bf16"):
+            _train_case(rec, f"dp_zero one-rank group grad_compress={compress}", process_group=dist.group.WORLD,
+                        force_collectives=True, dp_zero=True, grad_compress=compress)
+            _train_case(rec, f"all-reduce one-rank group grad_compress={compress}", process_group=dist.group.WORLD,
+                        force_collectives=True, grad_compress=compress)
+        dist.destroy_process_group()
+
+
 ROUTES = {"score": score, "live": live, "tracks": tracks}
 
 
@@ -233,6 +372,11 @@ def main(what):
     B, T = 4, constants.NSTEPS
     constants.NFEATURES = C
     rec = _lib._lib = Recorder(_lib.load())
+    rec.hook_sync()
+    if what == "train":
+        train(rec)
+        print("\n".join(rec.calls))
+        return
     if what in ROUTES:
         means = O.sample_distant_points(32, K, 10, 10).float().to(DEV)
         for mode in ("fp32", "bf16"):
