@@ -31,8 +31,6 @@ from torch.autograd.function import once_differentiable
 from . import frame_table, ops
 from ._lib import ACT_ELU, ACT_NONE, KC, PCAA_BF16, PCAA_F32, RC
 
-_W16_CACHE = {}           # weight data_ptr -> transposed bf16 shadow made in the forward pass of this step
-_WSPLIT_T_CACHE = {}      # fp16x3 mode: weight data_ptr -> SplitImage of W^T (forward -> backward of the same step)
 _PRECISION = {"mode": "fp32"}
 _SYNC_BN = {"group": None}
 
@@ -71,7 +69,7 @@ def get_precision() -> str:
 
 # How the eval-mode PointNet layers 2-4 multiply in bf16 mode: "bf16" (default) or "fp8" -- e4m3 operands on the block-scaled
 # MFMA (ops.gemm_fp8_affine_elu; the numerics contract is in include/pcaa_hip.h and DESIGN.md section 4).  A switch beside
-# the precision mode, read at each call like it; honoured exactly where the fused bf16 epilogue route runs (_fp8_route),
+# the precision mode, read at each call like it; honoured exactly where the fused bf16 epilogue route runs (_pointnet_plan),
 # ignored everywhere else: training, a forward that keeps what a backward reads, fp32 and fp16x3 modes, unsupported shapes.
 _EVAL_POINTNET = {"kind": "bf16"}
 
@@ -171,9 +169,9 @@ def _point_major(x):
 # TemporalConvolutionBlock models.py:108-160)
 # ======================================================================
 class _LayerSave:
-    __slots__ = ("a_in", "col", "y", "scale", "shift", "mean", "rstd", "rows", "cin", "cout", "dil", "pool_e", "mom")
+    __slots__ = ("a_in", "col", "y", "scale", "shift", "mean", "rstd", "rows", "cin", "cout", "dil", "pool_e", "mom", "wt")
 
-    def __init__(self, a_in, col, y, scale, shift, mean, rstd, rows, cin, cout, dil, pool_e=None, mom=None):
+    def __init__(self, a_in, col, y, scale, shift, mean, rstd, rows, cin, cout, dil, pool_e=None, mom=None, wt=None):
         self.a_in = a_in             # (one plain store per slot: ten of these are built in every forward)
         self.col = col
         self.y = y
@@ -187,6 +185,7 @@ class _LayerSave:
         self.dil = dil
         self.pool_e = pool_e
         self.mom = mom
+        self.wt = wt                 # the image of W^T the layer's dgrad multiplies by, where the forward made it
 
 
 class EncoderEvalConstants:
@@ -262,59 +261,66 @@ def _eval_w8(consts, conv, W2d, scale):
     return _quantize_layer(W2d, scale)
 
 
-def _fp8_route(layers, rows, training, mode, pool_rows, want_bwd):
-    """whether this eval-mode forward runs layers 2-4 on the fp8 MFMA: the kind asks for it, the call is one the fused bf16
-    epilogue route serves (bf16 mode, no training, nothing kept for a backward), the first layer is the recompute layer
-    (it writes the e4m3 operand) and every later layer has a shape pcaa_gemm_fp8_affine_elu takes -- all or none"""
-    if not (_EVAL_POINTNET["kind"] == "fp8" and _FUSE_EVAL_EPILOGUE and not training and not want_bwd and mode == "bf16"
-            and pool_rows in (0, 32, 64, 128) and len(layers) > 1 and (not pool_rows or rows % pool_rows == 0)):
-        return False
-    w0 = layers[0].module[0].weight
-    if not (w0.shape[1] <= 8 and ops.pointnet_in_ok(w0.shape[1], w0.shape[0])):
-        return False
-    return all(ops.gemm_fp8_supported(rows, l.module[0].weight.shape[0], l.module[0].weight.shape[1]) for l in layers[1:])
+def _linear_out_dtype(mode, in_pointnet):
+    """dtype of the pre-BatchNorm y of the general product: the PointNet stack stores its activations in bf16 in bf16 mode"""
+    return torch.bfloat16 if (mode == "bf16" and in_pointnet) else torch.float32
 
 
-def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None, conv=None):
+def _linear_route(a_dtype, rows, cin, cout, training, mode, in_pointnet):
+    """Which launch forms y[rows, cout] = a . W^T in _linear_bn.  Pure: launches and allocates nothing.  ``a_dtype``:
+    ops.SplitImage.dtype for a split image; ``in_pointnet``: the caller is the PointNet stack (pointnet_forward), whose
+    layer over raw points has a streaming kernel of its own and whose y is bf16 in bf16 mode."""
+    if a_dtype == ops.SplitImage.dtype:
+        return "split3"                  # fp16x3 mode: both operands as [hi | lo] images, three f16 MFMA passes, fp32 result
+    if in_pointnet and a_dtype == torch.float32 and cin <= 8 and ops.pointnet_in_ok(cin, cout):
+        return "in_store"                # raw points -> first PointNet layer: C-wide contraction, HBM-bound streaming kernel
+    if mode == "bf16" and a_dtype == torch.bfloat16 and cin % 8 == 0:
+        return "bf16"
+    tiles = ((rows + 127) // 128) * ((cout + 127) // 128)
+    sk = ops.pick_split_k(rows, cout, cin, target_blocks=512)
+    if (training and _linear_out_dtype(mode, in_pointnet) == torch.float32 and tiles < 128 and sk > 1 and cout % 4 == 0
+            and 256 % (cout // 4) == 0 and cout <= 1024):
+        # few output tiles, long K (the temporal block): split K through slabs; the reduction
+        # pass also produces the BatchNorm statistics the GEMM epilogue would have
+        return "fp32_slabs"
+    return "fp32"
+
+
+def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, in_pointnet, consts=None, conv=None, route=None):
     """y = a_in @ W2d^T (the linear bias is NOT added: it cancels in train-mode BatchNorm and
     is folded into ``shift`` in eval mode; see bn_finalize_kernel) with BatchNorm statistics;
-    returns the bias-free y and the BN coefficients that apply to it."""
+    returns the bias-free y, the BN coefficients that apply to it and, where a train-mode launch made it beside its own
+    operand, the image of W^T for the layer's dgrad (else None).  ``route``: _linear_route's answer where the caller has it."""
     rows, cin = a_in.shape
     cout = W2d.shape[0]
+    if route is None:
+        route = _linear_route(a_in.dtype, rows, cin, cout, training, mode, in_pointnet)
     stats = ops.new_stats(cout, a_in.device) if training else None
     # the finalize of these statistics rides on the launch that produces them where that launch can carry it
     # (csrc/bn_tail.h: its last workgroup writes the coefficients); else tail.resolve() ran the stand-alone kernel
     tail = ops.BnTailFwd(rows, lin_bias, bn, cout, sync=_sync_fn()) if training else None
-    use_bf16 = (mode == "bf16") and a_in.dtype == torch.bfloat16 and cin % 8 == 0
-    out_dtype = torch.bfloat16 if (mode == "bf16" and first_layer is not None) else torch.float32
-    if isinstance(a_in, ops.SplitImage):
-        # fp16x3 mode: both operands as [hi | lo] images, three f16 MFMA passes, fp32 result
+    out_dtype = _linear_out_dtype(mode, in_pointnet)
+    wt = None
+    if route == "split3":
         w_img = ops.split_f16(W2d)
         if training:
-            _WSPLIT_T_CACHE[W2d.data_ptr()] = ops.split_f16(W2d, transpose=True)      # the dgrad's operand
+            wt = ops.split_f16(W2d, transpose=True)
         y = ops.gemm_split3(a_in, w_img, KC, rows, cout, cin, colstats=stats, tail=tail)
-    elif first_layer is not None and a_in.dtype == torch.float32 and cin <= 8 and ops.pointnet_in_ok(cin, cout):
-        # raw points -> first PointNet layer: C-wide contraction, HBM-bound streaming kernel
+    elif route == "in_store":
         y = ops.pointnet_in_fwd(a_in, W2d, None, out_dtype, stats, tail=tail)
-    elif use_bf16:
+    elif route == "bf16":
         # bf16 shadow of the weights so both operands stream by LDS-DMA (the transposed copy
         # serves the dgrad GEMM of the backward pass)
         if consts is not None and not training:
-            w16, wt16 = _eval_w16(consts, conv, W2d), None
+            w16 = _eval_w16(consts, conv, W2d)
         else:
-            w16, wt16 = ops.cast_bf16(W2d, True, training)
-        _W16_CACHE[W2d.data_ptr()] = wt16
+            w16, wt = ops.cast_bf16(W2d, True, training)
         y = ops.gemm(a_in, KC, w16, KC, rows, cout, cin, colstats=stats, out_dtype=out_dtype, math=PCAA_BF16, tail=tail)
-    else:
-        tiles = ((rows + 127) // 128) * ((cout + 127) // 128)
+    elif route == "fp32_slabs":
         sk = ops.pick_split_k(rows, cout, cin, target_blocks=512)
-        if (training and out_dtype == torch.float32 and tiles < 128 and sk > 1 and cout % 4 == 0
-                and 256 % (cout // 4) == 0 and cout <= 1024):
-            # few output tiles, long K (the temporal block): split K through slabs; the reduction
-            # pass also produces the BatchNorm statistics the GEMM epilogue would have
-            y = ops.gemm_slabs(a_in, KC, W2d, KC, rows, cout, cin, sk, math=PCAA_F32, colstats=stats, tail=tail)
-        else:
-            y = ops.gemm(a_in, KC, W2d, KC, rows, cout, cin, colstats=stats, out_dtype=out_dtype, math=PCAA_F32, tail=tail)
+        y = ops.gemm_slabs(a_in, KC, W2d, KC, rows, cout, cin, sk, math=PCAA_F32, colstats=stats, tail=tail)
+    else:
+        y = ops.gemm(a_in, KC, W2d, KC, rows, cout, cin, colstats=stats, out_dtype=out_dtype, math=PCAA_F32, tail=tail)
     if training:
         scale, shift, mean, rstd = tail.out
         count = tail.count_out
@@ -322,7 +328,83 @@ def _linear_bn(a_in, W2d, lin_bias, bn, training, mode, first_layer, consts=None
         scale, shift = _eval_coeffs(consts, bn, cout, lin_bias)
         mean = rstd = None
         count = rows
-    return y, scale, shift, mean, rstd, count
+    return y, scale, shift, mean, rstd, count, wt
+
+
+def _epilogue_pools(pool_rows):
+    """whether the fused-epilogue GEMMs (ops.gemm_affine_elu, ops.gemm_fp8_affine_elu) take the mean over groups of
+    ``pool_rows`` rows in their epilogue"""
+    return pool_rows in (32, 64, 128)
+
+
+_IN_RECOMPUTE = ("in_moments", "in_stats", "in_eval")
+
+
+def _pointnet_plan(dims, rows, in_dtype, training, mode, pool_rows, want_bwd, last_pre_bn, kind, sync_bn, tails):
+    """What pointnet_forward launches.  Pure: plain values in, launches and allocates nothing.  ``dims``: (cin, cout) of each
+    layer; ``kind``: the eval-PointNet kind; ``sync_bn``: SyncBN is on; ``tails``: ops.TAILS["enabled"].
+    Returns (routes, hands, finish).  ``routes[i]``: "in_moments" / "in_stats" / "in_eval" (the layer over raw points, y
+    recomputed and never stored: statistics from the points' second moments, from a statistics pass, or frozen), "fp8" /
+    "bf16_epilogue" (eval mode: BatchNorm + ELU in the GEMM epilogue, no stored y), or a _linear_route name (y stored).
+    ``hands[i]``: dtype of what layer i hands on (ops.SplitImage.dtype for a split image).  ``finish``: what turns the last
+    layer's result into the output: "done" (its launch wrote it, pooled where pool_rows), "meanpool", "act" or "pre_bn"."""
+    nl = len(dims)
+    infer = not training and not want_bwd            # nothing is kept for a backward: the epilogue routes are open
+    from_points = in_dtype == torch.float32 and dims[0][0] <= 8 and ops.pointnet_in_ok(*dims[0])
+    # fp8: the kind asks for it, the call is one the bf16 epilogue route serves, the first layer is the recompute layer (it
+    # writes the e4m3 operand) and every later layer has a shape pcaa_gemm_fp8_affine_elu takes -- all or none
+    fp8 = (kind == "fp8" and infer and mode == "bf16" and nl > 1 and from_points
+           and (not pool_rows or (_epilogue_pools(pool_rows) and rows % pool_rows == 0))
+           and all(ops.gemm_fp8_supported(rows, cout, cin) for cin, cout in dims[1:]))
+    # fp16x3 mode: the activations between the layers are [hi | lo] images when every later product is one the
+    # LDS-DMA kernel serves (whole 256-tiles); else the layer stack runs in exact fp32 -- all or none
+    split = (mode == "fp16x3" and nl > 1 and (training or not want_bwd)
+             and all(ops.gemm_split3_supported(rows, cout, cin) and cin % 256 == 0 for cin, cout in dims[1:]))
+    y_dtype = _linear_out_dtype(mode, True)
+    routes, hands, finish, dtype = [], [], "done", in_dtype
+    for li, (cin, cout) in enumerate(dims):
+        pooled = li == nl - 1 and bool(pool_rows)
+        if dtype == torch.float32 and cin <= 8 and ops.pointnet_in_ok(cin, cout) and not pooled:
+            # y = x.W^T costs cin FMAs per element, less than reading it back.  It is linear in the points: without SyncBN
+            # the batch statistics follow from the points' C x C second moments, which the backward reuses
+            route = ("in_moments" if not sync_bn and tails else "in_stats") if training else "in_eval"
+            dtype = ops.FP8 if fp8 else torch.bfloat16 if mode == "bf16" else ops.SplitImage.dtype if split else torch.float32
+        elif fp8:
+            # layers 2 and 3 hand on e4m3, the last one bf16 rows (the ragged route's segment_weighted_mean reads them) or
+            # the fp32 mean over the frame's points
+            route = "fp8"
+            dtype = ops.FP8 if li < nl - 1 else (torch.float32 if pooled else torch.bfloat16)
+        elif (infer and mode == "bf16" and dtype == torch.bfloat16 and (not pooled or _epilogue_pools(pool_rows))
+                and ops.gemm_dgrad_bn_supported(rows, cout, cin)):
+            route = "bf16_epilogue"
+            dtype = torch.float32 if pooled else torch.bfloat16
+        else:
+            route = _linear_route(dtype, rows, cin, cout, training, mode, True)
+            dtype = ops.SplitImage.dtype if (split and li < nl - 1) else y_dtype
+            if li == nl - 1:
+                finish = "meanpool" if pooled else ("pre_bn" if last_pre_bn else "act")
+        routes.append(route)
+        hands.append(dtype)
+    return routes, hands, finish
+
+
+def _in_recompute_save(route, x, W2d, conv, bn, consts):
+    """the save of a recompute first layer, its BatchNorm coefficients by ``route``: y = x.W^T is never stored"""
+    rows, (cout, cin) = x.shape[0], W2d.shape
+    mean = rstd = mom = None
+    count = rows
+    if route == "in_moments":
+        # the layer's batch statistics from the points' second moments (a 4 MB read): no statistics pass over [P, cout]
+        scale, shift, mean, rstd, mom = ops.pointnet_in_moment_coeffs(x, W2d, conv.bias, bn)
+    elif route == "in_stats":
+        stats = ops.new_stats(cout, x.device)
+        tail = ops.BnTailFwd(rows, conv.bias, bn, cout, sync=_sync_fn())
+        ops.pointnet_in_fwd(x, W2d, None, None, stats, tail=tail)
+        scale, shift, mean, rstd = tail.out
+        count = tail.count_out
+    else:
+        scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
+    return _LayerSave(x, None, None, scale, shift, mean, rstd, count, cin, cout, 0, mom=mom)
 
 
 def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, want_bwd=False, last_pre_bn=False):
@@ -338,81 +420,46 @@ def pointnet_forward(xp2d, layers, training, mode, pool_rows=0, consts=None, wan
     if consts is not None and (training or consts.mode != mode):
         raise ValueError("pointnet_forward: consts are eval-mode constants of one precision mode "
                          f"(made for {consts.mode!r}, asked for {mode!r}, training={training})")
+    rows, nl = xp2d.shape[0], len(layers)
+    dims = [(l.module[0].weight.shape[1], l.module[0].weight.shape[0]) for l in layers]
+    routes, hands, finish = _pointnet_plan(dims, rows, xp2d.dtype, training, mode, pool_rows, want_bwd, last_pre_bn,
+                                           _EVAL_POINTNET["kind"], _SYNC_BN["group"] is not None, ops.TAILS["enabled"])
     saves = []
     a = xp2d
-    nl = len(layers)
-    fp8 = xp2d.dtype == torch.float32 and _fp8_route(layers, xp2d.shape[0], training, mode, pool_rows, want_bwd)
-    # fp16x3 mode: the activations between the layers are [hi | lo] images when every later product is one the
-    # LDS-DMA kernel serves (whole 256-tiles); else the layer stack runs in exact fp32
-    split = mode == "fp16x3" and nl > 1 and (training or not want_bwd) and all(
-        ops.gemm_split3_supported(xp2d.shape[0], l.module[0].weight.shape[0], l.module[0].weight.shape[1])
-        and l.module[0].weight.shape[1] % 256 == 0 for l in layers[1:])
     for li, layer in enumerate(layers):
         conv, bn = layer.module[0], layer.module[1]
-        cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+        (cin, cout), route = dims[li], routes[li]
         W2d = conv.weight.view(cout, cin)
-        if (a.dtype == torch.float32 and cin <= 8 and ops.pointnet_in_ok(cin, cout)
-                and not (li == nl - 1 and pool_rows)):
-            # raw points -> first layer: y = x.W^T costs cin FMAs per element, less than reading it back, so
-            # it is never stored: statistics pass, then a = ELU(BN(y)) straight from the points
-            rows = a.shape[0]
-            mom = None
-            if training and _MOMENT_STATS and _sync_fn() is None and ops.TAILS["enabled"]:
-                # y = x.W^T is linear in the points: the layer's batch statistics follow from the points' C x C second
-                # moments (a 4 MB read) -- no statistics pass over [P, cout]; the backward reuses the moments
-                scale, shift, mean, rstd, mom = ops.pointnet_in_moment_coeffs(a, W2d, conv.bias, bn)
-                count = rows
-            elif training:
-                stats = ops.new_stats(cout, a.device)
-                tail = ops.BnTailFwd(rows, conv.bias, bn, cout, sync=_sync_fn())
-                ops.pointnet_in_fwd(a, W2d, None, None, stats, tail=tail)
-                scale, shift, mean, rstd = tail.out
-                count = tail.count_out
-            else:
-                scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
-                mean = rstd = None
-                count = rows
-            saves.append(_LayerSave(a, None, None, scale, shift, mean, rstd, count, cin, cout, 0, mom=mom))
-            a = ops.pointnet_in_apply(a, W2d, scale, shift, ops.FP8 if fp8 else (torch.bfloat16 if mode == "bf16" else
-                                      (ops.SplitImage.dtype if split else torch.float32)))
-            continue
-        last_pool = li == nl - 1 and pool_rows
-        if fp8:
-            # as the fused bf16 route below, on e4m3 operands: layers 2 and 3 hand on e4m3, the last one bf16 rows (the
-            # ragged route's segment_weighted_mean reads them) or the fp32 mean over the frame's points
+        epilogue_pool = pool_rows if li == nl - 1 else 0
+        if route in _IN_RECOMPUTE:
+            s = _in_recompute_save(route, a, W2d, conv, bn, consts)
+            a = ops.pointnet_in_apply(a, W2d, s.scale, s.shift, hands[li])
+        elif route == "fp8":
+            # as the fused bf16 route below, on e4m3 operands
             scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
             W8, scale8 = _eval_w8(consts, conv, W2d, scale)
-            saves.append(_LayerSave(a, None, None, scale, shift, None, None, a.shape[0], cin, cout, 0))
-            if li == nl - 1:
-                return ops.gemm_fp8_affine_elu(a, W8, scale8, shift, pool_rows, None if pool_rows else torch.bfloat16), saves
-            a = ops.gemm_fp8_affine_elu(a, W8, scale8, shift)
-            continue
-        if (_FUSE_EVAL_EPILOGUE and not training and not want_bwd and mode == "bf16" and a.dtype == torch.bfloat16
-                and (not last_pool or pool_rows in (32, 64, 128))
-                and ops.gemm_dgrad_bn_supported(a.shape[0], cout, cin)):
+            s = _LayerSave(a, None, None, scale, shift, None, None, rows, cin, cout, 0)
+            a = ops.gemm_fp8_affine_elu(a, W8, scale8, shift, epilogue_pool, hands[li])
+        elif route == "bf16_epilogue":
             # eval mode: BatchNorm is a fixed per-channel affine map -> BN + ELU (and the mean over the frame's
             # points for the last layer) in the GEMM epilogue: no stored y, no separate pass
             scale, shift = _eval_coeffs(consts, bn, cout, conv.bias)
             w16 = _eval_w16(consts, conv, W2d)
-            a_next = ops.gemm_affine_elu(a, w16, scale, shift, pool_rows if last_pool else 0)
-            saves.append(_LayerSave(a, None, None, scale, shift, None, None, a.shape[0], cin, cout, 0))
-            if last_pool:
-                return a_next, saves
-            a = a_next
-            continue
-        y, scale, shift, mean, rstd, count = _linear_bn(a, W2d, conv.bias, bn, training, mode, True, consts, conv)
-        s = _LayerSave(a, None, y, scale, shift, mean, rstd, count, cin, cout, 0)
+            s = _LayerSave(a, None, None, scale, shift, None, None, rows, cin, cout, 0)
+            a = ops.gemm_affine_elu(a, w16, scale, shift, epilogue_pool)
+        else:
+            y, scale, shift, mean, rstd, count, wt = _linear_bn(a, W2d, conv.bias, bn, training, mode, True, consts, conv, route)
+            s = _LayerSave(a, None, y, scale, shift, mean, rstd, count, cin, cout, 0, wt=wt)
+            act = ops.bn_act_fwd_split if hands[li] == ops.SplitImage.dtype else ops.bn_act_fwd
+            a = act(y, scale, shift) if li < nl - 1 else y                 # (the last y: ``finish`` below)
         saves.append(s)
-        if li == nl - 1 and last_pre_bn and not pool_rows:
-            return y, saves
-        if li == nl - 1 and pool_rows:
-            if training:
-                out, s.pool_e = ops.bn_act_meanpool_fwd(y, scale, shift, y.shape[0] // pool_rows, pool_rows, mean, rstd)
-            else:
-                out = ops.bn_act_meanpool_fwd(y, scale, shift, y.shape[0] // pool_rows, pool_rows)
-            return out, saves
-        a = ops.bn_act_fwd_split(y, scale, shift) if (split and li < nl - 1) else ops.bn_act_fwd(y, scale, shift)
-    return a, saves
+    if finish == "act":
+        a = ops.bn_act_fwd(a, s.scale, s.shift)
+    elif finish == "meanpool" and training:
+        a, s.pool_e = ops.bn_act_meanpool_fwd(a, s.scale, s.shift, rows // pool_rows, pool_rows, s.mean, s.rstd)
+    elif finish == "meanpool":
+        a = ops.bn_act_meanpool_fwd(a, s.scale, s.shift, rows // pool_rows, pool_rows)
+    return a, saves                      # ("pre_bn": the last layer's y itself; "done": its launch wrote the output)
 
 
 class _FusedGrad:
@@ -465,14 +512,12 @@ class _on_wgrad_stream:
         return False
 
 
-# Fusions that have an unfused fallback for the shapes their kernels do not take were A/B-ed through environment switches in round 1
-# (docs/LAB_LOG.md section 4); what was decided is plain code now.  The PointNet weight gradients stay on the main stream (they fill
-# the chip either way), but the split-K slab reductions that follow them (12 us each, three per step, needed only by Adam) leave it
-_REDUCE_ASIDE = os.environ.get("PCAA_REDUCE_ASIDE", "1") != "0"
-# first PointNet layer, bf16 mode: one pass over the incoming gradient instead of two (ops.pointnet_in_bwd_onepass)
-_ONEPASS_IN_BWD = os.environ.get("PCAA_ONEPASS_IN_BWD", "1") != "0"
-# first PointNet layer, forward: BatchNorm statistics from the points' second moments instead of a pass over [P, cout]
-_MOMENT_STATS = os.environ.get("PCAA_MOMENT_STATS", "1") != "0"
+# Fusions that have an unfused fallback for the shapes their kernels do not take were A/B-ed through environment switches
+# (docs/LAB_LOG.md sections 4 and 8, profiles/r03_ab_runs.txt); what was decided is plain code, with no switch left here: the slab
+# reductions behind the PointNet weight gradients run on the side stream (_layer_wgrad), the first PointNet layer takes its
+# statistics from the points' second moments (_pointnet_plan) and its backward reads the incoming gradient once
+# (_in_bwd_route), the MLP heads and the eval-mode epilogues are fused wherever their kernels take the shape.  What still
+# has a switch: _FUSE_DTC (tests toggle it), ops.TAILS / PCAA_BN_TAIL, and PCAA_DTC_BF16 / PCAA_DTC_PAIR below.
 
 
 def _bwd_tail(save, bn, outs, ch):
@@ -599,7 +644,7 @@ def _layer_wgrad(dy, lhs, s, mode, dW_out, defer_wgrad):
         if sk > 1:
             # the slab sum only feeds the optimizer: off the main stream (joined before the encoder's Adam)
             return ops.gemm_slabs(dy, RC, lhs, RC, cout, K, rows, sk, out=dW_out, math=PCAA_BF16,
-                                  reduce_ctx=_on_wgrad_stream if (_REDUCE_ASIDE and dW_out is not None) else None)
+                                  reduce_ctx=_on_wgrad_stream if dW_out is not None else None)
         return ops.gemm(dy, RC, lhs, RC, cout, K, rows, out=dW_out, math=PCAA_BF16)
     if route == "grouped":
         dW = dW_out if dW_out is not None else torch.zeros((cout, K), dtype=torch.float32, device=dy.device)
@@ -611,13 +656,13 @@ def _layer_wgrad(dy, lhs, s, mode, dW_out, defer_wgrad):
     return ops.gemm(dy, RC, lhs, RC, cout, K, rows, out=None, split_k=sk, accumulate=sk > 1, math=PCAA_F32)
 
 
-# The dgrad by the image dy arrives in: (cache of the W^T image the forward made, its maker; dtype of the y below that the fused
+# The dgrad by the image dy arrives in: (maker of the W^T image where the layer's save holds none; dtype of the y below that the fused
 # op -- ELU' and the BatchNorm-backward statistics of the layer below in the epilogue -- takes, its predicate, that op; the plain op)
 _DGRAD_IMAGE = {
-    "split": (_WSPLIT_T_CACHE, lambda W2d: ops.split_f16(W2d, transpose=True), torch.float32,
+    "split": (lambda W2d: ops.split_f16(W2d, transpose=True), torch.float32,
               ops.gemm_dgrad_bn_split3_supported, ops.gemm_dgrad_bn_split3,
               lambda dy, wt, rows, K, cout: ops.gemm_split3(dy, wt, KC, rows, K, cout)),
-    "bf16": (_W16_CACHE, lambda W2d: ops.cast_bf16(W2d, False, True)[1], torch.bfloat16,
+    "bf16": (lambda W2d: ops.cast_bf16(W2d, False, True)[1], torch.bfloat16,
              ops.gemm_dgrad_bn_supported, ops.gemm_dgrad_bn,
              lambda dy, wt, rows, K, cout: ops.gemm(dy, KC, wt, KC, rows, K, cout, out_dtype=torch.bfloat16,
                                                     math=PCAA_BF16)),
@@ -637,7 +682,7 @@ def _dgrad_route(mode, adjoint, forms_dy=False, da_fused=False, dy_dtype=None, r
         image = "bf16"
     else:
         return "fp32"
-    y_dtype, supported = _DGRAD_IMAGE[image][2:4]
+    y_dtype, supported = _DGRAD_IMAGE[image][1:3]
     if (below_y is not None and below_has_mean and below_y[1] == y_dtype and tuple(below_y[0]) == (rows, K)
             and supported(rows, K, cout)):
         return image + "_bn"
@@ -658,9 +703,9 @@ def _layer_dgrad(dy, W2d, s, mode, below, adjoint):
     if route == "fp32":
         return ops.gemm(dy, KC, W2d, RC, rows, K, cout, out_dtype=torch.float32)
     image, _, with_bn = route.partition("_")
-    cache, make, _, _, fused_op, plain_op = _DGRAD_IMAGE[image]
-    wt = cache.pop(W2d.data_ptr(), None)             # the image of W^T [K, cout] made by the forward pass
-    if wt is None or tuple(wt.shape) != (K, cout):
+    make, _, _, fused_op, plain_op = _DGRAD_IMAGE[image]
+    wt, s.wt = s.wt, None            # the image of W^T [K, cout] the forward made: read once, so it dies with this launch
+    if wt is None:
         wt = make(W2d)
     if not with_bn:
         return plain_op(dy, wt, rows, K, cout)
@@ -708,6 +753,42 @@ def _layer_grads(names, conv, dW, dgamma, dbeta, dbias, bias_out):
     return {names[0]: dW.view_as(conv.weight), names[1]: zb, names[2]: dgamma, names[3]: dbeta}
 
 
+def _in_bwd_route(y_stored, train_save, has_da, need_in, da_fused, da_dtype, mode, dW_contiguous):
+    """How pointnet_backward differentiates a layer.  Pure: launches and allocates nothing.  "general": _bn_layer_backward
+    (y is stored, or the save is an eval-mode one, or the layer was pooled, or the gradient w.r.t. its input is wanted);
+    else the recompute path of the first layer, which reads the incoming gradient and the points and nothing else: "fused"
+    (the dgrad above already applied ELU' and reduced the statistics: one pass), "onepass" (bf16 and fp16x3 modes, a
+    contiguous dW destination given: statistics and G = dz^T.x from ONE read of da, the weight gradient then a combination of
+    G with the points' second moments) or "two_pass" (exact-fp32 mode: dy is formed per element before the contraction, as
+    the oracle's autograd does)."""
+    if y_stored or not train_save or not has_da or need_in:
+        return "general"
+    if da_fused:
+        return "fused"
+    if (da_dtype == torch.bfloat16 or (mode == "fp16x3" and da_dtype == torch.float32)) and dW_contiguous:
+        return "onepass"
+    return "two_pass"
+
+
+def _in_recompute_backward(route, da, s, bn, W2d, outs):
+    """(dW, dgamma, dbeta) of the recompute first layer by a route of _in_bwd_route other than "general" """
+    dW_out = outs[0].view(s.cout, s.cin) if outs else None
+    fused = route == "fused"
+    if fused:
+        coef, dg, db = _fused_coefficients(da, s, bn, outs)
+    else:
+        tail = _bwd_tail(s, bn, outs, s.cout)
+        if route == "onepass":
+            dW = ops.pointnet_in_bwd_onepass(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail, mom=s.mom, out=dW_out)
+            _, dg, db = tail.out
+            return dW, dg, db
+        ops.pointnet_in_bwd_stats(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail=tail)
+        coef, dg, db = tail.out
+    dW = ops.pointnet_in_bwd_wgrad(da.dz if fused else da, s.a_in, W2d, s.scale, s.shift, coef,
+                                   out=dW_out, out_is_zero=True, dz_is_pre=fused)
+    return dW, dg, db
+
+
 def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0, need_dx=False, gout=None,
                       prefix="pc_block.pointnet", ragged=None):
     """Returns ({param_name_suffix: grad} per layer list, dx2d or None).  ``gout``:
@@ -722,30 +803,10 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
         W2d = conv.weight.view(s.cout, s.cin)
         need_in = li > 0 or need_dx
         outs, bias_out = _layer_outs(gout, f"{prefix}{li + 1}.", _PN_NAMES)
-        if s.y is None and s.mean is not None and da is not None and not need_in:
-            # recompute path of the first layer: two passes over da (one, when the dgrad above already applied
-            # ELU' and reduced the statistics), nothing else is read or written
-            fused = isinstance(da, _FusedGrad)
-            dW_out = outs[0].view(s.cout, s.cin) if outs else None
-            if fused:
-                coef, dg, db = _fused_coefficients(da, s, bn, outs)
-            else:
-                tail = _bwd_tail(s, bn, outs, s.cout)
-                if (_ONEPASS_IN_BWD and (da.dtype == torch.bfloat16 or (mode == "fp16x3" and da.dtype == torch.float32))
-                        and outs is not None and outs[0].is_contiguous()):
-                    # bf16 and fp16x3 modes: statistics and G = dz^T.x from ONE read of da; the weight gradient is then a
-                    # combination of G with the points' second moments (exact-fp32 mode keeps the two passes: there
-                    # dy is formed per element before the contraction, as the oracle's autograd does)
-                    dW = ops.pointnet_in_bwd_onepass(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail,
-                                                     mom=s.mom, out=dW_out)
-                    coef, dg, db = tail.out
-                    grads.append(_layer_grads(_PN_NAMES, conv, dW, dg, db, None, bias_out))
-                    da = None
-                    continue
-                ops.pointnet_in_bwd_stats(da, s.a_in, W2d, s.scale, s.shift, s.mean, s.rstd, tail=tail)
-                coef, dg, db = tail.out
-            dW = ops.pointnet_in_bwd_wgrad(da.dz if fused else da, s.a_in, W2d, s.scale, s.shift, coef,
-                                           out=dW_out, out_is_zero=True, dz_is_pre=fused)
+        route = _in_bwd_route(s.y is not None, s.mean is not None, da is not None, need_in, isinstance(da, _FusedGrad),
+                              getattr(da, "dtype", None), mode, outs is not None and outs[0].is_contiguous())
+        if route != "general":
+            dW, dg, db = _in_recompute_backward(route, da, s, bn, W2d, outs)
             dbias = dprev = None
         else:
             pooled = li == len(layers) - 1 and dpool is not None
@@ -836,8 +897,8 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
             a_in = None
         else:
             col = ops.dtc_im2col(a, B, T, cin, layer.dilation)
-            y, scale, shift, mean, rstd, count = _linear_bn(col, W2d, conv.bias, bn, training, "fp32", None,
-                                                            consts if not training else None)
+            y, scale, shift, mean, rstd, count, _ = _linear_bn(col, W2d, conv.bias, bn, training, "fp32", False,
+                                                               consts if not training else None)
             a_in = a
         s = _LayerSave(a_in, col, y, scale, shift, mean, rstd, count, cin, cout, layer.dilation)
         saves.append(s)
@@ -1040,10 +1101,6 @@ class EncoderState:
     pass
 
 
-_FUSE_HEADS = True
-_FUSE_EVAL_EPILOGUE = True
-
-
 def _heads_mods(enc, gph):
     l1 = enc.MLP_sup1[0]
     lh = enc.MLP_head[0] if enc.use_projection_head else None
@@ -1053,8 +1110,6 @@ def _heads_mods(enc, gph):
 
 
 def _heads_fusable(enc, gph, B, backward):
-    if not _FUSE_HEADS:
-        return False
     l1, lh, l2, lg = _heads_mods(enc, gph)
     return ops.heads_supported(B, l2.weight.shape[0], l1.weight.shape[1], l1.weight.shape[0],
                                lh.weight.shape[0] if lh is not None else 0,
@@ -1134,7 +1189,7 @@ def frame_pad_quantum(N, mode=None):
     """Frames per chunk must be a multiple of this for the eval PointNet to stay on the fused-epilogue GEMM in bf16 mode
     (pcaa_gemm_affine_elu takes whole 256-row tiles: U * N % 256 == 0); 1 where that path does not apply."""
     mode = get_precision() if mode is None else mode
-    if not (_FUSE_EVAL_EPILOGUE and mode == "bf16" and N in (32, 64, 128)):
+    if not (mode == "bf16" and _epilogue_pools(N)):
         return 1
     return 256 // math.gcd(N, 256)
 
@@ -1943,7 +1998,7 @@ class _GmlFn(torch.autograd.Function):
         a = x
         for lin_i, bn_i in ((0, 1), (3, 4), (6, 7)):
             lin, bn = m[lin_i], m[bn_i]
-            y, scale, shift, mean, rstd, count = _linear_bn(a, lin.weight, lin.bias, bn, gml.training, "fp32", None)
+            y, scale, shift, mean, rstd, count, _ = _linear_bn(a, lin.weight, lin.bias, bn, gml.training, "fp32", False)
             saves.append(_LayerSave(a, None, y, scale, shift, mean, rstd, count, lin.weight.shape[1], lin.weight.shape[0], 0))
             a = ops.bn_act_fwd(y, scale, shift)
         out = linear_act_forward(a, m[9], ACT_NONE)

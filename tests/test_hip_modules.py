@@ -572,3 +572,102 @@ def test_dil_temp_conv1d_odd_channel_counts_forward_backward_vs_oracle(cin, cout
     got = dict(layer.named_parameters())
     for k, gr in zip(names, grads[1:]):
         _close(got[k].grad, gr, 5e-4, what=k)
+
+
+# ------------------------------------------------------------------------------------------------ the W^T image in the save
+# mode -> (widths of the smallest training stack at 256 rows whose last dgrad is the fused form, that route, gradient gate).
+# bf16: the fused dgrad contracts over cout >= 320 (tests/gemm_ref.py dgrad_bn_supported) and the BatchNorm / ELU passes take
+# widths whose quarter divides 256: 512.  fp16x3: its contraction could be as short as 128, but the forward keeps split images
+# only where every later layer has cout % 256 == 0 (split3_supported).
+# Reference: the fp64 oracle's autograd in train mode.  Gates: fp16x3 is fp32-grade -- the 5e-4 gradient gate of this file;
+# bf16 -- the 3e-2 of the tensor's scale this file gives bf16 gradients (test_decoder_bf16_mode_wide_layers): a gradient
+# passes about a dozen roundings to 8 mantissa bits (2^-9 each) between the output and the first layer.
+# The loss is a batch MEAN, mean(stack(x) * r): the fp16x3 mode's gradient images are scaled for gradients of such a loss
+# (ops.SPLIT_SCALE_GRAD), and ops.range_check() confirms that none saturated.
+IMAGE_ROWS = 256
+IMAGE_STACKS = {"bf16": ((4, 256, 256, 512), "bf16_bn", 3e-2), "fp16x3": ((4, 256, 256, 256), "split_bn", 5e-4)}
+IMAGE_NAMES = ("module.0.weight", "module.1.weight", "module.1.bias")
+
+
+def _image_stack(widths):
+    layers = [syn.deterministic_fill_(models.PointNetModule(a, b).float(), 11 + i)
+              for i, (a, b) in enumerate(zip(widths, widths[1:]))]
+    return [l.to(DEV).train() for l in layers]
+
+
+def _image_case(widths, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(IMAGE_ROWS, widths[0], generator=g), torch.randn(IMAGE_ROWS, widths[-1], generator=g)
+
+
+def _oracle_stack_grads(layers, x, r):
+    """fp64 train-mode gradients of mean(stack(x) * r) by the oracle's autograd, from the layers' CURRENT parameters"""
+    sds = [{k: v.detach().cpu().double().clone() for k, v in l.state_dict().items()} for l in layers]
+    for sd in sds:
+        for k in IMAGE_NAMES:
+            sd[k].requires_grad_(True)
+    a = x.double().t().reshape(1, x.shape[1], 1, x.shape[0])
+    for sd in sds:
+        a = O.pointnet_module(a, sd, "", True, update_stats=False)
+    out = a.reshape(a.shape[1], -1).t()
+    return torch.autograd.grad((out * r.double()).mean(), [sd[k] for sd in sds for k in IMAGE_NAMES])
+
+
+def _check_stack_grads(grads, ref, gate, what):
+    it = iter(ref)
+    for li, gd in enumerate(grads):
+        for k in IMAGE_NAMES:
+            r = next(it)
+            got = gd[k].detach().double().cpu().reshape(r.shape)
+            err, den = (got - r).abs().max().item(), max(r.abs().max().item(), 1e-6)
+            print(f"{what} layer {li + 1} d{k}: rel {err / den:.3e} (gate {gate:g})")
+            assert err <= gate * den, f"{what} layer {li + 1} d{k}: abs err {err:.3e}, scale {den:.3e}, rel {err / den:.3e}"
+
+
+def _assert_image_routes(saves, mode, route):
+    """the stack ran on the mode's image routes: the last layer's dgrad is the fused form (asked of the pure function with
+    what the saves hold) and every layer behind the first kept an image of W^T"""
+    top, below = saves[-1], saves[-2]
+    dy_dtype = ops.SplitImage.dtype if isinstance(top.a_in, ops.SplitImage) else top.y.dtype
+    assert F_hip._dgrad_route(mode, False, dy_dtype=dy_dtype, rows=IMAGE_ROWS, cout=top.cout, K=top.cin,
+                              below_y=(below.y.shape, below.y.dtype), below_has_mean=below.mean is not None) == route
+    assert saves[0].wt is None and all(s.wt is not None and tuple(s.wt.shape) == (s.cin, s.cout) for s in saves[1:])
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16x3"])
+def test_dgrad_image_rides_in_the_save_two_forwards_then_two_backwards(mode):
+    """Two forwards of one stack on different inputs, then both backwards: each forward's saves hold their own image of W^T
+    (no module-level store keyed by the weight's address is left for the second forward to overwrite or the first backward to
+    empty), and both sets of gradients meet the mode's gate."""
+    widths, route, gate = IMAGE_STACKS[mode]
+    assert not hasattr(F_hip, "_W16_CACHE") and not hasattr(F_hip, "_WSPLIT_T_CACHE")
+    layers = _image_stack(widths)
+    cases = [_image_case(widths, seed) for seed in (21, 22)]
+    with torch.no_grad():
+        saves = [F_hip.pointnet_forward(x.to(DEV), layers, True, mode)[1] for x, _ in cases]
+        for s in saves:
+            _assert_image_routes(s, mode, route)
+        for sa, sb in zip(*saves):
+            assert sa.wt is None or sa.wt is not sb.wt
+        grads = [F_hip.pointnet_backward(s, layers, mode, d_last=(r / r.numel()).to(DEV))[0] for s, (_, r) in zip(saves, cases)]
+    ops.range_check(DEV)
+    for i, ((x, r), g) in enumerate(zip(cases, grads)):
+        _check_stack_grads(g, _oracle_stack_grads(layers, x, r), gate, f"{mode} forward {i}")
+
+
+@pytest.mark.parametrize("mode", ["bf16", "fp16x3"])
+def test_dgrad_image_of_a_forward_without_backward_is_not_picked_up(mode):
+    """A train-mode forward that no backward follows, then the weights change in place (same addresses): the next forward
+    and backward differentiate the new weights."""
+    widths, route, gate = IMAGE_STACKS[mode]
+    layers = _image_stack(widths)
+    (x0, _), (x, r) = _image_case(widths, 23), _image_case(widths, 24)
+    with torch.no_grad():
+        F_hip.pointnet_forward(x0.to(DEV), layers, True, mode)
+        for l in layers:
+            l.module[0].weight.mul_(0.5)
+        _, saves = F_hip.pointnet_forward(x.to(DEV), layers, True, mode)
+        _assert_image_routes(saves, mode, route)
+        grads, _ = F_hip.pointnet_backward(saves, layers, mode, d_last=(r / r.numel()).to(DEV))
+    ops.range_check(DEV)
+    _check_stack_grads(grads, _oracle_stack_grads(layers, x, r), gate, f"{mode} after the weights changed")
