@@ -823,7 +823,7 @@ def cast_bf16(W2d, want_plain=True, want_transposed=True, out=None):
 
 
 def pointnet_in_ok(C, cout):
-    return 1 <= C <= 8 and cout % 4 == 0 and cout <= 1024 and 256 % (cout // 4) == 0
+    return 1 <= C <= 8 and cout % 4 == 0 and 4 <= cout <= 1024 and 256 % (cout // 4) == 0
 
 
 def pointnet_in_fwd(x2d, W2d, bias, out_dtype, stats=None, tail=None):
@@ -895,6 +895,8 @@ def pointnet_in_bwd_stats(da, x2d, W2d, scale, shift, mean, rstd, tail=None):
 def points_moments(x2d):
     """fp64 second moments and sums of the points (pcaa_points_moments) for pointnet_in_bwd_onepass."""
     _chk(x2d, "points_moments.x", torch.float32, 2)
+    if not (1 <= x2d.shape[1] <= 8 and x2d.shape[0] >= 1):
+        raise ValueError(f"points_moments: unsupported shape {tuple(x2d.shape)}")
     lib = _lib.load()
     n = lib.pcaa_points_moments_size()
     mom = STATS_POOL.take_raw(n) if (STATS_POOL is not None and STATS_POOL.buf.device == x2d.device) else None
@@ -910,8 +912,11 @@ def pointnet_in_moment_coeffs(x2d, W2d, lin_bias, bn, mom=None, update_running=T
     """Train-mode BatchNorm coefficients of the first PointNet layer from the points' moments (no pass over [P, cout]):
     -> (scale, shift, mean, rstd, mom)."""
     _chk(x2d, "pointnet_in_moment_coeffs.x", torch.float32, 2)
+    _chk(W2d, "pointnet_in_moment_coeffs.W", torch.float32, 2)
     P, C = x2d.shape
     cout = W2d.shape[0]
+    if W2d.shape[1] != C or not (1 <= C <= 8 and cout >= 1 and P >= 1):       # the kernel reads W as [cout, C]
+        raise ValueError(f"pointnet_in_moment_coeffs: unsupported shape C={C} W {tuple(W2d.shape)}")
     if mom is None:
         mom = points_moments(x2d)
     tail = BnTailFwd(P, lin_bias, bn, cout, update_running=update_running)
