@@ -702,6 +702,18 @@ int pcaa_stream_score(const float* logits, const float* sup_fv, const float* mea
 int pcaa_frames_from_raw(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
                          const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
                          float* out, int n_out, int* pick_out, int* err_flag, void* stream);
+/* ABI 29, added after it (the version is unchanged: a library without this entry point fails to load by name):
+ * a training batch straight from the detections of a whole split.  points / offsets [F + 1] / pick [F, N] (may be
+ * NULL) / frame_key [F, 2] are the tables of ALL F frames of a store; start [B] int32 is the store index of each crop's
+ * first frame; out [B, T, N, C] fp32, out[b, t] = the frame pcaa_frames_from_raw writes for store frame start[b] + t
+ * under the same pick row / key and seed, bit for bit (the same per-frame code, one workgroup per output frame): a
+ * frame's bits depend on its detections, its key / pick row and the seed, not on where it stands in the batch.  Crops may
+ * overlap and repeat.  The bad-frame rule of pcaa_frames_from_raw holds per frame (zeros, *err_flag set).  A crop with
+ * start[b] < 0 or start[b] + T > F is written as zeros and sets *err_flag: nothing is read outside the tables, nothing is
+ * checked on the host.  Vector stores when N * C % 4 == 0; no atomics on out.  B * T < 2^31, F < 2^31. */
+int pcaa_crops_from_raw(const void* points, int points_f64, long P, const int* offsets, long F, const int* start, int B,
+                        int T, const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                        int divide_by_std, float* out, int* err_flag, void* stream);
 /* ABI 25: the same frames without their padding.  A padded frame repeats detections, and in eval mode the per-point
  * network f is a pure function of the point, so mean over the N padded rows of f(row) = (1/N) sum_i m_i f(p_i) over the
  * frame's DISTINCT picked detections p_i with multiplicities m_i (pcaa_segment_weighted_mean below pools that way).

@@ -83,7 +83,13 @@ def load():
         import torch  # noqa: F401
         lib = ctypes.CDLL(LIB_PATH)
         for name, (ret, args) in parse_header().items():
-            fn = getattr(lib, name)     # AttributeError if the .so does not export it
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                # an entry point added without a new version number (pcaa_crops_from_raw under 29): a library built
+                # before it answers the version check below, so say what to do here
+                raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/pcaa_hip.h declares: it was built "
+                                   "from an older header; rebuild it (python -m opensetgaitrecognition_pcaa_amd.build)") from None
             fn.restype = ret
             fn.argtypes = args
         # libpcaa_hip.so is git-ignored and travels prebuilt: a stale one would export the same names with other

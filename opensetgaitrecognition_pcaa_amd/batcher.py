@@ -15,7 +15,10 @@ the ~10^4 sequences/s the HIP train step consumes.  Here:
 * :class:`DeviceBatcher` iterates batches: the epoch's order comes from the same draws
   ``DataLoader(shuffle=True)`` makes from torch's global RNG (so a seeded run sees the reference's
   batches), each batch is one ``pcaa_gather_rows`` launch (+ one for the labels) and is handed to
-  the trainer as the zero-copy ``[B,C,T,N]`` view of point-major ``[B,T,N,C]`` storage.
+  the trainer as the zero-copy ``[B,C,T,N]`` view of point-major ``[B,T,N,C]`` storage;
+* :class:`RawTrackBatcher` is the same iterable without the crop files: the raw detections of all tracks stay
+  packed in HBM (``datasets.RawTrackStore``) and each batch is padded / subsampled, centred and rounded from them
+  by one ``pcaa_crops_from_raw`` launch.
 """
 import json
 import os
@@ -23,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import datasets, ops
 
 MANIFEST = "manifest.json"
 
@@ -190,10 +193,143 @@ class DeviceBatcher:
             raise IndexError("DeviceBatcher: a batch index was outside the packed store")
 
 
+class RawTrackBatcher:
+    """The :class:`DeviceBatcher` contract over the raw detections of a split instead of stored crops: ``view`` is a
+    ``datasets.RawCrops`` (``RawTrackStore.crops``), a batch is ONE ``pcaa_crops_from_raw`` launch that pads / subsamples,
+    centres and rounds its ``B * T`` frames from the store resident in HBM.  Same epoch order, same consumption of torch's
+    global RNG, same sharding as ``DeviceBatcher``; the epoch's starts and labels are permuted once per epoch (two row
+    gathers), so a batch inside ``__iter__`` is slices of those plus the one launch.  No host synchronisation.
+
+    ``redraw="fixed"``: every epoch draws with ``seed`` -- frame (track serial, j) has the bits ``embed_raw_track(seed=seed,
+    track_key=serial)`` / ``push_raw`` give it.  ``"epoch"``: epoch e draws with ``datasets.epoch_draw_seed(seed, e)``: a
+    fresh pad / subset per epoch, reproducible from (seed, e).  ``picks`` (int32 [F, N] over the store's frames, e.g.
+    ``datasets.draw_picks(store.cards(), N)``): host-drawn picks instead, the reference's own crops.  ``jitter``: every
+    track's starts are shifted by a phase of (seed, epoch, serial) (``RawCrops.starts``).  Epochs count from 0 in the order
+    ``__iter__`` is called."""
+
+    def __init__(self, view, batch_size, shuffle=True, drop_last=True, rank=0, world=1, group=None, seed=0, redraw="fixed",
+                 jitter=False, picks=None):
+        if redraw not in ("fixed", "epoch"):
+            raise ValueError(f"RawTrackBatcher: redraw must be 'fixed' or 'epoch', got {redraw!r}")
+        self.view, self.store = view, view.store
+        self.batch_size, self.shuffle, self.drop_last = int(batch_size), shuffle, drop_last
+        self.rank, self.world, self.group = int(rank), int(world), group
+        if self.batch_size % self.world:
+            raise ValueError(f"RawTrackBatcher: global batch {batch_size} is not divisible by world size {world}")
+        self.seed, self.redraw, self.jitter = int(seed), redraw, bool(jitter)
+        self.epoch = 0                                   # the epoch the next __iter__ starts
+        self.err = self._labels = self._starts = self.picks = None
+        if picks is not None:
+            F, N = self.store.n_frames, view.N
+            if not torch.is_tensor(picks):
+                picks = torch.from_numpy(np.ascontiguousarray(picks, dtype=np.int32))
+            if picks.dtype != torch.int32 or tuple(picks.shape) != (F, N):
+                raise ValueError(f"RawTrackBatcher: picks must be int32 [{F}, {N}], got {tuple(picks.shape)} {picks.dtype}")
+            self.picks = picks
+        self._set_epoch(0)
+
+    def __len__(self):
+        n = len(self.view)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def seed_of(self, epoch):
+        """the seed of the device draws of that epoch"""
+        return self.seed if self.redraw == "fixed" else datasets.epoch_draw_seed(self.seed, epoch)
+
+    def starts_of(self, epoch):
+        """host int32 [M]: the store frame every crop starts at in that epoch"""
+        return self.view.starts(self.seed, epoch, self.jitter)
+
+    def _set_epoch(self, epoch):
+        """host side of an epoch: its draw seed, and its starts when they change (the device copy is made on first use)"""
+        self.draw_seed = self.seed_of(epoch)
+        if self._starts is None or self.jitter:
+            self._starts_host, self._starts = torch.from_numpy(self.starts_of(epoch)), None
+
+    def _device(self):
+        """upload what the epoch in progress needs and has not got yet (no host wait) -> the store's device"""
+        dev = self.store.device
+        if dev is None:
+            raise RuntimeError("RawTrackBatcher: call store.to_device() first; batches are built on the HIP device")
+        if self.err is None:
+            self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._labels = torch.from_numpy(self.view.labels).to(dev)
+            if self.picks is not None:
+                self.picks = self.picks.to(dev).contiguous()
+        if self._starts is None:
+            self._starts = self._starts_host.pin_memory().to(dev, non_blocking=True)
+        return dev
+
+    def epoch_order(self):
+        """Begin the next epoch on the host: its order from torch's global RNG (the draws of ``dataloader_epoch_order``, no
+        others), its draw seed and starts; counts the epoch.  -> the order (host int64 [M])"""
+        order = dataloader_epoch_order(len(self.view), self.shuffle)
+        self._set_epoch(self.epoch)
+        self.epoch += 1
+        return order
+
+    def __iter__(self):
+        order = self.epoch_order().to(self._device(), non_blocking=True)
+        if self.world > 1:
+            import torch.distributed as dist
+            dist.broadcast(order, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0,
+                           group=self.group)            # one order for all ranks (rank 0's RNG)
+        if not order.numel():
+            return
+        starts = ops.gather_rows_w4(self._starts, order, err_flag=self.err)      # the epoch's starts and labels in its order
+        labels = ops.gather_rows_w4(self._labels, order, err_flag=self.err)
+        for lo, hi in shard_slices(order.numel(), self.batch_size, self.drop_last, self.rank, self.world):
+            yield self._crops(starts[lo:hi]), labels[lo:hi]
+
+    def _crops(self, start):
+        st, v = self.store, self.view
+        pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, v.T, v.N, v.C, pick=self.picks, seed=self.draw_seed,
+                                frame_key=st.frame_key_dev, err_flag=self.err)   # [B,T,N,C]
+        return pm.permute(0, 3, 1, 2)
+
+    def batch(self, idx):
+        """The batch of the given device index vector (crop indices of the view) under the draws of the epoch in progress.
+        An index outside the view raises the error flag in the gathers (its row: crop start 0, label 0)."""
+        self._device()
+        start = ops.gather_rows_w4(self._starts, idx, err_flag=self.err)
+        lab = ops.gather_rows_w4(self._labels, idx, err_flag=self.err)
+        return self._crops(start), lab
+
+    def check(self):
+        """Raise if any batch so far used an index outside the view, a crop outside the store or a frame that cannot be
+        processed (one host sync)."""
+        if self.err is not None and int(self.err.item()):
+            raise IndexError("RawTrackBatcher: a batch index was outside the view, a crop outside the store, or a frame "
+                             "of the store cannot be processed")
+
+
+def shard_slices(n, batch_size, drop_last, rank=0, world=1):
+    """[lo, hi) into an epoch's order for every batch this rank assembles: global batch k is ``order[k B:(k + 1) B]``, rank
+    r takes its rows ``[r B / world, (r + 1) B / world)``; a ragged last global batch is kept (``drop_last=False``) on one
+    rank only, as it cannot be sharded evenly.  The rule of ``DeviceBatcher.__iter__``, on index ranges."""
+    nb = n // batch_size if drop_last else (n + batch_size - 1) // batch_size
+    per = batch_size // world
+    for k in range(nb):
+        lo, hi = k * batch_size, min(n, (k + 1) * batch_size)
+        if world > 1:
+            if hi - lo < batch_size:
+                break
+            lo, hi = lo + rank * per, lo + (rank + 1) * per
+        yield lo, hi
+
+
 def batcher_for(dataset, batch_size, device, shuffle, drop_last=True, cache_dir=None, rank=0, world=1, group=None):
     """A :class:`DeviceBatcher` over ``dataset``: in-memory point-major datasets (``SyntheticGaitDataset``:
     ``.pcs [M,T,N,C]``, ``.labels``) go to the device as they are; file-backed ones (``MSRadarDataset``) are
-    packed once into ``<dataset_dir>_packed`` (re-packed when the file list changed) and uploaded."""
+    packed once into ``<dataset_dir>_packed`` (re-packed when the file list changed) and uploaded.  A
+    ``datasets.RawCrops`` view (``RawTrackStore.crops``) gets a :class:`RawTrackBatcher` with the fixed draws of its
+    ``batcher_options`` (default: seed 0); the store is uploaded if it is not yet."""
+    if isinstance(dataset, datasets.RawCrops):
+        dataset.store.to_device(device)
+        opts = dict(dataset.batcher_options)
+        if not shuffle:                                  # the validation loader: the fixed draws, the reference's starts
+            opts.update(redraw="fixed", jitter=False)
+        return RawTrackBatcher(dataset, batch_size, shuffle, drop_last, rank, world, group, **opts)
     if hasattr(dataset, "pcs") and torch.is_tensor(dataset.pcs):
         crops = dataset.pcs.to(device).float().contiguous()
         labels = torch.as_tensor(dataset.labels).to(torch.int64).to(device)

@@ -15,6 +15,7 @@
 //      whole number of them (N * C % 4 == 0), 4-byte ones otherwise.
 // A frame whose cardinality is < 1 or > PCAA_RAW_MAX_CARD, whose offsets leave [0, P], or with a supplied pick outside
 // [0, card) is written as zeros (its pick_out row as -1) and *err_flag is set: no fault, no host check.
+// pcaa_crops_from_raw writes the same frames as training batches [B, T, N, C] from the tables of a whole store (below).
 //
 // Device-drawn picks.  h(seed, key, i) is a chain of the 32-bit mixer "lowbias32" (C. Wellons, hash-prospector:
 //   x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16) over the words
@@ -203,21 +204,16 @@ __device__ __forceinline__ float raw_frame_finish(const RawShared& sh, int e, co
   return (float)v;
 }
 
+// Steps 1 - 4 for store frame f into the padded frame at dst ([N, C] fp32): the one body of the kernels that write padded
+// frames (frames_from_raw_kernel, crops_from_raw_kernel), so that a frame has the same bits wherever it is written.
 template <typename T, int C>
-__global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
-    const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
-    const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
-    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err) {
-  __shared__ RawShared sh;
+__device__ __forceinline__ void raw_frame_write(
+    RawShared& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
+    const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
+    int standardize, int divide_by_std, float* __restrict__ dst, bool vec, int* __restrict__ pick_out,
+    int* __restrict__ err) {
   const int tid = threadIdx.x;
-  const long f = blockIdx.x;
   const int NC = N * C;
-  float* dst = out + f * (long)NC;
-  const bool vec = (NC % 4 == 0) && ((uintptr_t)out % 16 == 0);
-  if (f >= n) {                                   // whole-tile padding: rows n .. n_out - 1
-    zero_frame(dst, NC, vec);
-    return;
-  }
   double mean[C], denom[C];
   int card;
   if (!raw_frame_prepare<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
@@ -237,6 +233,53 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
   } else {
     for (int e = tid; e < NC; e += RAW_THREADS) dst[e] = raw_frame_finish<C>(sh, e, mean, denom, divide_by_std);
   }
+}
+
+template <typename T, int C>
+__global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
+    const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
+    const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
+    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err) {
+  __shared__ RawShared sh;
+  const long f = blockIdx.x;
+  const int NC = N * C;
+  float* dst = out + f * (long)NC;
+  const bool vec = (NC % 4 == 0) && ((uintptr_t)out % 16 == 0);
+  if (f >= n) {                                   // whole-tile padding: rows n .. n_out - 1
+    zero_frame(dst, NC, vec);
+    return;
+  }
+  raw_frame_write<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize, divide_by_std, dst,
+                        vec, pick_out, err);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// A training batch straight from the detections of a whole split (pcaa_crops_from_raw): `points` / `offsets` / `pick` /
+// `frame_key` are the tables of ALL F frames of the store, crop b is store frames start[b] .. start[b] + T - 1, out is
+// [B, T, N, C].  Workgroup b * T + t writes frame (b, t) through raw_frame_write: the frame that pcaa_frames_from_raw
+// writes for store frame start[b] + t, bit for bit, wherever it stands in the batch and however often it is asked for
+// (overlapping and repeated crops each get their own copy: no workgroup reads what another wrote).  A crop that leaves
+// the store (start[b] < 0 or start[b] + T > F; compared in 64 bits) is zeros and sets *err before any table is read.
+// The flag is raised as everywhere in this file (atomicOr); the output has no atomics.
+template <typename T, int C>
+__global__ __launch_bounds__(RAW_THREADS) void crops_from_raw_kernel(
+    const T* __restrict__ points, long P, const int* __restrict__ offsets, long F, const int* __restrict__ start, int Tc,
+    const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
+    int standardize, int divide_by_std, float* __restrict__ out, int* __restrict__ err) {
+  __shared__ RawShared sh;
+  const int NC = N * C;
+  const long slot = blockIdx.x;                   // b * T + t < B * T: the grid is exactly the batch's frames
+  const int b = (int)(slot / Tc), t = (int)(slot - (long)b * Tc);
+  float* dst = out + slot * (long)NC;
+  const bool vec = (NC % 4 == 0) && ((uintptr_t)out % 16 == 0);
+  const long s = start[b];                        // uniform over the workgroup
+  if (s < 0 || s + (long)Tc > F) {
+    zero_frame(dst, NC, vec);
+    if (err != nullptr && threadIdx.x == 0) atomicOr(err, 1);
+    return;
+  }
+  raw_frame_write<T, C>(sh, points, P, offsets, s + t, pick, frame_key, seed_lo, seed_hi, N, standardize, divide_by_std,
+                        dst, vec, nullptr, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -411,6 +454,22 @@ void launch_frames_from_raw(int C, dim3 grid, hipStream_t st, const T* points, l
 }
 
 template <typename T>
+void launch_crops_from_raw(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, long F,
+                           const int* start, int Tc, const int* pick, const int* frame_key, long seed, int N,
+                           int standardize, int divide_by_std, float* out, int* err) {
+  const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
+#define PCAA_RAW_CASE(CC)                                                                                              \
+  case CC:                                                                                                             \
+    hipLaunchKernelGGL((crops_from_raw_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, F, start,   \
+                       Tc, pick, frame_key, lo, hi, N, standardize, divide_by_std, out, err);                          \
+    break;
+  switch (C) {
+    PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
+  }
+#undef PCAA_RAW_CASE
+}
+
+template <typename T>
 void launch_frames_from_raw_unique(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
                                    const int* pick, const int* frame_key, long seed, int N, int standardize,
                                    int divide_by_std, float* rows, float* weight, const int* u_off, long M, int* pick_out,
@@ -449,6 +508,30 @@ extern "C" int pcaa_frames_from_raw(const void* points, int points_f64, long P, 
     launch_frames_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n, pick,
                                   frame_key, seed, N, standardize, divide_by_std, out, pick_out, err_flag);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_frames_from_raw");
+}
+
+extern "C" int pcaa_crops_from_raw(const void* points, int points_f64, long P, const int* offsets, long F,
+                                   const int* start, int B, int T, const int* pick, const int* frame_key, long seed,
+                                   int N, int C, int standardize, int divide_by_std, float* out, int* err_flag,
+                                   void* stream) {
+  PCAA_CHECK_ARG(B >= 1 && T >= 1 && F >= 0 && P >= 0 && (long)B * T < (1L << 31) && F < (1L << 31),
+                 "pcaa_crops_from_raw: needs B >= 1, T >= 1, B * T < 2^31, 0 <= F < 2^31, P >= 0");
+  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
+                 "pcaa_crops_from_raw: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5");
+  PCAA_CHECK_ARG(out != nullptr && ((uintptr_t)out % 4) == 0, "pcaa_crops_from_raw: out is null or not 4-B aligned");
+  PCAA_CHECK_ARG(start != nullptr && offsets != nullptr && (points != nullptr || P == 0),
+                 "pcaa_crops_from_raw: points / offsets / start are null");
+  PCAA_CHECK_ARG(F == 0 || pick != nullptr || frame_key != nullptr,
+                 "pcaa_crops_from_raw: without picks the frames need their keys (frame_key)");
+  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "pcaa_crops_from_raw: points are misaligned");
+  const dim3 grid((unsigned)((long)B * T));
+  if (points_f64)
+    launch_crops_from_raw<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, F, start,
+                                  T, pick, frame_key, seed, N, standardize, divide_by_std, out, err_flag);
+  else
+    launch_crops_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, F, start, T,
+                                 pick, frame_key, seed, N, standardize, divide_by_std, out, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS("pcaa_crops_from_raw");
 }
 
 extern "C" int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, const int* offsets, int n,

@@ -14,6 +14,10 @@ bit-identical to the reference's (golden: ``tests/golden/datagen.npz``).  Built 
 into one preallocated array (the reference re-concatenates the whole sequence per frame: O(frames^2))
 and the repeat-padding is one fancy-index instead of a Python loop per point.
 
+``RawTrackStore`` / ``RawCrops`` keep the raw tracks themselves, packed once, and list a split's windows as indices: what
+``batcher.RawTrackBatcher`` builds training batches from on the device, with no crop files (``split_track_files`` is the
+part of ``generate_splits`` that decides which track goes to which split).
+
 ``SyntheticGaitDataset`` produces mmGait10-shaped crops from a seed; items are
 permuted views of point-major ``[T,N,C]`` storage.
 """
@@ -212,6 +216,246 @@ def pack_raw_frames(raw_frames, dtype=torch.float32):
 LABEL_DICT = {i: f"target{i}" for i in range(10)}        # reference datasets.py:51-62
 
 
+def split_track_files(train_classes=(), ratios=(0.8, 0.1, 0.1), seed=0, listdir=None):
+    """Which raw track file ``generate_splits`` sends where -> a list of ``(path, subject, scenario, split)`` with split in
+    "train" / "valid" / "test" / "unseen", in the order ``generate_splits`` processes them (the order in which it consumes
+    numpy's global RNG): per training subject and scenario sklearn's ``train_test_split(random_state=seed)`` twice, then
+    every track of the other subjects.  As there, an empty ``train_classes`` trains on all ten subjects AND lists every
+    track a second time as unseen (the unseen subjects are worked out before the default is filled in).  Draws nothing from a global generator.  ``listdir`` as in ``generate_splits``."""
+    from sklearn.model_selection import train_test_split
+    ls = listdir or (lambda d: sorted(os.listdir(d)))
+    train_ratio, valid_ratio, test_ratio = ratios
+    assert train_ratio + valid_ratio + test_ratio == 1.0
+    train_classes = list(train_classes)
+    unseen_classes = np.setdiff1d(list(LABEL_DICT.keys()), train_classes).tolist()
+    if not train_classes:
+        train_classes = list(LABEL_DICT.keys())
+    files = []
+    for subj in train_classes:
+        subject_dir = os.path.join(constants.DATA_PATH, LABEL_DICT[subj])
+        for scenario in ls(subject_dir):
+            tracks = ls(os.path.join(subject_dir, scenario))
+            if not all(t[:2] == "pc" for t in tracks):
+                raise ValueError(f"invalid file in {os.path.join(subject_dir, scenario)}")
+            tr, vt = train_test_split(tracks, train_size=train_ratio, random_state=seed)
+            va, te = train_test_split(vt, train_size=valid_ratio / (valid_ratio + test_ratio), random_state=seed)
+            for group, key in ((tr, "train"), (va, "valid"), (te, "test")):
+                files += [(os.path.join(subject_dir, scenario, t), subj, scenario, key) for t in group]
+    for subj in unseen_classes:
+        subject_dir = os.path.join(constants.DATA_PATH, LABEL_DICT[subj])
+        for scenario in ls(subject_dir):
+            files += [(os.path.join(subject_dir, scenario, t), subj, scenario, "unseen")
+                      for t in ls(os.path.join(subject_dir, scenario))]
+    return files
+
+
+def track_file_index(pc_file):
+    """the track name ``generate_splits`` puts into a crop's file name: ``.../pc_tr12.obj`` -> ``"12"``"""
+    return pc_file.split("/")[-1][5:].split(".")[0]
+
+
+def epoch_draw_seed(seed, epoch):
+    """The seed of the device draws of epoch ``epoch`` under ``RawTrackBatcher(redraw="epoch")``: the words seed_lo,
+    seed_hi, epoch absorbed with the mixer of csrc/raw_frames.hip (``_absorb32``) from 0x9e3779b9 -> a 32-bit int."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s = _absorb32(_absorb32(np.uint64(0x9E3779B9), np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
+    return int(_absorb32(s, np.uint64(int(epoch) & 0xFFFFFFFF)))
+
+
+_JITTER_WORD = np.uint64(0x6A697474)          # "jitt": keeps the phase draws apart from the epoch seed's chain
+
+
+def jitter_phases(seed, epoch, serials, limits):
+    """The phase ``RawTrackBatcher(jitter=True)`` adds to all starts of a track in epoch ``epoch``: for track serial ``r``
+    and limit ``m`` (>= 1), ``(uint64(h) * m) >> 32`` with ``h`` = the words seed_lo, seed_hi, epoch, _JITTER_WORD, r
+    absorbed with the same mixer -> int64 array in ``[0, m)``."""
+    s = _absorb32(np.uint64(epoch_draw_seed(seed, epoch)), _JITTER_WORD)
+    h = _absorb32(s, np.asarray(serials, dtype=np.int64).astype(np.uint64) & _M32)
+    return ((h * np.asarray(limits, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
+class RawTrackStore:
+    """The raw detections of many tracks, packed once: what training reads instead of crop files.  A track is a list of
+    frame dicts (``synthetic.synthetic_raw_track``, the reference's pickles).  Host tensors, pinned where there is a device:
+
+    * ``points`` [P, 5] / ``offsets`` int32 [F + 1]: every frame of every track back to back (``pack_raw_frames``);
+    * ``track_first`` int64 [n_tracks + 1]: track i owns store frames ``track_first[i] .. track_first[i + 1] - 1``;
+    * per track ``subject``, ``scenario``, ``name`` (what ``generate_splits`` writes after ``_track``), ``serial``
+      (default: its index) and ``split`` (a ``SPLIT`` value or None), the latter set by ``assign``;
+    * ``frame_key`` int32 [F, 2] = (serial, frame in track), as ``frame_table.frame_keys`` forms it: the keys under which
+      ``embed_raw_track(track_key=serial)`` / ``push_raw`` draw the same frames' picks.
+
+    ``to_device`` uploads the tables once; ``crops`` lists a split's windows for ``batcher.RawTrackBatcher``."""
+
+    def __init__(self, tracks, subjects, scenarios, names, splits=None, serials=None, dtype=torch.float32):
+        n = len(tracks)
+        if not (len(subjects) == len(scenarios) == len(names) == n):
+            raise ValueError("RawTrackStore: one subject, scenario and name per track")
+        self.subject = [int(s) for s in subjects]
+        self.scenario = [getattr(s, "value", s) for s in scenarios]
+        self.name = [str(t) for t in names]
+        self.serial = np.arange(n, dtype=np.int64) if serials is None else np.asarray(serials, dtype=np.int64)
+        if self.serial.shape != (n,) or (n and (self.serial.min() < -2 ** 31 or self.serial.max() >= 2 ** 31)):
+            raise ValueError("RawTrackStore: one serial per track, each an int32 (it is a word of the frames' draw keys)")
+        self.split = [None] * n
+        lengths = np.array([len(t) for t in tracks], dtype=np.int64)
+        self.track_first = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        if int(self.track_first[-1]) >= 2 ** 31:
+            raise ValueError("RawTrackStore: the frame indices do not fit 32 bits")
+        self.points, self.offsets = pack_raw_frames([fr for t in tracks for fr in t], dtype)
+        F = int(self.track_first[-1])
+        self.frame_key = torch.empty((F, 2), dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        k = self.frame_key.numpy()
+        k[:, 0] = np.repeat(self.serial, lengths).astype(np.int32)
+        k[:, 1] = (np.arange(F, dtype=np.int64) - np.repeat(self.track_first[:-1], lengths)).astype(np.int32)
+        self.device = None
+        self.points_dev = self.offsets_dev = self.frame_key_dev = None
+        if splits is not None:
+            self.assign(splits)
+
+    @classmethod
+    def from_files(cls, files, dtype=torch.float32):
+        """From the list ``split_track_files`` returns: every pickle is read once, the splits are assigned."""
+        import pickle
+        tracks = []
+        for path, _, _, _ in files:
+            with open(path, "rb") as f:
+                tracks.append(pickle.load(f))
+        return cls(tracks, [f[1] for f in files], [f[2] for f in files], [track_file_index(f[0]) for f in files],
+                   splits=[f[3] for f in files], dtype=dtype)
+
+    # ------------------------------------------------------------------------------------------------ split assignment
+    def path(self, i):
+        """where ``generate_splits`` would look for track i under ``constants.DATA_PATH``"""
+        return os.path.join(constants.DATA_PATH, LABEL_DICT[self.subject[i]], self.scenario[i], f"pc_tr{self.name[i]}.obj")
+
+    def listdir(self, d):
+        """``listdir`` for ``split_track_files`` over the tracks held here (no file system): sorted names"""
+        names = set()
+        for i in range(len(self.name)):
+            rel = os.path.relpath(self.path(i), d)
+            if not rel.startswith(os.pardir):
+                names.add(rel.split(os.sep)[0])
+        return sorted(names)
+
+    def assign(self, splits):
+        """Set every track's split: a list with one "train" / "valid" / "test" / "unseen" / ``SPLIT`` / None per track, or
+        the list of ``split_track_files`` (matched by path; tracks it does not name get None; a track it names twice keeps
+        the first split).  -> self"""
+        splits = list(splits)
+        if splits and isinstance(splits[0], tuple):
+            by_path = {}
+            for f in splits:
+                by_path.setdefault(f[0], f[3])           # listed twice (empty train_classes: also as unseen): the first
+            splits = [by_path.get(self.path(i)) for i in range(len(self.name))]
+        if len(splits) != len(self.name):
+            raise ValueError("RawTrackStore.assign: one split per track")
+        self.split = [None if s is None else SPLIT(getattr(s, "value", s)) for s in splits]
+        return self
+
+    def assign_like_generate_splits(self, train_classes=(), ratios=(0.8, 0.1, 0.1), seed=0):
+        """the assignment ``generate_splits(train_classes, *ratios, seed)`` makes for these tracks"""
+        return self.assign(split_track_files(train_classes, ratios, seed, listdir=self.listdir))
+
+    # ---------------------------------------------------------------------------------------------------------- device
+    def to_device(self, device="cuda"):
+        """Upload points, offsets and frame keys once (pinned sources, one copy each).  -> self"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("RawTrackStore.to_device: batches are built on the HIP device; there is no CPU path")
+        if self.device != device:
+            self.points_dev = self.points.to(device, non_blocking=True)
+            self.offsets_dev = self.offsets.to(device, non_blocking=True)
+            self.frame_key_dev = self.frame_key.to(device, non_blocking=True)
+            self.device = device
+        return self
+
+    @property
+    def n_frames(self):
+        return int(self.track_first[-1])
+
+    def cards(self):
+        """detections per store frame, int64 [F]"""
+        return np.diff(self.offsets.numpy().astype(np.int64))
+
+    def crops(self, split, N=None, C=None, hop=None, order="filenames", T=None, scenarios=None):
+        """The crops of the split's tracks -> :class:`RawCrops` (see there)."""
+        return RawCrops(self, split, N, C, hop, order, T, scenarios)
+
+
+class RawCrops:
+    """The windows ``generate_splits`` would have cut from the tracks of one split of a :class:`RawTrackStore`, as indices:
+    per track of F frames the starts ``range(0, F - T, hop)`` (``frame_table.track_windows``: the reference's count; a
+    track with ``F <= T`` has none), ``N`` points per frame and the first ``C`` features.  Per crop: ``track`` (index into
+    the store), ``crop`` (index in its track), ``start`` (store frame of its first frame), ``filenames`` (the name
+    ``generate_splits`` would have written), ``original_labels`` and ``labels`` (dense over the subjects present, as
+    ``MSRadarDataset``); per listed track ``slack`` = F - T - hop (count - 1) >= 1, the room ``RawTrackBatcher``'s jitter has.
+    ``order="filenames"``: sorted by file name, the item order of ``MSRadarDataset(split)``; ``"sequential"``: by
+    (subject, track name, crop) on top of it, the order of ``MSRadarDataset(split, sequential=True)``.  ``scenarios``
+    (default ``constants.TRAIN_SCENARIOS``) filters as there.  Nothing here touches the device."""
+
+    def __init__(self, store, split, N=None, C=None, hop=None, order="filenames", T=None, scenarios=None):
+        from .frame_table import track_windows
+        if order not in ("filenames", "sequential"):
+            raise ValueError(f"RawCrops: order must be 'filenames' or 'sequential', got {order!r}")
+        self.store, self.split, self.order = store, SPLIT(getattr(split, "value", split)), order
+        self.N = constants.NMAX if N is None else int(N)
+        self.C = constants.NFEATURES if C is None else int(C)
+        self.T = constants.NSTEPS if T is None else int(T)
+        self.hop = constants.CROP_STEP if hop is None else int(hop)
+        wanted = {getattr(s, "value", s) for s in (constants.TRAIN_SCENARIOS if scenarios is None else scenarios)}
+        items = []                                        # (file name, track, crop)
+        for i, sp in enumerate(store.split):
+            if sp != self.split or store.scenario[i] not in wanted:
+                continue
+            W, _ = track_windows(int(store.track_first[i + 1] - store.track_first[i]), self.T, self.hop)
+            items += [(f"crop{ci}_subj{store.subject[i]}_{store.scenario[i]}_track{store.name[i]}.npy", i, ci)
+                      for ci in range(W)]
+        items.sort(key=lambda it: it[0])
+        if order == "sequential":
+            items.sort(key=lambda it: (filename2subj(it[0]), filename2track(it[0]), filename2crop(it[0])))
+        self.filenames = [it[0] for it in items]
+        self.track = np.array([it[1] for it in items], dtype=np.int64)
+        self.crop = np.array([it[2] for it in items], dtype=np.int64)
+        self.start = store.track_first[self.track] + self.hop * self.crop if items else np.zeros(0, np.int64)
+        self.original_labels = [store.subject[i] for i in self.track]
+        dense = {c: i for i, c in enumerate(sorted(set(self.original_labels)))}
+        self.labels = np.array([dense[j] for j in self.original_labels], dtype=np.int64)
+        length = store.track_first[self.track + 1] - store.track_first[self.track] if items else np.zeros(0, np.int64)
+        count = np.array([track_windows(int(n), self.T, self.hop)[0] for n in length], dtype=np.int64)
+        self.slack = length - self.T - self.hop * (count - 1)             # per crop: its track's
+        self.batcher_options = {}         # seed / redraw / jitter / picks of the RawTrackBatcher that batcher_for builds
+
+    def __len__(self):
+        return len(self.filenames)
+
+    def starts(self, seed=0, epoch=0, jitter=False):
+        """store frame of every crop's first frame, int32 [M]; with ``jitter`` each track's starts are shifted by its phase
+        of (seed, epoch, serial) in ``[0, min(hop, slack))`` (``jitter_phases``): every window stays inside its track"""
+        start = self.start
+        if jitter and len(self):
+            start = start + jitter_phases(seed, epoch, self.store.serial[self.track], np.minimum(self.hop, self.slack))
+        return start.astype(np.int32)
+
+    def materialize(self, seed=0, picks=None, epoch=0, jitter=False):
+        """All crops written out by the batch kernel, one launch -> ``(pcs [M, C, T, N] view of point-major storage,
+        labels int64 [M])`` on the store's device: what the evaluation procedures take."""
+        from . import ops
+        st = self.store
+        if st.device is None:
+            raise RuntimeError("RawCrops.materialize: call store.to_device() first; there is no CPU path")
+        if not len(self):
+            raise ValueError(f"RawCrops.materialize: the {self.split.value} split has no crops")
+        err = torch.zeros(1, dtype=torch.int32, device=st.device)
+        start = torch.from_numpy(self.starts(seed, epoch, jitter)).to(st.device)
+        pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, self.T, self.N, self.C, pick=picks, seed=seed,
+                                frame_key=st.frame_key_dev, err_flag=err)
+        if int(err.item()):
+            raise ValueError("RawCrops.materialize: a frame of the store cannot be processed (no detections, more than "
+                             f"{ops.RAW_MAX_CARD}, or a pick outside its frame)")
+        return pm.permute(0, 3, 1, 2), torch.from_numpy(self.labels).to(st.device)
+
+
 def generate_splits(train_classes=(), train_ratio=0.8, valid_ratio=0.1, test_ratio=0.1, seed=0,
                     force_pc_subsampling=0, nmax_points=None, listdir=None, verbose=True):
     """Train/valid/test/unseen crop files under ``constants.GEN_DATA_PATH`` from the raw tracks under
@@ -222,8 +466,6 @@ def generate_splits(train_classes=(), train_ratio=0.8, valid_ratio=0.1, test_rat
     ``crop{i}_subj{s}_{scenario}_track{t}.npy`` (float64 ``[T,N,C]``).  ``listdir`` (default: sorted
     ``os.listdir``) fixes the traversal order and with it the consumption of numpy's global RNG; the
     reference uses raw ``os.listdir`` (file-system order) and asks for ENTER first (``safe_mode``)."""
-    from sklearn.model_selection import train_test_split
-    ls = listdir or (lambda d: sorted(os.listdir(d)))
     nmax_points = constants.NMAX if nmax_points is None else nmax_points
     assert train_ratio + valid_ratio + test_ratio == 1.0
     dirs = {k: os.path.join(constants.GEN_DATA_PATH, k) for k in ("train", "valid", "test", "unseen")}
@@ -232,34 +474,17 @@ def generate_splits(train_classes=(), train_ratio=0.8, valid_ratio=0.1, test_rat
         for f in os.listdir(d):
             os.remove(os.path.join(d, f))
     train_classes = list(train_classes)
+    files = split_track_files(train_classes, (train_ratio, valid_ratio, test_ratio), seed, listdir)   # (the classes as given)
     unseen_classes = np.setdiff1d(list(LABEL_DICT.keys()), train_classes).tolist()
     if not train_classes:
         train_classes = list(LABEL_DICT.keys())
 
-    def emit(pc_file, subj, scenario, target_dir):
+    for pc_file, subj, scenario, key in files:
         arr = process_track(pc_file, standardize_point_cloud=True, divide_by_std=False,
                             force_pc_subsampling=force_pc_subsampling, nmax=nmax_points)
         crops = crop_with_step(arr, crop_len=constants.NSTEPS, step=constants.CROP_STEP)
-        track_index = pc_file.split("/")[-1][5:].split(".")[0]
         for ci in range(len(crops)):
-            np.save(os.path.join(target_dir, f"crop{ci}_subj{subj}_{scenario}_track{track_index}.npy"), crops[ci])
-
-    for subj in train_classes:
-        subject_dir = os.path.join(constants.DATA_PATH, LABEL_DICT[subj])
-        for scenario in ls(subject_dir):
-            tracks = ls(os.path.join(subject_dir, scenario))
-            if not all(t[:2] == "pc" for t in tracks):
-                raise ValueError(f"invalid file in {os.path.join(subject_dir, scenario)}")
-            tr, vt = train_test_split(tracks, train_size=train_ratio, random_state=seed)
-            va, te = train_test_split(vt, train_size=valid_ratio / (valid_ratio + test_ratio), random_state=seed)
-            for group, key in ((tr, "train"), (va, "valid"), (te, "test")):
-                for t in group:
-                    emit(os.path.join(subject_dir, scenario, t), subj, scenario, dirs[key])
-    for subj in unseen_classes:
-        subject_dir = os.path.join(constants.DATA_PATH, LABEL_DICT[subj])
-        for scenario in ls(subject_dir):
-            for t in ls(os.path.join(subject_dir, scenario)):
-                emit(os.path.join(subject_dir, scenario, t), subj, scenario, dirs["unseen"])
+            np.save(os.path.join(dirs[key], f"crop{ci}_subj{subj}_{scenario}_track{track_file_index(pc_file)}.npy"), crops[ci])
     stats = {k: len(os.listdir(d)) for k, d in dirs.items()}
     if verbose:
         from .utils import openness

@@ -448,8 +448,14 @@ def _sequential_split_on_device(split, scenarios_list, device):
     return crops.permute(0, 3, 1, 2), labels
 
 
+def _sequential_split_from_store(store, split, scenarios_list, N):
+    """The same tensors from a ``datasets.RawTrackStore`` (already assigned and on the device): the split's crops in
+    sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of seed 0; no files."""
+    return store.crops(split, N=N, C=constants.NFEATURES, order="sequential", scenarios=scenarios_list).materialize(seed=0)
+
+
 def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None, variation=False,
-                    generate_dataset=True, device=None, dedup_frames=False, dedup_points=False):
+                    generate_dataset=True, device=None, dedup_frames=False, dedup_points=False, raw_store=None):
     """Open-set evaluation driver with the reference's call surface and output files
     (inference_PCAA.py:382-469): for every model and k, the naive sequential procedure on the sequentially
     ordered test / unseen splits; writes ``naive_seq_log_{k}*.json`` (accuracy, F1 micro / macro / weighted),
@@ -458,24 +464,37 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
     call (the reference regenerates them for every (model, k) with identical arguments).  ``dedup_frames`` (opt-in):
     every frame that consecutive crops of the sequential splits share is encoded once.  ``dedup_points`` (opt-in): every
     point that the stored crops' padding repeats inside a frame is encoded once (it pays most with
-    ``force_pc_subsampling``, which pads from fewer points)."""
+    ``force_pc_subsampling``, which pads from fewer points).  ``raw_store`` (a ``datasets.RawTrackStore`` of the raw
+    tracks): nothing is generated or read from crop files -- per model the store's tracks are assigned as
+    ``generate_splits(TRAIN_CLASSES, seed=0)`` assigns them and the sequential TEST / UNSEEN crops are built on the device
+    at the model's NMAX (device draws of seed 0; ``force_pc_subsampling`` is a property of generated files and is refused)."""
     import json
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
     suffix = _file_suffix(force_pc_subsampling, scenarios_list)
     if suffix is None:
         raise ValueError("force_pc_subsampling and scenarios_list cannot be both different from default")
+    if raw_store is not None and force_pc_subsampling:
+        raise ValueError("CGAAE_inference: force_pc_subsampling needs generated crop files; it cannot be combined with raw_store")
     dev = torch.device(device or constants.DEVICE)
     out_log = {}
     generated = not generate_dataset
     for model_name in model_names:
         folder = os.path.join("models", model_name)
         os.makedirs(os.path.join("figures", model_name), exist_ok=True)
-        enc, means = CGAAE_inference_setup(model_name, 32, variation, generate_dataset=not generated,
+        enc, means = CGAAE_inference_setup(model_name, 32, variation,
+                                           generate_dataset=not generated and raw_store is None,
                                            force_pc_subsampling=force_pc_subsampling, device=dev)
         generated = True
-        known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
-        unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
+        if raw_store is not None:
+            with open(os.path.join(folder, "config.pkl"), "rb") as f:
+                config = pickle.load(f)
+            raw_store.assign_like_generate_splits(config["TRAIN_CLASSES"], seed=0).to_device(dev)
+            known_pcs, known_labels = _sequential_split_from_store(raw_store, SPLIT.TEST, scenarios_list, config["NMAX"])
+            unseen_pcs, unseen_labels = _sequential_split_from_store(raw_store, SPLIT.UNSEEN, scenarios_list, config["NMAX"])
+        else:
+            known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
+            unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
         for k in ks:
             preds, labels, thr = naive_sequential_procedure(k, enc, means, known_pcs, known_labels, unseen_pcs,
                                                             unseen_labels, seed=0, unseen_valid_ratio=0.2,

@@ -1698,6 +1698,53 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     return out
 
 
+def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
+                   divide_by_std=False, out=None, err_flag=None):
+    """A batch of crops straight from the packed detections of a whole store, one launch (pcaa_crops_from_raw):
+    ``points`` [P, 5] fp32 or fp64 and ``offsets`` int32 [F + 1] over ALL F frames of the store, ``start`` int32 [B] the
+    store index of each crop's first frame -> fp32 ``[B, T, N, C]``, ``out[b, t]`` bit-equal to the frame
+    ``frames_from_raw`` writes for store frame ``start[b] + t`` under the same ``pick`` row (int32 [F, N]) or, without
+    picks, ``frame_key`` row (int32 [F, 2]) and ``seed``.  Crops may overlap and repeat.  A frame that cannot be processed
+    (the rule of ``frames_from_raw``) and a crop that leaves the store (``start[b] < 0`` or ``start[b] + T > F``) come back
+    as zeros and set ``err_flag`` (int32 [1]); nothing is checked on the host.  ``out``: a [B, T, N, C] buffer to fill."""
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise TypeError("crops_from_raw.points: expected a float32 or float64 tensor")
+    _chk(points, "crops_from_raw.points", None, 2)
+    _chk(offsets, "crops_from_raw.offsets", torch.int32, 1)
+    _chk(start, "crops_from_raw.start", torch.int32, 1)
+    T, N, C, seed = int(T), int(N), int(C), int(seed)
+    F, B = offsets.numel() - 1, start.numel()
+    if points.shape[1] != 5 or F < 0 or T < 1 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5 or B * T >= 2 ** 31:
+        raise ValueError(f"crops_from_raw: needs points [P, 5], offsets [F + 1], T >= 1, 1 <= N <= {RAW_MAX_POINTS}, "
+                         f"1 <= C <= 5, B T < 2^31; got points {tuple(points.shape)}, F={F}, B={B}, T={T}, N={N}, C={C}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError("crops_from_raw: the seed must fit 64 bits")
+    if pick is not None:
+        _chk(pick, "crops_from_raw.pick", torch.int32, 2)
+        if tuple(pick.shape) != (F, N):
+            raise ValueError(f"crops_from_raw: pick must be [{F}, {N}], got {tuple(pick.shape)}")
+    elif F:
+        if frame_key is None:
+            raise ValueError("crops_from_raw: without picks every frame needs its key (frame_key int32 [F, 2])")
+        _chk(frame_key, "crops_from_raw.frame_key", torch.int32, 2)
+        if tuple(frame_key.shape) != (F, 2):
+            raise ValueError(f"crops_from_raw: frame_key must be [{F}, 2], got {tuple(frame_key.shape)}")
+    if err_flag is not None:
+        _chk(err_flag, "crops_from_raw.err_flag", torch.int32)
+    if out is None:
+        out = torch.empty((B, T, N, C), dtype=torch.float32, device=points.device)
+    else:
+        _chk(out, "crops_from_raw.out", torch.float32, 4)
+        if tuple(out.shape) != (B, T, N, C):
+            raise ValueError(f"crops_from_raw: out must be [{B}, {T}, {N}, {C}], got {tuple(out.shape)}")
+    if B:
+        _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw(
+            _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), F, _p(start), B, T, _p(pick),
+            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+            _p(out), _p(err_flag), _s()), "pcaa_crops_from_raw"), 0.0, B * T * N * C * 4)
+    return out
+
+
 UNIQUE_ROW_QUANTUM = 256  # rows of the compact table: whole 256-row GEMM tiles (pcaa_gemm_affine_elu, pcaa_gemm_split3)
 
 

@@ -1501,12 +1501,16 @@ def train_variant3(config, wandb_mode="online", **kw):
 
 
 def train_pointsubsampling(n_training_classes=(2, 4, 6, 8), n_points_subs=(50, 70, 90, 110, 130, 150), n_tests=5,
-                           ks=(1, 2, 4, 6), model_name_base="PCAA_npts_V4_", splits_seed=0, config=None):
+                           ks=(1, 2, 4, 6), model_name_base="PCAA_npts_V4_", splits_seed=0, config=None, raw_store=None):
     """The point-subsampling study of the reference's ``train_pointsubsampling.py`` (its ``__main__``, :19-76;
     BASELINE config[3]): for every number of training classes, ``n_tests`` distinct random class subsets
     (``default_rng(splits_seed).choice``, as there); for every NMAX the splits are regenerated from the raw
     tracks with that many points per frame, variant 4 is trained and evaluated open-set for each k.
-    Returns {model_name: CGAAE_inference's log}."""
+    Returns {model_name: CGAAE_inference's log}.  ``raw_store`` (a ``datasets.RawTrackStore`` of the raw tracks,
+    built once): no ``generate_splits``, no crop files -- per class subset the store's tracks are assigned as
+    ``generate_splits`` assigns them, and for every NMAX the loop trains from ``raw_store.crops(TRAIN / VALID, NMAX)``
+    (batches built on the device, fixed draws of seed 0) and ``CGAAE_inference(raw_store=...)`` evaluates on the
+    sequential crops of TEST / UNSEEN built by the same kernel."""
     from .datasets import LABEL_DICT, generate_splits
     from .inference import CGAAE_inference
     from .utils import openness
@@ -1523,14 +1527,21 @@ def train_pointsubsampling(n_training_classes=(2, 4, 6, 8), n_points_subs=(50, 7
             cfg = dict(constants.CONFIG if config is None else config)
             cfg["TRAIN_CLASSES"] = classes
             cfg["Openness"] = openness(n_tr, len(LABEL_DICT))
+            if raw_store is not None:
+                raw_store.assign_like_generate_splits(classes, seed=0)
             for n_points in n_points_subs:
                 cfg["NMAX"] = n_points
-                generate_splits(train_classes=classes, seed=0, nmax_points=n_points, verbose=False)
+                if raw_store is None:
+                    generate_splits(train_classes=classes, seed=0, nmax_points=n_points, verbose=False)
                 name = f"{model_name_base}{n_points}.{n_tr}.{i + 1}"
                 cfg["MODEL_NAME"] = name
                 cfg["NOTES"] = f"Runs with different number of points ({n_points}.{n_tr}.{i + 1})"
-                train_variant4(dict(cfg), wandb_mode="disabled", proj_head_on_discriminator=False)
+                if raw_store is None:
+                    train_variant4(dict(cfg), wandb_mode="disabled", proj_head_on_discriminator=False)
+                else:
+                    train_variant4(dict(cfg), wandb_mode="disabled", proj_head_on_discriminator=False,
+                                   dataset_factory=lambda split, n=n_points: raw_store.crops(split, n, constants.NFEATURES))
                 results[name] = CGAAE_inference(model_names=[name], ks=list(ks), variation="V4",
-                                                generate_dataset=False)
+                                                generate_dataset=False, raw_store=raw_store)
     return results
 
