@@ -18,9 +18,10 @@ Numerics modes (``set_precision``):
   * ``"bf16"``  -- PointNet activations stored in bf16, PointNet GEMMs on the
     bf16 MFMA pipe with fp32 accumulation; everything else fp32.
 """
+import collections
 import contextlib
+import functools
 import math
-import os
 import itertools
 
 import numpy as np
@@ -517,7 +518,8 @@ class _on_wgrad_stream:
 # reductions behind the PointNet weight gradients run on the side stream (_layer_wgrad), the first PointNet layer takes its
 # statistics from the points' second moments (_pointnet_plan) and its backward reads the incoming gradient once
 # (_in_bwd_route), the MLP heads and the eval-mode epilogues are fused wherever their kernels take the shape.  What still
-# has a switch: _FUSE_DTC (tests toggle it), ops.TAILS / PCAA_BN_TAIL, and PCAA_DTC_BF16 / PCAA_DTC_PAIR below.
+# has a switch: _FUSE_DTC (tests toggle it; an argument of _dtc_plan), ops.TAILS / PCAA_BN_TAIL, and the library's own
+# PCAA_DTC_PAIR (csrc/dtc_fused.hip reads it once; _dtc_plan asks the library, so the Python side follows it).
 
 
 def _bwd_tail(save, bn, outs, ch):
@@ -576,7 +578,7 @@ def _bn_dy(s, bn, da, pool, lhs_split, outs, lin_bias, dbias_out, adjoint_dy=Non
         if adjoint_dy is not None:
             # the adjoint kernel forms dy = c0*dz + c1*y + c2 while it stages its operand and hands it back
             # for the weight gradient: no separate elementwise pass
-            d_lhs, dy = adjoint_dy(None, dz=da.dz, y=y, coef=coef)
+            d_lhs, dy = adjoint_dy.forming_dy(da.dz, y, coef)
             return dy, dgamma, dbeta, None, d_lhs
         if lhs_split:
             # fp16x3 mode: dz (fp32) came out of the split-operand dgrad's epilogue; dy only feeds the two products below
@@ -692,8 +694,7 @@ def _dgrad_route(mode, adjoint, forms_dy=False, da_fused=False, dy_dtype=None, r
 def _layer_dgrad(dy, W2d, s, mode, below, adjoint):
     """Third stage: d_lhs = dy . W, through ``adjoint`` (the caller's own; temporal block: implicit col2im) if given"""
     if adjoint is not None:
-        d_lhs = adjoint(dy)
-        return d_lhs[0] if isinstance(d_lhs, tuple) else d_lhs
+        return adjoint.from_dy(dy)
     rows, cout = s.y.shape
     K = W2d.shape[1]
     bs, below_bn, below_outs = below if below is not None else (None, None, None)
@@ -714,24 +715,25 @@ def _layer_dgrad(dy, W2d, s, mode, below, adjoint):
 
 
 def _bn_layer_backward(s, bn, W2d, mode, lhs, da=None, pool=None, need_dinput=True, outs=None, below=None,
-                       dgrad_fn=None, defer_wgrad=None, lin_bias=None, dbias_out=None):
+                       adjoint=None, defer_wgrad=None, lin_bias=None, dbias_out=None):
     """Backward of one (linear, BN, ELU) layer.  ``lhs`` is the GEMM's left operand ([rows, K]: the input activation or
     the im2col matrix).  ``outs`` = (dW, dgamma, dbeta) destination views (dW PRE-ZEROED: the trainer's flat gradient
     buffer) or None to allocate.  ``da`` may be a _FusedGrad (the dgrad of the layer above already applied ELU' and reduced
     the statistics); ``pool`` = (dpool, group_rows, pool_scale) instead of ``da`` when the layer's output was mean-pooled.
     ``below`` = (save, bn, outs) of the layer that produced ``lhs`` -- if it qualifies, this layer's dgrad is fused with
-    the first half of ITS backward and a _FusedGrad is returned as d_lhs.
+    the first half of ITS backward and a _FusedGrad is returned as d_lhs.  ``adjoint``: the caller's own dgrad instead
+    (_DtcAdjoint: ``from_dy(dy) -> d_lhs`` and, where ``forms_dy``, ``forming_dy(dz, y, coef) -> (d_lhs, dy)``).
     With an eval-mode save (``s.mean is None``) the linear bias ``lin_bias`` in front of the BatchNorm has a gradient, dbias =
     scale*dbeta (written to ``dbias_out`` when given); in train mode dbias is None (analytically zero: the batch mean removes it).
     Returns (dW2d, dgamma, dbeta, dbias, d_lhs or None)."""
     # the caller's adjoint, where it forms dy itself, replaces the tail of the first stage; any other route follows from dy
-    forms_dy = need_dinput and dgrad_fn is not None and _dgrad_route(
-        mode, True, getattr(dgrad_fn, "forms_dy", False), s.mean is not None and isinstance(da, _FusedGrad)) == "adjoint_dy"
+    forms_dy = need_dinput and adjoint is not None and _dgrad_route(
+        mode, True, adjoint.forms_dy, s.mean is not None and isinstance(da, _FusedGrad)) == "adjoint_dy"
     dy, dgamma, dbeta, dbias, d_lhs = _bn_dy(s, bn, da, pool, isinstance(lhs, ops.SplitImage), outs, lin_bias,
-                                             dbias_out, adjoint_dy=dgrad_fn if forms_dy else None)
+                                             dbias_out, adjoint_dy=adjoint if forms_dy else None)
     dW = _layer_wgrad(dy, lhs, s, mode, outs[0].view(s.y.shape[1], lhs.shape[1]) if outs else None, defer_wgrad)
     if need_dinput and d_lhs is None:
-        d_lhs = _layer_dgrad(dy, W2d, s, mode, below, dgrad_fn)
+        d_lhs = _layer_dgrad(dy, W2d, s, mode, below, adjoint)
     return dW, dgamma, dbeta, dbias, d_lhs
 
 
@@ -830,23 +832,43 @@ def pointnet_backward(saves, layers, mode, d_last=None, dpool=None, pool_rows=0,
 _FUSE_DTC = True
 
 
-# The temporal block's products in the bf16 throughput mode (PCAA_DTC_BF16): "wide" (default) = the bf16 matrix pipe where
-# the two-sequence kernels take the layer (contraction over >= 128 channels, >= 64 output channels: layers 5 and 6 and
-# their adjoints -- csrc/dtc_fused.hip, dtc_pair_kernel), exact fp32 products elsewhere; "all" = the one-sequence bf16
-# variants as well (measured no faster than their fp32 forms: docs/LAB_LOG.md section 9); "0" = fp32 products everywhere.
-_DTC_BF16 = os.environ.get("PCAA_DTC_BF16", "wide")
+_DtcFwd = collections.namedtuple("_DtcFwd", "fused ksplit bf16 route keep_col window")
+_DtcBwd = collections.namedtuple("_DtcBwd", "fused ksplit bf16 route epilogue forms_dy")
 
 
-def _dtc_bf16(mode, kc, nc, adj=False):
-    """kc: channels the product contracts over, nc: channels it produces (forward: cin, cout; adjoint: cout, cin) --
-    the same rule as pair_takes() in csrc/dtc_fused.hip"""
-    if mode != "bf16" or _DTC_BF16 == "0":
-        return False
-    if _DTC_BF16 in ("all", "1"):
-        return True
-    which = os.environ.get("PCAA_DTC_PAIR", "1")[:1]
-    on = which not in ("0", "a" if not adj else "f")
-    return on and kc >= 128 and kc % 32 == 0 and nc >= 64 and nc % 4 == 0
+def _dtc_launch(adjoint, mode, B, cin, cout, windowed=False):
+    """(ksplit, bf16, route) of one fused launch, each the library's answer.  ``bf16`` (the _bf16 entry point) in the bf16
+    throughput mode where the two-sequence kernels would take the layer at ksplit 1: exact fp32 products elsewhere"""
+    ksplit = ops.dtc_conv_ksplit(adjoint, B, cin, cout)
+    bf16 = mode == "bf16" and ops.dtc_conv_route(adjoint, True, B, cin, cout, 1).startswith("pair")
+    return ksplit, bf16, ops.dtc_conv_route(adjoint, bf16, B, cin, cout, ksplit, windowed)
+
+
+@functools.lru_cache(maxsize=None)
+def _dtc_plan(dims, B, T, training, want_bwd, mode, windowed, fuse, a_dtype):
+    """What dtc_forward and dtc_backward launch.  Pure: plain values in, launches and allocates nothing, and every rule is
+    the library's (device-free queries; they never change within a process, hence the cache).  ``dims``: (cin, cout) of
+    each layer; ``training``: train-mode BatchNorm (backward: the saves are train-mode ones); ``windowed``: the source is a
+    frame table read through window rows; ``fuse``: _FUSE_DTC; ``a_dtype``: dtype of the block's input.
+    Returns (fwd, bwd), one entry per layer.  _DtcFwd: ``fused`` (one launch per layer -- every layer or none; else im2col +
+    _linear_bn), the launch's ``ksplit``, ``bf16`` flag and ``route`` (a name of ops.DTC_ROUTES), ``keep_col`` (the save
+    holds the im2col matrix) and ``window``: None, or on the first layer of a windowed source "in_place" (its launch reads
+    the table) / "gather" (the windows are written out first).  _DtcBwd: ``fused`` (the adjoint in one launch; else
+    dy . W and col2im), its ``ksplit``, ``bf16`` and ``route``, ``epilogue`` (the BatchNorm backward of the layer below
+    rides in it) and ``forms_dy`` (it forms dy from dz itself).
+    The bf16 flag is asked at ksplit 1 but the forward's pair kernels need ksplit == 1: a wide layer with few long tiles
+    (512 -> 64 channels at B = 64: ksplit 8) takes the one-sequence bf16 kernel, measured no faster than fp32
+    (docs/LAB_LOG.md section 9).  No shipped block has such a layer."""
+    fwd_fused = fuse and a_dtype == torch.float32 and all(ops.dtc_conv_supported(T, cin, cout) for cin, cout in dims)
+    fwd, bwd = [], []
+    for li, (cin, cout) in enumerate(dims):
+        window = ("in_place" if fwd_fused else "gather") if windowed and li == 0 else None
+        ks, bf16, route = _dtc_launch(False, mode, B, cin, cout, window is not None) if fwd_fused else (0, False, None)
+        fwd.append(_DtcFwd(fwd_fused, ks, bf16, route, not fwd_fused or training or want_bwd, window))
+        bwd_fused = fuse and ops.dtc_conv_dgrad_supported(T, cin, cout)
+        ks, bf16, route = _dtc_launch(True, mode, B, cin, cout) if bwd_fused else (0, False, None)
+        bwd.append(_DtcBwd(bwd_fused, ks, bf16, route, li > 0 and ks == 1 and training, ks == 1))
+    return tuple(fwd), tuple(bwd)
 
 
 def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=None, ring_rows=0, consts=None,
@@ -865,28 +887,27 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
     saves = []
     a = a2d
     nl = len(layers)
-    fused = _FUSE_DTC and a2d.dtype == torch.float32 and all(
-        ops.dtc_conv_supported(T, l.conv1d.weight.shape[1], l.conv1d.weight.shape[0]) for l in layers)
+    dims = tuple((l.conv1d.weight.shape[1], l.conv1d.weight.shape[0]) for l in layers)
+    plan = _dtc_plan(dims, B, T, training, want_bwd, mode, win_row is not None, _FUSE_DTC, a2d.dtype)[0]
     if win_row is not None:
         if training:
             raise ValueError("dtc_forward: win_row is an eval-mode form (train-mode BatchNorm needs every row's statistics)")
         if ring_rows != win_row.ring_rows or len(win_row) != B or win_row.T != T or win_row.table_rows != a2d.shape[0]:
             raise ValueError("dtc_forward: win_row does not describe B windows of T rows of this table / ring_rows")
-        if not fused:
+        if plan[0].window == "gather":
             a = ops.gather_frames(a2d.contiguous(), win_row.row_index())
-            win_row = None
     prev = None          # (scale, shift) of the layer whose bias-free output `a` is (fused path)
-    for li, layer in enumerate(layers):
+    for li, (layer, p) in enumerate(zip(layers, plan)):
         conv, bn = layer.conv1d, layer.batch_norm
-        cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+        cin, cout = dims[li]
         W2d = conv.weight.view(cout, cin * 3)
-        if fused:
+        if p.fused:
             # one launch: implicit im2col + BN/ELU of the previous layer on load + contraction + statistics
             stats = ops.new_stats(cout, a.device) if training else None
             tail = ops.BnTailFwd(a.shape[0], conv.bias, bn, cout, sync=_sync_fn()) if training else None
             y, col = ops.dtc_conv_fwd(a, prev[0] if prev else None, prev[1] if prev else None, W2d, B, T,
-                                      layer.dilation, stats=stats, want_col=training or want_bwd, tail=tail,
-                                      bf16=_dtc_bf16(mode, cin, cout), win_row=win_row if li == 0 else None)
+                                      layer.dilation, stats=stats, want_col=p.keep_col, tail=tail, bf16=p.bf16,
+                                      win_row=win_row if p.window == "in_place" else None, ksplit=p.ksplit)
             if training:
                 scale, shift, mean, rstd = tail.out
                 count = tail.count_out
@@ -907,50 +928,64 @@ def dtc_forward(a2d, B, T, layers, training, pool_time, mode="fp32", win_row=Non
                 out, s.pool_e = ops.bn_act_meanpool_fwd(y, scale, shift, B, T, mean, rstd)
                 return out, saves
             return ops.bn_act_meanpool_fwd(y, scale, shift, B, T), saves
-        if fused and li < nl - 1:
+        if p.fused and li < nl - 1:
             a, prev = y, (scale, shift)
         else:
             a = ops.bn_act_fwd(y, scale, shift)
     return a, saves
 
 
+class _DtcAdjoint:
+    """The adjoint of one fused temporal layer w.r.t. its input in one launch (implicit col2im), as its _DtcBwd plans it.
+    With ``sb`` / ``btail`` (save and finalize of the layer below) the first half of that layer's BatchNorm+ELU backward
+    rides in the epilogue -- dz and the two column sums: it then starts at bn_bwd_finalize -- and d_lhs is a _FusedGrad."""
+    __slots__ = ("forms_dy", "btail", "launch")
+
+    def __init__(self, p, W2d, B, T, s, sb, btail):
+        self.forms_dy, self.btail = p.forms_dy, btail
+        self.launch = functools.partial(ops.dtc_conv_dgrad, W2d=W2d, B=B, T=T, cin=s.cin, dilation=s.dil, tail=btail,
+                                        below=(sb.y, sb.scale, sb.shift, sb.mean, sb.rstd) if sb else None,
+                                        bf16=p.bf16, ksplit=p.ksplit)
+
+    def forming_dy(self, dz, y, coef):
+        """dy = c0*dz + c1*y + c2 formed while the operand is staged, and handed back -> (d_lhs, dy)"""
+        return self._run(None, dz=dz, y=y, coef=coef, want_dy=True)
+
+    def from_dy(self, dy):
+        return self._run(dy)[0]
+
+    def _run(self, dy, **formed):
+        out, stats, dy = self.launch(dy, **formed)
+        return (out if self.btail is None else _FusedGrad(out, stats, fin=self.btail.out)), dy
+
+
 def dtc_backward(saves, layers, B, T, d_last=None, dpool=None, need_dx=True, gout=None, prefix="tc_block.dtc", mode="fp32"):
     grads = []
     defer = []
     da = d_last
+    plan = _dtc_plan(tuple((s.cin, s.cout) for s in saves), B, T, saves[0].mean is not None, True, mode, False, _FUSE_DTC,
+                     torch.float32)[1]
     for li in range(len(layers) - 1, -1, -1):
-        layer, s = layers[li], saves[li]
+        layer, s, p = layers[li], saves[li], plan[li]
         conv, bn = layer.conv1d, layer.batch_norm
         W2d = conv.weight.view(s.cout, s.cin * 3)
         need_in = li > 0 or need_dx
         outs, bias_out = _layer_outs(gout, f"{prefix}{li + 1}.", _DTC_NAMES)
-        fused = _FUSE_DTC and T <= 32 and s.cin % 4 == 0 and s.cout % 4 == 0
-        # the adjoint w.r.t. the layer input in one launch (implicit col2im), with the first half of the
-        # BatchNorm+ELU backward of the layer below in its epilogue (dz and the two column sums: that layer then
-        # starts at bn_bwd_finalize); else dcol = dy . W, then col2im
-        dgrad_fn = None
-        if fused:
-            sb = saves[li - 1] if (li > 0 and s.cout <= 512 and saves[li - 1].mean is not None) else None
+        adjoint = None                      # else dcol = dy . W, then col2im
+        if p.fused:
+            sb = saves[li - 1] if p.epilogue else None
             btail = _bwd_tail(sb, layers[li - 1].batch_norm, _layer_outs(gout, f"{prefix}{li}.", _DTC_NAMES)[0],
-                              s.cin) if sb is not None else None
-
-            def dgrad_fn(dy, dz=None, y=None, coef=None, W2d=W2d, s=s, sb=sb, btail=btail):
-                out, stats, dy_used = ops.dtc_conv_dgrad(
-                    dy, W2d, B, T, s.cin, s.dil, dz=dz, y=y, coef=coef, want_dy=dy is None,
-                    below=(sb.y, sb.scale, sb.shift, sb.mean, sb.rstd) if sb else None, tail=btail,
-                    bf16=_dtc_bf16(mode, s.cout, s.cin, adj=True))
-                return (_FusedGrad(out, stats, fin=btail.out) if sb else out), dy_used
-
-            dgrad_fn.forms_dy = s.cout <= 512
+                              s.cin) if p.epilogue else None
+            adjoint = _DtcAdjoint(p, W2d, B, T, s, sb, btail)
         pooled = li == len(layers) - 1 and dpool is not None
         dW, dg, db, dbias, dcol = _bn_layer_backward(s, bn, W2d, "fp32", s.col, da=None if pooled else da,
                                                      pool=(dpool, T, 1.0 / T) if pooled else None, need_dinput=need_in,
-                                                     outs=outs, dgrad_fn=dgrad_fn, defer_wgrad=defer, lin_bias=conv.bias,
+                                                     outs=outs, adjoint=adjoint, defer_wgrad=defer, lin_bias=conv.bias,
                                                      dbias_out=bias_out)
         grads.append(_layer_grads(_DTC_NAMES, conv, dW, dg, db, dbias, bias_out))
         if not need_in:
             da = None
-        elif fused:
+        elif p.fused:
             da = dcol                       # already the gradient w.r.t. the layer's input
         else:
             da = ops.dtc_col2im(dcol, B, T, s.cin, s.dil)

@@ -2372,11 +2372,32 @@ def dtc_conv_supported(T, cin, cout):
     return bool(_lib.load().pcaa_dtc_conv_supported(int(T), int(cin), int(cout)))
 
 
-def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=False, tail=None, bf16=False, win_row=None):
+def dtc_conv_dgrad_supported(T, cin, cout):
+    """the shapes dtc_conv_dgrad takes (the first argument check of the launcher)"""
+    return T <= 32 and cin % 4 == 0 and cout % 4 == 0
+
+
+def dtc_conv_ksplit(adjoint, B, cin, cout):
+    """the ksplit the library wants for a forward (pcaa_dtc_conv_ksplit) or an adjoint (pcaa_dtc_conv_dgrad_ksplit) call"""
+    lib = _lib.load()
+    return (lib.pcaa_dtc_conv_dgrad_ksplit if adjoint else lib.pcaa_dtc_conv_ksplit)(int(B), int(cin), int(cout))
+
+
+DTC_ROUTES = ("one_f32", "one_bf16", "pair32_f32", "pair32_bf16", "pair64_f32", "pair64_bf16")     # PCAA_DTC_ROUTE_* 0 .. 5
+
+
+def dtc_conv_route(adjoint, bf16, B, cin, cout, ksplit, windowed=False):
+    """the kernel such a call takes, by the library's own dispatch (pcaa_dtc_conv_route) -> its name in DTC_ROUTES"""
+    return DTC_ROUTES[_lib.load().pcaa_dtc_conv_route(int(adjoint), int(bf16), int(B), int(cin), int(cout), int(ksplit),
+                                                      int(windowed))]
+
+
+def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=False, tail=None, bf16=False, win_row=None,
+                 ksplit=None):
     """One DilTempConv1d layer forward in one launch (see pcaa_dtc_conv_fwd): returns (y, col or None).
     ``win_row`` (a WindowRows of B windows): ``src`` is a frame-feature table [table_rows, cin] and sequence b reads its T
     rows from win_row[b] on (pcaa_dtc_conv_fwd_win, or pcaa_dtc_conv_fwd_seg for segmented rings; eval form: no
-    statistics, no im2col)."""
+    statistics, no im2col).  ``ksplit``: pcaa_dtc_conv_ksplit's answer where the caller has it."""
     _chk(src, "dtc_conv_fwd.src", torch.float32, 2)
     _chk(W2d, "dtc_conv_fwd.W", torch.float32, 2)
     rows, cin = src.shape
@@ -2404,7 +2425,8 @@ def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=Fa
     y = torch.empty((rows, cout), dtype=torch.float32, device=src.device)
     col = torch.empty((rows, cin * 3), dtype=torch.float32, device=src.device) if want_col else None
     lib = _lib.load()
-    ksplit = lib.pcaa_dtc_conv_ksplit(B, cin, cout)
+    if ksplit is None:
+        ksplit = dtc_conv_ksplit(False, B, cin, cout)
     if ksplit > 1:                 # split K: the partial products go to slabs, a reduction pass makes y (and the statistics)
         stride = rows * cout
         dst = torch.empty(ksplit * stride, dtype=torch.float32, device=src.device)
@@ -2438,17 +2460,18 @@ def dtc_conv_fwd(src, scale, shift, W2d, B, T, dilation, stats=None, want_col=Fa
 
 
 def dtc_conv_dgrad(dy, W2d, B, T, cin, dilation, dz=None, y=None, coef=None, want_dy=False, below=None, tail=None,
-                   bf16=False):
+                   bf16=False, ksplit=None):
     """Adjoint of the causal dilated convolution w.r.t. its input in one launch (pcaa_dtc_conv_dgrad).
     ``dy`` [B*T,cout], or None with ``dz``, ``y``, ``coef``: dy is formed on load (``want_dy``: also returned).
     ``below`` = (y, scale, shift, mean, rstd) of the layer below: the result is that layer's dz and its
-    BatchNorm-backward statistics come back too.  Returns (out [B*T,cin], stats or None, dy or None)."""
+    BatchNorm-backward statistics come back too.  ``ksplit``: pcaa_dtc_conv_dgrad_ksplit's answer where the caller has it.
+    Returns (out [B*T,cin], stats or None, dy or None)."""
     _chk(W2d, "dtc_conv_dgrad.W", torch.float32, 2)
     cout = W2d.shape[0]
     rows = B * T
     src = dy if dy is not None else dz
     _chk(src, "dtc_conv_dgrad.dy/dz", torch.float32, 2)
-    if tuple(src.shape) != (rows, cout) or tuple(W2d.shape) != (cout, cin * 3) or T > 32 or cin % 4 or cout % 4:
+    if tuple(src.shape) != (rows, cout) or tuple(W2d.shape) != (cout, cin * 3) or not dtc_conv_dgrad_supported(T, cin, cout):
         raise ValueError(f"dtc_conv_dgrad: unsupported shapes {tuple(src.shape)} W {tuple(W2d.shape)} B={B} T={T}")
     if dy is None:
         _chk(y, "dtc_conv_dgrad.y", torch.float32, 2)
@@ -2459,7 +2482,7 @@ def dtc_conv_dgrad(dy, W2d, B, T, cin, dilation, dz=None, y=None, coef=None, wan
     dev = src.device
     out = torch.empty((rows, cin), dtype=torch.float32, device=dev)
     dy_out = torch.empty((rows, cout), dtype=torch.float32, device=dev) if (want_dy and dy is None) else None
-    ks = lib.pcaa_dtc_conv_dgrad_ksplit(B, cin, cout)
+    ks = dtc_conv_ksplit(True, B, cin, cout) if ksplit is None else ksplit
     dgrad = lib.pcaa_dtc_conv_dgrad_bf16 if bf16 else lib.pcaa_dtc_conv_dgrad
     stats = None
     ep = [None] * 5

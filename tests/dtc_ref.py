@@ -142,6 +142,16 @@ def dgrad_ksplit(B, cin, cout):
     return max(1, cdiv(cout, DG_MAX_CR))
 
 
+def grid():
+    """(B, cin, cout) with both sides of every boundary of the predicates"""
+    Bs = (1, 2, 4, 8, 9, 45, 47, 64, 383)
+    cins = (4, 32, 96, 128, 132, 160, 256, 260, 288, 480, 512, 516, 544, 1024, 2080, 2304, 2560)
+    couts = (16, 32, 48, 64, 80, 128, 256, 512, 516, 1024)
+    # (2, 128, 66): forward nc % 4 != 0 with every other condition of pair_takes true -- no entry point accepts it, the route
+    # function takes any integers; (383, 128, 80): >= 192 workgroups with nc % 64 != 0
+    return [(B, ci, co) for B in Bs for ci in cins for co in couts] + [(2, 128, 66), (383, 128, 80)]
+
+
 def split_ranges(kc, ks):
     per_z = cdiv(cdiv(kc, CC), ks) * CC
     return [(min(kc, z * per_z), min(kc, (z + 1) * per_z)) for z in range(ks)]

@@ -318,23 +318,13 @@ def test_every_route_is_the_target_of_a_forward_and_an_adjoint_case_and_the_libr
     assert D.route(False, False, c["B"], c["cin"], c["cout"], 1, False) == 2, "a pair shape: only the window keeps it on the one-sequence kernel"
 
 
-def grid():
-    """(B, cin, cout) with both sides of every boundary of the predicates"""
-    Bs = (1, 2, 4, 8, 9, 45, 47, 64, 383)
-    cins = (4, 32, 96, 128, 132, 160, 256, 260, 288, 480, 512, 516, 544, 1024, 2080, 2304, 2560)
-    couts = (16, 32, 48, 64, 80, 128, 256, 512, 516, 1024)
-    # (2, 128, 66): forward nc % 4 != 0 with every other condition of pair_takes true -- no entry point accepts it, the route
-    # function takes any integers; (383, 128, 80): >= 192 workgroups with nc % 64 != 0
-    return [(B, ci, co) for B in Bs for ci in cins for co in couts] + [(2, 128, 66), (383, 128, 80)]
-
-
 def test_conditions_are_taken_both_ways_and_the_predicates_match_their_restatements():
     lib = _lib()
     seen = {}
 
     def note(name, v):
         seen.setdefault(name, set()).add(bool(v))
-    for B, cin, cout in grid():
+    for B, cin, cout in D.grid():          # (tests/test_dtc_plan_cpu.py walks the same grid)
         for adj in (False, True):
             kc, nc = (cout, cin) if adj else (cin, cout)
             for ks in (1, 2):
