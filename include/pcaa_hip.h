@@ -733,6 +733,38 @@ int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, cons
                                 const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
                                 float* rows, float* weight, int* u_off, long M, int* pick_out, int* err_flag,
                                 void* stream);
+/* ABI 29, added after it like pcaa_crops_from_raw (the version is unchanged: a library without these entry points fails to
+ * load by name): the three entry points above with a thinning stage in front of the draw -- a frame keeps at most k_f of its
+ * detections before it is padded or subsampled to N: what a sparser radar would deliver, the reference's
+ * force_pc_subsampling sweep, and point dropout for training, all from the same resident detections.  Arguments as the
+ * neighbour of the same name, then keep (K), keep_min (Kmin) and keep_rule (PCAA_RAW_KEEP_FIRST / _RANDOM);
+ * 1 <= keep_min <= keep <= PCAA_RAW_MAX_CARD.  With s the frame's chain state after seed_lo, seed_hi, key[0], key[1] and
+ * t = absorb(s, 0x6b656570) (raw_frames.hip: absorb(s, w) = mix((s ^ w) + 0x9e3779b9)):
+ *   k_f = keep_min + ((uint64)absorb(t, 0xffffffff) * (keep - keep_min + 1) >> 32), drawn only when keep_min < keep;
+ *   k_f >= card: the frame's picks and output bits are exactly those of the entry point without _thin;
+ *   FIRST: the kept raw indices are 0 .. k_f - 1;  RANDOM: the k_f detections with the smallest (absorb(t, i), i), in
+ *   rank order;  then the draw of pcaa_frames_from_raw, unchanged, over the k_f kept points (repeat-pad if k_f < N, a rank
+ *   subset otherwise), mapped back through the keep list: pick_out holds RAW indices.
+ * datasets.device_picks_host(..., keep, keep_min, keep_rule) restates it integer for integer.  The picks are drawn on the
+ * device only: pick must be NULL (supplied picks decide by themselves) and frame_key non-NULL when there are frames; these,
+ * the range of keep / keep_min and keep_rule outside {0, 1} are argument errors, refused before any launch.  A frame has
+ * the same bits in all three; the bad-frame rule, the zero padding rows and the launches per call are those of the
+ * neighbours.  pcaa_frames_from_raw_unique_thin: u_cnt[f] = min(card_f, k_f, N) (a bad frame: 1), so u_off depends on keep
+ * and, when keep_min < keep, on seed and frame_key as well; u_off[n] <= min(P + n, n min(N, keep)). */
+#define PCAA_RAW_KEEP_FIRST 0
+#define PCAA_RAW_KEEP_RANDOM 1
+int pcaa_frames_from_raw_thin(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
+                              const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
+                              float* out, int n_out, int* pick_out, int* err_flag, void* stream, int keep, int keep_min,
+                              int keep_rule);
+int pcaa_crops_from_raw_thin(const void* points, int points_f64, long P, const int* offsets, long F, const int* start,
+                             int B, int T, const int* pick, const int* frame_key, long seed, int N, int C,
+                             int standardize, int divide_by_std, float* out, int* err_flag, void* stream, int keep,
+                             int keep_min, int keep_rule);
+int pcaa_frames_from_raw_unique_thin(const void* points, int points_f64, long P, const int* offsets, int n,
+                                     const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                                     int divide_by_std, float* rows, float* weight, int* u_off, long M, int* pick_out,
+                                     int* err_flag, void* stream, int keep, int keep_min, int keep_rule);
 /* ABI 25 (segment_pool.hip): out[f, c] = (1 / N) sum_{r = u_off[f]}^{u_off[f + 1] - 1} weight[r] * v(a[r * lda + c]) for
  * n frames, a [M, ch] fp32 or bf16 (dtype) with leading dimension lda, out [n, ch] fp32.  v = identity; with scale / shift
  * [ch] (both or neither) a is a pre-BatchNorm y and v = ELU(a * scale[c] + shift[c]) (fused multiply-add, expm1f).  fp32

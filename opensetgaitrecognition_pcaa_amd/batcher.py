@@ -205,12 +205,19 @@ class RawTrackBatcher:
     fresh pad / subset per epoch, reproducible from (seed, e).  ``picks`` (int32 [F, N] over the store's frames, e.g.
     ``datasets.draw_picks(store.cards(), N)``): host-drawn picks instead, the reference's own crops.  ``jitter``: every
     track's starts are shifted by a phase of (seed, epoch, serial) (``RawCrops.starts``).  Epochs count from 0 in the order
-    ``__iter__`` is called."""
+    ``__iter__`` is called.  ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" /
+    "random"): point dropout -- every frame keeps at most that many of its detections before it is padded to N, by the
+    same launch (``ops.crops_from_raw(keep=...)``); the counts and the kept sets are drawn with the epoch's seed, so under
+    ``redraw="epoch"`` they are re-drawn per epoch as the padding is.  Not with ``picks``, which decide by themselves."""
 
     def __init__(self, view, batch_size, shuffle=True, drop_last=True, rank=0, world=1, group=None, seed=0, redraw="fixed",
-                 jitter=False, picks=None):
+                 jitter=False, picks=None, keep_points=0, keep_rule="first"):
         if redraw not in ("fixed", "epoch"):
             raise ValueError(f"RawTrackBatcher: redraw must be 'fixed' or 'epoch', got {redraw!r}")
+        if datasets.keep_arguments(keep_points, None, keep_rule, "RawTrackBatcher")[0] and picks is not None:
+            raise ValueError("RawTrackBatcher: keep_points thins the frames before the device draws their picks; supplied "
+                             "picks decide by themselves")
+        self.keep_points, self.keep_rule = keep_points, keep_rule
         self.view, self.store = view, view.store
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), shuffle, drop_last
         self.rank, self.world, self.group = int(rank), int(world), group
@@ -284,7 +291,8 @@ class RawTrackBatcher:
     def _crops(self, start):
         st, v = self.store, self.view
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, v.T, v.N, v.C, pick=self.picks, seed=self.draw_seed,
-                                frame_key=st.frame_key_dev, err_flag=self.err)   # [B,T,N,C]
+                                frame_key=st.frame_key_dev, err_flag=self.err, keep=self.keep_points,
+                                keep_rule=self.keep_rule)                       # [B,T,N,C]
         return pm.permute(0, 3, 1, 2)
 
     def batch(self, idx):
@@ -323,12 +331,13 @@ def batcher_for(dataset, batch_size, device, shuffle, drop_last=True, cache_dir=
     ``.pcs [M,T,N,C]``, ``.labels``) go to the device as they are; file-backed ones (``MSRadarDataset``) are
     packed once into ``<dataset_dir>_packed`` (re-packed when the file list changed) and uploaded.  A
     ``datasets.RawCrops`` view (``RawTrackStore.crops``) gets a :class:`RawTrackBatcher` with the fixed draws of its
-    ``batcher_options`` (default: seed 0); the store is uploaded if it is not yet."""
+    ``batcher_options`` (default: seed 0; ``keep_points`` / ``keep_rule`` among them: point dropout for the training
+    loader, while the validation loader sees the frames whole); the store is uploaded if it is not yet."""
     if isinstance(dataset, datasets.RawCrops):
         dataset.store.to_device(device)
         opts = dict(dataset.batcher_options)
         if not shuffle:                                  # the validation loader: the fixed draws, the reference's starts
-            opts.update(redraw="fixed", jitter=False)
+            opts.update(redraw="fixed", jitter=False, keep_points=0)
         return RawTrackBatcher(dataset, batch_size, shuffle, drop_last, rank, world, group, **opts)
     if hasattr(dataset, "pcs") and torch.is_tensor(dataset.pcs):
         crops = dataset.pcs.to(device).float().contiguous()

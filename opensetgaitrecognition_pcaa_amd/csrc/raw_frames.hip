@@ -27,6 +27,23 @@
 //   card >= N (its subsample without replacement): point i has the sort key (h(seed, key, i), i); its rank among the
 //              frame's card keys is counted against the keys in LDS (all lanes read the same word: a broadcast); rank
 //              r < N gives pick[r] = i: a uniform random N-subset in uniform random order, with no sequential shuffle.
+//
+// Thinning (the _thin entry points): a first stage that keeps at most k_f of a frame's detections before the draw above
+// pads or subsamples them to N -- what a sparser radar would deliver, and the reference's force_pc_subsampling sweep.
+// Parameters keep (K >= 1; 0 = off: the instantiations without the stage), keep_min (1 <= Kmin <= K) and keep_rule
+// (FIRST = 0, RANDOM = 1).  With s the chain state after seed_lo, seed_hi, key[0], key[1] and t = absorb(s, 0x6b656570)
+// ("keep"; absorb(s, w) = mix((s ^ w) + 0x9e3779b9)):
+//   count    k_f = Kmin + ((uint64)absorb(t, 0xffffffff) * (K - Kmin + 1) >> 32); the hash is drawn only when Kmin < K;
+//   k_f >= card: the frame is untouched -- its picks and output bits are those of the entry points without thinning;
+//   FIRST    the kept raw indices are 0 .. k_f - 1 (the support of the reference's quirk: datasets.process_track
+//            overwrites the cardinality before it chooses);
+//   RANDOM   the k_f detections with the smallest (absorb(t, i), i), in rank order, ranks counted against keys in LDS
+//            exactly like the card >= N branch above (the key array is reused: it is dead before stage 2 writes it);
+//   stage 2  the draw above, unchanged, over a virtual frame of k_f points (repeat-pad if k_f < N, a rank subset
+//            otherwise), still on absorb(s, i) with i < 1024, which can never meet the tagged chain t; the result is
+//            mapped through the keep list (16-bit, in LDS), so pick_out holds RAW indices.
+// datasets.device_picks_host(..., keep, keep_min, keep_rule) restates it.  A supplied pick decides by itself: together
+// with keep > 0 it is an argument error.
 #include "common.h"
 
 namespace {
@@ -40,6 +57,25 @@ __host__ __device__ __forceinline__ uint32_t raw_mix(uint32_t x) {
   return x;
 }
 __device__ __forceinline__ uint32_t raw_absorb(uint32_t s, uint32_t w) { return raw_mix((s ^ w) + 0x9e3779b9u); }
+
+// the chain state of frame f after the words seed_lo, seed_hi, key[0], key[1]
+__device__ __forceinline__ uint32_t raw_chain(uint32_t seed_lo, uint32_t seed_hi, const int* __restrict__ frame_key, long f) {
+  const uint32_t s = raw_absorb(raw_absorb(0x9e3779b9u, seed_lo), seed_hi);
+  return raw_absorb(raw_absorb(s, (uint32_t)frame_key[2 * f]), (uint32_t)frame_key[2 * f + 1]);
+}
+
+constexpr uint32_t RAW_KEEP_WORD = 0x6b656570u;  // "keep": the tag of the thinning stage's chain
+constexpr int RAW_KEEP_FIRST = 0, RAW_KEEP_RANDOM = 1;
+struct RawKeep {                                 // the thinning parameters: the kernels' last argument, read under KEEP only
+  int keep, keep_min, rule;
+};
+
+// k_f of the header comment from t = absorb(s, RAW_KEEP_WORD): the one place it is computed (the frames' kernels and
+// the scan of u_off must agree on it)
+__device__ __forceinline__ int raw_keep_count(uint32_t t, int keep, int keep_min) {
+  if (keep_min >= keep) return keep;
+  return keep_min + (int)(((uint64_t)raw_absorb(t, 0xffffffffu) * (uint64_t)(keep - keep_min + 1)) >> 32);
+}
 
 // the sum of v[c] over the workgroup, c < C, in the fixed order of the header comment; every thread gets the result
 template <int C>
@@ -85,15 +121,22 @@ struct RawShared {
   double red[RAW_WAVES * RAW_COLS];
   int bad;
 };
+// ... with the thinning stage: the kept raw indices by rank (a frame holds at most 1024: 16 bits each)
+struct RawSharedKeep : RawShared {
+  uint16_t keep[PCAA_RAW_MAX_CARD];
+};
+template <bool KEEP>
+using RawSharedOf = typename std::conditional<KEEP, RawSharedKeep, RawShared>::type;
 
 // Steps 1 - 3 of the header comment for frame f, shared by every kernel of this file so that they produce the same
 // bits: picks -> sh.pick (and pick_out), gather -> sh.val, mean / denom in every thread's registers.  Returns false
 // for a bad frame: pick_out is -1, *err set, sh.val / mean / denom undefined; the caller writes its zeros.
-template <typename T, int C>
+// KEEP: with the thinning stage of the header comment (kp is read only then).
+template <typename T, int C, bool KEEP>
 __device__ __forceinline__ bool raw_frame_prepare(
-    RawShared& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
+    RawSharedOf<KEEP>& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, int* __restrict__ pick_out, int* __restrict__ err, int& card_out,
+    int standardize, int divide_by_std, RawKeep kp, int* __restrict__ pick_out, int* __restrict__ err, int& card_out,
     double (&mean)[C], double (&denom)[C]) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
@@ -115,22 +158,50 @@ __device__ __forceinline__ bool raw_frame_prepare(
       }
       if (mine) sh.bad = 1;
     } else {
-      uint32_t s = raw_absorb(raw_absorb(0x9e3779b9u, seed_lo), seed_hi);
-      s = raw_absorb(raw_absorb(s, (uint32_t)frame_key[2 * f]), (uint32_t)frame_key[2 * f + 1]);
-      if (card < N) {
+      const uint32_t s = raw_chain(seed_lo, seed_hi, frame_key, f);
+      int vcard = card;                             // the frame stage 2 draws over
+      bool mapped = false;
+      if constexpr (KEEP) {
+        // stage 1: k_f, and under RANDOM the keep list (everything here is uniform over the workgroup)
+        const uint32_t t = raw_absorb(s, RAW_KEEP_WORD);
+        const int kf = raw_keep_count(t, kp.keep, kp.keep_min);
+        vcard = kf < card ? kf : card;
+        mapped = kf < card && kp.rule == RAW_KEEP_RANDOM;
+        if (mapped) {
+          for (int i = tid; i < card; i += RAW_THREADS) sh.key[i] = raw_absorb(t, (uint32_t)i);
+          __syncthreads();
+          for (int i = tid; i < card; i += RAW_THREADS) {
+            const uint32_t k = sh.key[i];
+            int rank = 0;
+            for (int j = 0; j < card; ++j) {
+              const uint32_t kj = sh.key[j];
+              rank += (kj < k) || (kj == k && j < i);
+            }
+            if (rank < vcard) sh.keep[rank] = (uint16_t)i;   // the ranks are a permutation: every slot < k_f is written
+          }
+          __syncthreads();                          // the list is complete, and sh.key is free for stage 2
+        }
+      }
+      if (vcard < N) {
         for (int p = tid; p < N; p += RAW_THREADS)
-          sh.pick[p] = p < card ? p : (int)(((uint64_t)raw_absorb(s, (uint32_t)p) * (uint64_t)card) >> 32);
+          sh.pick[p] = p < vcard ? p : (int)(((uint64_t)raw_absorb(s, (uint32_t)p) * (uint64_t)vcard) >> 32);
       } else {
-        for (int i = tid; i < card; i += RAW_THREADS) sh.key[i] = raw_absorb(s, (uint32_t)i);
+        for (int i = tid; i < vcard; i += RAW_THREADS) sh.key[i] = raw_absorb(s, (uint32_t)i);
         __syncthreads();
-        for (int i = tid; i < card; i += RAW_THREADS) {
+        for (int i = tid; i < vcard; i += RAW_THREADS) {
           const uint32_t k = sh.key[i];
           int rank = 0;
-          for (int j = 0; j < card; ++j) {
+          for (int j = 0; j < vcard; ++j) {
             const uint32_t kj = sh.key[j];
             rank += (kj < k) || (kj == k && j < i);
           }
           if (rank < N) sh.pick[rank] = i;
+        }
+      }
+      if constexpr (KEEP) {
+        if (mapped) {                               // virtual -> raw indices (FIRST: the list is the identity)
+          __syncthreads();
+          for (int p = tid; p < N; p += RAW_THREADS) sh.pick[p] = (int)sh.keep[sh.pick[p]];
         }
       }
     }
@@ -206,18 +277,18 @@ __device__ __forceinline__ float raw_frame_finish(const RawShared& sh, int e, co
 
 // Steps 1 - 4 for store frame f into the padded frame at dst ([N, C] fp32): the one body of the kernels that write padded
 // frames (frames_from_raw_kernel, crops_from_raw_kernel), so that a frame has the same bits wherever it is written.
-template <typename T, int C>
+template <typename T, int C, bool KEEP>
 __device__ __forceinline__ void raw_frame_write(
-    RawShared& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
+    RawSharedOf<KEEP>& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, float* __restrict__ dst, bool vec, int* __restrict__ pick_out,
+    int standardize, int divide_by_std, RawKeep kp, float* __restrict__ dst, bool vec, int* __restrict__ pick_out,
     int* __restrict__ err) {
   const int tid = threadIdx.x;
   const int NC = N * C;
   double mean[C], denom[C];
   int card;
-  if (!raw_frame_prepare<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                               divide_by_std, pick_out, err, card, mean, denom)) {
+  if (!raw_frame_prepare<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                     divide_by_std, kp, pick_out, err, card, mean, denom)) {
     zero_frame(dst, NC, vec);
     return;
   }
@@ -235,12 +306,12 @@ __device__ __forceinline__ void raw_frame_write(
   }
 }
 
-template <typename T, int C>
+template <typename T, int C, bool KEEP>
 __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
     const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
-    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err) {
-  __shared__ RawShared sh;
+    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err, RawKeep kp) {
+  __shared__ RawSharedOf<KEEP> sh;
   const long f = blockIdx.x;
   const int NC = N * C;
   float* dst = out + f * (long)NC;
@@ -249,8 +320,8 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     zero_frame(dst, NC, vec);
     return;
   }
-  raw_frame_write<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize, divide_by_std, dst,
-                        vec, pick_out, err);
+  raw_frame_write<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                              divide_by_std, kp, dst, vec, pick_out, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -261,12 +332,12 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
 // (overlapping and repeated crops each get their own copy: no workgroup reads what another wrote).  A crop that leaves
 // the store (start[b] < 0 or start[b] + T > F; compared in 64 bits) is zeros and sets *err before any table is read.
 // The flag is raised as everywhere in this file (atomicOr); the output has no atomics.
-template <typename T, int C>
+template <typename T, int C, bool KEEP>
 __global__ __launch_bounds__(RAW_THREADS) void crops_from_raw_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, long F, const int* __restrict__ start, int Tc,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, float* __restrict__ out, int* __restrict__ err) {
-  __shared__ RawShared sh;
+    int standardize, int divide_by_std, float* __restrict__ out, int* __restrict__ err, RawKeep kp) {
+  __shared__ RawSharedOf<KEEP> sh;
   const int NC = N * C;
   const long slot = blockIdx.x;                   // b * T + t < B * T: the grid is exactly the batch's frames
   const int b = (int)(slot / Tc), t = (int)(slot - (long)b * Tc);
@@ -278,20 +349,23 @@ __global__ __launch_bounds__(RAW_THREADS) void crops_from_raw_kernel(
     if (err != nullptr && threadIdx.x == 0) atomicOr(err, 1);
     return;
   }
-  raw_frame_write<T, C>(sh, points, P, offsets, s + t, pick, frame_key, seed_lo, seed_hi, N, standardize, divide_by_std,
-                        dst, vec, nullptr, err);
+  raw_frame_write<T, C, KEEP>(sh, points, P, offsets, s + t, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                              divide_by_std, kp, dst, vec, nullptr, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same frames without their padding (pcaa_frames_from_raw_unique): a padded frame repeats detections, and in eval mode
 // the per-point network is a pure function of the point, so mean over the N rows of f(row) = (1/N) sum_i m_i f(p_i) over
 // the DISTINCT picked detections p_i with multiplicities m_i.  Frame f owns u_cnt[f] = min(card, N) rows of a compact
-// [M, C] table from u_off[f] on (a frame whose offsets are bad: one row): u_off depends on the offsets alone.
+// [M, C] table from u_off[f] on (a frame whose offsets are bad: one row); thinned, min(card, k_f, N).  u_off depends on the
+// offsets alone, with thinning also on keep, and under a count range (keep_min < keep) on the seed and the frames' keys.
 
 // u_off[0 .. n] = exclusive scan of u_cnt: one workgroup walks the frames in chunks of its size with a running carry
 constexpr int SCAN_THREADS = 1024;
-__global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(const int* __restrict__ offsets, int n, long P,
-                                                                          int N, int* __restrict__ u_off) {
+template <bool KEEP>
+__global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(
+    const int* __restrict__ offsets, int n, long P, int N, int* __restrict__ u_off, const int* __restrict__ frame_key,
+    uint32_t seed_lo, uint32_t seed_hi, RawKeep kp) {
   __shared__ int s_wave[SCAN_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int carry = 0;                                  // the same in every thread
@@ -302,6 +376,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(const 
     if (f < n) {
       const long off0 = offsets[f], off1 = offsets[f + 1];
       cnt = raw_offsets_bad(off0, off1, P) ? 1 : (int)((off1 - off0) < (long)N ? (off1 - off0) : (long)N);
+      if constexpr (KEEP) {                       // k_f as raw_frame_prepare computes it; the keys are read for a range only
+        const int kf = kp.keep_min >= kp.keep
+                           ? kp.keep
+                           : raw_keep_count(raw_absorb(raw_chain(seed_lo, seed_hi, frame_key, f), RAW_KEEP_WORD), kp.keep,
+                                            kp.keep_min);
+        cnt = cnt < kf ? cnt : kf;                // a bad frame's one row stays: k_f >= 1
+      }
     }
     int incl = cnt;                               // inclusive scan inside the wave
 #pragma unroll
@@ -326,13 +407,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(const 
 
 constexpr int RAW_PER_THREAD = PCAA_RAW_MAX_POINTS / RAW_THREADS;      // pick positions one thread ranks
 
-template <typename T, int C>
+template <typename T, int C, bool KEEP>
 __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
     const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
     float* __restrict__ rows, float* __restrict__ weight, const int* __restrict__ u_off, long M,
-    int* __restrict__ pick_out, int* __restrict__ err) {
-  __shared__ RawShared sh;
+    int* __restrict__ pick_out, int* __restrict__ err, RawKeep kp) {
+  __shared__ RawSharedOf<KEEP> sh;
   __shared__ int s_cnt[PCAA_RAW_MAX_CARD];        // by raw index: how often it was picked
   __shared__ int s_first[PCAA_RAW_MAX_CARD];      // by raw index: the first pick position that holds it
   __shared__ int s_rank[PCAA_RAW_MAX_POINTS];     // by pick position: distinct detections first seen before it
@@ -362,8 +443,8 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
   }
   double mean[C], denom[C];
   int card;
-  if (!raw_frame_prepare<T, C>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                               divide_by_std, pick_out, err, card, mean, denom)) {
+  if (!raw_frame_prepare<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                     divide_by_std, kp, pick_out, err, card, mean, denom)) {
     zero_rows(u0, u1);                            // one row, the zero point N times: the padded path's all-zero frame
     __syncthreads();                              // (the weight below is written after the zeros, by the thread that wrote them)
     if (tid == 0) weight[u0] = (float)N;
@@ -412,7 +493,7 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
   }
   __syncthreads();
 
-  // distinct <= min(card, N) = u1 - u0: the rows the picks leave unused are zero with weight 0
+  // distinct <= min(card, k_f, N) = u1 - u0: the rows the picks leave unused are zero with weight 0
   if (vec) {
     for (int p = tid; p < N; p += RAW_THREADS) {
       const int r = s_rank[p];
@@ -437,53 +518,144 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
   zero_rows(u0 + distinct, u1);
 }
 
+// every launcher: KEEP = kp.keep > 0 picks the instantiation; without thinning the kernels are those of ABI 29
+#define PCAA_RAW_CASES(LAUNCH)                                                                                         \
+  switch (C) {                                                                                                         \
+    case 1: if (kp.keep > 0) { LAUNCH(1, true) } else { LAUNCH(1, false) } break;                                      \
+    case 2: if (kp.keep > 0) { LAUNCH(2, true) } else { LAUNCH(2, false) } break;                                      \
+    case 3: if (kp.keep > 0) { LAUNCH(3, true) } else { LAUNCH(3, false) } break;                                      \
+    case 4: if (kp.keep > 0) { LAUNCH(4, true) } else { LAUNCH(4, false) } break;                                      \
+    case 5: if (kp.keep > 0) { LAUNCH(5, true) } else { LAUNCH(5, false) } break;                                      \
+  }
+
 template <typename T>
 void launch_frames_from_raw(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
                             const int* pick, const int* frame_key, long seed, int N, int standardize, int divide_by_std,
-                            float* out, int* pick_out, int* err) {
+                            RawKeep kp, float* out, int* pick_out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
-#define PCAA_RAW_CASE(CC)                                                                                              \
-  case CC:                                                                                                             \
-    hipLaunchKernelGGL((frames_from_raw_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n, pick,   \
-                       frame_key, lo, hi, N, standardize, divide_by_std, out, pick_out, err);                          \
-    break;
-  switch (C) {
-    PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
-  }
-#undef PCAA_RAW_CASE
+#define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
+  hipLaunchKernelGGL((frames_from_raw_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n,     \
+                     pick, frame_key, lo, hi, N, standardize, divide_by_std, out, pick_out, err, kp);
+  PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
+#undef PCAA_RAW_LAUNCH
 }
 
 template <typename T>
 void launch_crops_from_raw(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, long F,
                            const int* start, int Tc, const int* pick, const int* frame_key, long seed, int N,
-                           int standardize, int divide_by_std, float* out, int* err) {
+                           int standardize, int divide_by_std, RawKeep kp, float* out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
-#define PCAA_RAW_CASE(CC)                                                                                              \
-  case CC:                                                                                                             \
-    hipLaunchKernelGGL((crops_from_raw_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, F, start,   \
-                       Tc, pick, frame_key, lo, hi, N, standardize, divide_by_std, out, err);                          \
-    break;
-  switch (C) {
-    PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
-  }
-#undef PCAA_RAW_CASE
+#define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
+  hipLaunchKernelGGL((crops_from_raw_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, F,      \
+                     start, Tc, pick, frame_key, lo, hi, N, standardize, divide_by_std, out, err, kp);
+  PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
+#undef PCAA_RAW_LAUNCH
 }
 
 template <typename T>
 void launch_frames_from_raw_unique(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
                                    const int* pick, const int* frame_key, long seed, int N, int standardize,
-                                   int divide_by_std, float* rows, float* weight, const int* u_off, long M, int* pick_out,
-                                   int* err) {
+                                   int divide_by_std, RawKeep kp, float* rows, float* weight, const int* u_off, long M,
+                                   int* pick_out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
-#define PCAA_RAW_CASE(CC)                                                                                              \
-  case CC:                                                                                                             \
-    hipLaunchKernelGGL((frames_from_raw_unique_kernel<T, CC>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n,  \
-                       pick, frame_key, lo, hi, N, standardize, divide_by_std, rows, weight, u_off, M, pick_out, err); \
-    break;
-  switch (C) {
-    PCAA_RAW_CASE(1) PCAA_RAW_CASE(2) PCAA_RAW_CASE(3) PCAA_RAW_CASE(4) PCAA_RAW_CASE(5)
-  }
-#undef PCAA_RAW_CASE
+#define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
+  hipLaunchKernelGGL((frames_from_raw_unique_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, \
+                     n, pick, frame_key, lo, hi, N, standardize, divide_by_std, rows, weight, u_off, M, pick_out, err, \
+                     kp);
+  PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
+#undef PCAA_RAW_LAUNCH
+}
+#undef PCAA_RAW_CASES
+
+// what the _thin entry points check on top of their neighbours' arguments: no launch follows a refusal
+int check_keep(const char* who, int keep, int keep_min, int keep_rule, const void* pick, const void* frame_key, long n) {
+  PCAA_CHECK_ARG(keep >= 1 && keep_min >= 1 && keep_min <= keep && keep <= PCAA_RAW_MAX_CARD,
+                 "%s: needs 1 <= keep_min <= keep <= PCAA_RAW_MAX_CARD", who);
+  PCAA_CHECK_ARG(keep_rule == RAW_KEEP_FIRST || keep_rule == RAW_KEEP_RANDOM, "%s: keep_rule is 0 (first) or 1 (random)", who);
+  PCAA_CHECK_ARG(pick == nullptr, "%s: supplied picks decide by themselves; pick must be NULL", who);
+  PCAA_CHECK_ARG(n == 0 || frame_key != nullptr, "%s: the frames need their keys (frame_key)", who);
+  return PCAA_OK;
+}
+
+// The bodies of the entry points, `who` the name in their messages; kp.keep == 0: without thinning.
+int frames_from_raw_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, int n,
+                         const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                         int divide_by_std, RawKeep kp, float* out, int n_out, int* pick_out, int* err_flag, void* stream) {
+  PCAA_CHECK_ARG(n >= 0 && n_out >= n && n_out >= 1 && P >= 0, "%s: needs 0 <= n <= n_out, n_out >= 1, P >= 0", who);
+  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
+                 "%s: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5", who);
+  PCAA_CHECK_ARG(out != nullptr && ((uintptr_t)out % 4) == 0, "%s: out is null or not 4-B aligned", who);
+  PCAA_CHECK_ARG(n == 0 || (offsets != nullptr && (points != nullptr || P == 0)), "%s: points / offsets are null", who);
+  PCAA_CHECK_ARG(n == 0 || pick != nullptr || frame_key != nullptr,
+                 "%s: without picks the frames need their keys (frame_key)", who);
+  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "%s: points are misaligned", who);
+  const dim3 grid((unsigned)n_out);
+  if (points_f64)
+    launch_frames_from_raw<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, n, pick,
+                                   frame_key, seed, N, standardize, divide_by_std, kp, out, pick_out, err_flag);
+  else
+    launch_frames_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n, pick,
+                                  frame_key, seed, N, standardize, divide_by_std, kp, out, pick_out, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS(who);
+}
+
+int crops_from_raw_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, long F,
+                        const int* start, int B, int T, const int* pick, const int* frame_key, long seed, int N, int C,
+                        int standardize, int divide_by_std, RawKeep kp, float* out, int* err_flag, void* stream) {
+  PCAA_CHECK_ARG(B >= 1 && T >= 1 && F >= 0 && P >= 0 && (long)B * T < (1L << 31) && F < (1L << 31),
+                 "%s: needs B >= 1, T >= 1, B * T < 2^31, 0 <= F < 2^31, P >= 0", who);
+  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
+                 "%s: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5", who);
+  PCAA_CHECK_ARG(out != nullptr && ((uintptr_t)out % 4) == 0, "%s: out is null or not 4-B aligned", who);
+  PCAA_CHECK_ARG(start != nullptr && offsets != nullptr && (points != nullptr || P == 0),
+                 "%s: points / offsets / start are null", who);
+  PCAA_CHECK_ARG(F == 0 || pick != nullptr || frame_key != nullptr,
+                 "%s: without picks the frames need their keys (frame_key)", who);
+  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "%s: points are misaligned", who);
+  const dim3 grid((unsigned)((long)B * T));
+  if (points_f64)
+    launch_crops_from_raw<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, F, start,
+                                  T, pick, frame_key, seed, N, standardize, divide_by_std, kp, out, err_flag);
+  else
+    launch_crops_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, F, start, T,
+                                 pick, frame_key, seed, N, standardize, divide_by_std, kp, out, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS(who);
+}
+
+int frames_from_raw_unique_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, int n,
+                                const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                                int divide_by_std, RawKeep kp, float* rows, float* weight, int* u_off, long M,
+                                int* pick_out, int* err_flag, void* stream) {
+  PCAA_CHECK_ARG(n >= 0 && M >= 1 && P >= 0 && (long)n * PCAA_RAW_MAX_POINTS < (1L << 31) && M < (1L << 31),
+                 "%s: needs n >= 0, 1 <= M < 2^31, P >= 0, n * 1024 < 2^31", who);
+  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
+                 "%s: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5", who);
+  PCAA_CHECK_ARG(rows != nullptr && weight != nullptr && u_off != nullptr && ((uintptr_t)rows % 4) == 0 &&
+                     ((uintptr_t)weight % 4) == 0 && ((uintptr_t)u_off % 4) == 0,
+                 "%s: rows / weight / u_off are null or not 4-B aligned", who);
+  PCAA_CHECK_ARG(n == 0 || (offsets != nullptr && (points != nullptr || P == 0)), "%s: points / offsets are null", who);
+  PCAA_CHECK_ARG(n == 0 || pick != nullptr || frame_key != nullptr,
+                 "%s: without picks the frames need their keys (frame_key)", who);
+  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "%s: points are misaligned", who);
+  const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
+  if (kp.keep > 0)
+    hipLaunchKernelGGL(raw_unique_offsets_kernel<true>, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n, P,
+                       N, u_off, frame_key, lo, hi, kp);
+  else
+    hipLaunchKernelGGL(raw_unique_offsets_kernel<false>, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n,
+                       P, N, u_off, frame_key, lo, hi, kp);
+  long tail = cdiv(M, 4096);                      // blocks that zero the rows no frame owns
+  tail = tail < 1 ? 1 : (tail > 64 ? 64 : tail);
+  const dim3 grid((unsigned)(n + tail));
+  if (points_f64)
+    launch_frames_from_raw_unique<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, n,
+                                          pick, frame_key, seed, N, standardize, divide_by_std, kp, rows, weight, u_off,
+                                          M, pick_out, err_flag);
+  else
+    launch_frames_from_raw_unique<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n,
+                                         pick, frame_key, seed, N, standardize, divide_by_std, kp, rows, weight, u_off,
+                                         M, pick_out, err_flag);
+  PCAA_RETURN_LAUNCH_STATUS(who);
 }
 
 }  // namespace
@@ -491,76 +663,55 @@ void launch_frames_from_raw_unique(int C, dim3 grid, hipStream_t st, const T* po
 extern "C" int pcaa_frames_from_raw(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
                                     const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
                                     float* out, int n_out, int* pick_out, int* err_flag, void* stream) {
-  PCAA_CHECK_ARG(n >= 0 && n_out >= n && n_out >= 1 && P >= 0, "pcaa_frames_from_raw: needs 0 <= n <= n_out, n_out >= 1, P >= 0");
-  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
-                 "pcaa_frames_from_raw: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5");
-  PCAA_CHECK_ARG(out != nullptr && ((uintptr_t)out % 4) == 0, "pcaa_frames_from_raw: out is null or not 4-B aligned");
-  PCAA_CHECK_ARG(n == 0 || (offsets != nullptr && (points != nullptr || P == 0)),
-                 "pcaa_frames_from_raw: points / offsets are null");
-  PCAA_CHECK_ARG(n == 0 || pick != nullptr || frame_key != nullptr,
-                 "pcaa_frames_from_raw: without picks the frames need their keys (frame_key)");
-  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "pcaa_frames_from_raw: points are misaligned");
-  const dim3 grid((unsigned)n_out);
-  if (points_f64)
-    launch_frames_from_raw<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, n, pick,
-                                   frame_key, seed, N, standardize, divide_by_std, out, pick_out, err_flag);
-  else
-    launch_frames_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n, pick,
-                                  frame_key, seed, N, standardize, divide_by_std, out, pick_out, err_flag);
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_frames_from_raw");
+  return frames_from_raw_impl("pcaa_frames_from_raw", points, points_f64, P, offsets, n, pick, frame_key, seed, N, C,
+                              standardize, divide_by_std, RawKeep{0, 0, 0}, out, n_out, pick_out, err_flag, stream);
+}
+
+extern "C" int pcaa_frames_from_raw_thin(const void* points, int points_f64, long P, const int* offsets, int n,
+                                         const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                                         int divide_by_std, float* out, int n_out, int* pick_out, int* err_flag,
+                                         void* stream, int keep, int keep_min, int keep_rule) {
+  const char* who = "pcaa_frames_from_raw_thin";
+  if (int rc = check_keep(who, keep, keep_min, keep_rule, pick, frame_key, n)) return rc;
+  return frames_from_raw_impl(who, points, points_f64, P, offsets, n, pick, frame_key, seed, N, C, standardize,
+                              divide_by_std, RawKeep{keep, keep_min, keep_rule}, out, n_out, pick_out, err_flag, stream);
 }
 
 extern "C" int pcaa_crops_from_raw(const void* points, int points_f64, long P, const int* offsets, long F,
                                    const int* start, int B, int T, const int* pick, const int* frame_key, long seed,
                                    int N, int C, int standardize, int divide_by_std, float* out, int* err_flag,
                                    void* stream) {
-  PCAA_CHECK_ARG(B >= 1 && T >= 1 && F >= 0 && P >= 0 && (long)B * T < (1L << 31) && F < (1L << 31),
-                 "pcaa_crops_from_raw: needs B >= 1, T >= 1, B * T < 2^31, 0 <= F < 2^31, P >= 0");
-  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
-                 "pcaa_crops_from_raw: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5");
-  PCAA_CHECK_ARG(out != nullptr && ((uintptr_t)out % 4) == 0, "pcaa_crops_from_raw: out is null or not 4-B aligned");
-  PCAA_CHECK_ARG(start != nullptr && offsets != nullptr && (points != nullptr || P == 0),
-                 "pcaa_crops_from_raw: points / offsets / start are null");
-  PCAA_CHECK_ARG(F == 0 || pick != nullptr || frame_key != nullptr,
-                 "pcaa_crops_from_raw: without picks the frames need their keys (frame_key)");
-  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "pcaa_crops_from_raw: points are misaligned");
-  const dim3 grid((unsigned)((long)B * T));
-  if (points_f64)
-    launch_crops_from_raw<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, F, start,
-                                  T, pick, frame_key, seed, N, standardize, divide_by_std, out, err_flag);
-  else
-    launch_crops_from_raw<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, F, start, T,
-                                 pick, frame_key, seed, N, standardize, divide_by_std, out, err_flag);
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_crops_from_raw");
+  return crops_from_raw_impl("pcaa_crops_from_raw", points, points_f64, P, offsets, F, start, B, T, pick, frame_key, seed,
+                             N, C, standardize, divide_by_std, RawKeep{0, 0, 0}, out, err_flag, stream);
+}
+
+extern "C" int pcaa_crops_from_raw_thin(const void* points, int points_f64, long P, const int* offsets, long F,
+                                        const int* start, int B, int T, const int* pick, const int* frame_key, long seed,
+                                        int N, int C, int standardize, int divide_by_std, float* out, int* err_flag,
+                                        void* stream, int keep, int keep_min, int keep_rule) {
+  const char* who = "pcaa_crops_from_raw_thin";
+  if (int rc = check_keep(who, keep, keep_min, keep_rule, pick, frame_key, F)) return rc;
+  return crops_from_raw_impl(who, points, points_f64, P, offsets, F, start, B, T, pick, frame_key, seed, N, C,
+                             standardize, divide_by_std, RawKeep{keep, keep_min, keep_rule}, out, err_flag, stream);
 }
 
 extern "C" int pcaa_frames_from_raw_unique(const void* points, int points_f64, long P, const int* offsets, int n,
                                            const int* pick, const int* frame_key, long seed, int N, int C,
                                            int standardize, int divide_by_std, float* rows, float* weight, int* u_off,
                                            long M, int* pick_out, int* err_flag, void* stream) {
-  PCAA_CHECK_ARG(n >= 0 && M >= 1 && P >= 0 && (long)n * PCAA_RAW_MAX_POINTS < (1L << 31) && M < (1L << 31),
-                 "pcaa_frames_from_raw_unique: needs n >= 0, 1 <= M < 2^31, P >= 0, n * 1024 < 2^31");
-  PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
-                 "pcaa_frames_from_raw_unique: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5");
-  PCAA_CHECK_ARG(rows != nullptr && weight != nullptr && u_off != nullptr && ((uintptr_t)rows % 4) == 0 &&
-                     ((uintptr_t)weight % 4) == 0 && ((uintptr_t)u_off % 4) == 0,
-                 "pcaa_frames_from_raw_unique: rows / weight / u_off are null or not 4-B aligned");
-  PCAA_CHECK_ARG(n == 0 || (offsets != nullptr && (points != nullptr || P == 0)),
-                 "pcaa_frames_from_raw_unique: points / offsets are null");
-  PCAA_CHECK_ARG(n == 0 || pick != nullptr || frame_key != nullptr,
-                 "pcaa_frames_from_raw_unique: without picks the frames need their keys (frame_key)");
-  PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "pcaa_frames_from_raw_unique: points are misaligned");
-  hipLaunchKernelGGL(raw_unique_offsets_kernel, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n, P, N, u_off);
-  long tail = cdiv(M, 4096);                      // blocks that zero the rows no frame owns
-  tail = tail < 1 ? 1 : (tail > 64 ? 64 : tail);
-  const dim3 grid((unsigned)(n + tail));
-  if (points_f64)
-    launch_frames_from_raw_unique<double>(C, grid, as_stream(stream), static_cast<const double*>(points), P, offsets, n,
-                                          pick, frame_key, seed, N, standardize, divide_by_std, rows, weight, u_off, M,
-                                          pick_out, err_flag);
-  else
-    launch_frames_from_raw_unique<float>(C, grid, as_stream(stream), static_cast<const float*>(points), P, offsets, n,
-                                         pick, frame_key, seed, N, standardize, divide_by_std, rows, weight, u_off, M,
-                                         pick_out, err_flag);
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_frames_from_raw_unique");
+  return frames_from_raw_unique_impl("pcaa_frames_from_raw_unique", points, points_f64, P, offsets, n, pick, frame_key,
+                                     seed, N, C, standardize, divide_by_std, RawKeep{0, 0, 0}, rows, weight, u_off, M,
+                                     pick_out, err_flag, stream);
+}
+
+extern "C" int pcaa_frames_from_raw_unique_thin(const void* points, int points_f64, long P, const int* offsets, int n,
+                                                const int* pick, const int* frame_key, long seed, int N, int C,
+                                                int standardize, int divide_by_std, float* rows, float* weight,
+                                                int* u_off, long M, int* pick_out, int* err_flag, void* stream, int keep,
+                                                int keep_min, int keep_rule) {
+  const char* who = "pcaa_frames_from_raw_unique_thin";
+  if (int rc = check_keep(who, keep, keep_min, keep_rule, pick, frame_key, n)) return rc;
+  return frames_from_raw_unique_impl(who, points, points_f64, P, offsets, n, pick, frame_key, seed, N, C, standardize,
+                                     divide_by_std, RawKeep{keep, keep_min, keep_rule}, rows, weight, u_off, M, pick_out,
+                                     err_flag, stream);
 }

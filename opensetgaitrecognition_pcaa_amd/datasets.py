@@ -169,16 +169,78 @@ def _absorb32(s, w):
     return _mix32(((s ^ w) + np.uint64(0x9E3779B9)) & _M32)
 
 
-def device_picks_host(seed, keys, cards, N):
+def _chain_state(seed, key):
+    """the chain state of csrc/raw_frames.hip after the words seed_lo, seed_hi, key[0], key[1]"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    s0 = _absorb32(_absorb32(np.uint64(0x9E3779B9), np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
+    return _absorb32(_absorb32(s0, np.uint64(int(key[0]) & 0xFFFFFFFF)), np.uint64(int(key[1]) & 0xFFFFFFFF))
+
+
+_KEEP_WORD = np.uint64(0x6B656570)            # "keep": the tag of the thinning stage's chain
+KEEP_RULES = ("first", "random")              # PCAA_RAW_KEEP_FIRST / PCAA_RAW_KEEP_RANDOM of include/pcaa_hip.h
+
+
+def keep_arguments(keep, keep_min=None, keep_rule="first", who="keep"):
+    """The thinning parameters as every raw entry point takes them -> ``(keep, keep_min, rule index)`` ints, (0, 0, 0) for
+    no thinning.  ``keep``: 0 / None (off), an int K >= 1, or a pair ``(lo, hi)`` = (keep_min, keep): a count per frame
+    drawn in ``lo .. hi``; ``keep_min`` defaults to K; ``keep_rule`` "first" / "random" (or 0 / 1)."""
+    if isinstance(keep, (tuple, list)):
+        if len(keep) != 2 or keep_min is not None:
+            raise ValueError(f"{who}: a range is (lo, hi), without a separate keep_min; got {keep!r}, keep_min={keep_min!r}")
+        keep_min, keep = keep
+    keep = 0 if keep is None else int(keep)
+    rule = KEEP_RULES.index(keep_rule) if keep_rule in KEEP_RULES else keep_rule
+    if isinstance(rule, bool) or rule not in (0, 1):
+        raise ValueError(f"{who}: keep_rule must be 'first' or 'random', got {keep_rule!r}")
+    if keep == 0:
+        if keep_min not in (None, 0):
+            raise ValueError(f"{who}: keep_min={keep_min!r} without keep")
+        return 0, 0, 0
+    keep_min = keep if keep_min is None else int(keep_min)
+    if not 1 <= keep_min <= keep <= 1024:
+        raise ValueError(f"{who}: needs 1 <= keep_min <= keep <= 1024 (a frame's detections), got keep_min={keep_min}, keep={keep}")
+    return keep, keep_min, int(rule)
+
+
+def device_keep_host(seed, keys, cards, keep, keep_min=None, keep_rule="first"):
+    """The thinning stage of csrc/raw_frames.hip restated in numpy -> a list with one int array per frame: the raw indices
+    it keeps, in the order stage 2 numbers them (``arange(card)`` for a frame it leaves alone: k_f >= card, or keep = 0)."""
+    keep, keep_min, rule = keep_arguments(keep, keep_min, keep_rule, "device_keep_host")
+    keys = np.asarray(keys).reshape(-1, 2)
+    kept = []
+    for key, card in zip(keys, np.asarray(cards).reshape(-1).tolist()):
+        if keep == 0:
+            kept.append(np.arange(card))
+            continue
+        t = _absorb32(_chain_state(seed, key), _KEEP_WORD)
+        k = keep
+        if keep_min < keep:
+            k = keep_min + ((int(_absorb32(t, np.uint64(0xFFFFFFFF))) * (keep - keep_min + 1)) >> 32)
+        if k >= card:
+            kept.append(np.arange(card))
+        elif rule == 0:
+            kept.append(np.arange(k))
+        else:
+            h = _absorb32(t, np.arange(card, dtype=np.uint64))
+            kept.append(np.lexsort((np.arange(card), h))[:k])      # the k smallest (h, i), in rank order
+    return kept
+
+
+def device_picks_host(seed, keys, cards, N, keep=0, keep_min=None, keep_rule="first"):
     """What ``pcaa_frames_from_raw`` draws when it is given no picks, restated in numpy, integer for integer -> int32
-    ``[n, N]``.  ``keys`` int ``[n, 2]``, ``cards`` ``[n]`` (1 <= card), ``seed`` any Python int (its low 64 bits)."""
+    ``[n, N]``.  ``keys`` int ``[n, 2]``, ``cards`` ``[n]`` (1 <= card), ``seed`` any Python int (its low 64 bits).
+    ``keep`` / ``keep_min`` / ``keep_rule`` (``keep_arguments``): the draws of the ``_thin`` entry points -- the same draw
+    over the ``min(card, k_f)`` detections ``device_keep_host`` keeps, mapped through its lists to raw indices."""
     keys = np.asarray(keys).reshape(-1, 2)
     cards = np.asarray(cards).reshape(-1)
-    N, seed = int(N), int(seed) & 0xFFFFFFFFFFFFFFFF
+    N = int(N)
+    kept = None
+    if keep_arguments(keep, keep_min, keep_rule, "device_picks_host")[0]:
+        kept = device_keep_host(seed, keys, cards, keep, keep_min, keep_rule)
+        cards = np.array([len(k) for k in kept], dtype=np.int64)
     picks = np.empty((cards.size, N), dtype=np.int32)
-    s0 = _absorb32(_absorb32(np.uint64(0x9E3779B9), np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
     for fi, card in enumerate(cards.tolist()):
-        s = _absorb32(_absorb32(s0, np.uint64(int(keys[fi, 0]) & 0xFFFFFFFF)), np.uint64(int(keys[fi, 1]) & 0xFFFFFFFF))
+        s = _chain_state(seed, keys[fi])
         if card < N:
             h = _absorb32(s, np.arange(card, N, dtype=np.uint64))
             picks[fi, :card] = np.arange(card)
@@ -186,6 +248,8 @@ def device_picks_host(seed, keys, cards, N):
         else:
             h = _absorb32(s, np.arange(card, dtype=np.uint64))
             picks[fi] = np.lexsort((np.arange(card), h))[:N]         # rank by (h, i): the N smallest, in key order
+        if kept is not None:
+            picks[fi] = kept[fi][picks[fi]]
     return picks
 
 
@@ -424,7 +488,8 @@ class RawCrops:
         length = store.track_first[self.track + 1] - store.track_first[self.track] if items else np.zeros(0, np.int64)
         count = np.array([track_windows(int(n), self.T, self.hop)[0] for n in length], dtype=np.int64)
         self.slack = length - self.T - self.hop * (count - 1)             # per crop: its track's
-        self.batcher_options = {}         # seed / redraw / jitter / picks of the RawTrackBatcher that batcher_for builds
+        # seed / redraw / jitter / picks / keep_points / keep_rule of the RawTrackBatcher that batcher_for builds
+        self.batcher_options = {}
 
     def __len__(self):
         return len(self.filenames)
@@ -437,9 +502,10 @@ class RawCrops:
             start = start + jitter_phases(seed, epoch, self.store.serial[self.track], np.minimum(self.hop, self.slack))
         return start.astype(np.int32)
 
-    def materialize(self, seed=0, picks=None, epoch=0, jitter=False):
+    def materialize(self, seed=0, picks=None, epoch=0, jitter=False, keep_points=0, keep_rule="first"):
         """All crops written out by the batch kernel, one launch -> ``(pcs [M, C, T, N] view of point-major storage,
-        labels int64 [M])`` on the store's device: what the evaluation procedures take."""
+        labels int64 [M])`` on the store's device: what the evaluation procedures take.  ``keep_points`` (k or ``(lo,
+        hi)``) / ``keep_rule``: every frame thinned to at most that many detections first (``keep_arguments``)."""
         from . import ops
         st = self.store
         if st.device is None:
@@ -449,7 +515,7 @@ class RawCrops:
         err = torch.zeros(1, dtype=torch.int32, device=st.device)
         start = torch.from_numpy(self.starts(seed, epoch, jitter)).to(st.device)
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, self.T, self.N, self.C, pick=picks, seed=seed,
-                                frame_key=st.frame_key_dev, err_flag=err)
+                                frame_key=st.frame_key_dev, err_flag=err, keep=keep_points, keep_rule=keep_rule)
         if int(err.item()):
             raise ValueError("RawCrops.materialize: a frame of the store cannot be processed (no detections, more than "
                              f"{ops.RAW_MAX_CARD}, or a pick outside its frame)")

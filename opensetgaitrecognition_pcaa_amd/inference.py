@@ -104,10 +104,13 @@ def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
     return first_t + within, win_row
 
 
-def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None):
-    """raw frames (``b``: frames a .. b - 1 of them) -> their distinct points and multiplicities -> (their [n, 1024] frame
-    features, the PointNet layer records, rows of the compact table): the ``dedup_points`` route of the raw entries"""
-    rows, weight, u_off = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a, b, dedup_points=True)
+def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None, keep=0,
+                     keep_rule="first"):
+    """raw frames (``b``: frames a .. b - 1 of them; ``keep``: thinned first) -> their distinct points and multiplicities
+    -> (their [n, 1024] frame features, the PointNet layer records, rows of the compact table): the ``dedup_points``
+    route of the raw entries"""
+    rows, weight, u_off = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a, b, dedup_points=True,
+                                                 keep=keep, keep_rule=keep_rule)
     feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, u_off.numel() - 1, N, mode, consts=consts)
     return feats, saves, rows.shape[0]
 
@@ -265,7 +268,7 @@ class OpenSetScorer:
     @torch.no_grad()
     def embed_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None, seed: int = 0,
                         track_key: int = 0, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True,
-                        dedup_points: bool = False):
+                        dedup_points: bool = False, keep_points=0, keep_rule: str = "first"):
         """``embed_track`` from the radar's detections: ``points`` [P,5] fp32 / fp64 and ``offsets`` int32 [F + 1] on the
         device (``datasets.pack_raw_frames``) -> one ``ops.frames_from_raw`` launch for the whole track (centred, not
         divided by std, as ``generate_splits`` prepares the crops) -> exactly ``embed_track`` on those frames.  ``pick``
@@ -274,19 +277,24 @@ class OpenSetScorer:
         ``dedup_points``: the padded frames are never written; every frame's DISTINCT picked detections go through the
         PointNet block once and are pooled with their multiplicities (``ops.frames_from_raw_unique``,
         ``functional.encoder_frame_features_ragged``): the same features up to fp32 summation order, from
-        ``sum(min(card, N))`` rows instead of ``F * N``.  ``last_rows_encoded`` is the number of table rows it ran."""
+        ``sum(min(card, N))`` rows instead of ``F * N``.  ``last_rows_encoded`` is the number of table rows it ran.
+        ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" / "random"): the track as
+        a sparser radar would deliver it -- every frame keeps at most that many detections before it is padded to N
+        (``ops.frames_from_raw(keep=...)``; device-drawn picks only).  With ``dedup_points`` the table then holds at most
+        ``F * min(k, N)`` rows (in whole GEMM tiles)."""
         enc = self.encoder
         N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
         F = frame_table.check_raw(points, offsets, pick, N, "embed_raw_track")
         keys = frame_table.frame_keys(track_key, 0, F, points.device) if pick is None and F else None
         if not dedup_points:
-            frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err)
+            frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err, keep=keep_points,
+                                            keep_rule=keep_rule)
             return self.embed_track(frames, hop, drop_last_aligned)
         step = max(self.batch_size * constants.NSTEPS, 1)
 
         def features(U):
             return self._chunk_features(((a, min(a + step, U)) for a in range(0, U, step)), lambda a, b: _ragged_features(
-                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b))
+                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, keep=keep_points, keep_rule=keep_rule))
         return self._score_track(F, hop, drop_last_aligned, True, points.device, features)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
@@ -404,15 +412,24 @@ def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pc
     Returns (open-set predictions, open-set labels, threshold).  ``dedup_frames``: frames that
     consecutive crops share are encoded once; ``dedup_points``: the points that padding repeated
     inside a frame are encoded once (both: ``OpenSetScorer.embed``)."""
-    rng = np.random.default_rng(seed)
     scorer = OpenSetScorer(encoder, discriminator_means, batch_size)
+    k_preds, _, k_lik = scorer.embed(known_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
+    u_preds, _, u_lik = scorer.embed(unseen_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
+    return _sequential_votes(k, scorer, (k_preds, k_lik), known_labels, (u_preds, u_lik), unseen_labels, seed,
+                             unseen_valid_ratio)
+
+
+def _sequential_votes(k, scorer, known, known_labels, unseen, unseen_labels, seed=0, unseen_valid_ratio=0.2):
+    """steps (1) and (2) of the procedure on crops that are embedded already: ``known`` / ``unseen`` = (preds,
+    likelihood) of the sequential TEST / UNSEEN crops -> (open-set predictions, open-set labels, threshold).  The
+    threshold is refit from these likelihoods; one embedding serves every k (``point_sweep``)."""
+    rng = np.random.default_rng(seed)
+    (k_preds, k_lik), (u_preds, u_lik) = known, unseen
     n_labels = int(len(np.unique(known_labels.cpu().numpy())))
     u_lab = unseen_labels.cpu().numpy()
     subjects = np.unique(u_lab)
     val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
     val_mask = np.isin(u_lab, val_subjects)
-    k_preds, _, k_lik = scorer.embed(known_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
-    u_preds, _, u_lik = scorer.embed(unseen_pcs, dedup_frames=dedup_frames, dedup_points=dedup_points)
     vm = torch.from_numpy(val_mask).to(u_lik.device)
     thr = scorer.fit_threshold(k_lik, u_lik[vm])
     preds, labels = [], []
@@ -448,14 +465,46 @@ def _sequential_split_on_device(split, scenarios_list, device):
     return crops.permute(0, 3, 1, 2), labels
 
 
-def _sequential_split_from_store(store, split, scenarios_list, N):
+def _sequential_split_from_store(store, split, scenarios_list, N, keep_points=0, keep_rule="first"):
     """The same tensors from a ``datasets.RawTrackStore`` (already assigned and on the device): the split's crops in
-    sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of seed 0; no files."""
-    return store.crops(split, N=N, C=constants.NFEATURES, order="sequential", scenarios=scenarios_list).materialize(seed=0)
+    sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of seed 0; no files.
+    ``keep_points``: every frame thinned to at most that many detections by the same launch."""
+    return store.crops(split, N=N, C=constants.NFEATURES, order="sequential", scenarios=scenarios_list).materialize(
+        seed=0, keep_points=keep_points, keep_rule=keep_rule)
+
+
+def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_points=True, keep_rule="first"):
+    """The paper's robustness curve -- open-set accuracy against the detections a frame keeps -- from one resident store:
+    ``store`` a ``datasets.RawTrackStore`` with its splits assigned, on the device -> ``{keep: {k: metrics}}``, ``metrics``
+    the record ``CGAAE_inference`` writes as ``naive_seq_log_{k}_subsampled{keep}.json`` (accuracy, F1 micro / macro /
+    weighted of the votes over k windows).  Per ``keep`` (k points, ``(lo, hi)``, or 0 for the frames as they are) the
+    sequential TEST / UNSEEN crops are built thinned on the device (seed 0) and embedded ONCE -- every frame that
+    consecutive crops share once, and with ``dedup_points`` (default) its distinct points only, so a sweep point costs
+    PointNet rows proportional to ``min(keep, N)`` -- then the threshold is refit and the votes are taken for every k of
+    ``ks``.  Writes no file."""
+    from .constants import SPLIT
+    if store.device is None:
+        raise RuntimeError("point_sweep: call store.to_device() first; there is no CPU path")
+    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
+    scorer = OpenSetScorer(encoder, means)
+    out = {}
+    for keep in keeps:
+        sets = []
+        for split in (SPLIT.TEST, SPLIT.UNSEEN):
+            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, keep, keep_rule)
+            preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
+            sets += [(preds, lik), labels]
+            del pcs
+        out[keep] = {}
+        for k in ks:
+            preds, labels, _ = _sequential_votes(k, scorer, *sets)
+            out[keep][k] = _metrics(k, preds, labels.astype(int))
+    return out
 
 
 def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None, variation=False,
-                    generate_dataset=True, device=None, dedup_frames=False, dedup_points=False, raw_store=None):
+                    generate_dataset=True, device=None, dedup_frames=False, dedup_points=False, raw_store=None,
+                    keep_points=0, keep_rule="first"):
     """Open-set evaluation driver with the reference's call surface and output files
     (inference_PCAA.py:382-469): for every model and k, the naive sequential procedure on the sequentially
     ordered test / unseen splits; writes ``naive_seq_log_{k}*.json`` (accuracy, F1 micro / macro / weighted),
@@ -467,13 +516,30 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
     ``force_pc_subsampling``, which pads from fewer points).  ``raw_store`` (a ``datasets.RawTrackStore`` of the raw
     tracks): nothing is generated or read from crop files -- per model the store's tracks are assigned as
     ``generate_splits(TRAIN_CLASSES, seed=0)`` assigns them and the sequential TEST / UNSEEN crops are built on the device
-    at the model's NMAX (device draws of seed 0; ``force_pc_subsampling`` is a property of generated files and is refused)."""
+    at the model's NMAX (device draws of seed 0; ``force_pc_subsampling`` is a property of generated files and is refused).
+    ``keep_points=k`` (with ``raw_store``; ``keep_rule`` "first" / "random") is the sweep over detections per frame
+    without crop files: the crops are built thinned to at most k detections a frame on the device, the threshold is refit
+    as the reference's rerun refits it, and the files carry the reference's ``_subsampled{k}`` names.  ``point_sweep``
+    returns the whole curve and writes nothing."""
     import json
     from .constants import SPLIT
     scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    suffix = _file_suffix(force_pc_subsampling, scenarios_list)
+    if keep_points:
+        if raw_store is None:
+            raise ValueError("CGAAE_inference: keep_points thins raw detections on the device and needs raw_store; crop "
+                             "files are thinned when they are generated (force_pc_subsampling)")
+        if isinstance(keep_points, (tuple, list)) or isinstance(keep_points, bool) or int(keep_points) != keep_points:
+            raise ValueError("CGAAE_inference: keep_points is one count k (the files are named _subsampled{k}); "
+                             "point_sweep takes ranges")
+        if force_pc_subsampling:
+            raise ValueError("CGAAE_inference: keep_points and force_pc_subsampling are the same sweep on two routes; give one")
+        keep_points = int(keep_points)
+        from .datasets import keep_arguments
+        keep_arguments(keep_points, None, keep_rule, "CGAAE_inference")
+    subsampled = keep_points or force_pc_subsampling
+    suffix = _file_suffix(subsampled, scenarios_list)
     if suffix is None:
-        raise ValueError("force_pc_subsampling and scenarios_list cannot be both different from default")
+        raise ValueError("force_pc_subsampling / keep_points and scenarios_list cannot be both different from default")
     if raw_store is not None and force_pc_subsampling:
         raise ValueError("CGAAE_inference: force_pc_subsampling needs generated crop files; it cannot be combined with raw_store")
     dev = torch.device(device or constants.DEVICE)
@@ -490,8 +556,10 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
             with open(os.path.join(folder, "config.pkl"), "rb") as f:
                 config = pickle.load(f)
             raw_store.assign_like_generate_splits(config["TRAIN_CLASSES"], seed=0).to_device(dev)
-            known_pcs, known_labels = _sequential_split_from_store(raw_store, SPLIT.TEST, scenarios_list, config["NMAX"])
-            unseen_pcs, unseen_labels = _sequential_split_from_store(raw_store, SPLIT.UNSEEN, scenarios_list, config["NMAX"])
+            known_pcs, known_labels = _sequential_split_from_store(raw_store, SPLIT.TEST, scenarios_list, config["NMAX"],
+                                                                   keep_points, keep_rule)
+            unseen_pcs, unseen_labels = _sequential_split_from_store(raw_store, SPLIT.UNSEEN, scenarios_list, config["NMAX"],
+                                                                     keep_points, keep_rule)
         else:
             known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
             unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
@@ -506,7 +574,7 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
             np.save(os.path.join(folder, f"final_preds_{k}{suffix}.npy"), preds)
             np.save(os.path.join(folder, f"final_labels_{k}{suffix}.npy"), labels)
             out_log[k] = {m: metrics[m] for m in ("f1_micro", "f1_macro", "f1_weighted")}
-        with open(os.path.join(folder, f"naive_seq_log_subsampled{force_pc_subsampling}.json"), "w") as f:
+        with open(os.path.join(folder, f"naive_seq_log_subsampled{subsampled}.json"), "w") as f:
             json.dump(out_log, f)
     return out_log
 
@@ -533,6 +601,14 @@ class _LiveScorer:
         self._width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]      # frame-feature width: a ring row
         self._N, self._C = encoder.nmax_points, encoder.pc_block.pointnet1.module[0].weight.shape[1]   # a raw frame becomes [N, C]
         self.last_pointnet_saves = None
+        self.keep_points, self.keep_rule = 0, "first"
+
+    def _set_keep(self, keep_points, keep_rule):
+        """``push_raw`` scores the stream as a sparser radar would deliver it: every frame keeps at most ``keep_points``
+        (k, or ``(lo, hi)``) detections under ``keep_rule`` before it is padded to N (``datasets.keep_arguments``)"""
+        from .datasets import keep_arguments
+        keep_arguments(keep_points, None, keep_rule, type(self).__name__)        # refused here, not at the first push
+        self.keep_points, self.keep_rule = keep_points, keep_rule
 
     def _check_eval(self):
         if self.encoder.training:
@@ -558,11 +634,12 @@ class StreamingScorer(_LiveScorer):
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0,
-                 dedup_points: bool = False):
+                 dedup_points: bool = False, keep_points=0, keep_rule: str = "first"):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         dev = self.means.device
         self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
         self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
+        self._set_keep(keep_points, keep_rule)           # push_raw: every frame thinned first
         self.seed, self.serial = int(seed), -1           # push_raw: frame f of the track is drawn under (serial, f)
         self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a raw frame that could not be processed
         # window j starts at ring row (j * hop) % ring_rows, a sequence of period ring_rows / gcd: kept on the device
@@ -608,20 +685,22 @@ class StreamingScorer(_LiveScorer):
         int32 [n, N]: host-drawn picks; None: drawn on the device, frame f of the track under the key ``(serial, f)`` and
         the constructor's ``seed``.  ``raw_err`` is set by a frame that could not be processed (its frame is zeros).
         With the constructor's ``dedup_points`` the padded frames are never written: ``ops.frames_from_raw_unique`` and
-        ``functional.encoder_frame_features_ragged`` give the same frame features from the frames' distinct points."""
+        ``functional.encoder_frame_features_ragged`` give the same frame features from the frames' distinct points.
+        The constructor's ``keep_points`` / ``keep_rule`` thin every frame first (device-drawn picks only)."""
         self._check_eval()
         n = frame_table.check_raw(points, offsets, pick, self._N, "StreamingScorer.push_raw")
         q = F_hip.frame_pad_quantum(self._N)
         keys = frame_table.frame_keys(self.serial, self.n_frames, n, points.device) if pick is None and n else None
         raw = (points, offsets, self._N, self._C, pick, self.seed, keys, self.raw_err)
+        keep = dict(keep=self.keep_points, keep_rule=self.keep_rule)
         out = []
         for a in range(0, n, self.max_push):
             b = min(a + self.max_push, n)
             if self.dedup_points:
-                feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, a, b)
+                feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, a, b, **keep)
                 out.append(self._push_features(feats, b - a))
             else:
-                out.append(self._push_padded(frame_table.raw_frames(*raw, a, b, n_out=b - a + (a - b) % q), b - a))
+                out.append(self._push_padded(frame_table.raw_frames(*raw, a, b, n_out=b - a + (a - b) % q, **keep), b - a))
         return self._gather(out)
 
     def _push(self, frames):
@@ -817,10 +896,12 @@ class MultiStreamScorer(_LiveScorer):
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
-                 batch_size: int = 1024, seed: int = 0, dedup_points: bool = False):
+                 batch_size: int = 1024, seed: int = 0, dedup_points: bool = False, keep_points=0,
+                 keep_rule: str = "first"):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         self.max_streams, self.batch_size = int(max_streams), int(batch_size)
         self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
+        self._set_keep(keep_points, keep_rule)           # push_raw: every frame thinned first
         if self.max_streams < 1 or self.batch_size < 1:
             raise ValueError("MultiStreamScorer: needs max_streams >= 1, batch_size >= 1")
         dev = self.means.device
@@ -900,7 +981,9 @@ class MultiStreamScorer(_LiveScorer):
         ``raw_err`` is set by a frame that could not be processed (it is encoded as zeros).
         With the constructor's ``dedup_points`` the padded frames are never written: the tick's distinct points go through
         the PointNet block once (``ops.frames_from_raw_unique``, ``functional.encoder_frame_features_ragged``: three
-        launches in place of one, still none per stream) and give the same frame features up to fp32 summation order."""
+        launches in place of one, still none per stream) and give the same frame features up to fp32 summation order.
+        The constructor's ``keep_points`` / ``keep_rule`` thin every frame first (device-drawn picks only): the same
+        launches, fewer table rows."""
         self._check_eval()
         n = frame_table.check_raw(points, offsets, pick, self._N, "MultiStreamScorer.push_raw")
         sids, plan, part, mode = self._begin_tick(sids, counts, n, self._N, "push_raw", pick is None,
@@ -909,10 +992,11 @@ class MultiStreamScorer(_LiveScorer):
             return self._empty(plan, self.ring.device)
         raw = (points, offsets, self._N, self._C, pick, self.seed, part["frame_key"].view(n, 2) if pick is None else None,
                self.raw_err)
+        keep = dict(keep=self.keep_points, keep_rule=self.keep_rule)
         if self.dedup_points:
-            feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, mode=mode, consts=self._consts)
+            feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, mode=mode, consts=self._consts, **keep)
             return self._finish_tick_features(sids, plan, part, mode, feats)
-        return self._finish_tick(sids, plan, part, mode, frame_table.raw_frames(*raw, n_out=plan.dst_row.size))
+        return self._finish_tick(sids, plan, part, mode, frame_table.raw_frames(*raw, n_out=plan.dst_row.size, **keep))
 
     def _begin_tick(self, sids, counts, n, N, what, want_keys, pad_to=None):
         """the arguments of a tick checked, its plan made and (unless the tick is empty) uploaded -> (sids, plan, the

@@ -1651,8 +1651,19 @@ RAW_MAX_CARD = 1024       # PCAA_RAW_MAX_CARD / PCAA_RAW_MAX_POINTS of include/p
 RAW_MAX_POINTS = 1024
 
 
+def _keep_args(who, keep, keep_min, keep_rule, pick):
+    """the thinning arguments of a raw entry point (``datasets.keep_arguments``: k, ``(lo, hi)`` or 0) -> the three ints
+    the ``_thin`` entry points take, (0, 0, 0) for the plain ones; supplied picks decide by themselves"""
+    from .datasets import keep_arguments
+    args = keep_arguments(keep, keep_min, keep_rule, who)
+    if args[0] and pick is not None:
+        raise ValueError(f"{who}: keep thins the frames before the device draws their picks; supplied picks decide by "
+                         "themselves (datasets.draw_picks(force_pc_subsampling=k) for the reference's)")
+    return args
+
+
 def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True, divide_by_std=False,
-                    n_out=None, pick_out=None, err_flag=None):
+                    n_out=None, pick_out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first"):
     """Raw radar detections -> processed frames in one launch (pcaa_frames_from_raw): ``points`` [P, 5] fp32 or fp64 (x,
     y, z, doppler, linear power), ``offsets`` int32 [n + 1] (frame f owns rows ``offsets[f] .. offsets[f + 1] - 1``) ->
     fp32 ``[n_out, N, C]``, rows ``n .. n_out - 1`` zero (``n_out`` defaults to n).  ``pick`` int32 [n, N]: output point p
@@ -1660,7 +1671,11 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     kernel draws them from ``frame_key`` int32 [n, 2] and ``seed`` (``datasets.device_picks_host`` restates the draw).
     ``pick_out`` int32 [n, N]: receives the picks used.  A frame that cannot be processed (cardinality < 1 or >
     RAW_MAX_CARD, offsets outside the points, a pick outside the frame) comes back as zeros and sets ``err_flag`` (int32
-    [1]); nothing is checked on the host."""
+    [1]); nothing is checked on the host.  ``keep`` (k, or ``(lo, hi)`` for a count drawn per frame; ``keep_min`` = lo)
+    and ``keep_rule`` ("first" / "random"): the frame keeps at most that many of its detections before the draw
+    (pcaa_frames_from_raw_thin; device-drawn picks only; ``pick_out`` holds raw indices); a frame with no more
+    detections than its count has the bits it has without ``keep``."""
+    keep, keep_min, keep_rule = _keep_args("frames_from_raw", keep, keep_min, keep_rule, pick)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("frames_from_raw.points: expected a float32 or float64 tensor")
     _chk(points, "frames_from_raw.points", None, 2)
@@ -1691,22 +1706,27 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
         _chk(err_flag, "frames_from_raw.err_flag", torch.int32)
     out = torch.empty((n_out, N, C), dtype=torch.float32, device=points.device)
     if n_out:
-        check(_lib.load().pcaa_frames_from_raw(
-            _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-            _p(out), n_out, _p(pick_out), _p(err_flag), _s()), "pcaa_frames_from_raw")
+        args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
+                None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+                _p(out), n_out, _p(pick_out), _p(err_flag), _s())
+        if keep:
+            check(_lib.load().pcaa_frames_from_raw_thin(*args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_thin")
+        else:
+            check(_lib.load().pcaa_frames_from_raw(*args), "pcaa_frames_from_raw")
     return out
 
 
 def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
-                   divide_by_std=False, out=None, err_flag=None):
+                   divide_by_std=False, out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first"):
     """A batch of crops straight from the packed detections of a whole store, one launch (pcaa_crops_from_raw):
     ``points`` [P, 5] fp32 or fp64 and ``offsets`` int32 [F + 1] over ALL F frames of the store, ``start`` int32 [B] the
     store index of each crop's first frame -> fp32 ``[B, T, N, C]``, ``out[b, t]`` bit-equal to the frame
     ``frames_from_raw`` writes for store frame ``start[b] + t`` under the same ``pick`` row (int32 [F, N]) or, without
     picks, ``frame_key`` row (int32 [F, 2]) and ``seed``.  Crops may overlap and repeat.  A frame that cannot be processed
     (the rule of ``frames_from_raw``) and a crop that leaves the store (``start[b] < 0`` or ``start[b] + T > F``) come back
-    as zeros and set ``err_flag`` (int32 [1]); nothing is checked on the host.  ``out``: a [B, T, N, C] buffer to fill."""
+    as zeros and set ``err_flag`` (int32 [1]); nothing is checked on the host.  ``out``: a [B, T, N, C] buffer to fill.
+    ``keep`` / ``keep_min`` / ``keep_rule``: as in ``frames_from_raw`` (pcaa_crops_from_raw_thin), the same frames."""
+    keep, keep_min, keep_rule = _keep_args("crops_from_raw", keep, keep_min, keep_rule, pick)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("crops_from_raw.points: expected a float32 or float64 tensor")
     _chk(points, "crops_from_raw.points", None, 2)
@@ -1738,30 +1758,40 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
         if tuple(out.shape) != (B, T, N, C):
             raise ValueError(f"crops_from_raw: out must be [{B}, {T}, {N}, {C}], got {tuple(out.shape)}")
     if B:
-        _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw(
-            _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), F, _p(start), B, T, _p(pick),
-            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-            _p(out), _p(err_flag), _s()), "pcaa_crops_from_raw"), 0.0, B * T * N * C * 4)
+        args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), F, _p(start), B, T, _p(pick),
+                None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+                _p(out), _p(err_flag), _s())
+        if keep:
+            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw_thin(
+                *args, keep, keep_min, keep_rule), "pcaa_crops_from_raw_thin"), 0.0, B * T * N * C * 4)
+        else:
+            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw(*args), "pcaa_crops_from_raw"),
+                   0.0, B * T * N * C * 4)
     return out
 
 
 UNIQUE_ROW_QUANTUM = 256  # rows of the compact table: whole 256-row GEMM tiles (pcaa_gemm_affine_elu, pcaa_gemm_split3)
 
 
-def unique_table_rows(P, n, N):
+def unique_table_rows(P, n, N, keep=0):
     """M of ``frames_from_raw_unique``: frame f owns min(card_f, N) rows, a bad frame one, so for ascending offsets the
-    frames own at most min(P + n, n N) rows; rounded up to whole GEMM tiles (at least one)."""
-    return unique_chunk_rows(min(int(P) + int(n), int(n) * int(N)))
+    frames own at most min(P + n, n N) rows; thinned to at most ``keep`` detections (0: not), min(P + n, n min(N, keep));
+    rounded up to whole GEMM tiles (at least one)."""
+    return unique_chunk_rows(min(int(P) + int(n), int(n) * min(int(N), int(keep) or int(N))))
 
 
 def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
-                           divide_by_std=False, M=None, pick_out=None, err_flag=None):
+                           divide_by_std=False, M=None, pick_out=None, err_flag=None, keep=0, keep_min=None,
+                           keep_rule="first"):
     """``frames_from_raw`` without the padding (pcaa_frames_from_raw_unique; arguments as there) -> ``(rows [M, C] fp32,
     weight [M] fp32, u_off [n + 1] int32)``: rows ``u_off[f] .. u_off[f + 1] - 1`` hold frame f's distinct picked
     detections in order of first occurrence, each bit-equal to the row ``frames_from_raw`` writes for that pick, ``weight``
     how often it was picked.  Unused rows of a frame's ``min(card, N)`` and the rows from ``u_off[n]`` on are zero with
     weight 0; a bad frame is one zero row of weight N and sets ``err_flag``.  ``M`` defaults to ``unique_table_rows``.
-    Two launches (the scan of ``u_off``, the rows); nothing comes back to the host."""
+    Two launches (the scan of ``u_off``, the rows); nothing comes back to the host.  ``keep`` / ``keep_min`` /
+    ``keep_rule``: as in ``frames_from_raw`` (pcaa_frames_from_raw_unique_thin); frame f then owns ``min(card, k_f, N)``
+    rows and ``M`` defaults to ``unique_table_rows(P, n, N, keep)``."""
+    keep, keep_min, keep_rule = _keep_args("frames_from_raw_unique", keep, keep_min, keep_rule, pick)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("frames_from_raw_unique.points: expected a float32 or float64 tensor")
     _chk(points, "frames_from_raw_unique.points", None, 2)
@@ -1771,7 +1801,7 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
     if points.shape[1] != 5 or n < 0 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
         raise ValueError(f"frames_from_raw_unique: needs points [P, 5], offsets [n + 1], 1 <= N <= {RAW_MAX_POINTS}, "
                          f"1 <= C <= 5; got points {tuple(points.shape)}, n={n}, N={N}, C={C}")
-    M = unique_table_rows(points.shape[0], n, N) if M is None else int(M)
+    M = unique_table_rows(points.shape[0], n, N, keep) if M is None else int(M)
     if not 1 <= M < 2 ** 31 or n * RAW_MAX_POINTS >= 2 ** 31:
         raise ValueError(f"frames_from_raw_unique: needs 1 <= M < 2^31 and n * {RAW_MAX_POINTS} < 2^31, got M={M}, n={n}")
     if not -2 ** 63 <= seed < 2 ** 63:
@@ -1796,11 +1826,16 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
     rows = torch.empty((M, C), dtype=torch.float32, device=dev)
     weight = torch.empty(M, dtype=torch.float32, device=dev)
     u_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique(
-        _p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-        None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-        _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s()), "pcaa_frames_from_raw_unique"),
-        0.0, points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4)
+    args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
+            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
+            _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s())
+    nbytes = points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4
+    if keep:
+        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique_thin(
+            *args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_unique_thin"), 0.0, nbytes)
+    else:
+        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique(*args),
+                                                              "pcaa_frames_from_raw_unique"), 0.0, nbytes)
     return rows, weight, u_off
 
 
