@@ -765,6 +765,53 @@ int pcaa_frames_from_raw_unique_thin(const void* points, int points_f64, long P,
                                      const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
                                      int divide_by_std, float* rows, float* weight, int* u_off, long M, int* pick_out,
                                      int* err_flag, void* stream, int keep, int keep_min, int keep_rule);
+/* ABI 29, added after them in the same way (the version is unchanged: a library without these entry points fails to load
+ * by name): the same three with an AUGMENTATION stage between the gather and the statistics -- the picked detections are
+ * moved in fp64, after the power column has become dB and BEFORE the frame is centred, then mean, std, the one rounding
+ * and the stores follow unchanged.  Arguments as the _thin neighbour, then aug: PCAA_RAW_AUG_PARAMS doubles on the HOST
+ * (read by the launcher, handed to the kernel by value), indexed by the macros below.
+ *   per TRACK (every frame of a track shares them: overlapping windows agree, the dynamics between frames survive):
+ *     u = absorb(absorb(absorb(absorb(0x9e3779b9, seed_lo), seed_hi), key[0]), 0x6175676d "augm"); key[1] is not absorbed;
+ *     w_j = absorb(u, j), r_j = (w_j + 0.5) 2^-32 in fp64, j = 0 .. 3;
+ *     theta = yaw (2 r_0 - 1);  m = w_1 >> 31 (used when mirror != 0);  a = scale_lo + (scale_hi - scale_lo) r_2;
+ *     v = speed_lo + (speed_hi - speed_lo) r_3;
+ *   per DETECTION, keyed by its RAW index i in its frame (not by the padded row: every copy of a detection carries the
+ *   same noise, so padded duplicates stay bit-equal rows and the compact-row route stays exact):
+ *     n = absorb(s, 0x6e6f6973 "nois"), s the frame's chain state after seed_lo, seed_hi, key[0], key[1]; q = absorb(n, i);
+ *     r1 = (absorb(q, 2c) + 0.5) 2^-32, r2 = (absorb(q, 2c + 1) + 0.5) 2^-32;  g(i, c) = sqrt(-2 ln r1) cos(2 pi r2);
+ *   per picked point, in this order, fp64, no contraction:
+ *     1. val[c] += sigma[c] g(i, c) for c < C with sigma[c] != 0 (metres, m/s, dB for the power column);
+ *     2. x, y, z *= a; doppler *= v;   3. x = -x when m;   4. (x, y) <- (x cos theta - y sin theta, x sin theta + y cos theta).
+ *   A step whose parameters are neutral (sigma[c] == 0, lo == hi == 1, mirror == 0, yaw == 0) is skipped.  Rotation about
+ *   the radar's vertical axis and the mirror across boresight leave range and radial velocity alone: after centring they
+ *   are what a person at another azimuth delivers, which is why they act before centring and never touch the Doppler.
+ * datasets.frames_from_picks(..., augment, seed, keys) restates the stage in numpy.  keep == 0 is allowed here and means
+ * no thinning (keep_min, keep_rule are then ignored); pick may be supplied, then keep must be 0; frame_key must be non-NULL
+ * when there are frames (with supplied picks too).  Argument errors, refused before any launch: aug NULL, yaw outside
+ * [0, pi] or not finite, yaw != 0 with C < 2, scale_lo <= 0, speed_lo <= 0, lo > hi, a range or sigma that is not finite,
+ * a negative sigma.  A frame has the same bits in all three; the bad-frame rule, the zero padding rows, the launches per
+ * call and u_off are those of the neighbours: u_off does not depend on aug.  The kernels of the entry points above are the
+ * instantiations they were before these existed. */
+#define PCAA_RAW_AUG_PARAMS 11
+#define PCAA_RAW_AUG_YAW 0      /* radians, 0 .. pi: theta uniform in (-yaw, yaw) */
+#define PCAA_RAW_AUG_MIRROR 1   /* != 0: x -> -x for the tracks whose bit m is set */
+#define PCAA_RAW_AUG_SCALE_LO 2 /* x, y, z times a factor uniform in [lo, hi] */
+#define PCAA_RAW_AUG_SCALE_HI 3
+#define PCAA_RAW_AUG_SPEED_LO 4 /* doppler times a factor uniform in [lo, hi] */
+#define PCAA_RAW_AUG_SPEED_HI 5
+#define PCAA_RAW_AUG_SIGMA 6    /* sigma[5]: x, y, z, doppler, power (dB) */
+int pcaa_frames_from_raw_aug(const void* points, int points_f64, long P, const int* offsets, int n, const int* pick,
+                             const int* frame_key, long seed, int N, int C, int standardize, int divide_by_std,
+                             float* out, int n_out, int* pick_out, int* err_flag, void* stream, int keep, int keep_min,
+                             int keep_rule, const double* aug);
+int pcaa_crops_from_raw_aug(const void* points, int points_f64, long P, const int* offsets, long F, const int* start,
+                            int B, int T, const int* pick, const int* frame_key, long seed, int N, int C,
+                            int standardize, int divide_by_std, float* out, int* err_flag, void* stream, int keep,
+                            int keep_min, int keep_rule, const double* aug);
+int pcaa_frames_from_raw_unique_aug(const void* points, int points_f64, long P, const int* offsets, int n,
+                                    const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                                    int divide_by_std, float* rows, float* weight, int* u_off, long M, int* pick_out,
+                                    int* err_flag, void* stream, int keep, int keep_min, int keep_rule, const double* aug);
 /* ABI 25 (segment_pool.hip): out[f, c] = (1 / N) sum_{r = u_off[f]}^{u_off[f + 1] - 1} weight[r] * v(a[r * lda + c]) for
  * n frames, a [M, ch] fp32 or bf16 (dtype) with leading dimension lda, out [n, ch] fp32.  v = identity; with scale / shift
  * [ch] (both or neither) a is a pre-BatchNorm y and v = ELU(a * scale[c] + shift[c]) (fused multiply-add, expm1f).  fp32

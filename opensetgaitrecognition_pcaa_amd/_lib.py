@@ -86,7 +86,7 @@ def load():
             try:
                 fn = getattr(lib, name)
             except AttributeError:
-                # an entry point added without a new version number (pcaa_crops_from_raw and the _thin entry points under 29): a library built
+                # an entry point added without a new version number (pcaa_crops_from_raw, the _thin and the _aug entry points under 29): a library built
                 # before it answers the version check below, so say what to do here
                 raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/pcaa_hip.h declares: it was built "
                                    "from an older header; rebuild it (python -m opensetgaitrecognition_pcaa_amd.build)") from None

@@ -208,16 +208,25 @@ class RawTrackBatcher:
     ``__iter__`` is called.  ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" /
     "random"): point dropout -- every frame keeps at most that many of its detections before it is padded to N, by the
     same launch (``ops.crops_from_raw(keep=...)``); the counts and the kept sets are drawn with the epoch's seed, so under
-    ``redraw="epoch"`` they are re-drawn per epoch as the padding is.  Not with ``picks``, which decide by themselves."""
+    ``redraw="epoch"`` they are re-drawn per epoch as the padding is.  Not with ``picks``, which decide by themselves.
+    ``augment`` (``datasets.augment_arguments``: yaw, mirror, scale, speed, noise): the detections are turned, mirrored,
+    scaled and perturbed before each frame is centred, by the same launch (``ops.crops_from_raw(augment=...)``).  The draws
+    per track (angle, mirror, factors) and per detection (noise) use the epoch's draw seed: under ``redraw="epoch"`` they
+    are re-drawn every epoch, under ``"fixed"`` they are the same every epoch -- one fixed distortion of the store, which
+    is rarely what training wants.  All windows of a track share its draws within an epoch.  May be combined with
+    ``picks`` and with ``keep_points``."""
 
     def __init__(self, view, batch_size, shuffle=True, drop_last=True, rank=0, world=1, group=None, seed=0, redraw="fixed",
-                 jitter=False, picks=None, keep_points=0, keep_rule="first"):
+                 jitter=False, picks=None, keep_points=0, keep_rule="first", augment=None):
         if redraw not in ("fixed", "epoch"):
             raise ValueError(f"RawTrackBatcher: redraw must be 'fixed' or 'epoch', got {redraw!r}")
         if datasets.keep_arguments(keep_points, None, keep_rule, "RawTrackBatcher")[0] and picks is not None:
             raise ValueError("RawTrackBatcher: keep_points thins the frames before the device draws their picks; supplied "
                              "picks decide by themselves")
         self.keep_points, self.keep_rule = keep_points, keep_rule
+        self.augment = datasets.augment_arguments(augment, "RawTrackBatcher")    # the 11 parameters, None when neutral
+        if self.augment is not None and self.augment[0] != 0 and view.C < 2:
+            raise ValueError("RawTrackBatcher: a rotation (yaw) needs the x and y columns, C >= 2")
         self.view, self.store = view, view.store
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), shuffle, drop_last
         self.rank, self.world, self.group = int(rank), int(world), group
@@ -292,7 +301,7 @@ class RawTrackBatcher:
         st, v = self.store, self.view
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, v.T, v.N, v.C, pick=self.picks, seed=self.draw_seed,
                                 frame_key=st.frame_key_dev, err_flag=self.err, keep=self.keep_points,
-                                keep_rule=self.keep_rule)                       # [B,T,N,C]
+                                keep_rule=self.keep_rule, augment=self.augment)  # [B,T,N,C]
         return pm.permute(0, 3, 1, 2)
 
     def batch(self, idx):
@@ -331,13 +340,14 @@ def batcher_for(dataset, batch_size, device, shuffle, drop_last=True, cache_dir=
     ``.pcs [M,T,N,C]``, ``.labels``) go to the device as they are; file-backed ones (``MSRadarDataset``) are
     packed once into ``<dataset_dir>_packed`` (re-packed when the file list changed) and uploaded.  A
     ``datasets.RawCrops`` view (``RawTrackStore.crops``) gets a :class:`RawTrackBatcher` with the fixed draws of its
-    ``batcher_options`` (default: seed 0; ``keep_points`` / ``keep_rule`` among them: point dropout for the training
-    loader, while the validation loader sees the frames whole); the store is uploaded if it is not yet."""
+    ``batcher_options`` (default: seed 0; ``keep_points`` / ``keep_rule`` and ``augment`` among them: point dropout and
+    augmentation for the training loader, while the validation loader sees the frames whole and where they were
+    measured); the store is uploaded if it is not yet."""
     if isinstance(dataset, datasets.RawCrops):
         dataset.store.to_device(device)
         opts = dict(dataset.batcher_options)
         if not shuffle:                                  # the validation loader: the fixed draws, the reference's starts
-            opts.update(redraw="fixed", jitter=False, keep_points=0)
+            opts.update(redraw="fixed", jitter=False, keep_points=0, augment=None)
         return RawTrackBatcher(dataset, batch_size, shuffle, drop_last, rank, world, group, **opts)
     if hasattr(dataset, "pcs") and torch.is_tensor(dataset.pcs):
         crops = dataset.pcs.to(device).float().contiguous()

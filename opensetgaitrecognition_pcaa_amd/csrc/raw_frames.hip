@@ -44,6 +44,27 @@
 //            mapped through the keep list (16-bit, in LDS), so pick_out holds RAW indices.
 // datasets.device_picks_host(..., keep, keep_min, keep_rule) restates it.  A supplied pick decides by itself: together
 // with keep > 0 it is an argument error.
+//
+// Augmentation (the _aug entry points): a stage between steps 2 and 3 that moves the picked detections in fp64 in LDS,
+// after the power column has become dB and before the frame is centred; steps 3 and 4 follow unchanged, so the compact-row
+// route and the bit-equality of a frame across the three kernels hold as without it.  Parameters (RawAug; pcaa_hip.h):
+// yaw, mirror, scale_lo / _hi, speed_lo / _hi, sigma[5].
+//   per track   u = absorb(absorb(absorb(absorb(0x9e3779b9, seed_lo), seed_hi), key[0]), 0x6175676d) ("augm"; key[1] is
+//               NOT absorbed: every frame of a track shares the draws, so overlapping windows agree and the gait dynamics
+//               between frames survive);  w_j = absorb(u, j), r_j = (w_j + 0.5) 2^-32, j = 0 .. 3;
+//               theta = yaw (2 r_0 - 1);  m = w_1 >> 31 (when mirror);  a = scale_lo + (scale_hi - scale_lo) r_2;
+//               v = speed_lo + (speed_hi - speed_lo) r_3;
+//   per detection, keyed by its RAW index i (every copy of a detection carries the same noise: padded duplicates stay
+//               bit-equal rows):  n = absorb(s, 0x6e6f6973) ("nois"), q = absorb(n, i), r1 = (absorb(q, 2c) + 0.5) 2^-32,
+//               r2 = (absorb(q, 2c + 1) + 0.5) 2^-32, g(i, c) = sqrt(-2 ln r1) cos(2 pi r2).  Both tags exceed 1024 and
+//               differ from "keep": these chains never meet the pick draws;
+//   per picked point, in order:  val[c] += sigma[c] g(i, c);  x, y, z *= a, doppler *= v;  x = -x when m;
+//               (x, y) <- (x cos theta - y sin theta, x sin theta + y cos theta).  Neutral steps are skipped.
+// Steps 1 - 3 of the list are element-wise and ride on the gather; the rotation is one pass over the points in place: no
+// further LDS array.  A rotation about the radar's vertical axis and a mirror across boresight leave range and radial
+// velocity alone; after centring they are what a person at another azimuth delivers -- hence before centring, and the
+// Doppler untouched.  The stage is a template flag beside KEEP: the kernels without it are the code they were.
+// datasets.frames_from_picks(..., augment=, seed=, keys=) restates it in numpy.
 #include "common.h"
 
 namespace {
@@ -75,6 +96,70 @@ struct RawKeep {                                 // the thinning parameters: the
 __device__ __forceinline__ int raw_keep_count(uint32_t t, int keep, int keep_min) {
   if (keep_min >= keep) return keep;
   return keep_min + (int)(((uint64_t)raw_absorb(t, 0xffffffffu) * (uint64_t)(keep - keep_min + 1)) >> 32);
+}
+
+// The augmentation stage's parameters (the _aug entry points; PCAA_RAW_AUG_* of pcaa_hip.h), by value behind the thinning
+// ones: the kernels without the stage take RawKeep alone, as before it existed.
+constexpr uint32_t RAW_AUG_WORD = 0x6175676du;   // "augm": the tag of a track's draws
+constexpr uint32_t RAW_NOISE_WORD = 0x6e6f6973u; // "nois": the tag of a frame's noise chain
+struct RawAug {
+  double yaw, scale_lo, scale_hi, speed_lo, speed_hi, sigma[5];
+  int mirror;
+};
+struct RawKeepAug : RawKeep {
+  RawAug aug;
+};
+template <bool AUG>
+using RawParams = typename std::conditional<AUG, RawKeepAug, RawKeep>::type;
+
+// a hash word as a number in (0, 1): exact in fp64
+__device__ __forceinline__ double raw_unit(uint32_t w) { return ((double)w + 0.5) * 0x1p-32; }
+
+// what a track's frames share (the header comment's per-track draws), the same in every thread of every frame of it
+struct RawAugDraw {
+  double cos_t, sin_t, scale, speed;
+  bool rotate, flip, do_scale, do_speed;
+};
+__device__ __forceinline__ RawAugDraw raw_aug_draw(const RawAug& ag, uint32_t seed_lo, uint32_t seed_hi, uint32_t key0) {
+#pragma clang fp contract(off)
+  const uint32_t u =
+      raw_absorb(raw_absorb(raw_absorb(raw_absorb(0x9e3779b9u, seed_lo), seed_hi), key0), RAW_AUG_WORD);
+  RawAugDraw d;
+  d.rotate = ag.yaw != 0.0;
+  d.cos_t = 1.0;
+  d.sin_t = 0.0;
+  if (d.rotate) {
+    const double theta = ag.yaw * (2.0 * raw_unit(raw_absorb(u, 0u)) - 1.0);
+    d.cos_t = cos(theta);
+    d.sin_t = sin(theta);
+  }
+  d.flip = ag.mirror != 0 && (raw_absorb(u, 1u) >> 31) != 0;
+  d.do_scale = !(ag.scale_lo == 1.0 && ag.scale_hi == 1.0);
+  d.scale = d.do_scale ? ag.scale_lo + (ag.scale_hi - ag.scale_lo) * raw_unit(raw_absorb(u, 2u)) : 1.0;
+  d.do_speed = !(ag.speed_lo == 1.0 && ag.speed_hi == 1.0);
+  d.speed = d.do_speed ? ag.speed_lo + (ag.speed_hi - ag.speed_lo) * raw_unit(raw_absorb(u, 3u)) : 1.0;
+  return d;
+}
+
+// steps 1 - 3 of the stage for column c of the detection whose noise chain is q = absorb(n, raw index): noise, scale /
+// speed, mirror; a neutral step is skipped
+template <int C>
+__device__ __forceinline__ double raw_aug_element(double v, int c, uint32_t q, const RawAug& ag, const RawAugDraw& d) {
+#pragma clang fp contract(off)
+  double sg = 0.0;
+#pragma unroll
+  for (int k = 0; k < C; ++k) sg = c == k ? ag.sigma[k] : sg;   // a select chain: no indexed copy of the parameters
+  if (sg != 0.0) {
+    const double r1 = raw_unit(raw_absorb(q, 2u * (uint32_t)c)), r2 = raw_unit(raw_absorb(q, 2u * (uint32_t)c + 1u));
+    v += sg * (sqrt(-2.0 * log(r1)) * cos(6.283185307179586 * r2));
+  }
+  if (c < 3) {
+    if (d.do_scale) v *= d.scale;
+  } else if (c == 3) {
+    if (d.do_speed) v *= d.speed;
+  }
+  if (c == 0 && d.flip) v = -v;
+  return v;
 }
 
 // the sum of v[c] over the workgroup, c < C, in the fixed order of the header comment; every thread gets the result
@@ -131,13 +216,14 @@ using RawSharedOf = typename std::conditional<KEEP, RawSharedKeep, RawShared>::t
 // Steps 1 - 3 of the header comment for frame f, shared by every kernel of this file so that they produce the same
 // bits: picks -> sh.pick (and pick_out), gather -> sh.val, mean / denom in every thread's registers.  Returns false
 // for a bad frame: pick_out is -1, *err set, sh.val / mean / denom undefined; the caller writes its zeros.
-// KEEP: with the thinning stage of the header comment (kp is read only then).
-template <typename T, int C, bool KEEP>
+// KEEP: with the thinning stage of the header comment (kp is read only then).  AUG: with the augmentation stage between
+// the gather and the statistics (kp.aug); those kernels are instantiated with KEEP and take kp.keep == 0 as "no thinning".
+template <typename T, int C, bool KEEP, bool AUG>
 __device__ __forceinline__ bool raw_frame_prepare(
     RawSharedOf<KEEP>& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, RawKeep kp, int* __restrict__ pick_out, int* __restrict__ err, int& card_out,
-    double (&mean)[C], double (&denom)[C]) {
+    int standardize, int divide_by_std, const RawParams<AUG>& kp, int* __restrict__ pick_out, int* __restrict__ err,
+    int& card_out, double (&mean)[C], double (&denom)[C]) {
 #pragma clang fp contract(off)
   const int tid = threadIdx.x;
   const int NC = N * C;
@@ -162,9 +248,10 @@ __device__ __forceinline__ bool raw_frame_prepare(
       int vcard = card;                             // the frame stage 2 draws over
       bool mapped = false;
       if constexpr (KEEP) {
-        // stage 1: k_f, and under RANDOM the keep list (everything here is uniform over the workgroup)
+        // stage 1: k_f, and under RANDOM the keep list (everything here is uniform over the workgroup); the _aug
+        // kernels take keep == 0 as k_f = card: the frame is untouched
         const uint32_t t = raw_absorb(s, RAW_KEEP_WORD);
-        const int kf = raw_keep_count(t, kp.keep, kp.keep_min);
+        const int kf = (AUG && kp.keep == 0) ? card : raw_keep_count(t, kp.keep, kp.keep_min);
         vcard = kf < card ? kf : card;
         mapped = kf < card && kp.rule == RAW_KEEP_RANDOM;
         if (mapped) {
@@ -219,13 +306,37 @@ __device__ __forceinline__ bool raw_frame_prepare(
 
   // gather, point-major; the power column to dB
   const T* src = points + off0 * RAW_COLS;
-  for (int e = tid; e < NC; e += RAW_THREADS) {
-    const int p = e / C, c = e - p * C;
-    double v = (double)src[(long)sh.pick[p] * RAW_COLS + c];
-    if (C == RAW_COLS && c == RAW_COLS - 1) v = 10.0 * log10(v + 1e-8);
-    sh.val[e] = v;
+  if constexpr (AUG) {
+    // the stage's element-wise steps ride on the gather, keyed by the RAW index: every copy of a detection gets the same
+    // noise; then the rotation, point by point, in place
+    const RawAugDraw d = raw_aug_draw(kp.aug, seed_lo, seed_hi, (uint32_t)frame_key[2 * f]);
+    const uint32_t nz = raw_absorb(raw_chain(seed_lo, seed_hi, frame_key, f), RAW_NOISE_WORD);
+    for (int e = tid; e < NC; e += RAW_THREADS) {
+      const int p = e / C, c = e - p * C, i = sh.pick[p];
+      double v = (double)src[(long)i * RAW_COLS + c];
+      if (C == RAW_COLS && c == RAW_COLS - 1) v = 10.0 * log10(v + 1e-8);
+      sh.val[e] = raw_aug_element<C>(v, c, raw_absorb(nz, (uint32_t)i), kp.aug, d);
+    }
+    __syncthreads();
+    if constexpr (C >= 2) {
+      if (d.rotate) {                               // uniform over the workgroup
+        for (int p = tid; p < N; p += RAW_THREADS) {
+          const double x = sh.val[p * C], y = sh.val[p * C + 1];
+          sh.val[p * C] = x * d.cos_t - y * d.sin_t;
+          sh.val[p * C + 1] = x * d.sin_t + y * d.cos_t;
+        }
+        __syncthreads();
+      }
+    }
+  } else {
+    for (int e = tid; e < NC; e += RAW_THREADS) {
+      const int p = e / C, c = e - p * C;
+      double v = (double)src[(long)sh.pick[p] * RAW_COLS + c];
+      if (C == RAW_COLS && c == RAW_COLS - 1) v = 10.0 * log10(v + 1e-8);
+      sh.val[e] = v;
+    }
+    __syncthreads();
   }
-  __syncthreads();
 
 #pragma unroll
   for (int c = 0; c < C; ++c) { mean[c] = 0.0; denom[c] = 1.0; }
@@ -277,18 +388,18 @@ __device__ __forceinline__ float raw_frame_finish(const RawShared& sh, int e, co
 
 // Steps 1 - 4 for store frame f into the padded frame at dst ([N, C] fp32): the one body of the kernels that write padded
 // frames (frames_from_raw_kernel, crops_from_raw_kernel), so that a frame has the same bits wherever it is written.
-template <typename T, int C, bool KEEP>
+template <typename T, int C, bool KEEP, bool AUG>
 __device__ __forceinline__ void raw_frame_write(
     RawSharedOf<KEEP>& sh, const T* __restrict__ points, long P, const int* __restrict__ offsets, long f,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, RawKeep kp, float* __restrict__ dst, bool vec, int* __restrict__ pick_out,
-    int* __restrict__ err) {
+    int standardize, int divide_by_std, const RawParams<AUG>& kp, float* __restrict__ dst, bool vec,
+    int* __restrict__ pick_out, int* __restrict__ err) {
   const int tid = threadIdx.x;
   const int NC = N * C;
   double mean[C], denom[C];
   int card;
-  if (!raw_frame_prepare<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                                     divide_by_std, kp, pick_out, err, card, mean, denom)) {
+  if (!raw_frame_prepare<T, C, KEEP, AUG>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                          divide_by_std, kp, pick_out, err, card, mean, denom)) {
     zero_frame(dst, NC, vec);
     return;
   }
@@ -306,11 +417,11 @@ __device__ __forceinline__ void raw_frame_write(
   }
 }
 
-template <typename T, int C, bool KEEP>
+template <typename T, int C, bool KEEP, bool AUG>
 __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
     const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
-    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err, RawKeep kp) {
+    float* __restrict__ out, int* __restrict__ pick_out, int* __restrict__ err, RawParams<AUG> kp) {
   __shared__ RawSharedOf<KEEP> sh;
   const long f = blockIdx.x;
   const int NC = N * C;
@@ -320,8 +431,8 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
     zero_frame(dst, NC, vec);
     return;
   }
-  raw_frame_write<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                              divide_by_std, kp, dst, vec, pick_out, err);
+  raw_frame_write<T, C, KEEP, AUG>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                   divide_by_std, kp, dst, vec, pick_out, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -332,11 +443,11 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_kernel(
 // (overlapping and repeated crops each get their own copy: no workgroup reads what another wrote).  A crop that leaves
 // the store (start[b] < 0 or start[b] + T > F; compared in 64 bits) is zeros and sets *err before any table is read.
 // The flag is raised as everywhere in this file (atomicOr); the output has no atomics.
-template <typename T, int C, bool KEEP>
+template <typename T, int C, bool KEEP, bool AUG>
 __global__ __launch_bounds__(RAW_THREADS) void crops_from_raw_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, long F, const int* __restrict__ start, int Tc,
     const int* __restrict__ pick, const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N,
-    int standardize, int divide_by_std, float* __restrict__ out, int* __restrict__ err, RawKeep kp) {
+    int standardize, int divide_by_std, float* __restrict__ out, int* __restrict__ err, RawParams<AUG> kp) {
   __shared__ RawSharedOf<KEEP> sh;
   const int NC = N * C;
   const long slot = blockIdx.x;                   // b * T + t < B * T: the grid is exactly the batch's frames
@@ -349,8 +460,8 @@ __global__ __launch_bounds__(RAW_THREADS) void crops_from_raw_kernel(
     if (err != nullptr && threadIdx.x == 0) atomicOr(err, 1);
     return;
   }
-  raw_frame_write<T, C, KEEP>(sh, points, P, offsets, s + t, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                              divide_by_std, kp, dst, vec, nullptr, err);
+  raw_frame_write<T, C, KEEP, AUG>(sh, points, P, offsets, s + t, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                   divide_by_std, kp, dst, vec, nullptr, err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -407,12 +518,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void raw_unique_offsets_kernel(
 
 constexpr int RAW_PER_THREAD = PCAA_RAW_MAX_POINTS / RAW_THREADS;      // pick positions one thread ranks
 
-template <typename T, int C, bool KEEP>
+template <typename T, int C, bool KEEP, bool AUG>
 __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
     const T* __restrict__ points, long P, const int* __restrict__ offsets, int n, const int* __restrict__ pick,
     const int* __restrict__ frame_key, uint32_t seed_lo, uint32_t seed_hi, int N, int standardize, int divide_by_std,
     float* __restrict__ rows, float* __restrict__ weight, const int* __restrict__ u_off, long M,
-    int* __restrict__ pick_out, int* __restrict__ err, RawKeep kp) {
+    int* __restrict__ pick_out, int* __restrict__ err, RawParams<AUG> kp) {
   __shared__ RawSharedOf<KEEP> sh;
   __shared__ int s_cnt[PCAA_RAW_MAX_CARD];        // by raw index: how often it was picked
   __shared__ int s_first[PCAA_RAW_MAX_CARD];      // by raw index: the first pick position that holds it
@@ -443,8 +554,8 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
   }
   double mean[C], denom[C];
   int card;
-  if (!raw_frame_prepare<T, C, KEEP>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
-                                     divide_by_std, kp, pick_out, err, card, mean, denom)) {
+  if (!raw_frame_prepare<T, C, KEEP, AUG>(sh, points, P, offsets, f, pick, frame_key, seed_lo, seed_hi, N, standardize,
+                                          divide_by_std, kp, pick_out, err, card, mean, denom)) {
     zero_rows(u0, u1);                            // one row, the zero point N times: the padded path's all-zero frame
     __syncthreads();                              // (the weight below is written after the zeros, by the thread that wrote them)
     if (tid == 0) weight[u0] = (float)N;
@@ -518,54 +629,58 @@ __global__ __launch_bounds__(RAW_THREADS) void frames_from_raw_unique_kernel(
   zero_rows(u0 + distinct, u1);
 }
 
-// every launcher: KEEP = kp.keep > 0 picks the instantiation; without thinning the kernels are those of ABI 29
+// every launcher: KEEP = kp.keep > 0 picks the instantiation; without thinning the kernels are those of ABI 29.  KP is
+// RawKeep, or RawKeepAug for the kernels with the augmentation stage (one instantiation per C: KEEP, keep == 0 allowed).
+#define PCAA_RAW_CASE(LAUNCH, CC)                                                                                      \
+  case CC:                                                                                                             \
+    if constexpr (AUG) { LAUNCH(CC, true) } else if (kp.keep > 0) { LAUNCH(CC, true) } else { LAUNCH(CC, false) }      \
+    break;
 #define PCAA_RAW_CASES(LAUNCH)                                                                                         \
+  constexpr bool AUG = std::is_same<KP, RawKeepAug>::value;                                                            \
   switch (C) {                                                                                                         \
-    case 1: if (kp.keep > 0) { LAUNCH(1, true) } else { LAUNCH(1, false) } break;                                      \
-    case 2: if (kp.keep > 0) { LAUNCH(2, true) } else { LAUNCH(2, false) } break;                                      \
-    case 3: if (kp.keep > 0) { LAUNCH(3, true) } else { LAUNCH(3, false) } break;                                      \
-    case 4: if (kp.keep > 0) { LAUNCH(4, true) } else { LAUNCH(4, false) } break;                                      \
-    case 5: if (kp.keep > 0) { LAUNCH(5, true) } else { LAUNCH(5, false) } break;                                      \
+    PCAA_RAW_CASE(LAUNCH, 1) PCAA_RAW_CASE(LAUNCH, 2) PCAA_RAW_CASE(LAUNCH, 3) PCAA_RAW_CASE(LAUNCH, 4)                \
+    PCAA_RAW_CASE(LAUNCH, 5)                                                                                           \
   }
 
-template <typename T>
+template <typename T, typename KP>
 void launch_frames_from_raw(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
                             const int* pick, const int* frame_key, long seed, int N, int standardize, int divide_by_std,
-                            RawKeep kp, float* out, int* pick_out, int* err) {
+                            KP kp, float* out, int* pick_out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
 #define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
-  hipLaunchKernelGGL((frames_from_raw_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, n,     \
-                     pick, frame_key, lo, hi, N, standardize, divide_by_std, out, pick_out, err, kp);
+  hipLaunchKernelGGL((frames_from_raw_kernel<T, CC, KEEP, AUG>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets,   \
+                     n, pick, frame_key, lo, hi, N, standardize, divide_by_std, out, pick_out, err, kp);
   PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
 #undef PCAA_RAW_LAUNCH
 }
 
-template <typename T>
+template <typename T, typename KP>
 void launch_crops_from_raw(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, long F,
                            const int* start, int Tc, const int* pick, const int* frame_key, long seed, int N,
-                           int standardize, int divide_by_std, RawKeep kp, float* out, int* err) {
+                           int standardize, int divide_by_std, KP kp, float* out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
 #define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
-  hipLaunchKernelGGL((crops_from_raw_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, F,      \
+  hipLaunchKernelGGL((crops_from_raw_kernel<T, CC, KEEP, AUG>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, F, \
                      start, Tc, pick, frame_key, lo, hi, N, standardize, divide_by_std, out, err, kp);
   PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
 #undef PCAA_RAW_LAUNCH
 }
 
-template <typename T>
+template <typename T, typename KP>
 void launch_frames_from_raw_unique(int C, dim3 grid, hipStream_t st, const T* points, long P, const int* offsets, int n,
                                    const int* pick, const int* frame_key, long seed, int N, int standardize,
-                                   int divide_by_std, RawKeep kp, float* rows, float* weight, const int* u_off, long M,
+                                   int divide_by_std, KP kp, float* rows, float* weight, const int* u_off, long M,
                                    int* pick_out, int* err) {
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
 #define PCAA_RAW_LAUNCH(CC, KEEP)                                                                                      \
-  hipLaunchKernelGGL((frames_from_raw_unique_kernel<T, CC, KEEP>), grid, dim3(RAW_THREADS), 0, st, points, P, offsets, \
-                     n, pick, frame_key, lo, hi, N, standardize, divide_by_std, rows, weight, u_off, M, pick_out, err, \
-                     kp);
+  hipLaunchKernelGGL((frames_from_raw_unique_kernel<T, CC, KEEP, AUG>), grid, dim3(RAW_THREADS), 0, st, points, P,    \
+                     offsets, n, pick, frame_key, lo, hi, N, standardize, divide_by_std, rows, weight, u_off, M,       \
+                     pick_out, err, kp);
   PCAA_RAW_CASES(PCAA_RAW_LAUNCH)
 #undef PCAA_RAW_LAUNCH
 }
 #undef PCAA_RAW_CASES
+#undef PCAA_RAW_CASE
 
 // what the _thin entry points check on top of their neighbours' arguments: no launch follows a refusal
 int check_keep(const char* who, int keep, int keep_min, int keep_rule, const void* pick, const void* frame_key, long n) {
@@ -577,10 +692,41 @@ int check_keep(const char* who, int keep, int keep_min, int keep_rule, const voi
   return PCAA_OK;
 }
 
-// The bodies of the entry points, `who` the name in their messages; kp.keep == 0: without thinning.
+// what the _aug entry points check on top of their neighbours' arguments (thinning is optional there, picks allowed
+// without it), and the parameters as the kernels take them: no launch follows a refusal
+int check_aug(const char* who, const double* aug, int C, int keep, int keep_min, int keep_rule, const void* pick,
+              const void* frame_key, long n, RawKeepAug& kp) {
+  PCAA_CHECK_ARG(aug != nullptr, "%s: aug is null (PCAA_RAW_AUG_PARAMS doubles)", who);
+  PCAA_CHECK_ARG(n == 0 || frame_key != nullptr, "%s: the frames need their keys (frame_key), with supplied picks too", who);
+  if (keep != 0) {
+    if (int rc = check_keep(who, keep, keep_min, keep_rule, pick, frame_key, n)) return rc;
+  } else {
+    keep_min = keep_rule = 0;
+  }
+  const double yaw = aug[PCAA_RAW_AUG_YAW], s0 = aug[PCAA_RAW_AUG_SCALE_LO], s1 = aug[PCAA_RAW_AUG_SCALE_HI];
+  const double v0 = aug[PCAA_RAW_AUG_SPEED_LO], v1 = aug[PCAA_RAW_AUG_SPEED_HI];
+  PCAA_CHECK_ARG(yaw >= 0.0 && yaw <= 3.14159265358979323846, "%s: yaw must lie in [0, pi]", who);   // a NaN fails too
+  PCAA_CHECK_ARG(yaw == 0.0 || C >= 2, "%s: a rotation needs the x and y columns (C >= 2)", who);
+  PCAA_CHECK_ARG(std::isfinite(aug[PCAA_RAW_AUG_MIRROR]), "%s: mirror is 0 or 1", who);
+  PCAA_CHECK_ARG(s0 > 0.0 && s0 <= s1 && std::isfinite(s1), "%s: needs 0 < scale_lo <= scale_hi, finite", who);
+  PCAA_CHECK_ARG(v0 > 0.0 && v0 <= v1 && std::isfinite(v1), "%s: needs 0 < speed_lo <= speed_hi, finite", who);
+  kp.keep = keep, kp.keep_min = keep_min, kp.rule = keep_rule;
+  kp.aug.yaw = yaw, kp.aug.scale_lo = s0, kp.aug.scale_hi = s1, kp.aug.speed_lo = v0, kp.aug.speed_hi = v1;
+  kp.aug.mirror = aug[PCAA_RAW_AUG_MIRROR] != 0.0;
+  for (int c = 0; c < RAW_COLS; ++c) {
+    const double sg = aug[PCAA_RAW_AUG_SIGMA + c];
+    PCAA_CHECK_ARG(sg >= 0.0 && std::isfinite(sg), "%s: a sigma is negative or not finite", who);
+    kp.aug.sigma[c] = sg;
+  }
+  return PCAA_OK;
+}
+
+// The bodies of the entry points, `who` the name in their messages; kp.keep == 0: without thinning.  KP = RawKeepAug:
+// with the augmentation stage.
+template <typename KP>
 int frames_from_raw_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, int n,
                          const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
-                         int divide_by_std, RawKeep kp, float* out, int n_out, int* pick_out, int* err_flag, void* stream) {
+                         int divide_by_std, KP kp, float* out, int n_out, int* pick_out, int* err_flag, void* stream) {
   PCAA_CHECK_ARG(n >= 0 && n_out >= n && n_out >= 1 && P >= 0, "%s: needs 0 <= n <= n_out, n_out >= 1, P >= 0", who);
   PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
                  "%s: needs 1 <= N <= PCAA_RAW_MAX_POINTS and 1 <= C <= 5", who);
@@ -599,9 +745,10 @@ int frames_from_raw_impl(const char* who, const void* points, int points_f64, lo
   PCAA_RETURN_LAUNCH_STATUS(who);
 }
 
+template <typename KP>
 int crops_from_raw_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, long F,
                         const int* start, int B, int T, const int* pick, const int* frame_key, long seed, int N, int C,
-                        int standardize, int divide_by_std, RawKeep kp, float* out, int* err_flag, void* stream) {
+                        int standardize, int divide_by_std, KP kp, float* out, int* err_flag, void* stream) {
   PCAA_CHECK_ARG(B >= 1 && T >= 1 && F >= 0 && P >= 0 && (long)B * T < (1L << 31) && F < (1L << 31),
                  "%s: needs B >= 1, T >= 1, B * T < 2^31, 0 <= F < 2^31, P >= 0", who);
   PCAA_CHECK_ARG(N >= 1 && N <= PCAA_RAW_MAX_POINTS && C >= 1 && C <= RAW_COLS,
@@ -622,9 +769,10 @@ int crops_from_raw_impl(const char* who, const void* points, int points_f64, lon
   PCAA_RETURN_LAUNCH_STATUS(who);
 }
 
+template <typename KP>
 int frames_from_raw_unique_impl(const char* who, const void* points, int points_f64, long P, const int* offsets, int n,
                                 const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
-                                int divide_by_std, RawKeep kp, float* rows, float* weight, int* u_off, long M,
+                                int divide_by_std, KP kp, float* rows, float* weight, int* u_off, long M,
                                 int* pick_out, int* err_flag, void* stream) {
   PCAA_CHECK_ARG(n >= 0 && M >= 1 && P >= 0 && (long)n * PCAA_RAW_MAX_POINTS < (1L << 31) && M < (1L << 31),
                  "%s: needs n >= 0, 1 <= M < 2^31, P >= 0, n * 1024 < 2^31", who);
@@ -638,12 +786,13 @@ int frames_from_raw_unique_impl(const char* who, const void* points, int points_
                  "%s: without picks the frames need their keys (frame_key)", who);
   PCAA_CHECK_ARG(((uintptr_t)points % (points_f64 ? 8 : 4)) == 0, "%s: points are misaligned", who);
   const uint32_t lo = (uint32_t)((uint64_t)seed & 0xffffffffu), hi = (uint32_t)((uint64_t)seed >> 32);
+  const RawKeep& thin = kp;                       // u_off does not depend on the augmentation
   if (kp.keep > 0)
     hipLaunchKernelGGL(raw_unique_offsets_kernel<true>, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n, P,
-                       N, u_off, frame_key, lo, hi, kp);
+                       N, u_off, frame_key, lo, hi, thin);
   else
     hipLaunchKernelGGL(raw_unique_offsets_kernel<false>, dim3(1), dim3(SCAN_THREADS), 0, as_stream(stream), offsets, n,
-                       P, N, u_off, frame_key, lo, hi, kp);
+                       P, N, u_off, frame_key, lo, hi, thin);
   long tail = cdiv(M, 4096);                      // blocks that zero the rows no frame owns
   tail = tail < 1 ? 1 : (tail > 64 ? 64 : tail);
   const dim3 grid((unsigned)(n + tail));
@@ -714,4 +863,38 @@ extern "C" int pcaa_frames_from_raw_unique_thin(const void* points, int points_f
   return frames_from_raw_unique_impl(who, points, points_f64, P, offsets, n, pick, frame_key, seed, N, C, standardize,
                                      divide_by_std, RawKeep{keep, keep_min, keep_rule}, rows, weight, u_off, M, pick_out,
                                      err_flag, stream);
+}
+
+extern "C" int pcaa_frames_from_raw_aug(const void* points, int points_f64, long P, const int* offsets, int n,
+                                        const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
+                                        int divide_by_std, float* out, int n_out, int* pick_out, int* err_flag,
+                                        void* stream, int keep, int keep_min, int keep_rule, const double* aug) {
+  const char* who = "pcaa_frames_from_raw_aug";
+  RawKeepAug kp;
+  if (int rc = check_aug(who, aug, C, keep, keep_min, keep_rule, pick, frame_key, n, kp)) return rc;
+  return frames_from_raw_impl(who, points, points_f64, P, offsets, n, pick, frame_key, seed, N, C, standardize,
+                              divide_by_std, kp, out, n_out, pick_out, err_flag, stream);
+}
+
+extern "C" int pcaa_crops_from_raw_aug(const void* points, int points_f64, long P, const int* offsets, long F,
+                                       const int* start, int B, int T, const int* pick, const int* frame_key, long seed,
+                                       int N, int C, int standardize, int divide_by_std, float* out, int* err_flag,
+                                       void* stream, int keep, int keep_min, int keep_rule, const double* aug) {
+  const char* who = "pcaa_crops_from_raw_aug";
+  RawKeepAug kp;
+  if (int rc = check_aug(who, aug, C, keep, keep_min, keep_rule, pick, frame_key, F, kp)) return rc;
+  return crops_from_raw_impl(who, points, points_f64, P, offsets, F, start, B, T, pick, frame_key, seed, N, C,
+                             standardize, divide_by_std, kp, out, err_flag, stream);
+}
+
+extern "C" int pcaa_frames_from_raw_unique_aug(const void* points, int points_f64, long P, const int* offsets, int n,
+                                               const int* pick, const int* frame_key, long seed, int N, int C,
+                                               int standardize, int divide_by_std, float* rows, float* weight,
+                                               int* u_off, long M, int* pick_out, int* err_flag, void* stream, int keep,
+                                               int keep_min, int keep_rule, const double* aug) {
+  const char* who = "pcaa_frames_from_raw_unique_aug";
+  RawKeepAug kp;
+  if (int rc = check_aug(who, aug, C, keep, keep_min, keep_rule, pick, frame_key, n, kp)) return rc;
+  return frames_from_raw_unique_impl(who, points, points_f64, P, offsets, n, pick, frame_key, seed, N, C, standardize,
+                                     divide_by_std, kp, rows, weight, u_off, M, pick_out, err_flag, stream);
 }

@@ -21,6 +21,7 @@ part of ``generate_splits`` that decides which track goes to which split).
 ``SyntheticGaitDataset`` produces mmGait10-shaped crops from a seed; items are
 permuted views of point-major ``[T,N,C]`` storage.
 """
+import math
 import os
 
 import numpy as np
@@ -134,16 +135,56 @@ def _raw_columns(frame):
                            frame["powers"][:, np.newaxis]], axis=1).astype(np.float64, copy=False)
 
 
-def frames_from_picks(raw_frames, picks, nfeatures, divide_by_std=False):
-    """The arithmetic half of ``process_track`` on given picks (``draw_picks``, ``device_picks_host``, or the ``pick_out``
-    of ``ops.frames_from_raw``): powers to dB, the first ``nfeatures`` columns, ``arr[picks[f]]``, per-frame centring
-    (and division by ``std + 1e-8``) -> float64 ``[n, nmax, nfeatures]``."""
-    picks = np.asarray(picks)
-    out = np.empty((len(raw_frames), picks.shape[1], int(nfeatures)), dtype=np.float64)
+def augmented_columns(raw_frames, nfeatures, augment=None, seed=0, keys=None):
+    """What the frames' detections are before they are picked and centred -> a list with one float64 ``[card,
+    nfeatures]`` array per frame: x, y, z, doppler, power in dB, and with ``augment`` (``augment_arguments``; ``seed`` and
+    ``keys`` int ``[n, 2]``) moved by the augmentation stage of csrc/raw_frames.hip, restated in fp64 in its order: noise
+    by raw index, scale / speed, mirror, rotation; a neutral step is skipped."""
+    nfeatures = int(nfeatures)
+    aug = augment_arguments(augment, "augmented_columns")
+    if aug is not None:
+        if keys is None:
+            raise ValueError("augmented_columns: augment needs the frames' keys")
+        keys = np.asarray(keys).reshape(-1, 2)
+        if aug[0] != 0 and nfeatures < 2:
+            raise ValueError("augmented_columns: a rotation needs the x and y columns")
+        cards = [len(fr["z_coord"]) for fr in raw_frames]
+        sigma = np.asarray(aug[6:6 + nfeatures])
+        noise = device_noise_host(seed, keys, cards, nfeatures) if sigma.any() else None
+        draws = augment_draws_host(seed, keys[:, 0], aug)
+    out = []
     for fi, frame in enumerate(raw_frames):
         arr = _raw_columns(frame)
         arr[:, 4] = 10 * np.log10(arr[:, 4] + 1e-8)
-        final = arr[:, :nfeatures][picks[fi], :]
+        arr = arr[:, :nfeatures]
+        if aug is not None:
+            for c in range(nfeatures):
+                if sigma[c] != 0:
+                    arr[:, c] = arr[:, c] + sigma[c] * noise[fi][:, c]
+            if not (aug[2] == 1 and aug[3] == 1):
+                arr[:, :3] = arr[:, :3] * draws["scale"][fi]
+            if nfeatures > 3 and not (aug[4] == 1 and aug[5] == 1):
+                arr[:, 3] = arr[:, 3] * draws["speed"][fi]
+            if draws["mirror"][fi]:
+                arr[:, 0] = -arr[:, 0]
+            if aug[0] != 0:
+                ct, st = np.cos(draws["yaw"][fi]), np.sin(draws["yaw"][fi])
+                x, y = arr[:, 0].copy(), arr[:, 1].copy()
+                arr[:, 0] = x * ct - y * st
+                arr[:, 1] = x * st + y * ct
+        out.append(arr)
+    return out
+
+
+def frames_from_picks(raw_frames, picks, nfeatures, divide_by_std=False, augment=None, seed=0, keys=None):
+    """The arithmetic half of ``process_track`` on given picks (``draw_picks``, ``device_picks_host``, or the ``pick_out``
+    of ``ops.frames_from_raw``): powers to dB, the first ``nfeatures`` columns, ``arr[picks[f]]``, per-frame centring
+    (and division by ``std + 1e-8``) -> float64 ``[n, nmax, nfeatures]``.  ``augment`` with ``seed`` and ``keys``: the
+    detections moved first (``augmented_columns``), what the ``augment=`` of ``ops.frames_from_raw`` computes."""
+    picks = np.asarray(picks)
+    out = np.empty((len(raw_frames), picks.shape[1], int(nfeatures)), dtype=np.float64)
+    for fi, arr in enumerate(augmented_columns(raw_frames, nfeatures, augment, seed, keys)):
+        final = arr[picks[fi], :]
         mean = final.mean(axis=0)
         std = final.std(axis=0)
         final = final - mean
@@ -251,6 +292,107 @@ def device_picks_host(seed, keys, cards, N, keep=0, keep_min=None, keep_rule="fi
         if kept is not None:
             picks[fi] = kept[fi][picks[fi]]
     return picks
+
+
+_AUG_WORD = np.uint64(0x6175676D)             # "augm": the tag of a track's augmentation draws
+_NOISE_WORD = np.uint64(0x6E6F6973)           # "nois": the tag of a frame's noise chain
+AUG_PARAMS = 11                               # PCAA_RAW_AUG_PARAMS of include/pcaa_hip.h: yaw, mirror, scale lo / hi,
+AUG_COLUMNS = ("x", "y", "z", "doppler", "power")                           # speed lo / hi, sigma[5] over these columns
+_AUG_NEUTRAL = (0.0, 0.0, 1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def augment_arguments(augment, who="augment"):
+    """The augmentation parameters as every raw entry point takes them -> a tuple of the ``AUG_PARAMS`` doubles of
+    ``pcaa_*_aug`` (yaw, mirror, scale_lo, scale_hi, speed_lo, speed_hi, sigma x / y / z / doppler / power), or None when
+    every step is neutral (None, an empty dict, or neutral values): the caller then makes the call it makes without
+    augmentation.  ``augment`` is a dict with any of ``yaw`` (radians, 0 .. pi: each track is turned by an angle uniform in
+    (-yaw, yaw) about the radar's vertical axis), ``mirror`` (bool: each track is mirrored across boresight with
+    probability 1/2), ``scale`` and ``speed`` (``(lo, hi)`` or one factor, > 0: x, y, z resp. the Doppler times a factor
+    uniform in the range, per track) and ``noise`` (up to 5 sigmas in column order, or a dict over ``AUG_COLUMNS``: Gaussian
+    noise per detection, in metres, m/s and dB).  A tuple of ``AUG_PARAMS`` numbers (what this returns) passes through
+    the same checks."""
+    if augment is None:
+        return None
+    if isinstance(augment, (tuple, list, np.ndarray)):
+        vals = [float(v) for v in np.asarray(augment, dtype=np.float64).reshape(-1)]
+        if len(vals) != AUG_PARAMS:
+            raise ValueError(f"{who}: the parameter form of augment has {AUG_PARAMS} numbers, got {len(vals)}")
+    elif isinstance(augment, dict):
+        unknown = set(augment) - {"yaw", "mirror", "scale", "speed", "noise"}
+        if unknown:
+            raise ValueError(f"{who}: unknown augment keys {sorted(unknown)}; known: yaw, mirror, scale, speed, noise")
+        vals = list(_AUG_NEUTRAL)
+        vals[0] = float(augment.get("yaw", 0.0))
+        vals[1] = 1.0 if augment.get("mirror", False) else 0.0
+        for at, name in ((2, "scale"), (4, "speed")):
+            r = augment.get(name, 1.0)
+            if isinstance(r, (tuple, list, np.ndarray)):
+                if len(r) != 2:
+                    raise ValueError(f"{who}: {name} is one factor or (lo, hi), got {r!r}")
+                vals[at], vals[at + 1] = float(r[0]), float(r[1])
+            else:
+                vals[at] = vals[at + 1] = float(r)
+        noise = augment.get("noise", ())
+        if isinstance(noise, dict):
+            unknown = set(noise) - set(AUG_COLUMNS)
+            if unknown:
+                raise ValueError(f"{who}: unknown noise columns {sorted(unknown)}; known: {', '.join(AUG_COLUMNS)}")
+            for c, name in enumerate(AUG_COLUMNS):
+                vals[6 + c] = float(noise.get(name, 0.0))
+        else:
+            noise = [float(v) for v in np.asarray(noise, dtype=np.float64).reshape(-1)]
+            if len(noise) > 5:
+                raise ValueError(f"{who}: noise has at most 5 sigmas ({', '.join(AUG_COLUMNS)}), got {len(noise)}")
+            vals[6:6 + len(noise)] = noise
+    else:
+        raise ValueError(f"{who}: augment is a dict (yaw, mirror, scale, speed, noise) or None, got {type(augment).__name__}")
+    yaw, _, s0, s1, v0, v1 = vals[:6]
+    if not 0.0 <= yaw <= math.pi:                          # a NaN fails too
+        raise ValueError(f"{who}: yaw must lie in [0, pi] radians, got {yaw}")
+    for name, lo, hi in (("scale", s0, s1), ("speed", v0, v1)):
+        if not (0.0 < lo <= hi and math.isfinite(hi)):
+            raise ValueError(f"{who}: {name} needs 0 < lo <= hi, finite; got ({lo}, {hi})")
+    if not all(s >= 0.0 and math.isfinite(s) for s in vals[6:]):
+        raise ValueError(f"{who}: the noise sigmas must be finite and >= 0, got {vals[6:]}")
+    vals[1] = 1.0 if vals[1] != 0.0 else 0.0
+    return None if tuple(vals) == _AUG_NEUTRAL else tuple(vals)
+
+
+def _unit(w):
+    """a 32-bit hash word as a number in (0, 1): (w + 0.5) 2^-32, exact in fp64"""
+    return (np.asarray(w).astype(np.float64) + 0.5) * 2.0 ** -32
+
+
+def augment_draws_host(seed, serials, augment):
+    """The per-track draws of the augmentation stage of csrc/raw_frames.hip, restated -> a dict of arrays, one entry per
+    element of ``serials`` (``key[0]`` of the frames; the frame number is not part of the chain, so all frames of a track
+    share them): ``yaw`` (theta, radians), ``mirror`` (bool), ``scale``, ``speed``."""
+    aug = augment_arguments(augment, "augment_draws_host") or _AUG_NEUTRAL
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    serials = np.asarray(serials, dtype=np.int64).reshape(-1).astype(np.uint64) & _M32
+    s0 = _absorb32(_absorb32(np.uint64(0x9E3779B9), np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
+    u = _absorb32(_absorb32(s0, serials), _AUG_WORD)
+    w = [_absorb32(u, np.uint64(j)) for j in range(4)]
+    r = [_unit(x) for x in w]
+    return {"yaw": aug[0] * (2.0 * r[0] - 1.0),
+            "mirror": ((w[1] >> np.uint64(31)) != 0) & (aug[1] != 0),
+            "scale": aug[2] + (aug[3] - aug[2]) * r[2],
+            "speed": aug[4] + (aug[5] - aug[4]) * r[3]}
+
+
+def device_noise_host(seed, keys, cards, C):
+    """The standard normal draws g(i, c) of the augmentation stage, restated -> a list with one float64 ``[card, C]`` array
+    per frame: row i belongs to the frame's RAW detection i, whichever padded rows it lands in."""
+    keys = np.asarray(keys).reshape(-1, 2)
+    out = []
+    for key, card in zip(keys, np.asarray(cards).reshape(-1).tolist()):
+        q = _absorb32(_absorb32(_chain_state(seed, key), _NOISE_WORD), np.arange(card, dtype=np.uint64))
+        g = np.empty((card, int(C)), dtype=np.float64)
+        for c in range(int(C)):
+            r1, r2 = _unit(_absorb32(q, np.uint64(2 * c))), _unit(_absorb32(q, np.uint64(2 * c + 1)))
+            g[:, c] = np.sqrt(-2.0 * np.log(r1)) * np.cos(6.283185307179586 * r2)
+        out.append(g)
+    return out
 
 
 def pack_raw_frames(raw_frames, dtype=torch.float32):
@@ -502,10 +644,11 @@ class RawCrops:
             start = start + jitter_phases(seed, epoch, self.store.serial[self.track], np.minimum(self.hop, self.slack))
         return start.astype(np.int32)
 
-    def materialize(self, seed=0, picks=None, epoch=0, jitter=False, keep_points=0, keep_rule="first"):
+    def materialize(self, seed=0, picks=None, epoch=0, jitter=False, keep_points=0, keep_rule="first", augment=None):
         """All crops written out by the batch kernel, one launch -> ``(pcs [M, C, T, N] view of point-major storage,
         labels int64 [M])`` on the store's device: what the evaluation procedures take.  ``keep_points`` (k or ``(lo,
-        hi)``) / ``keep_rule``: every frame thinned to at most that many detections first (``keep_arguments``)."""
+        hi)``) / ``keep_rule``: every frame thinned to at most that many detections first (``keep_arguments``).
+        ``augment`` (``augment_arguments``): the detections moved in the same launch, drawn under ``seed``."""
         from . import ops
         st = self.store
         if st.device is None:
@@ -515,7 +658,8 @@ class RawCrops:
         err = torch.zeros(1, dtype=torch.int32, device=st.device)
         start = torch.from_numpy(self.starts(seed, epoch, jitter)).to(st.device)
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, self.T, self.N, self.C, pick=picks, seed=seed,
-                                frame_key=st.frame_key_dev, err_flag=err, keep=keep_points, keep_rule=keep_rule)
+                                frame_key=st.frame_key_dev, err_flag=err, keep=keep_points, keep_rule=keep_rule,
+                                augment=augment)
         if int(err.item()):
             raise ValueError("RawCrops.materialize: a frame of the store cannot be processed (no detections, more than "
                              f"{ops.RAW_MAX_CARD}, or a pick outside its frame)")

@@ -105,12 +105,12 @@ def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
 
 
 def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None, keep=0,
-                     keep_rule="first"):
-    """raw frames (``b``: frames a .. b - 1 of them; ``keep``: thinned first) -> their distinct points and multiplicities
-    -> (their [n, 1024] frame features, the PointNet layer records, rows of the compact table): the ``dedup_points``
+                     keep_rule="first", augment=None):
+    """raw frames (``b``: frames a .. b - 1 of them; ``keep``: thinned first; ``augment``: moved first) -> their distinct
+    points and multiplicities -> (their [n, 1024] frame features, the PointNet layer records, rows of the compact table): the ``dedup_points``
     route of the raw entries"""
     rows, weight, u_off = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a, b, dedup_points=True,
-                                                 keep=keep, keep_rule=keep_rule)
+                                                 keep=keep, keep_rule=keep_rule, augment=augment)
     feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, u_off.numel() - 1, N, mode, consts=consts)
     return feats, saves, rows.shape[0]
 
@@ -268,7 +268,7 @@ class OpenSetScorer:
     @torch.no_grad()
     def embed_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, pick: torch.Tensor = None, seed: int = 0,
                         track_key: int = 0, hop: int = constants.CROP_STEP, drop_last_aligned: bool = True,
-                        dedup_points: bool = False, keep_points=0, keep_rule: str = "first"):
+                        dedup_points: bool = False, keep_points=0, keep_rule: str = "first", augment=None):
         """``embed_track`` from the radar's detections: ``points`` [P,5] fp32 / fp64 and ``offsets`` int32 [F + 1] on the
         device (``datasets.pack_raw_frames``) -> one ``ops.frames_from_raw`` launch for the whole track (centred, not
         divided by std, as ``generate_splits`` prepares the crops) -> exactly ``embed_track`` on those frames.  ``pick``
@@ -281,20 +281,27 @@ class OpenSetScorer:
         ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" / "random"): the track as
         a sparser radar would deliver it -- every frame keeps at most that many detections before it is padded to N
         (``ops.frames_from_raw(keep=...)``; device-drawn picks only).  With ``dedup_points`` the table then holds at most
-        ``F * min(k, N)`` rows (in whole GEMM tiles)."""
+        ``F * min(k, N)`` rows (in whole GEMM tiles).  ``augment`` (``datasets.augment_arguments``: yaw, mirror, scale,
+        speed, noise): the track as a person at another azimuth, of another size or pace, or a noisier sensor would deliver
+        it -- the detections are moved by the same launch before each frame is centred (``ops.frames_from_raw(augment=)``),
+        on both routes; the draws come from ``seed`` and the keys ``(track_key, f)``, with supplied ``pick`` too."""
         enc = self.encoder
         N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
         F = frame_table.check_raw(points, offsets, pick, N, "embed_raw_track")
-        keys = frame_table.frame_keys(track_key, 0, F, points.device) if pick is None and F else None
+        from .datasets import augment_arguments
+        augment = augment_arguments(augment, "embed_raw_track")
+        keyed = (pick is None or augment is not None) and F            # the augmentation draws need the keys as well
+        keys = frame_table.frame_keys(track_key, 0, F, points.device) if keyed else None
         if not dedup_points:
             frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err, keep=keep_points,
-                                            keep_rule=keep_rule)
+                                            keep_rule=keep_rule, augment=augment)
             return self.embed_track(frames, hop, drop_last_aligned)
         step = max(self.batch_size * constants.NSTEPS, 1)
 
         def features(U):
             return self._chunk_features(((a, min(a + step, U)) for a in range(0, U, step)), lambda a, b: _ragged_features(
-                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, keep=keep_points, keep_rule=keep_rule))
+                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, keep=keep_points, keep_rule=keep_rule,
+                augment=augment))
         return self._score_track(F, hop, drop_last_aligned, True, points.device, features)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
@@ -419,10 +426,13 @@ def naive_sequential_procedure_tensors(k, encoder, discriminator_means, known_pc
                              unseen_valid_ratio)
 
 
-def _sequential_votes(k, scorer, known, known_labels, unseen, unseen_labels, seed=0, unseen_valid_ratio=0.2):
+def _sequential_votes(k, scorer, known, known_labels, unseen, unseen_labels, seed=0, unseen_valid_ratio=0.2,
+                      threshold=None):
     """steps (1) and (2) of the procedure on crops that are embedded already: ``known`` / ``unseen`` = (preds,
     likelihood) of the sequential TEST / UNSEEN crops -> (open-set predictions, open-set labels, threshold).  The
-    threshold is refit from these likelihoods; one embedding serves every k (``point_sweep``)."""
+    threshold is refit from these likelihoods; one embedding serves every k (``point_sweep``).  ``threshold``: used as it
+    is instead (a deployed threshold; ``perturbation_sweep``): nothing is fitted, the validation subjects are held out
+    all the same."""
     rng = np.random.default_rng(seed)
     (k_preds, k_lik), (u_preds, u_lik) = known, unseen
     n_labels = int(len(np.unique(known_labels.cpu().numpy())))
@@ -431,7 +441,10 @@ def _sequential_votes(k, scorer, known, known_labels, unseen, unseen_labels, see
     val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
     val_mask = np.isin(u_lab, val_subjects)
     vm = torch.from_numpy(val_mask).to(u_lik.device)
-    thr = scorer.fit_threshold(k_lik, u_lik[vm])
+    if threshold is None:
+        thr = scorer.fit_threshold(k_lik, u_lik[vm])
+    else:
+        thr = scorer.threshold = float(threshold)
     preds, labels = [], []
 
     def windows(lik, pr, lab, unknown):
@@ -465,12 +478,14 @@ def _sequential_split_on_device(split, scenarios_list, device):
     return crops.permute(0, 3, 1, 2), labels
 
 
-def _sequential_split_from_store(store, split, scenarios_list, N, keep_points=0, keep_rule="first"):
+def _sequential_split_from_store(store, split, scenarios_list, N, keep_points=0, keep_rule="first", augment=None,
+                                 seed=0):
     """The same tensors from a ``datasets.RawTrackStore`` (already assigned and on the device): the split's crops in
-    sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of seed 0; no files.
-    ``keep_points``: every frame thinned to at most that many detections by the same launch."""
+    sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of ``seed``; no files.
+    ``keep_points``: every frame thinned to at most that many detections by the same launch; ``augment``: its detections
+    moved by it; ``seed``: of the picks and of the augmentation draws alike."""
     return store.crops(split, N=N, C=constants.NFEATURES, order="sequential", scenarios=scenarios_list).materialize(
-        seed=0, keep_points=keep_points, keep_rule=keep_rule)
+        seed=seed, keep_points=keep_points, keep_rule=keep_rule, augment=augment)
 
 
 def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_points=True, keep_rule="first"):
@@ -499,6 +514,43 @@ def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_
         for k in ks:
             preds, labels, _ = _sequential_votes(k, scorer, *sets)
             out[keep][k] = _metrics(k, preds, labels.astype(int))
+    return out
+
+
+def perturbation_sweep(encoder, means, store, augments, ks, N, seed=0, refit=False, scenarios_list=None,
+                       dedup_points=True):
+    """The sibling of ``point_sweep`` for the ways a deployed radar degrades or differs other than by losing points:
+    position and Doppler noise, people at other azimuths, of other sizes and paces.  ``augments``: a dict from a name to an
+    augment (``datasets.augment_arguments``: yaw, mirror, scale, speed, noise; None or ``{}``: the crops as they are) ->
+    ``{name: {k: metrics}}``, ``metrics`` as in ``point_sweep``.  Per entry the sequential TEST / UNSEEN crops are built
+    augmented on the device under ``seed`` (one ``pcaa_crops_from_raw_aug`` launch per split) and embedded ONCE with
+    ``dedup_frames=True`` (and ``dedup_points``, default).  ``refit=False``: the votes use the threshold fitted on the
+    UN-augmented crops (built and embedded once, first) -- a deployed threshold meeting a degraded sensor; ``refit=True``:
+    the threshold is refit on each entry's own likelihoods, as ``point_sweep`` does per ``keep``.  Writes no file."""
+    from .constants import SPLIT
+    if store.device is None:
+        raise RuntimeError("perturbation_sweep: call store.to_device() first; there is no CPU path")
+    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
+    scorer = OpenSetScorer(encoder, means)
+
+    def embedded(augment):
+        sets = []
+        for split in (SPLIT.TEST, SPLIT.UNSEEN):
+            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, augment=augment, seed=seed)
+            preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
+            sets += [(preds, lik), labels]
+            del pcs
+        return sets
+
+    # the threshold does not depend on k: one fit on the crops as they are (same seed: the same picks)
+    clean = None if refit else _sequential_votes(ks[0], scorer, *embedded(None))[2]
+    out = {}
+    for name, augment in augments.items():
+        sets = embedded(augment)
+        out[name] = {}
+        for k in ks:
+            preds, labels, _ = _sequential_votes(k, scorer, *sets, threshold=clean)
+            out[name][k] = _metrics(k, preds, labels.astype(int))
     return out
 
 

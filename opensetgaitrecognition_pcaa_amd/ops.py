@@ -1662,8 +1662,21 @@ def _keep_args(who, keep, keep_min, keep_rule, pick):
     return args
 
 
+def _aug_args(who, augment, C):
+    """the augmentation of a raw entry point (``datasets.augment_arguments``: a dict, or None) -> the host array of
+    PCAA_RAW_AUG_PARAMS doubles the ``_aug`` entry points read, None for the neutral one: the caller then makes the call it
+    makes without augmentation"""
+    from .datasets import augment_arguments
+    vals = augment_arguments(augment, who)
+    if vals is None:
+        return None
+    if vals[0] != 0 and int(C) < 2:
+        raise ValueError(f"{who}: a rotation (yaw) needs the x and y columns, C >= 2; got C={int(C)}")
+    return (ctypes.c_double * len(vals))(*vals)
+
+
 def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True, divide_by_std=False,
-                    n_out=None, pick_out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first"):
+                    n_out=None, pick_out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first", augment=None):
     """Raw radar detections -> processed frames in one launch (pcaa_frames_from_raw): ``points`` [P, 5] fp32 or fp64 (x,
     y, z, doppler, linear power), ``offsets`` int32 [n + 1] (frame f owns rows ``offsets[f] .. offsets[f + 1] - 1``) ->
     fp32 ``[n_out, N, C]``, rows ``n .. n_out - 1`` zero (``n_out`` defaults to n).  ``pick`` int32 [n, N]: output point p
@@ -1674,8 +1687,12 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     [1]); nothing is checked on the host.  ``keep`` (k, or ``(lo, hi)`` for a count drawn per frame; ``keep_min`` = lo)
     and ``keep_rule`` ("first" / "random"): the frame keeps at most that many of its detections before the draw
     (pcaa_frames_from_raw_thin; device-drawn picks only; ``pick_out`` holds raw indices); a frame with no more
-    detections than its count has the bits it has without ``keep``."""
+    detections than its count has the bits it has without ``keep``.  ``augment`` (``datasets.augment_arguments``: yaw,
+    mirror, scale, speed, noise): the picked detections are moved in fp64 before the frame is centred, per track and per
+    detection under ``seed`` and ``frame_key`` (needed with supplied picks too), in the same launch
+    (pcaa_frames_from_raw_aug; ``datasets.frames_from_picks(augment=)`` restates it); neutral: today's call."""
     keep, keep_min, keep_rule = _keep_args("frames_from_raw", keep, keep_min, keep_rule, pick)
+    aug = _aug_args("frames_from_raw", augment, C)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("frames_from_raw.points: expected a float32 or float64 tensor")
     _chk(points, "frames_from_raw.points", None, 2)
@@ -1692,9 +1709,10 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
         _chk(pick, "frames_from_raw.pick", torch.int32, 2)
         if tuple(pick.shape) != (n, N):
             raise ValueError(f"frames_from_raw: pick must be [{n}, {N}], got {tuple(pick.shape)}")
-    elif n:
+    if (pick is None or aug is not None) and n:
         if frame_key is None:
-            raise ValueError("frames_from_raw: without picks every frame needs its key (frame_key int32 [n, 2])")
+            raise ValueError("frames_from_raw: without picks, and to augment, every frame needs its key (frame_key int32 "
+                             "[n, 2])")
         _chk(frame_key, "frames_from_raw.frame_key", torch.int32, 2)
         if tuple(frame_key.shape) != (n, 2):
             raise ValueError(f"frames_from_raw: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
@@ -1707,9 +1725,11 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     out = torch.empty((n_out, N, C), dtype=torch.float32, device=points.device)
     if n_out:
         args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-                None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-                _p(out), n_out, _p(pick_out), _p(err_flag), _s())
-        if keep:
+                None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
+                int(bool(divide_by_std)), _p(out), n_out, _p(pick_out), _p(err_flag), _s())
+        if aug is not None:
+            check(_lib.load().pcaa_frames_from_raw_aug(*args, keep, keep_min, keep_rule, aug), "pcaa_frames_from_raw_aug")
+        elif keep:
             check(_lib.load().pcaa_frames_from_raw_thin(*args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_thin")
         else:
             check(_lib.load().pcaa_frames_from_raw(*args), "pcaa_frames_from_raw")
@@ -1717,7 +1737,8 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
 
 
 def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
-                   divide_by_std=False, out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first"):
+                   divide_by_std=False, out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first",
+                   augment=None):
     """A batch of crops straight from the packed detections of a whole store, one launch (pcaa_crops_from_raw):
     ``points`` [P, 5] fp32 or fp64 and ``offsets`` int32 [F + 1] over ALL F frames of the store, ``start`` int32 [B] the
     store index of each crop's first frame -> fp32 ``[B, T, N, C]``, ``out[b, t]`` bit-equal to the frame
@@ -1725,8 +1746,10 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
     picks, ``frame_key`` row (int32 [F, 2]) and ``seed``.  Crops may overlap and repeat.  A frame that cannot be processed
     (the rule of ``frames_from_raw``) and a crop that leaves the store (``start[b] < 0`` or ``start[b] + T > F``) come back
     as zeros and set ``err_flag`` (int32 [1]); nothing is checked on the host.  ``out``: a [B, T, N, C] buffer to fill.
-    ``keep`` / ``keep_min`` / ``keep_rule``: as in ``frames_from_raw`` (pcaa_crops_from_raw_thin), the same frames."""
+    ``keep`` / ``keep_min`` / ``keep_rule``: as in ``frames_from_raw`` (pcaa_crops_from_raw_thin), the same frames;
+    ``augment``: as there (pcaa_crops_from_raw_aug), the same frames again -- a track's draws are shared by its windows."""
     keep, keep_min, keep_rule = _keep_args("crops_from_raw", keep, keep_min, keep_rule, pick)
+    aug = _aug_args("crops_from_raw", augment, C)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("crops_from_raw.points: expected a float32 or float64 tensor")
     _chk(points, "crops_from_raw.points", None, 2)
@@ -1743,9 +1766,10 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
         _chk(pick, "crops_from_raw.pick", torch.int32, 2)
         if tuple(pick.shape) != (F, N):
             raise ValueError(f"crops_from_raw: pick must be [{F}, {N}], got {tuple(pick.shape)}")
-    elif F:
+    if (pick is None or aug is not None) and F:
         if frame_key is None:
-            raise ValueError("crops_from_raw: without picks every frame needs its key (frame_key int32 [F, 2])")
+            raise ValueError("crops_from_raw: without picks, and to augment, every frame needs its key (frame_key int32 "
+                             "[F, 2])")
         _chk(frame_key, "crops_from_raw.frame_key", torch.int32, 2)
         if tuple(frame_key.shape) != (F, 2):
             raise ValueError(f"crops_from_raw: frame_key must be [{F}, 2], got {tuple(frame_key.shape)}")
@@ -1759,9 +1783,12 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
             raise ValueError(f"crops_from_raw: out must be [{B}, {T}, {N}, {C}], got {tuple(out.shape)}")
     if B:
         args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), F, _p(start), B, T, _p(pick),
-                None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-                _p(out), _p(err_flag), _s())
-        if keep:
+                None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
+                int(bool(divide_by_std)), _p(out), _p(err_flag), _s())
+        if aug is not None:
+            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw_aug(
+                *args, keep, keep_min, keep_rule, aug), "pcaa_crops_from_raw_aug"), 0.0, B * T * N * C * 4)
+        elif keep:
             _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw_thin(
                 *args, keep, keep_min, keep_rule), "pcaa_crops_from_raw_thin"), 0.0, B * T * N * C * 4)
         else:
@@ -1782,7 +1809,7 @@ def unique_table_rows(P, n, N, keep=0):
 
 def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
                            divide_by_std=False, M=None, pick_out=None, err_flag=None, keep=0, keep_min=None,
-                           keep_rule="first"):
+                           keep_rule="first", augment=None):
     """``frames_from_raw`` without the padding (pcaa_frames_from_raw_unique; arguments as there) -> ``(rows [M, C] fp32,
     weight [M] fp32, u_off [n + 1] int32)``: rows ``u_off[f] .. u_off[f + 1] - 1`` hold frame f's distinct picked
     detections in order of first occurrence, each bit-equal to the row ``frames_from_raw`` writes for that pick, ``weight``
@@ -1790,8 +1817,11 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
     weight 0; a bad frame is one zero row of weight N and sets ``err_flag``.  ``M`` defaults to ``unique_table_rows``.
     Two launches (the scan of ``u_off``, the rows); nothing comes back to the host.  ``keep`` / ``keep_min`` /
     ``keep_rule``: as in ``frames_from_raw`` (pcaa_frames_from_raw_unique_thin); frame f then owns ``min(card, k_f, N)``
-    rows and ``M`` defaults to ``unique_table_rows(P, n, N, keep)``."""
+    rows and ``M`` defaults to ``unique_table_rows(P, n, N, keep)``.  ``augment``: as in ``frames_from_raw``
+    (pcaa_frames_from_raw_unique_aug): the noise is keyed by the raw detection, so the distinct rows, their weights and
+    ``u_off`` are those without it and every row is the padded route's."""
     keep, keep_min, keep_rule = _keep_args("frames_from_raw_unique", keep, keep_min, keep_rule, pick)
+    aug = _aug_args("frames_from_raw_unique", augment, C)
     if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
         raise TypeError("frames_from_raw_unique.points: expected a float32 or float64 tensor")
     _chk(points, "frames_from_raw_unique.points", None, 2)
@@ -1810,9 +1840,10 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
         _chk(pick, "frames_from_raw_unique.pick", torch.int32, 2)
         if tuple(pick.shape) != (n, N):
             raise ValueError(f"frames_from_raw_unique: pick must be [{n}, {N}], got {tuple(pick.shape)}")
-    elif n:
+    if (pick is None or aug is not None) and n:
         if frame_key is None:
-            raise ValueError("frames_from_raw_unique: without picks every frame needs its key (frame_key int32 [n, 2])")
+            raise ValueError("frames_from_raw_unique: without picks, and to augment, every frame needs its key "
+                             "(frame_key int32 [n, 2])")
         _chk(frame_key, "frames_from_raw_unique.frame_key", torch.int32, 2)
         if tuple(frame_key.shape) != (n, 2):
             raise ValueError(f"frames_from_raw_unique: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
@@ -1827,10 +1858,13 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
     weight = torch.empty(M, dtype=torch.float32, device=dev)
     u_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
     args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-            None if pick is not None else _p(frame_key), seed, N, C, int(bool(standardize)), int(bool(divide_by_std)),
-            _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s())
+            None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
+            int(bool(divide_by_std)), _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s())
     nbytes = points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4
-    if keep:
+    if aug is not None:
+        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique_aug(
+            *args, keep, keep_min, keep_rule, aug), "pcaa_frames_from_raw_unique_aug"), 0.0, nbytes)
+    elif keep:
         _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique_thin(
             *args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_unique_thin"), 0.0, nbytes)
     else:
