@@ -205,28 +205,21 @@ class RawTrackBatcher:
     fresh pad / subset per epoch, reproducible from (seed, e).  ``picks`` (int32 [F, N] over the store's frames, e.g.
     ``datasets.draw_picks(store.cards(), N)``): host-drawn picks instead, the reference's own crops.  ``jitter``: every
     track's starts are shifted by a phase of (seed, epoch, serial) (``RawCrops.starts``).  Epochs count from 0 in the order
-    ``__iter__`` is called.  ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" /
-    "random"): point dropout -- every frame keeps at most that many of its detections before it is padded to N, by the
-    same launch (``ops.crops_from_raw(keep=...)``); the counts and the kept sets are drawn with the epoch's seed, so under
-    ``redraw="epoch"`` they are re-drawn per epoch as the padding is.  Not with ``picks``, which decide by themselves.
-    ``augment`` (``datasets.augment_arguments``: yaw, mirror, scale, speed, noise): the detections are turned, mirrored,
-    scaled and perturbed before each frame is centred, by the same launch (``ops.crops_from_raw(augment=...)``).  The draws
-    per track (angle, mirror, factors) and per detection (noise) use the epoch's draw seed: under ``redraw="epoch"`` they
-    are re-drawn every epoch, under ``"fixed"`` they are the same every epoch -- one fixed distortion of the store, which
-    is rarely what training wants.  All windows of a track share its draws within an epoch.  May be combined with
-    ``picks`` and with ``keep_points``."""
+    ``__iter__`` is called.  ``keep_points`` / ``keep_rule`` (point dropout) and ``augment`` (``datasets.RawPrep``, held
+    as ``prep``): applied by the same launch, drawn with the epoch's draw seed -- the counts, the kept sets, the draws per
+    track (angle, mirror, factors) and per detection (noise) are re-drawn every epoch under ``redraw="epoch"`` as the
+    padding is, and are the same every epoch under ``"fixed"``: one fixed distortion of the store, which is rarely what
+    training wants.  All windows of a track share its draws within an epoch.  ``keep_points`` not with ``picks``, which
+    decide by themselves; ``augment`` may be combined with ``picks`` and with ``keep_points``."""
 
     def __init__(self, view, batch_size, shuffle=True, drop_last=True, rank=0, world=1, group=None, seed=0, redraw="fixed",
                  jitter=False, picks=None, keep_points=0, keep_rule="first", augment=None):
         if redraw not in ("fixed", "epoch"):
             raise ValueError(f"RawTrackBatcher: redraw must be 'fixed' or 'epoch', got {redraw!r}")
-        if datasets.keep_arguments(keep_points, None, keep_rule, "RawTrackBatcher")[0] and picks is not None:
-            raise ValueError("RawTrackBatcher: keep_points thins the frames before the device draws their picks; supplied "
-                             "picks decide by themselves")
+        self.prep = datasets.RawPrep.of(keep_points, None, keep_rule, augment, "RawTrackBatcher")   # decided once, not per batch
+        self.prep.check("RawTrackBatcher", picks, view.C)
         self.keep_points, self.keep_rule = keep_points, keep_rule
-        self.augment = datasets.augment_arguments(augment, "RawTrackBatcher")    # the 11 parameters, None when neutral
-        if self.augment is not None and self.augment[0] != 0 and view.C < 2:
-            raise ValueError("RawTrackBatcher: a rotation (yaw) needs the x and y columns, C >= 2")
+        self.augment = self.prep.augment                 # the 11 parameters, None when neutral
         self.view, self.store = view, view.store
         self.batch_size, self.shuffle, self.drop_last = int(batch_size), shuffle, drop_last
         self.rank, self.world, self.group = int(rank), int(world), group
@@ -300,8 +293,7 @@ class RawTrackBatcher:
     def _crops(self, start):
         st, v = self.store, self.view
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, v.T, v.N, v.C, pick=self.picks, seed=self.draw_seed,
-                                frame_key=st.frame_key_dev, err_flag=self.err, keep=self.keep_points,
-                                keep_rule=self.keep_rule, augment=self.augment)  # [B,T,N,C]
+                                frame_key=st.frame_key_dev, err_flag=self.err, prep=self.prep)  # [B,T,N,C]
         return pm.permute(0, 3, 1, 2)
 
     def batch(self, idx):

@@ -21,6 +21,8 @@ part of ``generate_splits`` that decides which track goes to which split).
 ``SyntheticGaitDataset`` produces mmGait10-shaped crops from a seed; items are
 permuted views of point-major ``[T,N,C]`` storage.
 """
+import ctypes
+import dataclasses
 import math
 import os
 
@@ -358,6 +360,56 @@ def augment_arguments(augment, who="augment"):
     return None if tuple(vals) == _AUG_NEUTRAL else tuple(vals)
 
 
+@dataclasses.dataclass(frozen=True)
+class RawPrep:
+    """How a raw frame is prepared on its way to ``[N, C]``, decided once: what every raw route (``ops.frames_from_raw``,
+    ``crops_from_raw``, ``frames_from_raw_unique`` and all that call them) takes as ``prep=``, or builds from its keywords.
+
+    ``keep`` (k, or ``(lo, hi)`` for a count drawn per frame; ``keep_min`` = lo) and ``keep_rule`` ("first" / "random"):
+    the frame keeps at most that many of its detections before its picks are drawn (the ``_thin`` entry points;
+    device-drawn picks only, the picks are raw indices); a frame with no more detections than its count has the bits it
+    has without ``keep`` (``keep_arguments``; ``device_picks_host(keep=)`` restates the draw).  ``augment`` (yaw, mirror,
+    scale, speed, noise: ``augment_arguments``): the picked detections are moved in fp64 before the frame is centred,
+    per track and per detection under the call's seed and frame keys -- which it needs with supplied picks too -- in the
+    same launch (the ``_aug`` entry points; ``frames_from_picks(augment=)`` restates it).  Neutral values: the plain call.
+
+    Holds the three thinning ints, the ``AUG_PARAMS`` doubles (None when neutral), and what a call needs of them: the
+    entry point's ``suffix`` ("", "_thin", "_aug") and its trailing C arguments ``tail``."""
+    keep: int = 0
+    keep_min: int = 0
+    rule: int = 0
+    augment: tuple = None
+    suffix: str = ""
+    tail: tuple = ()
+
+    @classmethod
+    def of(cls, keep=0, keep_min=None, keep_rule="first", augment=None, who="RawPrep", prep=None):
+        """The keywords of a raw route normalised (``keep_arguments``, ``augment_arguments``: their errors, under ``who``);
+        ``prep``: one built earlier, returned as it is -- then the keywords must be at their defaults."""
+        if prep is not None:
+            if keep or keep_min is not None or keep_rule != "first" or augment is not None:
+                raise ValueError(f"{who}: prep= already says how the frames are prepared; give it or keep / keep_min / "
+                                 "keep_rule / augment, not both")
+            return prep
+        thin = keep_arguments(keep, keep_min, keep_rule, who)
+        aug = augment_arguments(augment, who)
+        if aug is not None:
+            return cls(*thin, aug, "_aug", thin + ((ctypes.c_double * AUG_PARAMS)(*aug),))
+        return cls(*thin, None, "_thin", thin) if thin[0] else cls()
+
+    def check(self, who, pick, C):
+        """the rules between the preparation and the call it serves (the C library checks them again)"""
+        if self.keep and pick is not None:
+            raise ValueError(f"{who}: keep thins the frames before the device draws their picks; supplied picks decide by "
+                             "themselves (datasets.draw_picks(force_pc_subsampling=k) for the reference's)")
+        if self.augment is not None and self.augment[0] != 0 and int(C) < 2:
+            raise ValueError(f"{who}: a rotation (yaw) needs the x and y columns, C >= 2; got C={int(C)}")
+
+    def needs_keys(self, pick):
+        """whether the frames' keys are read: by the device's own draw of the picks, and by the augmentation's draws"""
+        return pick is None or self.augment is not None
+
+
 def _unit(w):
     """a 32-bit hash word as a number in (0, 1): (w + 0.5) 2^-32, exact in fp64"""
     return (np.asarray(w).astype(np.float64) + 0.5) * 2.0 ** -32
@@ -644,11 +696,11 @@ class RawCrops:
             start = start + jitter_phases(seed, epoch, self.store.serial[self.track], np.minimum(self.hop, self.slack))
         return start.astype(np.int32)
 
-    def materialize(self, seed=0, picks=None, epoch=0, jitter=False, keep_points=0, keep_rule="first", augment=None):
+    def materialize(self, seed=0, picks=None, epoch=0, jitter=False, keep_points=0, keep_rule="first", augment=None,
+                    prep=None):
         """All crops written out by the batch kernel, one launch -> ``(pcs [M, C, T, N] view of point-major storage,
-        labels int64 [M])`` on the store's device: what the evaluation procedures take.  ``keep_points`` (k or ``(lo,
-        hi)``) / ``keep_rule``: every frame thinned to at most that many detections first (``keep_arguments``).
-        ``augment`` (``augment_arguments``): the detections moved in the same launch, drawn under ``seed``."""
+        labels int64 [M])`` on the store's device: what the evaluation procedures take.  ``keep_points`` / ``keep_rule`` /
+        ``augment``, or ``prep`` built from them: how every frame is prepared (:class:`RawPrep`), drawn under ``seed``."""
         from . import ops
         st = self.store
         if st.device is None:
@@ -659,7 +711,7 @@ class RawCrops:
         start = torch.from_numpy(self.starts(seed, epoch, jitter)).to(st.device)
         pm = ops.crops_from_raw(st.points_dev, st.offsets_dev, start, self.T, self.N, self.C, pick=picks, seed=seed,
                                 frame_key=st.frame_key_dev, err_flag=err, keep=keep_points, keep_rule=keep_rule,
-                                augment=augment)
+                                augment=augment, prep=prep)
         if int(err.item()):
             raise ValueError("RawCrops.materialize: a frame of the store cannot be processed (no detections, more than "
                              f"{ops.RAW_MAX_CARD}, or a pick outside its frame)")

@@ -131,20 +131,17 @@ def frame_keys(serial, first, n, dev):
     return host.to(dev, non_blocking=True)
 
 
-def raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, dedup_points=False, n_out=None, keep=0,
-               keep_rule="first", augment=None):
+def raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, dedup_points=False, n_out=None, prep=None):
     """Raw detections -> the padded frames [n_out or n, N, C] (``ops.frames_from_raw``) or, with ``dedup_points``, their
     distinct points ``(rows, weight, u_off)`` (``ops.frames_from_raw_unique``), one launch.  ``b``: of frames a .. b - 1 only
     (``offsets``, ``pick``, ``keys``: the whole track's).  ``err_flag``, the caller's, is set by a frame that cannot be processed.
-    ``keep`` (k or ``(lo, hi)``) / ``keep_rule``: the frames thinned first (the ``keep`` of ``ops.frames_from_raw``): the one
-    place the scorers' ``keep_points`` goes through.  ``augment``: the ``augment`` of ``ops.frames_from_raw``, likewise (the
-    frames' ``keys`` are then needed with supplied picks too)."""
+    ``prep`` (``datasets.RawPrep``; None: the frames as they are): how the scorers' frames are thinned and moved first."""
     if b is not None:
         offsets = offsets[a:b + 1]
         pick = None if pick is None else pick[a:b]
         keys = None if keys is None else keys[a:b]
     if dedup_points:
         return ops.frames_from_raw_unique(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, err_flag=err_flag,
-                                          keep=keep, keep_rule=keep_rule, augment=augment)
+                                          prep=prep)
     return ops.frames_from_raw(points, offsets, N, C, pick=pick, seed=seed, frame_key=keys, n_out=n_out, err_flag=err_flag,
-                               keep=keep, keep_rule=keep_rule, augment=augment)
+                               prep=prep)

@@ -20,6 +20,7 @@ from . import _lib, constants, frame_table
 from . import functional as F_hip
 from . import ops
 from ._lib import check
+from .datasets import RawPrep
 from .models import CGEncoder
 
 
@@ -104,13 +105,12 @@ def plan_frames(same, M, T=constants.NSTEPS, hop=constants.CROP_STEP):
     return first_t + within, win_row
 
 
-def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None, keep=0,
-                     keep_rule="first", augment=None):
-    """raw frames (``b``: frames a .. b - 1 of them; ``keep``: thinned first; ``augment``: moved first) -> their distinct
+def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0, b=None, mode=None, consts=None, prep=None):
+    """raw frames (``b``: frames a .. b - 1 of them; ``prep``: thinned and moved first) -> their distinct
     points and multiplicities -> (their [n, 1024] frame features, the PointNet layer records, rows of the compact table): the ``dedup_points``
     route of the raw entries"""
     rows, weight, u_off = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, err_flag, a, b, dedup_points=True,
-                                                 keep=keep, keep_rule=keep_rule, augment=augment)
+                                                 prep=prep)
     feats, saves = F_hip.encoder_frame_features_ragged(enc, rows, weight, u_off, u_off.numel() - 1, N, mode, consts=consts)
     return feats, saves, rows.shape[0]
 
@@ -278,30 +278,23 @@ class OpenSetScorer:
         PointNet block once and are pooled with their multiplicities (``ops.frames_from_raw_unique``,
         ``functional.encoder_frame_features_ragged``): the same features up to fp32 summation order, from
         ``sum(min(card, N))`` rows instead of ``F * N``.  ``last_rows_encoded`` is the number of table rows it ran.
-        ``keep_points`` (k, or ``(lo, hi)`` for a count drawn per frame) / ``keep_rule`` ("first" / "random"): the track as
-        a sparser radar would deliver it -- every frame keeps at most that many detections before it is padded to N
-        (``ops.frames_from_raw(keep=...)``; device-drawn picks only).  With ``dedup_points`` the table then holds at most
-        ``F * min(k, N)`` rows (in whole GEMM tiles).  ``augment`` (``datasets.augment_arguments``: yaw, mirror, scale,
-        speed, noise): the track as a person at another azimuth, of another size or pace, or a noisier sensor would deliver
-        it -- the detections are moved by the same launch before each frame is centred (``ops.frames_from_raw(augment=)``),
-        on both routes; the draws come from ``seed`` and the keys ``(track_key, f)``, with supplied ``pick`` too."""
+        ``keep_points`` / ``keep_rule`` / ``augment`` (``datasets.RawPrep``): the track as a sparser radar, a person at
+        another azimuth, of another size or pace, or a noisier sensor would deliver it, by the same launch on both routes;
+        the draws come from ``seed`` and the keys ``(track_key, f)``, those of ``augment`` with supplied ``pick`` too.  With
+        ``keep_points`` and ``dedup_points`` the table holds at most ``F * min(k, N)`` rows (in whole GEMM tiles)."""
         enc = self.encoder
         N, C = enc.nmax_points, enc.pc_block.pointnet1.module[0].weight.shape[1]
         F = frame_table.check_raw(points, offsets, pick, N, "embed_raw_track")
-        from .datasets import augment_arguments
-        augment = augment_arguments(augment, "embed_raw_track")
-        keyed = (pick is None or augment is not None) and F            # the augmentation draws need the keys as well
-        keys = frame_table.frame_keys(track_key, 0, F, points.device) if keyed else None
+        prep = RawPrep.of(keep_points, None, keep_rule, augment, "embed_raw_track")
+        keys = frame_table.frame_keys(track_key, 0, F, points.device) if prep.needs_keys(pick) and F else None
         if not dedup_points:
-            frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err, keep=keep_points,
-                                            keep_rule=keep_rule, augment=augment)
+            frames = frame_table.raw_frames(points, offsets, N, C, pick, seed, keys, self.raw_err, prep=prep)
             return self.embed_track(frames, hop, drop_last_aligned)
         step = max(self.batch_size * constants.NSTEPS, 1)
 
         def features(U):
             return self._chunk_features(((a, min(a + step, U)) for a in range(0, U, step)), lambda a, b: _ragged_features(
-                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, keep=keep_points, keep_rule=keep_rule,
-                augment=augment))
+                enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, prep=prep))
         return self._score_track(F, hop, drop_last_aligned, True, points.device, features)
 
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
@@ -478,14 +471,13 @@ def _sequential_split_on_device(split, scenarios_list, device):
     return crops.permute(0, 3, 1, 2), labels
 
 
-def _sequential_split_from_store(store, split, scenarios_list, N, keep_points=0, keep_rule="first", augment=None,
-                                 seed=0):
+def _sequential_split_from_store(store, split, scenarios_list, N, seed=0, **how):
     """The same tensors from a ``datasets.RawTrackStore`` (already assigned and on the device): the split's crops in
     sequential order, written out by one ``pcaa_crops_from_raw`` launch under the fixed draws of ``seed``; no files.
-    ``keep_points``: every frame thinned to at most that many detections by the same launch; ``augment``: its detections
-    moved by it; ``seed``: of the picks and of the augmentation draws alike."""
+    ``how``: ``prep=`` (or the keywords it is built from) of ``RawCrops.materialize``: the frames thinned and moved by the
+    same launch; ``seed``: of the picks and of those draws alike."""
     return store.crops(split, N=N, C=constants.NFEATURES, order="sequential", scenarios=scenarios_list).materialize(
-        seed=seed, keep_points=keep_points, keep_rule=keep_rule, augment=augment)
+        seed=seed, **how)
 
 
 def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_points=True, keep_rule="first"):
@@ -504,9 +496,9 @@ def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_
     scorer = OpenSetScorer(encoder, means)
     out = {}
     for keep in keeps:
-        sets = []
+        sets, prep = [], RawPrep.of(keep, None, keep_rule, who="point_sweep")
         for split in (SPLIT.TEST, SPLIT.UNSEEN):
-            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, keep, keep_rule)
+            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, prep=prep)
             preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
             sets += [(preds, lik), labels]
             del pcs
@@ -534,9 +526,9 @@ def perturbation_sweep(encoder, means, store, augments, ks, N, seed=0, refit=Fal
     scorer = OpenSetScorer(encoder, means)
 
     def embedded(augment):
-        sets = []
+        sets, prep = [], RawPrep.of(augment=augment, who="perturbation_sweep")
         for split in (SPLIT.TEST, SPLIT.UNSEEN):
-            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, augment=augment, seed=seed)
+            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, seed, prep=prep)
             preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
             sets += [(preds, lik), labels]
             del pcs
@@ -586,8 +578,7 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
         if force_pc_subsampling:
             raise ValueError("CGAAE_inference: keep_points and force_pc_subsampling are the same sweep on two routes; give one")
         keep_points = int(keep_points)
-        from .datasets import keep_arguments
-        keep_arguments(keep_points, None, keep_rule, "CGAAE_inference")
+    prep = RawPrep.of(keep_points, None, keep_rule, who="CGAAE_inference") if raw_store is not None else None
     subsampled = keep_points or force_pc_subsampling
     suffix = _file_suffix(subsampled, scenarios_list)
     if suffix is None:
@@ -609,9 +600,9 @@ def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None
                 config = pickle.load(f)
             raw_store.assign_like_generate_splits(config["TRAIN_CLASSES"], seed=0).to_device(dev)
             known_pcs, known_labels = _sequential_split_from_store(raw_store, SPLIT.TEST, scenarios_list, config["NMAX"],
-                                                                   keep_points, keep_rule)
+                                                                   prep=prep)
             unseen_pcs, unseen_labels = _sequential_split_from_store(raw_store, SPLIT.UNSEEN, scenarios_list, config["NMAX"],
-                                                                     keep_points, keep_rule)
+                                                                     prep=prep)
         else:
             known_pcs, known_labels = _sequential_split_on_device(SPLIT.TEST, scenarios_list, dev)
             unseen_pcs, unseen_labels = _sequential_split_on_device(SPLIT.UNSEEN, scenarios_list, dev)
@@ -653,13 +644,11 @@ class _LiveScorer:
         self._width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]      # frame-feature width: a ring row
         self._N, self._C = encoder.nmax_points, encoder.pc_block.pointnet1.module[0].weight.shape[1]   # a raw frame becomes [N, C]
         self.last_pointnet_saves = None
-        self.keep_points, self.keep_rule = 0, "first"
 
     def _set_keep(self, keep_points, keep_rule):
         """``push_raw`` scores the stream as a sparser radar would deliver it: every frame keeps at most ``keep_points``
-        (k, or ``(lo, hi)``) detections under ``keep_rule`` before it is padded to N (``datasets.keep_arguments``)"""
-        from .datasets import keep_arguments
-        keep_arguments(keep_points, None, keep_rule, type(self).__name__)        # refused here, not at the first push
+        detections under ``keep_rule`` before it is padded to N (``datasets.RawPrep``, built here once)"""
+        self.prep = RawPrep.of(keep_points, None, keep_rule, who=type(self).__name__)    # refused here, not at the first push
         self.keep_points, self.keep_rule = keep_points, keep_rule
 
     def _check_eval(self):
@@ -744,15 +733,15 @@ class StreamingScorer(_LiveScorer):
         q = F_hip.frame_pad_quantum(self._N)
         keys = frame_table.frame_keys(self.serial, self.n_frames, n, points.device) if pick is None and n else None
         raw = (points, offsets, self._N, self._C, pick, self.seed, keys, self.raw_err)
-        keep = dict(keep=self.keep_points, keep_rule=self.keep_rule)
         out = []
         for a in range(0, n, self.max_push):
             b = min(a + self.max_push, n)
             if self.dedup_points:
-                feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, a, b, **keep)
+                feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, a, b, prep=self.prep)
                 out.append(self._push_features(feats, b - a))
             else:
-                out.append(self._push_padded(frame_table.raw_frames(*raw, a, b, n_out=b - a + (a - b) % q, **keep), b - a))
+                out.append(self._push_padded(frame_table.raw_frames(*raw, a, b, n_out=b - a + (a - b) % q, prep=self.prep),
+                                             b - a))
         return self._gather(out)
 
     def _push(self, frames):
@@ -1044,11 +1033,11 @@ class MultiStreamScorer(_LiveScorer):
             return self._empty(plan, self.ring.device)
         raw = (points, offsets, self._N, self._C, pick, self.seed, part["frame_key"].view(n, 2) if pick is None else None,
                self.raw_err)
-        keep = dict(keep=self.keep_points, keep_rule=self.keep_rule)
         if self.dedup_points:
-            feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, mode=mode, consts=self._consts, **keep)
+            feats, self.last_pointnet_saves, _ = _ragged_features(self.encoder, *raw, mode=mode, consts=self._consts,
+                                                                  prep=self.prep)
             return self._finish_tick_features(sids, plan, part, mode, feats)
-        return self._finish_tick(sids, plan, part, mode, frame_table.raw_frames(*raw, n_out=plan.dst_row.size, **keep))
+        return self._finish_tick(sids, plan, part, mode, frame_table.raw_frames(*raw, n_out=plan.dst_row.size, prep=self.prep))
 
     def _begin_tick(self, sids, counts, n, N, what, want_keys, pad_to=None):
         """the arguments of a tick checked, its plan made and (unless the tick is empty) uploaded -> (sids, plan, the

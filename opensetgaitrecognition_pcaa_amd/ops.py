@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_ELU, ACT_NONE, KC, PCAA_BF16, PCAA_F32, RC, check
+from .datasets import RawPrep
 
 PCAA_SPLIT_F16 = 2      # include/pcaa_hip.h
 
@@ -1651,32 +1652,55 @@ RAW_MAX_CARD = 1024       # PCAA_RAW_MAX_CARD / PCAA_RAW_MAX_POINTS of include/p
 RAW_MAX_POINTS = 1024
 
 
-def _keep_args(who, keep, keep_min, keep_rule, pick):
-    """the thinning arguments of a raw entry point (``datasets.keep_arguments``: k, ``(lo, hi)`` or 0) -> the three ints
-    the ``_thin`` entry points take, (0, 0, 0) for the plain ones; supplied picks decide by themselves"""
-    from .datasets import keep_arguments
-    args = keep_arguments(keep, keep_min, keep_rule, who)
-    if args[0] and pick is not None:
-        raise ValueError(f"{who}: keep thins the frames before the device draws their picks; supplied picks decide by "
-                         "themselves (datasets.draw_picks(force_pc_subsampling=k) for the reference's)")
-    return args
+def _raw_entry(base, points, offsets, N, C, pick, seed, frame_key, standardize, divide_by_std, pick_out, err_flag, keep,
+               keep_min, keep_rule, augment, prep):
+    """What the raw routes share: the preparation decided (``datasets.RawPrep``: built from the keywords, or ``prep``) and
+    checked against the call before any tensor is looked at, the inputs checked, the frames' keys required where the
+    preparation reads them -> ``(prep, n, N, C, launch)``: ``n`` frames under ``offsets``, and ``launch(window, outs)`` =
+    ``pcaa_<base><prep.suffix>(points .., n, *window, pick .., divide_by_std, *outs, err_flag, stream, *prep.tail)``."""
+    prep = RawPrep.of(keep, keep_min, keep_rule, augment, base, prep)
+    prep.check(base, pick, C)
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{base}.points: expected a float32 or float64 tensor")
+    _chk(points, base + ".points", None, 2)
+    _chk(offsets, base + ".offsets", torch.int32, 1)
+    N, C, seed = int(N), int(C), int(seed)
+    n = offsets.numel() - 1
+    if points.shape[1] != 5 or n < 0 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
+        raise ValueError(f"{base}: needs points [P, 5], offsets [n + 1], 1 <= N <= {RAW_MAX_POINTS}, 1 <= C <= 5; got "
+                         f"points {tuple(points.shape)}, n={n}, N={N}, C={C}")
+    if not -2 ** 63 <= seed < 2 ** 63:
+        raise ValueError(f"{base}: the seed must fit 64 bits")
 
+    def per_frame(t, name, width):
+        _chk(t, f"{base}.{name}", torch.int32, 2)
+        if tuple(t.shape) != (n, width):
+            raise ValueError(f"{base}: {name} must be [{n}, {width}], got {tuple(t.shape)}")
 
-def _aug_args(who, augment, C):
-    """the augmentation of a raw entry point (``datasets.augment_arguments``: a dict, or None) -> the host array of
-    PCAA_RAW_AUG_PARAMS doubles the ``_aug`` entry points read, None for the neutral one: the caller then makes the call it
-    makes without augmentation"""
-    from .datasets import augment_arguments
-    vals = augment_arguments(augment, who)
-    if vals is None:
-        return None
-    if vals[0] != 0 and int(C) < 2:
-        raise ValueError(f"{who}: a rotation (yaw) needs the x and y columns, C >= 2; got C={int(C)}")
-    return (ctypes.c_double * len(vals))(*vals)
+    if pick is not None:
+        per_frame(pick, "pick", N)
+    keyed = prep.needs_keys(pick)
+    if keyed and n:
+        if frame_key is None:
+            raise ValueError(f"{base}: without picks, and to augment, every frame needs its key (frame_key int32 [n, 2])")
+        per_frame(frame_key, "frame_key", 2)
+    if pick_out is not None:
+        per_frame(pick_out, "pick_out", N)
+    if err_flag is not None:
+        _chk(err_flag, base + ".err_flag", torch.int32)
+    head = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n)
+    mid = (_p(pick), _p(frame_key) if keyed else None, seed, N, C, int(bool(standardize)), int(bool(divide_by_std)))
+    name = "pcaa_" + base + prep.suffix
+
+    def launch(window, outs):
+        check(getattr(_lib.load(), name)(*head, *window, *mid, *outs, _p(err_flag), _s(), *prep.tail), name)
+
+    return prep, n, N, C, launch
 
 
 def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True, divide_by_std=False,
-                    n_out=None, pick_out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first", augment=None):
+                    n_out=None, pick_out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first", augment=None,
+                    prep=None):
     """Raw radar detections -> processed frames in one launch (pcaa_frames_from_raw): ``points`` [P, 5] fp32 or fp64 (x,
     y, z, doppler, linear power), ``offsets`` int32 [n + 1] (frame f owns rows ``offsets[f] .. offsets[f + 1] - 1``) ->
     fp32 ``[n_out, N, C]``, rows ``n .. n_out - 1`` zero (``n_out`` defaults to n).  ``pick`` int32 [n, N]: output point p
@@ -1684,61 +1708,23 @@ def frames_from_raw(points, offsets, N, C, *, pick=None, seed=0, frame_key=None,
     kernel draws them from ``frame_key`` int32 [n, 2] and ``seed`` (``datasets.device_picks_host`` restates the draw).
     ``pick_out`` int32 [n, N]: receives the picks used.  A frame that cannot be processed (cardinality < 1 or >
     RAW_MAX_CARD, offsets outside the points, a pick outside the frame) comes back as zeros and sets ``err_flag`` (int32
-    [1]); nothing is checked on the host.  ``keep`` (k, or ``(lo, hi)`` for a count drawn per frame; ``keep_min`` = lo)
-    and ``keep_rule`` ("first" / "random"): the frame keeps at most that many of its detections before the draw
-    (pcaa_frames_from_raw_thin; device-drawn picks only; ``pick_out`` holds raw indices); a frame with no more
-    detections than its count has the bits it has without ``keep``.  ``augment`` (``datasets.augment_arguments``: yaw,
-    mirror, scale, speed, noise): the picked detections are moved in fp64 before the frame is centred, per track and per
-    detection under ``seed`` and ``frame_key`` (needed with supplied picks too), in the same launch
-    (pcaa_frames_from_raw_aug; ``datasets.frames_from_picks(augment=)`` restates it); neutral: today's call."""
-    keep, keep_min, keep_rule = _keep_args("frames_from_raw", keep, keep_min, keep_rule, pick)
-    aug = _aug_args("frames_from_raw", augment, C)
-    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
-        raise TypeError("frames_from_raw.points: expected a float32 or float64 tensor")
-    _chk(points, "frames_from_raw.points", None, 2)
-    _chk(offsets, "frames_from_raw.offsets", torch.int32, 1)
-    N, C, seed = int(N), int(C), int(seed)
-    n = offsets.numel() - 1
+    [1]); nothing is checked on the host.  ``keep`` / ``keep_min`` / ``keep_rule`` / ``augment``, or ``prep`` built from
+    them: the frames thinned and moved first, by the same launch (``datasets.RawPrep``: pcaa_frames_from_raw_thin,
+    pcaa_frames_from_raw_aug); neutral: the plain call."""
+    _, n, N, C, launch = _raw_entry("frames_from_raw", points, offsets, N, C, pick, seed, frame_key, standardize,
+                                    divide_by_std, pick_out, err_flag, keep, keep_min, keep_rule, augment, prep)
     n_out = n if n_out is None else int(n_out)
-    if points.shape[1] != 5 or n < 0 or n_out < n or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
-        raise ValueError(f"frames_from_raw: needs points [P, 5], offsets [n + 1], n_out >= n, 1 <= N <= {RAW_MAX_POINTS}, "
-                         f"1 <= C <= 5; got points {tuple(points.shape)}, n={n}, n_out={n_out}, N={N}, C={C}")
-    if not -2 ** 63 <= seed < 2 ** 63:
-        raise ValueError("frames_from_raw: the seed must fit 64 bits")
-    if pick is not None:
-        _chk(pick, "frames_from_raw.pick", torch.int32, 2)
-        if tuple(pick.shape) != (n, N):
-            raise ValueError(f"frames_from_raw: pick must be [{n}, {N}], got {tuple(pick.shape)}")
-    if (pick is None or aug is not None) and n:
-        if frame_key is None:
-            raise ValueError("frames_from_raw: without picks, and to augment, every frame needs its key (frame_key int32 "
-                             "[n, 2])")
-        _chk(frame_key, "frames_from_raw.frame_key", torch.int32, 2)
-        if tuple(frame_key.shape) != (n, 2):
-            raise ValueError(f"frames_from_raw: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
-    if pick_out is not None:
-        _chk(pick_out, "frames_from_raw.pick_out", torch.int32, 2)
-        if tuple(pick_out.shape) != (n, N):
-            raise ValueError(f"frames_from_raw: pick_out must be [{n}, {N}], got {tuple(pick_out.shape)}")
-    if err_flag is not None:
-        _chk(err_flag, "frames_from_raw.err_flag", torch.int32)
+    if n_out < n:
+        raise ValueError(f"frames_from_raw: needs n_out >= n, got n={n}, n_out={n_out}")
     out = torch.empty((n_out, N, C), dtype=torch.float32, device=points.device)
     if n_out:
-        args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-                None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
-                int(bool(divide_by_std)), _p(out), n_out, _p(pick_out), _p(err_flag), _s())
-        if aug is not None:
-            check(_lib.load().pcaa_frames_from_raw_aug(*args, keep, keep_min, keep_rule, aug), "pcaa_frames_from_raw_aug")
-        elif keep:
-            check(_lib.load().pcaa_frames_from_raw_thin(*args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_thin")
-        else:
-            check(_lib.load().pcaa_frames_from_raw(*args), "pcaa_frames_from_raw")
+        launch((), (_p(out), n_out, _p(pick_out)))
     return out
 
 
 def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
                    divide_by_std=False, out=None, err_flag=None, keep=0, keep_min=None, keep_rule="first",
-                   augment=None):
+                   augment=None, prep=None):
     """A batch of crops straight from the packed detections of a whole store, one launch (pcaa_crops_from_raw):
     ``points`` [P, 5] fp32 or fp64 and ``offsets`` int32 [F + 1] over ALL F frames of the store, ``start`` int32 [B] the
     store index of each crop's first frame -> fp32 ``[B, T, N, C]``, ``out[b, t]`` bit-equal to the frame
@@ -1746,35 +1732,14 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
     picks, ``frame_key`` row (int32 [F, 2]) and ``seed``.  Crops may overlap and repeat.  A frame that cannot be processed
     (the rule of ``frames_from_raw``) and a crop that leaves the store (``start[b] < 0`` or ``start[b] + T > F``) come back
     as zeros and set ``err_flag`` (int32 [1]); nothing is checked on the host.  ``out``: a [B, T, N, C] buffer to fill.
-    ``keep`` / ``keep_min`` / ``keep_rule``: as in ``frames_from_raw`` (pcaa_crops_from_raw_thin), the same frames;
-    ``augment``: as there (pcaa_crops_from_raw_aug), the same frames again -- a track's draws are shared by its windows."""
-    keep, keep_min, keep_rule = _keep_args("crops_from_raw", keep, keep_min, keep_rule, pick)
-    aug = _aug_args("crops_from_raw", augment, C)
-    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
-        raise TypeError("crops_from_raw.points: expected a float32 or float64 tensor")
-    _chk(points, "crops_from_raw.points", None, 2)
-    _chk(offsets, "crops_from_raw.offsets", torch.int32, 1)
+    ``keep`` / ``keep_min`` / ``keep_rule`` / ``augment`` or ``prep``: as in ``frames_from_raw`` (pcaa_crops_from_raw_thin,
+    pcaa_crops_from_raw_aug), the same frames -- a track's augmentation draws are shared by its windows."""
+    _, F, N, C, launch = _raw_entry("crops_from_raw", points, offsets, N, C, pick, seed, frame_key, standardize,
+                                    divide_by_std, None, err_flag, keep, keep_min, keep_rule, augment, prep)
     _chk(start, "crops_from_raw.start", torch.int32, 1)
-    T, N, C, seed = int(T), int(N), int(C), int(seed)
-    F, B = offsets.numel() - 1, start.numel()
-    if points.shape[1] != 5 or F < 0 or T < 1 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5 or B * T >= 2 ** 31:
-        raise ValueError(f"crops_from_raw: needs points [P, 5], offsets [F + 1], T >= 1, 1 <= N <= {RAW_MAX_POINTS}, "
-                         f"1 <= C <= 5, B T < 2^31; got points {tuple(points.shape)}, F={F}, B={B}, T={T}, N={N}, C={C}")
-    if not -2 ** 63 <= seed < 2 ** 63:
-        raise ValueError("crops_from_raw: the seed must fit 64 bits")
-    if pick is not None:
-        _chk(pick, "crops_from_raw.pick", torch.int32, 2)
-        if tuple(pick.shape) != (F, N):
-            raise ValueError(f"crops_from_raw: pick must be [{F}, {N}], got {tuple(pick.shape)}")
-    if (pick is None or aug is not None) and F:
-        if frame_key is None:
-            raise ValueError("crops_from_raw: without picks, and to augment, every frame needs its key (frame_key int32 "
-                             "[F, 2])")
-        _chk(frame_key, "crops_from_raw.frame_key", torch.int32, 2)
-        if tuple(frame_key.shape) != (F, 2):
-            raise ValueError(f"crops_from_raw: frame_key must be [{F}, 2], got {tuple(frame_key.shape)}")
-    if err_flag is not None:
-        _chk(err_flag, "crops_from_raw.err_flag", torch.int32)
+    T, B = int(T), start.numel()
+    if T < 1 or B * T >= 2 ** 31:
+        raise ValueError(f"crops_from_raw: needs T >= 1, B T < 2^31; got B={B}, T={T}")
     if out is None:
         out = torch.empty((B, T, N, C), dtype=torch.float32, device=points.device)
     else:
@@ -1782,18 +1747,7 @@ def crops_from_raw(points, offsets, start, T, N, C, *, pick=None, seed=0, frame_
         if tuple(out.shape) != (B, T, N, C):
             raise ValueError(f"crops_from_raw: out must be [{B}, {T}, {N}, {C}], got {tuple(out.shape)}")
     if B:
-        args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), F, _p(start), B, T, _p(pick),
-                None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
-                int(bool(divide_by_std)), _p(out), _p(err_flag), _s())
-        if aug is not None:
-            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw_aug(
-                *args, keep, keep_min, keep_rule, aug), "pcaa_crops_from_raw_aug"), 0.0, B * T * N * C * 4)
-        elif keep:
-            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw_thin(
-                *args, keep, keep_min, keep_rule), "pcaa_crops_from_raw_thin"), 0.0, B * T * N * C * 4)
-        else:
-            _timed("crops_from_raw_kernel", lambda: check(_lib.load().pcaa_crops_from_raw(*args), "pcaa_crops_from_raw"),
-                   0.0, B * T * N * C * 4)
+        _timed("crops_from_raw_kernel", lambda: launch((_p(start), B, T), (_p(out),)), 0.0, B * T * N * C * 4)
     return out
 
 
@@ -1809,67 +1763,27 @@ def unique_table_rows(P, n, N, keep=0):
 
 def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_key=None, standardize=True,
                            divide_by_std=False, M=None, pick_out=None, err_flag=None, keep=0, keep_min=None,
-                           keep_rule="first", augment=None):
+                           keep_rule="first", augment=None, prep=None):
     """``frames_from_raw`` without the padding (pcaa_frames_from_raw_unique; arguments as there) -> ``(rows [M, C] fp32,
     weight [M] fp32, u_off [n + 1] int32)``: rows ``u_off[f] .. u_off[f + 1] - 1`` hold frame f's distinct picked
     detections in order of first occurrence, each bit-equal to the row ``frames_from_raw`` writes for that pick, ``weight``
     how often it was picked.  Unused rows of a frame's ``min(card, N)`` and the rows from ``u_off[n]`` on are zero with
     weight 0; a bad frame is one zero row of weight N and sets ``err_flag``.  ``M`` defaults to ``unique_table_rows``.
-    Two launches (the scan of ``u_off``, the rows); nothing comes back to the host.  ``keep`` / ``keep_min`` /
-    ``keep_rule``: as in ``frames_from_raw`` (pcaa_frames_from_raw_unique_thin); frame f then owns ``min(card, k_f, N)``
-    rows and ``M`` defaults to ``unique_table_rows(P, n, N, keep)``.  ``augment``: as in ``frames_from_raw``
-    (pcaa_frames_from_raw_unique_aug): the noise is keyed by the raw detection, so the distinct rows, their weights and
-    ``u_off`` are those without it and every row is the padded route's."""
-    keep, keep_min, keep_rule = _keep_args("frames_from_raw_unique", keep, keep_min, keep_rule, pick)
-    aug = _aug_args("frames_from_raw_unique", augment, C)
-    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
-        raise TypeError("frames_from_raw_unique.points: expected a float32 or float64 tensor")
-    _chk(points, "frames_from_raw_unique.points", None, 2)
-    _chk(offsets, "frames_from_raw_unique.offsets", torch.int32, 1)
-    N, C, seed = int(N), int(C), int(seed)
-    n = offsets.numel() - 1
-    if points.shape[1] != 5 or n < 0 or not 1 <= N <= RAW_MAX_POINTS or not 1 <= C <= 5:
-        raise ValueError(f"frames_from_raw_unique: needs points [P, 5], offsets [n + 1], 1 <= N <= {RAW_MAX_POINTS}, "
-                         f"1 <= C <= 5; got points {tuple(points.shape)}, n={n}, N={N}, C={C}")
-    M = unique_table_rows(points.shape[0], n, N, keep) if M is None else int(M)
+    Two launches (the scan of ``u_off``, the rows); nothing comes back to the host.  Thinned
+    (pcaa_frames_from_raw_unique_thin), frame f owns ``min(card, k_f, N)`` rows and ``M`` defaults to
+    ``unique_table_rows(P, n, N, keep)``.  Augmented (pcaa_frames_from_raw_unique_aug), the noise is keyed by the raw
+    detection, so the distinct rows, their weights and ``u_off`` are those without it and every row is the padded route's."""
+    prep, n, N, C, launch = _raw_entry("frames_from_raw_unique", points, offsets, N, C, pick, seed, frame_key, standardize,
+                                       divide_by_std, pick_out, err_flag, keep, keep_min, keep_rule, augment, prep)
+    M = unique_table_rows(points.shape[0], n, N, prep.keep) if M is None else int(M)
     if not 1 <= M < 2 ** 31 or n * RAW_MAX_POINTS >= 2 ** 31:
         raise ValueError(f"frames_from_raw_unique: needs 1 <= M < 2^31 and n * {RAW_MAX_POINTS} < 2^31, got M={M}, n={n}")
-    if not -2 ** 63 <= seed < 2 ** 63:
-        raise ValueError("frames_from_raw_unique: the seed must fit 64 bits")
-    if pick is not None:
-        _chk(pick, "frames_from_raw_unique.pick", torch.int32, 2)
-        if tuple(pick.shape) != (n, N):
-            raise ValueError(f"frames_from_raw_unique: pick must be [{n}, {N}], got {tuple(pick.shape)}")
-    if (pick is None or aug is not None) and n:
-        if frame_key is None:
-            raise ValueError("frames_from_raw_unique: without picks, and to augment, every frame needs its key "
-                             "(frame_key int32 [n, 2])")
-        _chk(frame_key, "frames_from_raw_unique.frame_key", torch.int32, 2)
-        if tuple(frame_key.shape) != (n, 2):
-            raise ValueError(f"frames_from_raw_unique: frame_key must be [{n}, 2], got {tuple(frame_key.shape)}")
-    if pick_out is not None:
-        _chk(pick_out, "frames_from_raw_unique.pick_out", torch.int32, 2)
-        if tuple(pick_out.shape) != (n, N):
-            raise ValueError(f"frames_from_raw_unique: pick_out must be [{n}, {N}], got {tuple(pick_out.shape)}")
-    if err_flag is not None:
-        _chk(err_flag, "frames_from_raw_unique.err_flag", torch.int32)
     dev = points.device
     rows = torch.empty((M, C), dtype=torch.float32, device=dev)
     weight = torch.empty(M, dtype=torch.float32, device=dev)
     u_off = torch.empty(n + 1, dtype=torch.int32, device=dev)
-    args = (_p(points), int(points.dtype == torch.float64), points.shape[0], _p(offsets), n, _p(pick),
-            None if pick is not None and aug is None else _p(frame_key), seed, N, C, int(bool(standardize)),
-            int(bool(divide_by_std)), _p(rows), _p(weight), _p(u_off), M, _p(pick_out), _p(err_flag), _s())
-    nbytes = points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4
-    if aug is not None:
-        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique_aug(
-            *args, keep, keep_min, keep_rule, aug), "pcaa_frames_from_raw_unique_aug"), 0.0, nbytes)
-    elif keep:
-        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique_thin(
-            *args, keep, keep_min, keep_rule), "pcaa_frames_from_raw_unique_thin"), 0.0, nbytes)
-    else:
-        _timed("frames_from_raw_unique_kernel", lambda: check(_lib.load().pcaa_frames_from_raw_unique(*args),
-                                                              "pcaa_frames_from_raw_unique"), 0.0, nbytes)
+    _timed("frames_from_raw_unique_kernel", lambda: launch((), (_p(rows), _p(weight), _p(u_off), M, _p(pick_out))), 0.0,
+           points.shape[0] * 5 * points.element_size() + M * (C + 1) * 4)
     return rows, weight, u_off
 
 

@@ -234,7 +234,7 @@ def test_the_augmented_launch_receives_the_epochs_seed(redraw, monkeypatch):
     seen = []
 
     def fake(points, offsets, start, T, N, C, **kw):             # stands in for the launch: records what it is given
-        seen.append((kw["seed"], kw["augment"]))
+        seen.append((kw["seed"], kw["prep"].augment))
         return torch.zeros((1, T, N, C))
 
     monkeypatch.setattr(batcher.ops, "crops_from_raw", fake)
