@@ -482,7 +482,7 @@ int pcaa_kvote(const double* lik, const long long* preds, double threshold, int 
  * fwd/dgrad split the contraction into `nsplit` slabs in `ws` (>= nsplit*M*N resp. nsplit*M*K
  * floats) and reduce them deterministically; nsplit must come from pcaa_skinny_splits (kind 0
  * fwd, 1 dgrad; 2 / 3: the _exact forms) -- the deepest split whose grid still fits the chip's resident workgroups of
- * that kernel in ONE round.  pcaa_skinny_supported: M <= 64, N and K multiples of 64 and >= 128. */
+ * that kernel in ONE round.  pcaa_skinny_supported: 1 <= M <= 64, N and K multiples of 64, N >= 128, K >= 64, N K < 2^31 - 2^20. */
 int pcaa_skinny_supported(int M, int N, int K);
 int pcaa_skinny_splits(int kind, int M, int N, int K);
 int pcaa_skinny_linear_fwd(const float* x, long ldx, const float* W, long ldw, const float* bias, int act,

@@ -362,7 +362,7 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float* __restrict
     lds_barrier();
   }
   if (gridDim.y == 1) {
-    // no split (a contraction of one or two chunks, or more column groups than the chip holds workgroups): `slabs` is the
+    // no split (a contraction of one to three chunks, or more column groups than the chip holds workgroups): `slabs` is the
     // output itself and the reduction kernel's epilogue -- bias, ELU, in its order of operations -- runs here: one launch
     // less on the decoder's dependent chain (the 64 -> S/16 first layer)
     const int col = n0 + l31;
