@@ -681,6 +681,51 @@ int pcaa_stream_score(const float* logits, const float* sup_fv, const float* mea
                       double threshold, int k, int n_labels, int n_classes, double* hist_lik, long long* hist_pred,
                       int max_streams, long long* preds, double* lik, long long* votes, int n_votes, void* stream);
 
+/* ------------------------------------------------------------------ run-time enrolment (gallery.hip)
+ * Added after ABI 29 like pcaa_crops_from_raw (the version is unchanged: a library without these entry points fails to
+ * load by name).  A gallery holds modes that did not come from training, beside the K prior means, in three device
+ * buffers: sums fp64 [E_max, D], counts int32 [E_max], centroids fp32 [E_max, D].  Slot e with counts[e] > 0 is a live
+ * mode N(centroids[e], I) and is identity e; a slot with count 0 contributes nothing anywhere.  E is the host's
+ * high-water mark of slots ever used: the kernels scan slots 0 .. E - 1.
+ *
+ * pcaa_gallery_accumulate: sums[slot] += (double)fv[rows[i]] for i = 0 .. m - 1 in that order, plain fp64 adds (rows:
+ * int32 [m] on the device, or NULL for rows 0 .. m - 1 of fv [n_rows, D]); then counts[slot] += the number added and
+ * centroids[slot] = (float)(sums[slot] / counts[slot]).  A row index outside [0, n_rows) is skipped and sets *err_flag
+ * (may be NULL).  Repeated calls continue the running sum.  One launch; on the host the centroid is
+ * np.float32(cumsum_in_float64[-1] / count), bit for bit. */
+int pcaa_gallery_accumulate(const float* fv, int n_rows, int D, const int* rows, int m, int slot, int E_max,
+                            double* sums, int* counts, float* centroids, int* err_flag, void* stream);
+/* B windows sup_fv [B, D] with the classifier's preds [B] against means [Kc, D] and the gallery:
+ *   lik[b]    = (acc_prior + acc_gallery) / Kc: acc_prior the sum pcaa_joint_likelihood forms (same operations, same
+ *               order, before its division), acc_gallery the sum of exp(-0.5 (D log 2pi + |x - c_e|^2)) over the live
+ *               slots in fp64 (every lane of a wavefront adds its slots e = lane, lane + 64, ... in ascending order, the
+ *               64 partials meet in a fixed butterfly).  The divisor stays Kc: with an empty gallery (acc_gallery = +0.0)
+ *               lik is bit-equal to pcaa_joint_likelihood's.
+ *   near[b]   = the index in 0 .. Kc + E - 1 (prior modes first) of the mode with the smallest fp64 squared distance,
+ *               the lowest index on exact ties;
+ *   labels[b] = preds[b] when near < Kc, else n_labels + 1 + (near - Kc); n_labels stays "unknown".
+ * One wavefront per window: a window's outputs do not depend on B, its position or the grid.  E = 0: centroids and
+ * counts may be NULL. */
+int pcaa_gallery_score(const float* sup_fv, const long long* preds, const float* means, int B, int Kc, int D,
+                       const float* centroids, const int* counts, int E, int n_labels, double* lik, long long* labels,
+                       int* near, void* stream);
+/* The rule of pcaa_kvote over arbitrary non-negative labels: a group is known iff #(lik > threshold) > k/2 and then
+ * takes the most frequent label of its k windows (the lowest on ties: argmax(bincount)), else n_labels.  On labels
+ * below n_classes it equals pcaa_kvote. */
+int pcaa_gallery_kvote(const double* lik, const long long* labels, double threshold, int k, int n_labels, int n_windows,
+                       long long* out, void* stream);
+/* pcaa_stream_score with the score of pcaa_gallery_score (same bits) and the vote of pcaa_gallery_kvote: same runs,
+ * history and barriers, one launch whatever the number of streams and slots.  hist_label [max_streams, k] holds the
+ * extended labels as they were stored: a label is never recomputed when the gallery changes between ticks.  H > 0:
+ * window j's sup_fv is also written to fv_hist[stream * H + j % H] (fv_hist fp32 [max_streams * H, D]); H = 0: fv_hist
+ * may be NULL. */
+int pcaa_stream_score_gallery(const float* logits, const float* sup_fv, const float* means, const int* run_start,
+                              int n_runs, const int* win_stream, const int* win_j, const int* vote_pos, int nw, int K,
+                              int D, int Kc, double threshold, int k, int n_labels, const float* centroids,
+                              const int* counts, int E, double* hist_lik, long long* hist_label, int max_streams,
+                              float* fv_hist, int H, long long* labels, double* lik, int* near, long long* votes,
+                              int n_votes, void* stream);
+
 /* ------------------------------------------------------------------ raw radar detections -> frames (raw_frames.hip)
  * ABI 20: what datasets.process_track does per frame on the host (reference datasets.py:79-161), for the n frames of a
  * tick in one launch.  points [P, 5] (x, y, z, doppler, linear power; fp32, or fp64 when points_f64: the reference's

@@ -115,6 +115,18 @@ def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0
     return feats, saves, rows.shape[0]
 
 
+def _checked_gallery(gallery, n_labels, D, who):
+    """the ``gallery=`` argument of a scorer: None, or a ``gallery.Gallery`` of the embedding width with the "unknown" id"""
+    if gallery is None:
+        return None
+    from .gallery import Gallery
+    if not isinstance(gallery, Gallery) or gallery.D != int(D):
+        raise ValueError(f"{who}: gallery must be a gallery.Gallery of width {int(D)}")
+    if n_labels is None or int(n_labels) < 1:
+        raise ValueError(f"{who}: a gallery needs n_labels >= 1 (the \"unknown\" id its labels are counted from)")
+    return gallery
+
+
 def _empty_triple(D, dev):
     """(preds, sup_fv, likelihood) of no window at all"""
     return (torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, D), dtype=torch.float32, device=dev),
@@ -124,7 +136,15 @@ def _empty_triple(D, dev):
 class OpenSetScorer:
     """Encoder + centroids -> predictions, likelihoods, threshold, k-window votes."""
 
-    def __init__(self, encoder: CGEncoder, discriminator_means: torch.Tensor, batch_size: int = 1024):
+    def __init__(self, encoder: CGEncoder, discriminator_means: torch.Tensor, batch_size: int = 1024, gallery=None,
+                 n_labels: int = None):
+        """``gallery`` (a ``gallery.Gallery``, with ``n_labels``, the "unknown" id): the identities enrolled at run time
+        are scored beside the prior's modes -- every embed route then returns the extended labels (``preds`` where a
+        prior mode is closest, ``n_labels + 1 + identity`` otherwise) in place of ``preds`` and the extended likelihood,
+        and ``vote`` takes the majority over those labels.  Without one nothing changes."""
+        self.gallery = _checked_gallery(gallery, n_labels, discriminator_means.shape[1], "OpenSetScorer")
+        self.n_labels = None if n_labels is None else int(n_labels)
+        self.last_preds = None               # with a gallery: the classifier's own predictions of the last embed
         self.encoder = encoder.eval()
         dev = next(encoder.parameters()).device
         self.means = discriminator_means.float().to(dev).contiguous()
@@ -161,6 +181,10 @@ class OpenSetScorer:
             preds.append(p)
             fvs.append(sup_fv)
         preds, fvs = torch.cat(preds), torch.cat(fvs)
+        if self.gallery is not None:
+            self.last_preds = preds
+            lik, labels, _ = self.gallery.score(fvs.contiguous(), preds, self.means, self.n_labels)
+            return labels, fvs, lik
         return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
 
     def _unique_features(self, frames):
@@ -297,6 +321,20 @@ class OpenSetScorer:
                 enc, points, offsets, N, C, pick, seed, keys, self.raw_err, a, b, prep=prep))
         return self._score_track(F, hop, drop_last_aligned, True, points.device, features)
 
+    def _enrol(self, triple, ident, windows, who):
+        if self.gallery is None:
+            raise RuntimeError(f"OpenSetScorer.{who}: the scorer was built without a gallery")
+        return self.gallery.enrol(triple[1].contiguous(), ident, windows)
+
+    def enrol_track(self, track: torch.Tensor, ident=None, windows=None, **how):
+        """``embed_track(track, **how)``, then ``gallery.enrol`` of its windows (``windows``: which, host ints in the
+        order they are added; None: all) -> the identity"""
+        return self._enrol(self.embed_track(track, **how), ident, windows, "enrol_track")
+
+    def enrol_raw_track(self, points: torch.Tensor, offsets: torch.Tensor, ident=None, windows=None, **how):
+        """``embed_raw_track(points, offsets, **how)``, then ``gallery.enrol`` of its windows -> the identity"""
+        return self._enrol(self.embed_raw_track(points, offsets, **how), ident, windows, "enrol_raw_track")
+
     def fit_threshold(self, known_lik: torch.Tensor, unseen_valid_lik: torch.Tensor) -> float:
         """ROC-optimal (Youden J) separation of known-test vs held-out-unseen likelihoods
         (inference_PCAA.py:225-231: unseen first with label 0, known with label 1)."""
@@ -308,6 +346,8 @@ class OpenSetScorer:
     def vote(self, lik: torch.Tensor, preds: torch.Tensor, k: int, n_labels: int) -> torch.Tensor:
         if self.threshold is None:
             raise RuntimeError("fit_threshold() first")
+        if self.gallery is not None:
+            return ops.gallery_vote(lik, preds, self.threshold, k, n_labels)
         return k_vote(lik, preds, self.threshold, k, n_labels, n_classes=self.encoder.MLP_sup2[0].weight.shape[0])
 
 
@@ -546,6 +586,85 @@ def perturbation_sweep(encoder, means, store, augments, ks, N, seed=0, refit=Fal
     return out
 
 
+def plan_enrolment(unseen_labels, shots, seed=0, unseen_valid_ratio=0.2, enrol_ratio=0.5):
+    """Host plan of one ``enrolment_sweep`` point, numpy only.  ``unseen_labels``: the subject of every sequential UNSEEN
+    crop.  The validation subjects are drawn exactly as ``_sequential_votes`` draws them (same generator, same first
+    draw); of the others ``ceil(enrol_ratio * n)`` are drawn next and numbered 0, 1, ... in ascending subject order.
+    A drawn subject is enrolled from its first ``shots`` crops when it has more than ``shots`` of them (something must be
+    left to evaluate) and ``shots > 0``.  -> (val_subjects, {subject: identity} of the enrolled, {subject: its enrolment
+    rows}, keep mask over the crops: False on the enrolment rows)."""
+    u_lab = np.asarray(unseen_labels)
+    rng = np.random.default_rng(seed)
+    subjects = np.unique(u_lab)
+    val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
+    rest = subjects[~np.isin(subjects, val_subjects)]
+    if not 0.0 <= enrol_ratio <= 1.0 or int(shots) < 0:
+        raise ValueError("plan_enrolment: needs 0 <= enrol_ratio <= 1 and shots >= 0")
+    drawn = np.sort(rng.choice(rest, size=int(np.ceil(enrol_ratio * len(rest))), replace=False)) if len(rest) else rest
+    idents, rows, keep = {}, {}, np.ones(len(u_lab), bool)
+    for s in drawn:
+        at = np.flatnonzero(u_lab == s)
+        if 0 < int(shots) < at.size:
+            idents[int(s)] = len(idents)
+            rows[int(s)] = at[:int(shots)]
+            keep[at[:int(shots)]] = False
+    return val_subjects, idents, rows, keep
+
+
+def enrolment_sweep(encoder, means, store, shots, ks, N, enrol_ratio=0.5, seed=0, scenarios_list=None, dedup_points=True,
+                    unseen_valid_ratio=0.2):
+    """Open-set accuracy against the windows a new person is enrolled from, the sibling of ``point_sweep``: ``store`` a
+    ``datasets.RawTrackStore`` with its splits assigned, on the device -> ``{shots: {k: metrics}}``, ``metrics`` what
+    ``_metrics`` returns.  The sequential TEST / UNSEEN crops are built and embedded ONCE, as ``point_sweep`` does for
+    ``keep = 0``.  The threshold is fitted first, with an empty gallery, as ``_sequential_votes`` fits it; the held-out
+    validation subjects are never enrolled.  Per entry of ``shots`` a fresh ``gallery.Gallery`` enrols the subjects
+    ``plan_enrolment`` draws under ``seed`` from their first ``shots`` windows; those windows are left out of the
+    evaluation, every other window is scored against prior and gallery (``ops.gallery_score``), and the votes over k
+    windows (``ops.gallery_vote``) carry ``n_labels + 1 + identity`` for an enrolled subject and ``n_labels`` for every
+    other unseen one.  With nobody enrolled an entry is ``point_sweep``'s record for ``keep = 0``.  Writes no file."""
+    from .constants import SPLIT
+    from .gallery import Gallery
+    if store.device is None:
+        raise RuntimeError("enrolment_sweep: call store.to_device() first; there is no CPU path")
+    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
+    scorer = OpenSetScorer(encoder, means)
+    prep = RawPrep.of(0, None, "first", who="enrolment_sweep")
+    emb = []
+    for split in (SPLIT.TEST, SPLIT.UNSEEN):
+        pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, prep=prep)
+        preds, fv, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
+        emb.append((preds, fv.contiguous(), lik, labels.cpu().numpy()))
+        del pcs
+    (k_preds, k_fv, k_lik, k_lab), (u_preds, u_fv, u_lik, u_lab) = emb
+    n_labels = int(len(np.unique(k_lab)))
+    dev = k_fv.device
+    out = {}
+    for n_shots in shots:
+        val_subjects, idents, rows, keep = plan_enrolment(u_lab, n_shots, seed, unseen_valid_ratio, enrol_ratio)
+        thr = scorer.fit_threshold(k_lik, u_lik[torch.from_numpy(np.isin(u_lab, val_subjects)).to(dev)])
+        gal = Gallery(k_fv.shape[1], max(len(idents), 1), dev)
+        for s, ident in idents.items():                                   # (ascending subjects: identity = slot)
+            gal.enrol(u_fv, ident, rows[s])
+        kept = torch.from_numpy(np.flatnonzero(keep)).to(dev)
+        sets = ((k_preds, k_fv, k_lab, False), (u_preds[kept], u_fv[kept].contiguous(), u_lab[keep], True))
+        scored = [gal.score(fv, pr.contiguous(), scorer.means, n_labels)[:2] + (lab, unknown) for pr, fv, lab, unknown in sets]
+        out[n_shots] = {}
+        for k in ks:
+            preds, labels = [], []
+            for lik, ext, lab, unknown in scored:
+                n = (len(lab) // k) * k
+                votes = ops.gallery_vote(lik[:n].contiguous(), ext[:n].contiguous(), thr, k, n_labels).cpu().numpy()
+                for w in range(n // k):
+                    seg = lab[w * k:(w + 1) * k]
+                    if len(np.unique(seg)) != 1 or (unknown and seg[0] in val_subjects):
+                        continue               # straddling two subjects, or a validation subject: as _sequential_votes
+                    preds.append(int(votes[w]))
+                    labels.append(int(seg[0]) if not unknown else
+                                  n_labels + 1 + idents[int(seg[0])] if int(seg[0]) in idents else n_labels)
+            out[n_shots][k] = _metrics(k, np.asarray(preds), np.asarray(labels).astype(int))
+    return out
+
+
 def CGAAE_inference(model_names, ks, force_pc_subsampling=0, scenarios_list=None, variation=False,
                     generate_dataset=True, device=None, dedup_frames=False, dedup_points=False, raw_store=None,
                     keep_points=0, keep_rule="first"):
@@ -675,9 +794,11 @@ class StreamingScorer(_LiveScorer):
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0,
-                 dedup_points: bool = False, keep_points=0, keep_rule: str = "first"):
+                 dedup_points: bool = False, keep_points=0, keep_rule: str = "first", gallery=None):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
         dev = self.means.device
+        # run-time enrolment: windows are scored against the gallery too and carry extended labels (OpenSetScorer)
+        self.gallery = _checked_gallery(gallery, n_labels, self._D, "StreamingScorer")
         self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
         self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
         self._set_keep(keep_points, keep_rule)           # push_raw: every frame thinned first
@@ -771,7 +892,10 @@ class StreamingScorer(_LiveScorer):
         plan = ops.WindowRows(self._starts[o:o + nw], self.T, self.ring_rows, self.ring_rows, dev=self._starts_dev[o:o + nw])
         logits, sup_fv, _ = F_hip.encoder_forward_windows(self.encoder, self.ring, plan, self.T)
         _, _, preds = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
-        lik = joint_likelihood(sup_fv.contiguous(), self.means)
+        if self.gallery is not None:
+            lik, preds, _ = self.gallery.score(sup_fv.contiguous(), preds, self.means, self.n_labels)
+        else:
+            lik = joint_likelihood(sup_fv.contiguous(), self.means)
         self.n_windows = done
         self._preds.append(preds)
         self._lik.append(lik)
@@ -784,6 +908,8 @@ class StreamingScorer(_LiveScorer):
         preds, lik = torch.cat(self._preds), torch.cat(self._lik)
         self._preds, self._lik = [preds], [lik]
         n = (preds.numel() // self.k) * self.k
+        if self.gallery is not None:
+            return ops.gallery_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels)
         return k_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels,
                       n_classes=self.n_classes)
 
@@ -895,7 +1021,8 @@ class Tick:
     """The result of one ``MultiStreamScorer.push``.  ``stream`` / ``window`` int64 [nw] and ``vote_stream`` /
     ``vote_group`` int64 [g]: host numpy arrays (known from the plan: no device sync); ``preds`` int64 [nw], ``sup_fv``
     fp32 [nw, 32], ``lik`` f64 [nw], ``votes`` int64 [g]: device tensors.  Windows are ordered by the position of their
-    stream in ``sids``, ascending within a stream."""
+    stream in ``sids``, ascending within a stream.  From a scorer with a gallery ``preds`` holds the extended labels
+    (``n_labels + 1 + identity`` where an enrolled person's mode is the nearest) and ``lik`` counts the enrolled modes."""
     __slots__ = ("stream", "window", "vote_stream", "vote_group", "preds", "sup_fv", "lik", "votes")
 
     def __len__(self):
@@ -933,13 +1060,22 @@ class MultiStreamScorer(_LiveScorer):
     ``StreamingScorer``'s (eager: window j comes back from the tick that brings its stream to ``NSTEPS + j * hop`` frames).
     ``push`` synchronises nothing and copies nothing to the host; the tick's plan (``plan_tick``) goes up as one pinned
     buffer.  The encoder's eval constants (``functional.encoder_eval_constants``) are folded once and rebuilt when a
-    parameter, a buffer or the precision mode changes.  Per-stream state is O(k): the incomplete vote group."""
+    parameter, a buffer or the precision mode changes.  Per-stream state is O(k): the incomplete vote group.
+    ``gallery`` (a ``gallery.Gallery``): the identities enrolled at run time are scored beside the prior's modes by the
+    same single launch (``ops.stream_score_gallery``); ``history=H`` keeps every stream's last H embeddings on the device
+    for ``enrol_stream``.  Without a gallery the tick is the one described above, launch for launch."""
 
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
                  batch_size: int = 1024, seed: int = 0, dedup_points: bool = False, keep_points=0,
-                 keep_rule: str = "first"):
+                 keep_rule: str = "first", gallery=None, history: int = 0):
         super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
+        # run-time enrolment: the tick's scoring launch is ops.stream_score_gallery; ``history`` = H > 0 also keeps every
+        # stream's last H embeddings on the device (fv_hist), from which ``enrol_stream`` enrols
+        self.gallery = _checked_gallery(gallery, n_labels, self._D, "MultiStreamScorer")
+        self.history = int(history)
+        if self.history < 0 or (self.history and self.gallery is None):
+            raise ValueError("MultiStreamScorer: history must be >= 0, and a history needs a gallery to enrol into")
         self.max_streams, self.batch_size = int(max_streams), int(batch_size)
         self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
         self._set_keep(keep_points, keep_rule)           # push_raw: every frame thinned first
@@ -951,6 +1087,8 @@ class MultiStreamScorer(_LiveScorer):
         self.ring = torch.zeros((self.max_streams * self.ring_rows, self._width), dtype=torch.float32, device=dev)
         self.hist_lik = torch.zeros((self.max_streams, self.k), dtype=torch.float64, device=dev)
         self.hist_pred = torch.zeros((self.max_streams, self.k), dtype=torch.int64, device=dev)
+        self.fv_hist = (torch.zeros((self.max_streams * self.history, self._D), dtype=torch.float32, device=dev)
+                        if self.history else None)
         self.scatter_err = torch.zeros(1, dtype=torch.int32, device=dev)     # set by a scatter destination out of range
         self.raw_err = torch.zeros(1, dtype=torch.int32, device=dev)         # set by a raw frame that could not be processed
         self.seed = int(seed)                                  # push_raw draws frame f of a track under (its serial, f)
@@ -979,6 +1117,17 @@ class MultiStreamScorer(_LiveScorer):
         """end the track in slot ``sid``; the slot may be handed out again"""
         self._slots([sid], "close")
         self._open[int(sid)] = False
+
+    def enrol_stream(self, sid: int, windows: int, ident=None) -> int:
+        """Enrol the person in slot ``sid`` from the last ``windows <= min(history, windows so far)`` windows of the
+        stream, oldest first -> the identity (``ident=None``: the lowest free one; a live one is refined).  The rows of
+        ``fv_hist`` come from the host's own window counter and go up with the launch: nothing is read back and nothing
+        waits for the device.  Labels already stored in the vote history stay as they are."""
+        from .gallery import ring_rows
+        if not self.history:
+            raise RuntimeError("MultiStreamScorer.enrol_stream: built with history=0; there is nothing to enrol from")
+        sid = int(self._slots([sid], "enrol_stream")[0])
+        return self.gallery.enrol(self.fv_hist, ident, ring_rows(self.n_windows[sid], self.history, windows, sid))
 
     def _slots(self, sids, what):
         arr = _host_ints(sids)
@@ -1086,6 +1235,13 @@ class MultiStreamScorer(_LiveScorer):
                                              nw > self.batch_size else rows, self.T, mode, consts=self._consts)[:2]
                for i in range(0, nw, self.batch_size)]
         logits, sup_fv = (frame_table.join_rows(part).contiguous() for part in zip(*out))
+        if self.gallery is not None:
+            g = self.gallery
+            labels, lik, _, votes = ops.stream_score_gallery(
+                logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
+                plan.vote_group.size, self.threshold, self.k, self.n_labels, g.centroids, g.counts, g.high_water,
+                self.hist_lik, self.hist_pred, self.fv_hist)
+            return _tick(plan, labels, sup_fv, lik, votes)
         preds, lik, votes = ops.stream_score(
             logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
             plan.vote_group.size, self.threshold, self.k, self.n_labels, self.n_classes, self.hist_lik, self.hist_pred)

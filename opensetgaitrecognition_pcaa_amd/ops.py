@@ -1993,6 +1993,124 @@ def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, 
     return preds, lik, votes
 
 
+# ------------------------------------------------------------------ run-time enrolment (csrc/gallery.hip)
+def _chk_gallery(who, sums, counts, centroids, E, D):
+    """the three buffers of a gallery (``gallery.Gallery``) and its high-water mark against an embedding width"""
+    _chk(centroids, who + ".centroids", torch.float32, 2)
+    _chk(counts, who + ".counts", torch.int32, 1)
+    if sums is not None:
+        _chk(sums, who + ".sums", torch.float64, 2)
+        if tuple(sums.shape) != tuple(centroids.shape):
+            raise ValueError(f"{who}: sums {tuple(sums.shape)} and centroids {tuple(centroids.shape)} differ")
+    E_max = centroids.shape[0]
+    if E_max < 1 or counts.numel() != E_max or centroids.shape[1] != D or not 0 <= int(E) <= E_max:
+        raise ValueError(f"{who}: needs centroids [E_max, {D}], counts [E_max] and 0 <= E <= E_max; got "
+                         f"{tuple(centroids.shape)}, {tuple(counts.shape)}, E = {E}")
+    return E_max
+
+
+def gallery_accumulate(fv, slot, sums, counts, centroids, rows=None, err_flag=None):
+    """Add rows of ``fv`` fp32 [n, D] to slot ``slot`` of a gallery in one launch (pcaa_gallery_accumulate): ``sums[slot] +=
+    fv[rows[i]]`` in the order of ``rows`` (int32 [m] on the device; None: every row of ``fv`` in order) with plain fp64
+    adds, then the slot's count and its centroid ``float32(sum / count)``.  An index outside ``[0, n)`` is skipped and
+    sets ``err_flag`` (int32 [1]).  Nothing comes back to the host."""
+    _chk(fv, "gallery_accumulate.fv", torch.float32, 2)
+    n, D = fv.shape
+    E_max = _chk_gallery("gallery_accumulate", sums, counts, centroids, 0, D)
+    if rows is not None:
+        _chk(rows, "gallery_accumulate.rows", torch.int32, 1)
+    m = n if rows is None else rows.numel()
+    if err_flag is not None:
+        _chk(err_flag, "gallery_accumulate.err_flag", torch.int32, 1)
+    if n < 1 or m < 1 or n >= 2 ** 31 or not 0 <= int(slot) < E_max:
+        raise ValueError(f"gallery_accumulate: needs at least one row to add and a slot in 0..{E_max - 1}; got fv "
+                         f"{tuple(fv.shape)}, {m} rows, slot {slot}")
+    check(_lib.load().pcaa_gallery_accumulate(_p(fv), n, D, _p(rows), m, int(slot), E_max, _p(sums), _p(counts),
+                                              _p(centroids), _p(err_flag), _s()), "pcaa_gallery_accumulate")
+
+
+def gallery_score(sup_fv, preds, means, centroids, counts, E, n_labels):
+    """Windows against the prior means AND a gallery (pcaa_gallery_score) -> (lik f64 [B], labels int64 [B], near int32
+    [B]): ``lik = (sum over the Kc prior modes + sum over the live slots) / Kc``, ``near`` the closest mode (prior modes
+    first), ``labels = preds`` where a prior mode is closest, else ``n_labels + 1 + slot``.  ``E``: slots ``0 .. E - 1`` are
+    scanned.  With no live slot ``lik`` has the bits of ``inference.joint_likelihood``."""
+    _chk(sup_fv, "gallery_score.sup_fv", torch.float32, 2)
+    _chk(preds, "gallery_score.preds", torch.int64, 1)
+    _chk(means, "gallery_score.means", torch.float32, 2)
+    B, D = sup_fv.shape
+    _chk_gallery("gallery_score", None, counts, centroids, E, D)
+    if preds.numel() != B or means.shape[1] != D or means.shape[0] < 1 or int(n_labels) < 1:
+        raise ValueError("gallery_score: needs one prediction per window, means [Kc, D] with Kc >= 1 and n_labels >= 1")
+    dev = sup_fv.device
+    lik = torch.empty(B, dtype=torch.float64, device=dev)
+    labels = torch.empty(B, dtype=torch.int64, device=dev)
+    near = torch.empty(B, dtype=torch.int32, device=dev)
+    if B:
+        check(_lib.load().pcaa_gallery_score(_p(sup_fv), _p(preds), _p(means), B, means.shape[0], D, _p(centroids),
+                                             _p(counts), int(E), int(n_labels), _p(lik), _p(labels), _p(near), _s()),
+              "pcaa_gallery_score")
+    return lik, labels, near
+
+
+def gallery_vote(lik, labels, threshold, k, n_labels):
+    """``inference.k_vote`` over the extended labels of ``gallery_score`` (pcaa_gallery_kvote): groups of k consecutive
+    windows (a trailing partial group is dropped) -> [n // k] int64, the most frequent label of a known group (lowest on
+    ties), ``n_labels`` for the others."""
+    _chk(lik, "gallery_vote.lik", torch.float64, 1)
+    _chk(labels, "gallery_vote.labels", torch.int64, 1)
+    k = int(k)
+    if k < 1 or labels.numel() != lik.numel() or int(n_labels) < 1:
+        raise ValueError("gallery_vote: needs k >= 1, n_labels >= 1 and one label per likelihood")
+    nwin = lik.numel() // k
+    out = torch.empty(nwin, dtype=torch.int64, device=lik.device)
+    if nwin:
+        check(_lib.load().pcaa_gallery_kvote(_p(lik), _p(labels), ctypes.c_double(float(threshold)), k, int(n_labels), nwin,
+                                             _p(out), _s()), "pcaa_gallery_kvote")
+    return out
+
+
+def stream_score_gallery(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
+                         centroids, counts, E, hist_lik, hist_label, fv_hist=None):
+    """``stream_score`` with the score of ``gallery_score`` and the vote of ``gallery_vote``, still one launch
+    (pcaa_stream_score_gallery) -> (labels [nw] int64, lik [nw] f64, near [nw] int32, votes [n_votes] int64).
+    ``hist_label`` int64 [max_streams, k] keeps the extended labels as they were stored.  ``fv_hist`` fp32
+    [max_streams * H, D] (optional): window j of stream s also leaves its ``sup_fv`` in row ``s * H + j % H``."""
+    _chk(logits, "stream_score_gallery.logits", torch.float32, 2)
+    _chk(sup_fv, "stream_score_gallery.sup_fv", torch.float32, 2)
+    _chk(means, "stream_score_gallery.means", torch.float32, 2)
+    _chk(hist_lik, "stream_score_gallery.hist_lik", torch.float64, 2)
+    _chk(hist_label, "stream_score_gallery.hist_label", torch.int64, 2)
+    for t, name in ((run_start, "run_start"), (win_stream, "win_stream"), (win_j, "win_j"), (vote_pos, "vote_pos")):
+        _chk(t, "stream_score_gallery." + name, torch.int32, 1)
+    nw, K = logits.shape
+    D = sup_fv.shape[1]
+    _chk_gallery("stream_score_gallery", None, counts, centroids, E, D)
+    k, n_votes, n_runs = int(k), int(n_votes), run_start.numel() - 1
+    if (sup_fv.shape[0] != nw or means.shape[1] != D or win_stream.numel() != nw or win_j.numel() != nw
+            or vote_pos.numel() != nw or k < 1 or tuple(hist_lik.shape) != tuple(hist_label.shape)
+            or hist_lik.shape[1] != k or not 0 <= n_votes <= nw or not (1 <= n_runs <= nw or nw == 0)):
+        raise ValueError("stream_score_gallery: shapes do not describe one tick")
+    H = 0
+    if fv_hist is not None:
+        _chk(fv_hist, "stream_score_gallery.fv_hist", torch.float32, 2)
+        H = fv_hist.shape[0] // hist_lik.shape[0]
+        if H < 1 or fv_hist.shape[0] != H * hist_lik.shape[0] or fv_hist.shape[1] != D:
+            raise ValueError(f"stream_score_gallery: fv_hist must be [max_streams * H, {D}] with H >= 1, got "
+                             f"{tuple(fv_hist.shape)} for {hist_lik.shape[0]} streams")
+    dev = logits.device
+    labels = torch.empty(nw, dtype=torch.int64, device=dev)
+    lik = torch.empty(nw, dtype=torch.float64, device=dev)
+    near = torch.empty(nw, dtype=torch.int32, device=dev)
+    votes = torch.empty(n_votes, dtype=torch.int64, device=dev)
+    if nw:
+        check(_lib.load().pcaa_stream_score_gallery(
+            _p(logits), _p(sup_fv), _p(means), _p(run_start), n_runs, _p(win_stream), _p(win_j), _p(vote_pos), nw, K, D,
+            means.shape[0], ctypes.c_double(float(threshold)), k, int(n_labels), _p(centroids), _p(counts), int(E),
+            _p(hist_lik), _p(hist_label), hist_lik.shape[0], _p(fv_hist), H, _p(labels), _p(lik), _p(near),
+            _p(votes) if n_votes else None, n_votes, _s()), "pcaa_stream_score_gallery")
+    return labels, lik, near, votes
+
+
 def dtc_im2col(a, B, T, Cin, d):
     _chk(a, "im2col.a", torch.float32, 2)
     col = torch.empty((B * T, 3 * Cin), dtype=torch.float32, device=a.device)
