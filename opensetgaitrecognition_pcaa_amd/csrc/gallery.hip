@@ -6,10 +6,11 @@
 //   near  = the mode of smallest fp64 squared distance among 0 .. Kc + E - 1 (lowest index on exact ties)
 //   label = preds                 when near < Kc   (a trained class: the classifier names it)
 //           n_labels + 1 + slot   otherwise        (n_labels itself stays "unknown")
-// One wavefront scores one window: lanes stride the modes, every lane walks one mode's D coordinates in the order of
-// mixture_likelihood, and the partials meet in a fixed order -- a window's outputs are a function of the window and the
-// gallery alone, whatever the batch, its position or the grid.
-#include "common.h"
+// One wavefront scores one window: lanes stride the modes, every lane forms one mode's term with the maha_of / term_of
+// that mixture_likelihood is written in (score_tick.h), and the partials meet in a fixed order -- a window's outputs are a
+// function of the window and the gallery alone, whatever the batch, its position or the grid.  The live tick is the
+// shared body stream_tick_kernel (score_tick.h) under the GalleryTick policy below.
+#include "score_tick.h"
 
 namespace {
 
@@ -21,22 +22,6 @@ struct GalleryView {
   const int* counts;        // [E_max]
   int E;                    // slots 0 .. E - 1 are scanned
 };
-
-// |x - c|^2 in fp64, the loop of mixture_likelihood (scoring.hip)
-__device__ __forceinline__ double maha_of(const float* __restrict__ x, const float* __restrict__ c, int D) {
-  double maha = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double diff = (double)x[d] - (double)c[d];
-    maha += diff * diff;
-  }
-  return maha;
-}
-
-// its term, written as mixture_likelihood writes it
-__device__ __forceinline__ double term_of(double maha, int D) {
-  const double log2pi = 1.8378770664093453;
-  return exp(-0.5 * ((double)D * log2pi + maha));
-}
 
 struct Nearest {
   double d2;
@@ -103,11 +88,6 @@ __global__ __launch_bounds__(WAVE* SCORE_WAVES) void gallery_score_kernel(
   }
 }
 
-struct Scored {
-  double lik;
-  long long label;
-};
-
 // the rule of vote_of (scoring.hip) over arbitrary labels: known iff #(lik > thr) > k/2, then the most frequent label of
 // the k windows, the lowest on ties (argmax(bincount)), else n_labels
 template <typename Get>
@@ -160,86 +140,45 @@ __global__ __launch_bounds__(256) void gallery_accumulate_kernel(
   if (threadIdx.x == 0) counts[slot] = total;
 }
 
-// pcaa_stream_score's tick with this score and this vote: one workgroup of SCORE_WAVES wavefronts per run, the phases
-// and barriers of stream_score_kernel.  Phase 1 gives every window to one wavefront (wave_score); phase 3 also keeps the
-// run's last H embeddings in the stream's ring fv_hist (slot j % H).
-struct StreamGalleryParams {
-  const float* logits;          // [nw, K]
-  const float* sup_fv;          // [nw, D]
-  const float* means;           // [Kc, D]
-  const int* run_start;         // [n_runs + 1]
-  const int* win_stream;        // [nw]
-  const int* win_j;             // [nw]
-  const int* vote_pos;          // [nw], < 0: the window completes no group
-  double* hist_lik;             // [max_streams, k]
-  long long* hist_label;        // [max_streams, k]
-  float* fv_hist;               // [max_streams * H, D] (H > 0)
-  long long* labels;            // [nw]
-  double* lik;                  // [nw]
-  int* near;                    // [nw]
-  long long* votes;             // [n_votes]
-  GalleryView g;
-  double thr;
-  int nw, K, D, Kc, k, n_labels, max_streams, n_votes, H;
-};
-
-__global__ __launch_bounds__(WAVE* SCORE_WAVES) void stream_score_gallery_kernel(StreamGalleryParams p) {
-  const int i0 = p.run_start[blockIdx.x], i1 = p.run_start[blockIdx.x + 1];
-  if (i0 < 0 || i1 > p.nw || i0 >= i1) return;                  // (uniform: the whole workgroup leaves)
-  const int s = p.win_stream[i0];
-  if (s < 0 || s >= p.max_streams) return;
-  const int k = p.k, nt = WAVE * SCORE_WAVES, tid = threadIdx.x;
-  double* hl = p.hist_lik + (long)s * k;
-  long long* hp = p.hist_label + (long)s * k;
-  for (int i = i0 + tid / WAVE; i < i1; i += SCORE_WAVES) {      // (uniform per wavefront)
-    const float* x = p.logits + (long)i * p.K;
-    float mx = x[0];
-    for (int c = 1; c < p.K; ++c) mx = fmaxf(mx, x[c]);
-    float se = 0.f;
-    for (int c = 0; c < p.K; ++c) se += expf(x[c] - mx);
-    int am = 0;
-    float pbest = -1.f;
-    for (int c = 0; c < p.K; ++c) {
-      const float pk = expf(x[c] - mx) / se;   // softmax exactly as exp / sum
-      if (pk > pbest) { pbest = pk; am = c; }  // first index on ties
-    }
-    double l;
-    int nr;
-    wave_score(p.sup_fv + (long)i * p.D, p.means, p.Kc, p.D, p.g, l, nr);
-    if ((tid & (WAVE - 1)) == 0) {
-      p.lik[i] = l;
-      p.near[i] = nr;
-      p.labels[i] = label_of(am, nr, p.Kc, p.n_labels);
+// the tick (score_tick.h) with this score and this vote: one workgroup of SCORE_WAVES wavefronts per run.  Phase 1 gives
+// every window to one wavefront (wave_score); after phase 3 the run's last H embeddings also stay in the stream's ring
+// fv_hist (slot j % H).
+struct GalleryTick {
+  static constexpr int THREADS = WAVE * SCORE_WAVES;
+  struct Params : TickParams {
+    float* fv_hist;               // [max_streams * H, D] (H > 0)
+    int* near;                    // [nw]
+    GalleryView g;
+    int H;
+  };
+  static __device__ __forceinline__ void score(const Params& p, int i0, int i1) {
+    const int tid = threadIdx.x;
+    for (int i = i0 + tid / WAVE; i < i1; i += SCORE_WAVES) {      // (uniform per wavefront)
+      const int am = softmax_argmax(p.logits + (long)i * p.K, p.K);
+      double l;
+      int nr;
+      wave_score(p.sup_fv + (long)i * p.D, p.means, p.Kc, p.D, p.g, l, nr);
+      if ((tid & (WAVE - 1)) == 0) {
+        p.lik[i] = l;
+        p.near[i] = nr;
+        p.labels[i] = label_of(am, nr, p.Kc, p.n_labels);
+      }
     }
   }
-  __syncthreads();
-  for (int i = i0 + tid; i < i1; i += nt) {
-    const int j = p.win_j[i], pos = p.vote_pos[i];
-    if (j < 0 || j % k != k - 1 || pos < 0 || pos >= p.n_votes) continue;
-    p.votes[pos] = gallery_vote_of(
-        [&](int m) {
-          const int im = i - (k - 1) + m;                         // window j - (k - 1) + m
-          if (im >= i0) return Scored{p.lik[im], p.labels[im]};
-          return Scored{hl[m], hp[m]};                            // (j - (k - 1) + m) % k == m
-        },
-        p.thr, k, p.n_labels);
+  template <typename Get>
+  static __device__ __forceinline__ long long vote(const Params& p, Get get) {
+    return gallery_vote_of(get, p.thr, p.k, p.n_labels);
   }
-  __syncthreads();
-  for (int i = max(i0, i1 - k) + tid; i < i1; i += nt) {
-    const int j = p.win_j[i];
-    if (j < 0) continue;
-    hl[j % k] = p.lik[i];
-    hp[j % k] = p.labels[i];
-  }
-  if (p.H > 0) {                                                  // two windows H apart share a slot: the later one only
-    const int a = max(i0, i1 - p.H);
-    for (long e = tid; e < (long)(i1 - a) * p.D; e += nt) {
+  static __device__ __forceinline__ void keep(const Params& p, int s, int i0, int i1) {
+    if (p.H <= 0) return;
+    const int a = max(i0, i1 - p.H);                                // two windows H apart share a slot: the later one only
+    for (long e = threadIdx.x; e < (long)(i1 - a) * p.D; e += THREADS) {
       const int i = a + (int)(e / p.D), d = (int)(e % p.D), j = p.win_j[i];
       if (j < 0) continue;
       p.fv_hist[((long)s * p.H + j % p.H) * p.D + d] = p.sup_fv[(long)i * p.D + d];
     }
   }
-}
+};
 
 }  // namespace
 
@@ -286,10 +225,10 @@ extern "C" int pcaa_stream_score_gallery(const float* logits, const float* sup_f
                  max_streams >= 1 && n_votes >= 0 && (votes != nullptr || n_votes == 0) && E >= 0 &&
                  (E == 0 || (centroids && counts)) && (long)Kc + E < 0x7fffffffL && H >= 0 && (H == 0 || fv_hist),
                  "pcaa_stream_score_gallery: bad args");
-  StreamGalleryParams p{logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, hist_lik, hist_label, fv_hist,
-                        labels, lik, near, votes, GalleryView{centroids, counts, E}, threshold, nw, K, D, Kc, k, n_labels,
-                        max_streams, n_votes, H};
-  hipLaunchKernelGGL(stream_score_gallery_kernel, dim3((unsigned)n_runs), dim3(WAVE * SCORE_WAVES), 0, as_stream(stream),
-                     p);
+  GalleryTick::Params p{{logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, hist_lik, hist_label, labels, lik,
+                         votes, threshold, nw, K, D, Kc, k, n_labels, max_streams, n_votes},
+                        fv_hist, near, GalleryView{centroids, counts, E}, H};
+  hipLaunchKernelGGL(stream_tick_kernel<GalleryTick>, dim3((unsigned)n_runs), dim3(GalleryTick::THREADS), 0,
+                     as_stream(stream), p);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_stream_score_gallery");
 }

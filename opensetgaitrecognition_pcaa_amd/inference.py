@@ -115,16 +115,45 @@ def _ragged_features(enc, points, offsets, N, C, pick, seed, keys, err_flag, a=0
     return feats, saves, rows.shape[0]
 
 
-def _checked_gallery(gallery, n_labels, D, who):
-    """the ``gallery=`` argument of a scorer: None, or a ``gallery.Gallery`` of the embedding width with the "unknown" id"""
-    if gallery is None:
-        return None
-    from .gallery import Gallery
-    if not isinstance(gallery, Gallery) or gallery.D != int(D):
-        raise ValueError(f"{who}: gallery must be a gallery.Gallery of width {int(D)}")
-    if n_labels is None or int(n_labels) < 1:
-        raise ValueError(f"{who}: a gallery needs n_labels >= 1 (the \"unknown\" id its labels are counted from)")
-    return gallery
+class _Rule:
+    """The open-set rule of a scorer, decided once in its constructor: under the prior's modes alone (``gallery=None``),
+    or with the identities a ``gallery.Gallery`` of the embedding width enrolled at run time beside them -- labels are
+    then the extended ones (``preds`` where a prior mode is closest, ``n_labels + 1 + identity`` otherwise)."""
+
+    def __init__(self, means, n_labels, n_classes, gallery, who):
+        self.means, self.n_classes, self.gallery = means, int(n_classes), gallery
+        self.n_labels = None if n_labels is None else int(n_labels)
+        if gallery is None:
+            return
+        from .gallery import Gallery
+        if not isinstance(gallery, Gallery) or gallery.D != int(means.shape[1]):
+            raise ValueError(f"{who}: gallery must be a gallery.Gallery of width {int(means.shape[1])}")
+        if self.n_labels is None or self.n_labels < 1:
+            raise ValueError(f"{who}: a gallery needs n_labels >= 1 (the \"unknown\" id its labels are counted from)")
+
+    def score(self, sup_fv, preds):
+        """embeddings and the classifier's predictions -> (labels, likelihood)"""
+        if self.gallery is None:
+            return preds, joint_likelihood(sup_fv, self.means)
+        lik, labels, _ = self.gallery.score(sup_fv, preds, self.means, self.n_labels)
+        return labels, lik
+
+    def vote(self, lik, labels, threshold, k, n_labels):
+        if self.gallery is None:
+            return k_vote(lik, labels, threshold, k, n_labels, n_classes=self.n_classes)
+        return ops.gallery_vote(lik, labels, threshold, k, n_labels)
+
+    def tick(self, logits, sup_fv, part, n_votes, threshold, k, hist_lik, hist_label, fv_hist):
+        """one scoring launch for a tick's windows (``part``: its plan on the device) -> what ``_tick`` takes after the plan"""
+        args = (logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"], n_votes,
+                threshold, k, self.n_labels)
+        if self.gallery is None:
+            labels, lik, votes = ops.stream_score(*args, self.n_classes, hist_lik, hist_label)
+        else:
+            g = self.gallery
+            labels, lik, _, votes = ops.stream_score_gallery(*args, g.centroids, g.counts, g.high_water, hist_lik, hist_label,
+                                                             fv_hist)
+        return labels, sup_fv, lik, votes
 
 
 def _empty_triple(D, dev):
@@ -142,12 +171,12 @@ class OpenSetScorer:
         are scored beside the prior's modes -- every embed route then returns the extended labels (``preds`` where a
         prior mode is closest, ``n_labels + 1 + identity`` otherwise) in place of ``preds`` and the extended likelihood,
         and ``vote`` takes the majority over those labels.  Without one nothing changes."""
-        self.gallery = _checked_gallery(gallery, n_labels, discriminator_means.shape[1], "OpenSetScorer")
-        self.n_labels = None if n_labels is None else int(n_labels)
         self.last_preds = None               # with a gallery: the classifier's own predictions of the last embed
         self.encoder = encoder.eval()
         dev = next(encoder.parameters()).device
         self.means = discriminator_means.float().to(dev).contiguous()
+        self._rule = _Rule(self.means, n_labels, encoder.MLP_sup2[0].weight.shape[0], gallery, "OpenSetScorer")
+        self.gallery, self.n_labels = gallery, self._rule.n_labels
         self.batch_size = batch_size
         self.threshold = None
         self.last_frames_encoded = None      # unique frames the last deduplicated embed / embed_track encoded (no padding)
@@ -183,9 +212,8 @@ class OpenSetScorer:
         preds, fvs = torch.cat(preds), torch.cat(fvs)
         if self.gallery is not None:
             self.last_preds = preds
-            lik, labels, _ = self.gallery.score(fvs.contiguous(), preds, self.means, self.n_labels)
-            return labels, fvs, lik
-        return preds, fvs, joint_likelihood(fvs.contiguous(), self.means)
+        labels, lik = self._rule.score(fvs.contiguous(), preds)
+        return labels, fvs, lik
 
     def _unique_features(self, frames):
         """padded frames [U, N, C] -> the chunks of their [U, 1024] feature table from their distinct rows: one offsets
@@ -346,9 +374,7 @@ class OpenSetScorer:
     def vote(self, lik: torch.Tensor, preds: torch.Tensor, k: int, n_labels: int) -> torch.Tensor:
         if self.threshold is None:
             raise RuntimeError("fit_threshold() first")
-        if self.gallery is not None:
-            return ops.gallery_vote(lik, preds, self.threshold, k, n_labels)
-        return k_vote(lik, preds, self.threshold, k, n_labels, n_classes=self.encoder.MLP_sup2[0].weight.shape[0])
+        return self._rule.vote(lik, preds, self.threshold, k, n_labels)
 
 
 def _variation_uses_head(variation, model_name=""):
@@ -466,37 +492,48 @@ def _sequential_votes(k, scorer, known, known_labels, unseen, unseen_labels, see
     threshold is refit from these likelihoods; one embedding serves every k (``point_sweep``).  ``threshold``: used as it
     is instead (a deployed threshold; ``perturbation_sweep``): nothing is fitted, the validation subjects are held out
     all the same."""
-    rng = np.random.default_rng(seed)
     (k_preds, k_lik), (u_preds, u_lik) = known, unseen
     n_labels = int(len(np.unique(known_labels.cpu().numpy())))
     u_lab = unseen_labels.cpu().numpy()
-    subjects = np.unique(u_lab)
-    val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
-    val_mask = np.isin(u_lab, val_subjects)
-    vm = torch.from_numpy(val_mask).to(u_lik.device)
+    val_subjects = _validation_subjects(u_lab, np.random.default_rng(seed), unseen_valid_ratio)
+    vm = torch.from_numpy(np.isin(u_lab, val_subjects)).to(u_lik.device)
     if threshold is None:
         thr = scorer.fit_threshold(k_lik, u_lik[vm])
     else:
         thr = scorer.threshold = float(threshold)
     preds, labels = [], []
-
-    def windows(lik, pr, lab, unknown):
-        lab_np = lab.cpu().numpy()
-        n = (len(lab_np) // k) * k
-        votes = scorer.vote(lik[:n].contiguous(), pr[:n].contiguous(), k, n_labels).cpu().numpy()
-        for w in range(n // k):
-            seg = lab_np[w * k:(w + 1) * k]
-            if len(np.unique(seg)) != 1:
-                continue                       # windows straddling two subjects are skipped (:243-245)
-            if unknown and seg[0] in val_subjects:
-                continue                       # validation subjects only chose the threshold (:286)
-            preds.append(int(votes[w]))
-            labels.append(n_labels if unknown else int(seg[0]))
-
-    # windows are cut over the WHOLE sequential set, as the reference's DataLoader(batch_size=k) does
-    windows(k_lik, k_preds, known_labels, False)
-    windows(u_lik, u_preds, unseen_labels, True)
+    for lik, pr, lab, unknown in ((k_lik, k_preds, known_labels, False), (u_lik, u_preds, unseen_labels, True)):
+        voted, truth = _voted_windows(
+            k, lab.cpu().numpy(), lambda n: scorer.vote(lik[:n].contiguous(), pr[:n].contiguous(), k, n_labels),
+            val_subjects, unknown, (lambda s: n_labels) if unknown else (lambda s: s))
+        preds += voted
+        labels += truth
     return np.asarray(preds), np.asarray(labels), thr
+
+
+def _validation_subjects(u_lab, rng, ratio):
+    """the unseen subjects held out to choose the threshold: ``ceil(ratio * n)`` of them, the FIRST draw of ``rng``"""
+    subjects = np.unique(u_lab)
+    return rng.choice(subjects, size=int(np.ceil(ratio * len(subjects))), replace=False)
+
+
+def _voted_windows(k, lab, vote, val_subjects, unknown, label_of):
+    """The window loop of the sequential procedure over one split.  ``lab``: the subject of every crop, in order (numpy);
+    ``vote(n)``: the votes of the ``n // k`` groups of its first n crops, on the device; ``label_of(subject)``: the
+    open-set label of a group.  Windows are cut over the WHOLE sequential set, as the reference's DataLoader(batch_size=k)
+    does -> (votes, labels) of the windows that count, as lists."""
+    n = (len(lab) // k) * k
+    votes = vote(n).cpu().numpy()
+    preds, labels = [], []
+    for w in range(n // k):
+        seg = lab[w * k:(w + 1) * k]
+        if len(np.unique(seg)) != 1:
+            continue                           # windows straddling two subjects are skipped (:243-245)
+        if unknown and seg[0] in val_subjects:
+            continue                           # validation subjects only chose the threshold (:286)
+        preds.append(int(votes[w]))
+        labels.append(label_of(int(seg[0])))
+    return preds, labels
 
 
 def _sequential_split_on_device(split, scenarios_list, device):
@@ -520,6 +557,32 @@ def _sequential_split_from_store(store, split, scenarios_list, N, seed=0, **how)
         seed=seed, **how)
 
 
+def _sweep_scorer(encoder, means, store, who):
+    """the scorer of a sweep over ``store``, refused before anything is built when the store is not on the device"""
+    if store.device is None:
+        raise RuntimeError(f"{who}: call store.to_device() first; there is no CPU path")
+    return OpenSetScorer(encoder, means)
+
+
+def _embed_splits(scorer, store, scenarios_list, N, seed, prep, dedup_points):
+    """What every sweep does per point: the sequential TEST and UNSEEN crops of ``store`` (a ``datasets.RawTrackStore``
+    with its splits assigned, on the device) built under ``seed`` and ``prep``, embedded ONCE each with
+    ``dedup_frames=True``, the crops freed before the next split -> per split (preds, sup_fv, likelihood, labels)."""
+    from .constants import SPLIT
+    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
+    out = []
+    for split in (SPLIT.TEST, SPLIT.UNSEEN):
+        pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, seed, prep=prep)
+        out.append(scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points) + (labels,))
+        del pcs
+    return out
+
+
+def _vote_sets(emb):
+    """``_embed_splits``' result as the four arguments ``_sequential_votes`` takes after the scorer"""
+    return [x for preds, _, lik, labels in emb for x in ((preds, lik), labels)]
+
+
 def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_points=True, keep_rule="first"):
     """The paper's robustness curve -- open-set accuracy against the detections a frame keeps -- from one resident store:
     ``store`` a ``datasets.RawTrackStore`` with its splits assigned, on the device -> ``{keep: {k: metrics}}``, ``metrics``
@@ -529,19 +592,11 @@ def point_sweep(encoder, means, store, keeps, ks, N, scenarios_list=None, dedup_
     consecutive crops share once, and with ``dedup_points`` (default) its distinct points only, so a sweep point costs
     PointNet rows proportional to ``min(keep, N)`` -- then the threshold is refit and the votes are taken for every k of
     ``ks``.  Writes no file."""
-    from .constants import SPLIT
-    if store.device is None:
-        raise RuntimeError("point_sweep: call store.to_device() first; there is no CPU path")
-    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    scorer = OpenSetScorer(encoder, means)
+    scorer = _sweep_scorer(encoder, means, store, "point_sweep")
     out = {}
     for keep in keeps:
-        sets, prep = [], RawPrep.of(keep, None, keep_rule, who="point_sweep")
-        for split in (SPLIT.TEST, SPLIT.UNSEEN):
-            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, prep=prep)
-            preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
-            sets += [(preds, lik), labels]
-            del pcs
+        sets = _vote_sets(_embed_splits(scorer, store, scenarios_list, N, 0, RawPrep.of(keep, None, keep_rule, who="point_sweep"),
+                                        dedup_points))
         out[keep] = {}
         for k in ks:
             preds, labels, _ = _sequential_votes(k, scorer, *sets)
@@ -559,20 +614,11 @@ def perturbation_sweep(encoder, means, store, augments, ks, N, seed=0, refit=Fal
     ``dedup_frames=True`` (and ``dedup_points``, default).  ``refit=False``: the votes use the threshold fitted on the
     UN-augmented crops (built and embedded once, first) -- a deployed threshold meeting a degraded sensor; ``refit=True``:
     the threshold is refit on each entry's own likelihoods, as ``point_sweep`` does per ``keep``.  Writes no file."""
-    from .constants import SPLIT
-    if store.device is None:
-        raise RuntimeError("perturbation_sweep: call store.to_device() first; there is no CPU path")
-    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    scorer = OpenSetScorer(encoder, means)
+    scorer = _sweep_scorer(encoder, means, store, "perturbation_sweep")
 
     def embedded(augment):
-        sets, prep = [], RawPrep.of(augment=augment, who="perturbation_sweep")
-        for split in (SPLIT.TEST, SPLIT.UNSEEN):
-            pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, seed, prep=prep)
-            preds, _, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
-            sets += [(preds, lik), labels]
-            del pcs
-        return sets
+        return _vote_sets(_embed_splits(scorer, store, scenarios_list, N, seed,
+                                        RawPrep.of(augment=augment, who="perturbation_sweep"), dedup_points))
 
     # the threshold does not depend on k: one fit on the crops as they are (same seed: the same picks)
     clean = None if refit else _sequential_votes(ks[0], scorer, *embedded(None))[2]
@@ -588,7 +634,7 @@ def perturbation_sweep(encoder, means, store, augments, ks, N, seed=0, refit=Fal
 
 def plan_enrolment(unseen_labels, shots, seed=0, unseen_valid_ratio=0.2, enrol_ratio=0.5):
     """Host plan of one ``enrolment_sweep`` point, numpy only.  ``unseen_labels``: the subject of every sequential UNSEEN
-    crop.  The validation subjects are drawn exactly as ``_sequential_votes`` draws them (same generator, same first
+    crop.  The validation subjects are the draw ``_sequential_votes`` makes (``_validation_subjects``: same generator, first
     draw); of the others ``ceil(enrol_ratio * n)`` are drawn next and numbered 0, 1, ... in ascending subject order.
     A drawn subject is enrolled from its first ``shots`` crops when it has more than ``shots`` of them (something must be
     left to evaluate) and ``shots > 0``.  -> (val_subjects, {subject: identity} of the enrolled, {subject: its enrolment
@@ -596,7 +642,7 @@ def plan_enrolment(unseen_labels, shots, seed=0, unseen_valid_ratio=0.2, enrol_r
     u_lab = np.asarray(unseen_labels)
     rng = np.random.default_rng(seed)
     subjects = np.unique(u_lab)
-    val_subjects = rng.choice(subjects, size=int(np.ceil(unseen_valid_ratio * len(subjects))), replace=False)
+    val_subjects = _validation_subjects(u_lab, rng, unseen_valid_ratio)
     rest = subjects[~np.isin(subjects, val_subjects)]
     if not 0.0 <= enrol_ratio <= 1.0 or int(shots) < 0:
         raise ValueError("plan_enrolment: needs 0 <= enrol_ratio <= 1 and shots >= 0")
@@ -622,20 +668,11 @@ def enrolment_sweep(encoder, means, store, shots, ks, N, enrol_ratio=0.5, seed=0
     evaluation, every other window is scored against prior and gallery (``ops.gallery_score``), and the votes over k
     windows (``ops.gallery_vote``) carry ``n_labels + 1 + identity`` for an enrolled subject and ``n_labels`` for every
     other unseen one.  With nobody enrolled an entry is ``point_sweep``'s record for ``keep = 0``.  Writes no file."""
-    from .constants import SPLIT
     from .gallery import Gallery
-    if store.device is None:
-        raise RuntimeError("enrolment_sweep: call store.to_device() first; there is no CPU path")
-    scenarios_list = constants.TRAIN_SCENARIOS if scenarios_list is None else scenarios_list
-    scorer = OpenSetScorer(encoder, means)
-    prep = RawPrep.of(0, None, "first", who="enrolment_sweep")
-    emb = []
-    for split in (SPLIT.TEST, SPLIT.UNSEEN):
-        pcs, labels = _sequential_split_from_store(store, split, scenarios_list, N, prep=prep)
-        preds, fv, lik = scorer.embed(pcs, dedup_frames=True, dedup_points=dedup_points)
-        emb.append((preds, fv.contiguous(), lik, labels.cpu().numpy()))
-        del pcs
-    (k_preds, k_fv, k_lik, k_lab), (u_preds, u_fv, u_lik, u_lab) = emb
+    scorer = _sweep_scorer(encoder, means, store, "enrolment_sweep")
+    (k_preds, k_fv, k_lik, k_lab), (u_preds, u_fv, u_lik, u_lab) = (
+        (preds, fv.contiguous(), lik, labels.cpu().numpy()) for preds, fv, lik, labels in _embed_splits(
+            scorer, store, scenarios_list, N, 0, RawPrep.of(0, None, "first", who="enrolment_sweep"), dedup_points))
     n_labels = int(len(np.unique(k_lab)))
     dev = k_fv.device
     out = {}
@@ -652,15 +689,12 @@ def enrolment_sweep(encoder, means, store, shots, ks, N, enrol_ratio=0.5, seed=0
         for k in ks:
             preds, labels = [], []
             for lik, ext, lab, unknown in scored:
-                n = (len(lab) // k) * k
-                votes = ops.gallery_vote(lik[:n].contiguous(), ext[:n].contiguous(), thr, k, n_labels).cpu().numpy()
-                for w in range(n // k):
-                    seg = lab[w * k:(w + 1) * k]
-                    if len(np.unique(seg)) != 1 or (unknown and seg[0] in val_subjects):
-                        continue               # straddling two subjects, or a validation subject: as _sequential_votes
-                    preds.append(int(votes[w]))
-                    labels.append(int(seg[0]) if not unknown else
-                                  n_labels + 1 + idents[int(seg[0])] if int(seg[0]) in idents else n_labels)
+                voted, truth = _voted_windows(
+                    k, lab, lambda n: ops.gallery_vote(lik[:n].contiguous(), ext[:n].contiguous(), thr, k, n_labels),
+                    val_subjects, unknown,
+                    (lambda s: n_labels + 1 + idents[s] if s in idents else n_labels) if unknown else (lambda s: s))
+                preds += voted
+                labels += truth
             out[n_shots][k] = _metrics(k, np.asarray(preds), np.asarray(labels).astype(int))
     return out
 
@@ -745,7 +779,7 @@ class _LiveScorer:
     """What the two live scorers are built from: the window rule's arguments checked, the ring sized
     (``ring_rows >= NSTEPS + max_push``), the centroids on the encoder's device, the encoder's widths."""
 
-    def __init__(self, encoder, means, threshold, k, n_labels, hop, max_push, ring_rows):
+    def __init__(self, encoder, means, threshold, k, n_labels, hop, max_push, ring_rows, gallery):
         self.encoder = encoder
         self._check_eval()
         who = type(self).__name__
@@ -760,6 +794,9 @@ class _LiveScorer:
         self.means = means.float().to(next(encoder.parameters()).device).contiguous()
         self.n_classes = encoder.MLP_sup2[0].weight.shape[0]
         self._D = encoder.MLP_sup1[0].weight.shape[0]                          # embedding width
+        # run-time enrolment: with a gallery windows are scored against it too and carry extended labels (OpenSetScorer)
+        self._rule = _Rule(self.means, n_labels, self.n_classes, gallery, who)
+        self.gallery = gallery
         self._width = encoder.tc_block.layers()[0].conv1d.weight.shape[1]      # frame-feature width: a ring row
         self._N, self._C = encoder.nmax_points, encoder.pc_block.pointnet1.module[0].weight.shape[1]   # a raw frame becomes [N, C]
         self.last_pointnet_saves = None
@@ -795,10 +832,8 @@ class StreamingScorer(_LiveScorer):
     def __init__(self, encoder: CGEncoder, means: torch.Tensor, threshold: float, k: int, n_labels: int,
                  hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None, seed: int = 0,
                  dedup_points: bool = False, keep_points=0, keep_rule: str = "first", gallery=None):
-        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
+        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows, gallery)
         dev = self.means.device
-        # run-time enrolment: windows are scored against the gallery too and carry extended labels (OpenSetScorer)
-        self.gallery = _checked_gallery(gallery, n_labels, self._D, "StreamingScorer")
         self.ring = torch.zeros((self.ring_rows, self._width), dtype=torch.float32, device=dev)
         self.dedup_points = bool(dedup_points)           # push_raw: distinct points once, pooled with their multiplicities
         self._set_keep(keep_points, keep_rule)           # push_raw: every frame thinned first
@@ -892,10 +927,7 @@ class StreamingScorer(_LiveScorer):
         plan = ops.WindowRows(self._starts[o:o + nw], self.T, self.ring_rows, self.ring_rows, dev=self._starts_dev[o:o + nw])
         logits, sup_fv, _ = F_hip.encoder_forward_windows(self.encoder, self.ring, plan, self.T)
         _, _, preds = ops.cross_entropy(logits, None, want_loss=False, want_preds=True)
-        if self.gallery is not None:
-            lik, preds, _ = self.gallery.score(sup_fv.contiguous(), preds, self.means, self.n_labels)
-        else:
-            lik = joint_likelihood(sup_fv.contiguous(), self.means)
+        preds, lik = self._rule.score(sup_fv.contiguous(), preds)
         self.n_windows = done
         self._preds.append(preds)
         self._lik.append(lik)
@@ -908,10 +940,7 @@ class StreamingScorer(_LiveScorer):
         preds, lik = torch.cat(self._preds), torch.cat(self._lik)
         self._preds, self._lik = [preds], [lik]
         n = (preds.numel() // self.k) * self.k
-        if self.gallery is not None:
-            return ops.gallery_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels)
-        return k_vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels,
-                      n_classes=self.n_classes)
+        return self._rule.vote(lik[:n].contiguous(), preds[:n].contiguous(), self.threshold, self.k, self.n_labels)
 
 
 class TickPlan:
@@ -1069,10 +1098,9 @@ class MultiStreamScorer(_LiveScorer):
                  max_streams: int = 64, hop: int = constants.CROP_STEP, max_push: int = 64, ring_rows: int = None,
                  batch_size: int = 1024, seed: int = 0, dedup_points: bool = False, keep_points=0,
                  keep_rule: str = "first", gallery=None, history: int = 0):
-        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows)
+        super().__init__(encoder, means, threshold, k, n_labels, hop, max_push, ring_rows, gallery)
         # run-time enrolment: the tick's scoring launch is ops.stream_score_gallery; ``history`` = H > 0 also keeps every
         # stream's last H embeddings on the device (fv_hist), from which ``enrol_stream`` enrols
-        self.gallery = _checked_gallery(gallery, n_labels, self._D, "MultiStreamScorer")
         self.history = int(history)
         if self.history < 0 or (self.history and self.gallery is None):
             raise ValueError("MultiStreamScorer: history must be >= 0, and a history needs a gallery to enrol into")
@@ -1235,14 +1263,5 @@ class MultiStreamScorer(_LiveScorer):
                                              nw > self.batch_size else rows, self.T, mode, consts=self._consts)[:2]
                for i in range(0, nw, self.batch_size)]
         logits, sup_fv = (frame_table.join_rows(part).contiguous() for part in zip(*out))
-        if self.gallery is not None:
-            g = self.gallery
-            labels, lik, _, votes = ops.stream_score_gallery(
-                logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
-                plan.vote_group.size, self.threshold, self.k, self.n_labels, g.centroids, g.counts, g.high_water,
-                self.hist_lik, self.hist_pred, self.fv_hist)
-            return _tick(plan, labels, sup_fv, lik, votes)
-        preds, lik, votes = ops.stream_score(
-            logits, sup_fv, self.means, part["run_start"], part["win_stream"], part["win_j"], part["vote_pos"],
-            plan.vote_group.size, self.threshold, self.k, self.n_labels, self.n_classes, self.hist_lik, self.hist_pred)
-        return _tick(plan, preds, sup_fv, lik, votes)
+        return _tick(plan, *self._rule.tick(logits, sup_fv, part, plan.vote_group.size, self.threshold, self.k, self.hist_lik,
+                                            self.hist_pred, self.fv_hist))

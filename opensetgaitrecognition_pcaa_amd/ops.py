@@ -1960,30 +1960,37 @@ def segment_weighted_mean_bwd(dpool, y, weight, u_off, N, scale, shift, mean, rs
     return dy, stats
 
 
+def _tick_io(who, logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, k, hist_lik, hist_lab, lab_name):
+    """the tensors of one tick checked for ``who`` (``stream_score`` / ``stream_score_gallery``) and its outputs allocated
+    -> (nw, K, D, k, n_votes, n_runs, labels [nw] int64, lik [nw] f64, votes [n_votes] int64)"""
+    _chk(logits, who + ".logits", torch.float32, 2)
+    _chk(sup_fv, who + ".sup_fv", torch.float32, 2)
+    _chk(means, who + ".means", torch.float32, 2)
+    _chk(hist_lik, who + ".hist_lik", torch.float64, 2)
+    _chk(hist_lab, f"{who}.{lab_name}", torch.int64, 2)
+    for t, name in ((run_start, "run_start"), (win_stream, "win_stream"), (win_j, "win_j"), (vote_pos, "vote_pos")):
+        _chk(t, f"{who}.{name}", torch.int32, 1)
+    nw, K = logits.shape
+    D = sup_fv.shape[1]
+    k, n_votes, n_runs = int(k), int(n_votes), run_start.numel() - 1
+    if (sup_fv.shape[0] != nw or means.shape[1] != D or win_stream.numel() != nw or win_j.numel() != nw
+            or vote_pos.numel() != nw or k < 1 or tuple(hist_lik.shape) != tuple(hist_lab.shape)
+            or hist_lik.shape[1] != k or not 0 <= n_votes <= nw or not (1 <= n_runs <= nw or nw == 0)):
+        raise ValueError(f"{who}: shapes do not describe one tick")
+    dev = logits.device
+    return (nw, K, D, k, n_votes, n_runs, torch.empty(nw, dtype=torch.int64, device=dev),
+            torch.empty(nw, dtype=torch.float64, device=dev), torch.empty(n_votes, dtype=torch.int64, device=dev))
+
+
 def stream_score(logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, threshold, k, n_labels,
                  n_classes, hist_lik, hist_pred):
     """One tick of many live streams in one launch (pcaa_stream_score) -> (preds [nw] int64, lik [nw] f64, votes [n_votes]
     int64).  ``run_start`` [n_runs + 1], ``win_stream`` / ``win_j`` / ``vote_pos`` [nw]: int32 on the device, from
     ``inference.plan_tick`` (a stream's windows are one contiguous ascending run).  ``hist_lik`` f64 / ``hist_pred`` int64
     [max_streams, k]: the streams' incomplete vote groups, read and updated in place."""
-    _chk(logits, "stream_score.logits", torch.float32, 2)
-    _chk(sup_fv, "stream_score.sup_fv", torch.float32, 2)
-    _chk(means, "stream_score.means", torch.float32, 2)
-    _chk(hist_lik, "stream_score.hist_lik", torch.float64, 2)
-    _chk(hist_pred, "stream_score.hist_pred", torch.int64, 2)
-    for t, name in ((run_start, "run_start"), (win_stream, "win_stream"), (win_j, "win_j"), (vote_pos, "vote_pos")):
-        _chk(t, "stream_score." + name, torch.int32, 1)
-    nw, K = logits.shape
-    D = sup_fv.shape[1]
-    k, n_votes, n_runs = int(k), int(n_votes), run_start.numel() - 1
-    if (sup_fv.shape[0] != nw or means.shape[1] != D or win_stream.numel() != nw or win_j.numel() != nw
-            or vote_pos.numel() != nw or k < 1 or tuple(hist_lik.shape) != tuple(hist_pred.shape)
-            or hist_lik.shape[1] != k or not 0 <= n_votes <= nw or not (1 <= n_runs <= nw or nw == 0)):
-        raise ValueError("stream_score: shapes do not describe one tick")
-    dev = logits.device
-    preds = torch.empty(nw, dtype=torch.int64, device=dev)
-    lik = torch.empty(nw, dtype=torch.float64, device=dev)
-    votes = torch.empty(n_votes, dtype=torch.int64, device=dev)
+    nw, K, D, k, n_votes, n_runs, preds, lik, votes = _tick_io(
+        "stream_score", logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, k, hist_lik, hist_pred,
+        "hist_pred")
     if nw:
         check(_lib.load().pcaa_stream_score(
             _p(logits), _p(sup_fv), _p(means), _p(run_start), n_runs, _p(win_stream), _p(win_j), _p(vote_pos), nw, K, D,
@@ -2075,21 +2082,10 @@ def stream_score_gallery(logits, sup_fv, means, run_start, win_stream, win_j, vo
     (pcaa_stream_score_gallery) -> (labels [nw] int64, lik [nw] f64, near [nw] int32, votes [n_votes] int64).
     ``hist_label`` int64 [max_streams, k] keeps the extended labels as they were stored.  ``fv_hist`` fp32
     [max_streams * H, D] (optional): window j of stream s also leaves its ``sup_fv`` in row ``s * H + j % H``."""
-    _chk(logits, "stream_score_gallery.logits", torch.float32, 2)
-    _chk(sup_fv, "stream_score_gallery.sup_fv", torch.float32, 2)
-    _chk(means, "stream_score_gallery.means", torch.float32, 2)
-    _chk(hist_lik, "stream_score_gallery.hist_lik", torch.float64, 2)
-    _chk(hist_label, "stream_score_gallery.hist_label", torch.int64, 2)
-    for t, name in ((run_start, "run_start"), (win_stream, "win_stream"), (win_j, "win_j"), (vote_pos, "vote_pos")):
-        _chk(t, "stream_score_gallery." + name, torch.int32, 1)
-    nw, K = logits.shape
-    D = sup_fv.shape[1]
+    nw, K, D, k, n_votes, n_runs, labels, lik, votes = _tick_io(
+        "stream_score_gallery", logits, sup_fv, means, run_start, win_stream, win_j, vote_pos, n_votes, k, hist_lik,
+        hist_label, "hist_label")
     _chk_gallery("stream_score_gallery", None, counts, centroids, E, D)
-    k, n_votes, n_runs = int(k), int(n_votes), run_start.numel() - 1
-    if (sup_fv.shape[0] != nw or means.shape[1] != D or win_stream.numel() != nw or win_j.numel() != nw
-            or vote_pos.numel() != nw or k < 1 or tuple(hist_lik.shape) != tuple(hist_label.shape)
-            or hist_lik.shape[1] != k or not 0 <= n_votes <= nw or not (1 <= n_runs <= nw or nw == 0)):
-        raise ValueError("stream_score_gallery: shapes do not describe one tick")
     H = 0
     if fv_hist is not None:
         _chk(fv_hist, "stream_score_gallery.fv_hist", torch.float32, 2)
@@ -2097,11 +2093,7 @@ def stream_score_gallery(logits, sup_fv, means, run_start, win_stream, win_j, vo
         if H < 1 or fv_hist.shape[0] != H * hist_lik.shape[0] or fv_hist.shape[1] != D:
             raise ValueError(f"stream_score_gallery: fv_hist must be [max_streams * H, {D}] with H >= 1, got "
                              f"{tuple(fv_hist.shape)} for {hist_lik.shape[0]} streams")
-    dev = logits.device
-    labels = torch.empty(nw, dtype=torch.int64, device=dev)
-    lik = torch.empty(nw, dtype=torch.float64, device=dev)
-    near = torch.empty(nw, dtype=torch.int32, device=dev)
-    votes = torch.empty(n_votes, dtype=torch.int64, device=dev)
+    near = torch.empty(nw, dtype=torch.int32, device=logits.device)
     if nw:
         check(_lib.load().pcaa_stream_score_gallery(
             _p(logits), _p(sup_fv), _p(means), _p(run_start), n_runs, _p(win_stream), _p(win_j), _p(vote_pos), nw, K, D,

@@ -198,10 +198,11 @@ def test_gallery_refusals(host_gallery):
     with pytest.raises(ValueError, match="in use"):
         g.enrol(fv)
     with pytest.raises(ValueError):
-        inference._checked_gallery(g, None, 4, "x")
+        inference._Rule(torch.zeros(2, 4), None, 2, g, "x")
     with pytest.raises(ValueError):
-        inference._checked_gallery(g, 3, 5, "x")
-    assert inference._checked_gallery(None, None, 4, "x") is None
+        inference._Rule(torch.zeros(2, 5), 3, 2, g, "x")
+    assert inference._Rule(torch.zeros(2, 4), 3, 2, g, "x").gallery is g
+    assert inference._Rule(torch.zeros(2, 4), None, 2, None, "x").gallery is None
 
 
 def test_state_dict_round_trip(host_gallery):
@@ -250,6 +251,49 @@ def test_plan_enrolment_is_the_draw_of_sequential_votes():
     for shots in (0, 100):
         _, idents, rows, keep = inference.plan_enrolment(lab, shots)
         assert not idents and not rows and keep.all()
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("unknown", [False, True])
+def test_voted_windows_is_the_loop_of_the_sequential_procedure(k, unknown):
+    """``_voted_windows`` against the loop as ``_sequential_votes`` and ``enrolment_sweep`` each carried it before they
+    shared it, copied here: 31 crops of 4 subjects (a trailing partial group at k = 2 and 3), groups that straddle two
+    subjects, one validation subject, one enrolled subject"""
+    lab = np.repeat([12, 10, 13, 11], [9, 7, 8, 7])
+    val_subjects, idents, n_labels = np.array([13]), {10: 0}, 5
+    n = (len(lab) // k) * k
+    all_votes = np.arange(100, 100 + n // k)
+    label_of = (lambda s: n_labels + 1 + idents[s] if s in idents else n_labels) if unknown else (lambda s: s)
+    seen = []
+
+    def vote(m):
+        seen.append(m)
+        return torch.from_numpy(all_votes)
+    want_preds, want_labels = [], []
+    for w in range(n // k):
+        seg = lab[w * k:(w + 1) * k]
+        if len(np.unique(seg)) != 1:
+            continue
+        if unknown and seg[0] in val_subjects:
+            continue
+        want_preds.append(int(all_votes[w]))
+        want_labels.append(int(seg[0]) if not unknown else
+                           n_labels + 1 + idents[int(seg[0])] if int(seg[0]) in idents else n_labels)
+    got_preds, got_labels = inference._voted_windows(k, lab, vote, val_subjects, unknown, label_of)
+    assert seen == [n] and got_preds == want_preds and got_labels == want_labels
+    assert all(type(x) is int for x in got_preds + got_labels)
+    straddling = sum(len(np.unique(lab[w * k:(w + 1) * k])) != 1 for w in range(n // k))
+    assert (straddling > 0) == (k > 1), "the case must hold a window that straddles two subjects"
+    assert (13 in [int(lab[w * k]) for w in range(n // k)]) and (unknown or 13 in got_labels)
+
+
+def test_validation_subjects_is_the_first_draw():
+    lab = np.repeat(np.arange(10, 20), [5, 3, 8, 2, 9, 4, 6, 7, 1, 5])
+    for seed, ratio in ((0, 0.2), (3, 0.35), (1, 0.0)):
+        subjects = np.unique(lab)
+        want = np.random.default_rng(seed).choice(subjects, size=int(np.ceil(ratio * len(subjects))), replace=False)
+        assert np.array_equal(inference._validation_subjects(lab, np.random.default_rng(seed), ratio), want)
+        assert np.array_equal(inference.plan_enrolment(lab, 3, seed=seed, unseen_valid_ratio=ratio)[0], want)
 
 
 def test_header_declares_the_entry_points():
