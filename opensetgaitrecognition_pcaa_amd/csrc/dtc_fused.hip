@@ -134,149 +134,15 @@ __device__ __forceinline__ void write_col(float* col, int K, const float* a_lds,
   }
 }
 
-// gridDim.z > 1 splits the input channels over workgroups (the 1024->16 layer: 64 workgroups walking
-// K = 3072 was one long chain of load latencies): split z writes its partial tile to y + z*slab_stride
-// and pcaa_splitk_reduce_stats finishes the sum and the statistics.
-__global__ __launch_bounds__(256) void dtc_fwd_kernel(DtcFwdParams p) {
-  __shared__ __attribute__((aligned(16))) float a_lds[(ROWS + 1) * (MAX_CR + 4)];   // later: the 4 partial tiles
-  __shared__ __attribute__((aligned(16))) float Ws[32 * WP];
-  __shared__ float red[2][8][32];
-  __shared__ int tail_flag;
-  static_assert(4 * ROWS * 33 <= (ROWS + 1) * (MAX_CR + 4), "partial tiles alias the sequence tile");
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const int b = blockIdx.x, n0 = blockIdx.y * 32;
-  const int T = p.T, cin = p.cin, K = cin * 3, d = p.dil;
-  const bool split = gridDim.z > 1;
-  float* yout = p.y + (long)blockIdx.z * p.slab_stride;
-  // this workgroup's input-channel range [cz0, cz0+cr)
-  const int per_z = ((cin + CC - 1) / CC + (int)gridDim.z - 1) / (int)gridDim.z * CC;
-  const int cz0 = blockIdx.z * per_z;
-  const int cr = max(0, min(cin, cz0 + per_z) - cz0);
-  const int AP = cr + 4;
-
-  DTC_T0();
-  // ---- the activated sequence tile, once
-  {
-    const int q4 = cr >> 2;
-    const bool act = p.scale != nullptr;
-    const DtcSrc row0 = dtc_src_row0(p, b);
-    for (int q = tid; q < T * q4; q += 256) {
-      const int r = q / q4, c4 = (q - r * q4) << 2;
-      f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
-      if (act) {
-        const f32x4 sc = load4(p.scale + cz0 + c4), sh = load4(p.shift + cz0 + c4);
-        v.x = elu_stage(fmaf(sc.x, v.x, sh.x));
-        v.y = elu_stage(fmaf(sc.y, v.y, sh.y));
-        v.z = elu_stage(fmaf(sc.z, v.z, sh.z));
-        v.w = elu_stage(fmaf(sc.w, v.w, sh.w));
-      }
-      *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
-    }
-    for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;     // rows T..31 and the zero row
-  }
-  f32x4 rw[3];
-  auto load_w = [&](int c0) {
-    // 32 columns x 96 contiguous floats W[n0+c][(cz0+c0)*3 ...]: float4 q -> (column c = q / 24, run offset f)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = tid + j * 256;
-      const int c = q / 24, f = (q - c * 24) << 2;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (n0 + c < p.cout && c0 * 3 + f < cr * 3) v = load4(p.W + (long)(n0 + c) * K + (long)(cz0 + c0) * 3 + f);
-      rw[j] = v;
-    }
-  };
-  auto store_w = [&]() {
-    // scatter tap-major: run element kk = ci_l*3 + tap -> Ws[c][tap*CC + ci_l]
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = tid + j * 256;
-      const int c = q / 24, f = (q - c * 24) << 2;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int kk = f + m, ci_l = kk / 3, tap = kk - ci_l * 3;
-        Ws[c * WP + tap * CC + ci_l] = rw[j][m];
-      }
-    }
-  };
-  if (cr > 0) load_w(0);
-  __syncthreads();
-  DTC_MARK(0);      // staging
-  if (p.col != nullptr) write_col(p.col + (long)b * T * K + (long)cz0 * 3, K, a_lds, AP, T, cr, d, tid);
-
-  DTC_MARK(1);      // im2col
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  for (int c0 = 0; c0 < cr; c0 += CC) {
-    if (c0 > 0) __syncthreads();          // previous trip's readers are done with the weight tile
-    store_w();
-    __syncthreads();
-    if (c0 + CC < cr) load_w(c0 + CC);    // in flight while this chunk is consumed
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      const int gg = wave * 3 + g;        // 12 groups of 8 per chunk: tap = gg / 4, 8 channels each
-      const int tap = gg >> 2, ci_l = ((gg & 3) << 3) + (half << 2);
-      const int rs = l31 - (2 - tap) * d;
-      const float* ap = (rs >= 0 && c0 + ci_l < cr) ? &a_lds[rs * AP + c0 + ci_l] : &a_lds[ZROW * AP];
-      const f32x4 av = *reinterpret_cast<const f32x4*>(ap);
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(&Ws[l31 * WP + tap * CC + ci_l]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wv.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wv.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wv.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wv.w, acc, 0, 0, 0);
-    }
-  }
-  DTC_MARK(2);      // contraction
-  // combine the four waves' partial tiles (accumulator i of lane (l31, half) is row (i&3) + 8*(i>>2) + 4*half,
-  // column l31); the sequence tile is dead by now
-  __syncthreads();
-  float (*part)[ROWS][33] = reinterpret_cast<float (*)[ROWS][33]>(a_lds);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) part[wave][(i & 3) + 8 * (i >> 2) + 4 * half][l31] = acc[i];
-  __syncthreads();
-  const int colx = tid & 31, rg = tid >> 5, gn = n0 + colx;
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = rg + 8 * i;
-    const float v = (part[0][r][colx] + part[1][r][colx]) + (part[2][r][colx] + part[3][r][colx]);
-    if (r < T && gn < p.cout) {
-      yout[((long)b * T + r) * p.cout + gn] = v;
-      s1 += v;
-      s2 += v * v;
-    }
-  }
-  DTC_MARK(3);      // combine + store
-  if (p.stats != nullptr && !split) {
-    red[0][rg][colx] = s1;
-    red[1][rg][colx] = s2;
-    __syncthreads();
-    if (tid < 64) {
-      const int stat = tid >> 5, c = tid & 31;
-      if (n0 + c < p.cout) {
-        double v = 0.0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) v += (double)red[stat][g][c];
-        unsafeAtomicAdd(&p.stats[((long)(b % p.nrep) * 2 + stat) * p.cout + n0 + c], v);
-      }
-    }
-  }
-  DTC_MARK(4);      // statistics
-  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, &tail_flag);
-  DTC_MARK(5);      // tail
-}
-
-
-// ------------------------------------------------------------------ round 4: the bf16 throughput mode's variant
-// Same staging, same implicit im2col, same statistics -- but the contraction runs on v_mfma_f32_32x32x16_bf16 (the
-// operands are rounded to bf16 as the fragments are built: the activated tile stays fp32 in the LDS, so the im2col
-// matrix for the weight gradient is unchanged; the weight chunk is stored as bf16), and a workgroup owns 128 output
-// channels -- one 32-column block per wave, the whole contraction in that wave, no cross-wave reduction -- so a
-// sequence's tile is staged and activated by 4 workgroups instead of 16 (256 -> 512 layer).  A 96-deep chunk is 6 MFMAs
-// of 32 cycles per wave instead of 12 of 64: the contraction leaves the kernel's critical path (layer 6: 22 us of 45).
-constexpr int NCT = 128;            // output channels per workgroup
+// ------------------------------------------------------------------ the pieces every kernel of this file is built from
+// A workgroup stages its sequence tile once, then walks the contraction in 96-deep chunks (CC channels x 3 taps): the
+// chunk's weights go from HBM to registers (chunk_load), from there tap-major into an LDS tile of NT output columns
+// (chunk_store), and meet the sequence tile on the matrix pipe (contract_chunk); the results leave through Emit and one
+// of the statistics commits.  ADJ: the adjoint (rows offset forwards in time, weights read along their rows and scattered
+// transposed).  BF: the bf16 throughput mode, v_mfma_f32_32x32x16_bf16 on operands rounded as the fragments are built
+// (the sequence tile stays fp32 in the LDS, so the im2col matrix for the weight gradient is unchanged; the weight chunk is
+// stored as bf16): a 96-deep chunk is 6 MFMAs of 32 cycles instead of 12 of 64.
+constexpr int NCT = 128;            // output channels of a one-sequence bf16 workgroup
 constexpr int WPH = 3 * CC + 8;     // bf16 pitch of a weight-tile row (208 B)
 
 __device__ __forceinline__ bf16x8 cvt8(const float* p) {
@@ -287,114 +153,276 @@ __device__ __forceinline__ bf16x8 cvt8(const float* p) {
   return r;
 }
 
-__global__ __launch_bounds__(256) void dtc_fwd_bf16_kernel(DtcFwdParams p) {
-  __shared__ __attribute__((aligned(16))) float a_lds[(ROWS + 1) * (MAX_CR + 4)];
-  __shared__ __attribute__((aligned(16))) bf16_t Ws[NCT * WPH];
-  __shared__ int tail_flag;
+// BatchNorm + ELU of the layer before on one staged quad
+__device__ __forceinline__ f32x4 activate4(f32x4 v, const f32x4& sc, const f32x4& sh) {
+  v.x = elu_stage(fmaf(sc.x, v.x, sh.x));
+  v.y = elu_stage(fmaf(sc.y, v.y, sh.y));
+  v.z = elu_stage(fmaf(sc.z, v.z, sh.z));
+  v.w = elu_stage(fmaf(sc.w, v.w, sh.w));
+  return v;
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const int b = blockIdx.x, n0 = blockIdx.y * NCT;
-  const int T = p.T, cin = p.cin, K = cin * 3, d = p.dil;
-  const bool split = gridDim.z > 1;
-  float* yout = p.y + (long)blockIdx.z * p.slab_stride;
-  const int per_z = ((cin + CC - 1) / CC + (int)gridDim.z - 1) / (int)gridDim.z * CC;
-  const int cz0 = blockIdx.z * per_z;
-  const int cr = max(0, min(cin, cz0 + per_z) - cz0);
-  const int AP = cr + 4;
-  {
-    const int q4 = cr >> 2;
-    const bool act = p.scale != nullptr;
-    const DtcSrc row0 = dtc_src_row0(p, b);
-    for (int q = tid; q < T * q4; q += 256) {
-      const int r = q / q4, c4 = (q - r * q4) << 2;
-      f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * cin + cz0 + c4);
-      if (act) {
-        const f32x4 sc = load4(p.scale + cz0 + c4), sh = load4(p.shift + cz0 + c4);
-        v.x = elu_stage(fmaf(sc.x, v.x, sh.x));
-        v.y = elu_stage(fmaf(sc.y, v.y, sh.y));
-        v.z = elu_stage(fmaf(sc.z, v.z, sh.z));
-        v.w = elu_stage(fmaf(sc.w, v.w, sh.w));
-      }
-      *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
+// (dy = coef0*dz + coef1*y + coef2 stays spelled out in both adjoint staging loops: as a function of the quad the compiler
+// contracts the other of its two products into the fused multiply-add in the pair kernel, and dy changes in the last bit)
+
+// One chunk of weights into registers, NT * 24 / 256 quads per thread.  c0g: the chunk's first contraction channel, kend:
+// the end of the workgroup's contraction range, wrow: floats per row of W, nc: output columns.
+//   forward: NT columns x 96 contiguous floats W[n0 + c][c0g * 3 ...]: quad q -> (column c = q / 24, run offset f)
+//   adjoint: 32 contraction rows x (NT * 3) contiguous floats W[c0g + co_l][n0 * 3 ...]
+template <bool ADJ, int NT>
+__device__ __forceinline__ void chunk_load(f32x4 (&rw)[NT * 24 / 256], const float* W, long wrow, int n0, int nc, int c0g,
+                                           int kend, int tid) {
+#pragma unroll
+  for (int j = 0; j < NT * 24 / 256; ++j) {
+    const int q = tid + j * 256;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (!ADJ) {
+      const int c = q / 24, f = (q - c * 24) << 2;
+      if (n0 + c < nc && c0g * 3 + f < kend * 3) v = load4(W + (long)(n0 + c) * wrow + (long)(c0g * 3 + f));
+    } else {
+      constexpr int RUN4 = NT * 3 / 4;
+      const int co_l = q / RUN4, f = (q - co_l * RUN4) << 2;
+      if (c0g + co_l < kend && (long)n0 * 3 + f < wrow) v = load4(W + (long)(c0g + co_l) * wrow + (long)n0 * 3 + f);
     }
+    rw[j] = v;
+  }
+}
+
+// ... and from the registers tap-major into the weight tile: run element kk = channel * 3 + tap goes to
+// row = output column, k' = tap * CC + contraction channel (fp32 rows of WP floats, bf16 rows of WPH halves)
+template <bool ADJ, bool BF, int NT>
+__device__ __forceinline__ void chunk_store(const f32x4 (&rw)[NT * 24 / 256], float* wtile, int tid) {
+  bf16_t* wh = reinterpret_cast<bf16_t*>(wtile);
+#pragma unroll
+  for (int j = 0; j < NT * 24 / 256; ++j) {
+    const int q = tid + j * 256;
+    int row0, f;          // forward: row0 = the column, k' from f;  adjoint: row0 = contraction channel, column from f
+    if (!ADJ) { row0 = q / 24; f = (q - row0 * 24) << 2; }
+    else { constexpr int RUN4 = NT * 3 / 4; row0 = q / RUN4; f = (q - row0 * RUN4) << 2; }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int kk = f + m, a = kk / 3, tap = kk - a * 3;
+      const int col = ADJ ? a : row0, kl = ADJ ? row0 : a;
+      if (BF) wh[col * WPH + tap * CC + kl] = (bf16_t)rw[j][m];
+      else wtile[col * WP + tap * CC + kl] = rw[j][m];
+    }
+  }
+}
+
+// The MFMAs of one chunk on a wave's 32 x 32 block: tile-local channels cl .. cl + 31 of the kr staged ones against column
+// wcol of the weight tile, k-groups g0 .. g0 + NG - 1.  fp32: 12 groups of 8 per chunk (tap = g / 4), a lane's four
+// consecutive k' feed four 32x32x2 MFMAs;  bf16: 6 steps of 16 (tap = g / 2), a lane's eight feed one 32x32x16.  The taps
+// are row offsets of the A-fragment reads; a row outside the sequence, or a channel outside the range, reads the zero row.
+template <bool ADJ, bool BF, int NG>
+__device__ __forceinline__ void contract_chunk(f32x16& acc, const float* tile, int AP, const float* wtile, int wcol, int g0,
+                                               int cl, int kr, int T, int d, int l31, int half) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int gg = g0 + g;
+    const int tap = BF ? gg >> 1 : gg >> 2;
+    const int kl = BF ? ((gg & 1) << 4) + (half << 3) : ((gg & 3) << 3) + (half << 2);
+    const int rs = ADJ ? l31 + (2 - tap) * d : l31 - (2 - tap) * d;
+    const bool ok = (ADJ ? rs < T : rs >= 0) && cl + kl < kr;
+    const float* ap = ok ? &tile[rs * AP + cl + kl] : &tile[ZROW * AP];
+    if (BF) {
+      const bf16x8 av = cvt8(ap);
+      const bf16x8 wv = *reinterpret_cast<const bf16x8*>(&reinterpret_cast<const bf16_t*>(wtile)[wcol * WPH + tap * CC + kl]);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, acc, 0, 0, 0);
+    } else {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(ap);
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(&wtile[wcol * WP + tap * CC + kl]);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wv.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wv.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wv.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wv.w, acc, 0, 0, 0);
+    }
+  }
+}
+
+// accumulator i of lane (l31, half) is row acc_row(i, half), column l31 of the wave's block
+__device__ __forceinline__ constexpr int acc_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
+
+// Waves that split a chunk's k-groups combine their partial tiles through part[.][ROWS][33], which aliases the sequence
+// tile: a barrier before the stores (the tile's readers are done) and one after
+__device__ __forceinline__ void part_store(float* part, int w, const f32x16& acc, int l31, int half) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) part[(w * ROWS + acc_row(i, half)) * 33 + l31] = acc[i];
+}
+__device__ __forceinline__ float part_at(const float* part, int w, int r, int c) { return part[(w * ROWS + r) * 33 + c]; }
+
+// One result leaves: the store and its two statistic terms (a thread calls it in ascending row order).
+//   forward: y and {sum y, sum y^2}
+//   adjoint: da, or with ``ep`` the first half of the BatchNorm+ELU backward of the layer below: dz = da * ELU'(z) and
+//            {sum dz, sum dz * yhat}
+template <bool ADJ>
+struct Emit {
+  float* out;           // [B*T, nc]
+  int T, nc;
+  bool ep;
+  const float* ep_y;
+  float esc = 0.f, esh = 0.f, emu = 0.f, ers = 0.f;
+  float s1 = 0.f, s2 = 0.f;
+  // the epilogue's per-column constants, for the one column gn this thread emits
+  template <class P>
+  __device__ __forceinline__ void column(const P& p, int gn) {
+    if (ep && gn < nc) { esc = p.ep_scale[gn]; esh = p.ep_shift[gn]; emu = p.ep_mean[gn]; ers = p.ep_rstd[gn]; }
+  }
+  __device__ __forceinline__ void operator()(float v, int b, int r, int gn) {
+    const long g = ((long)b * T + r) * nc + gn;
+    if (!ADJ) {
+      out[g] = v;
+      s1 += v;
+      s2 += v * v;
+    } else {
+      if (ep) {
+        const float yb = ep_y[g];
+        v *= elu_grad_from_pre(fmaf(yb, esc, esh));
+        s1 += v;
+        s2 += v * ((yb - emu) * ers);
+      }
+      out[g] = v;
+    }
+  }
+};
+
+// Statistics of a 32-column tile whose thread (row group tid >> 5, column tid & 31) holds the sums of its rows: the 8 row
+// groups meet in red[2][8][32], 64 threads add them in fp64, ascending, and issue one atomic each into replica ``rep``
+__device__ __forceinline__ void commit_stats_rows(float* red, float s1, float s2, int tid, double* stats, int rep, int nc, int n0) {
+  red[(0 * 8 + (tid >> 5)) * 32 + (tid & 31)] = s1;
+  red[(1 * 8 + (tid >> 5)) * 32 + (tid & 31)] = s2;
+  __syncthreads();
+  if (tid < 64) {
+    const int stat = tid >> 5, c = tid & 31;
+    if (n0 + c < nc) {
+      double v = 0.0;
+#pragma unroll
+      for (int g = 0; g < 8; ++g) v += (double)red[(stat * 8 + g) * 32 + c];
+      unsafeAtomicAdd(&stats[((long)rep * 2 + stat) * nc + n0 + c], v);
+    }
+  }
+}
+
+// Statistics of a wave that holds all rows of its 32 columns in registers: the two half-waves' sums meet by a shuffle and
+// half 0 adds (``own``: this lane is in half 0 and its column gn exists)
+__device__ __forceinline__ void commit_stats_wave(float s1, float s2, bool own, double* stats, int rep, int nc, int gn) {
+  s1 += __shfl_xor(s1, 32, 64);
+  s2 += __shfl_xor(s2, 32, 64);
+  if (own) {
+    unsafeAtomicAdd(&stats[((long)rep * 2 + 0) * nc + gn], (double)s1);
+    unsafeAtomicAdd(&stats[((long)rep * 2 + 1) * nc + gn], (double)s2);
+  }
+}
+
+// ------------------------------------------------------------------ one sequence per workgroup
+// gridDim.z > 1 splits the contraction channels over workgroups in whole chunks (the 1024->16 layer: 64 workgroups walking
+// K = 3072 was one long chain of load latencies): split z writes its partial product to its slab and
+// pcaa_splitk_reduce_stats finishes the sum and the statistics.  This workgroup's range is [cz0, cz0 + cr).
+struct ZRange { int cz0, cr; };
+__device__ __forceinline__ ZRange split_range(int kc) {
+  const int per_z = ((kc + CC - 1) / CC + (int)gridDim.z - 1) / (int)gridDim.z * CC;
+  const int cz0 = blockIdx.z * per_z;
+  return ZRange{cz0, max(0, min(kc, cz0 + per_z) - cz0)};
+}
+
+// what both staging loops leave behind the T staged rows of the tile (pitch AP = cr + 4)
+template <bool BF>
+__device__ __forceinline__ void stage_zero_rest(float* a_lds, int T, int cr, int AP, int tid) {
+  if (BF) {
     // cvt8 reads 8 floats from a column that is a multiple of 8: with cr % 8 == 4 a row's last fragment takes in the
     // row's four pad floats, which meet zero weights -- and 0 x NaN is NaN on the matrix pipe: the pad is zeros
     for (int r = tid; r < T; r += 256) *reinterpret_cast<f32x4*>(&a_lds[r * AP + cr]) = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;
   }
-  // weight chunk: 128 columns x 96 contiguous floats W[n0 + c][(cz0 + c0) * 3 ...], 12 float4 per thread
-  f32x4 rw[12];
-  auto load_w = [&](int c0) {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      const int q = tid + j * 256;
-      const int c = q / 24, f = (q - c * 24) << 2;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (n0 + c < p.cout && c0 * 3 + f < cr * 3) v = load4(p.W + (long)(n0 + c) * K + (long)(cz0 + c0) * 3 + f);
-      rw[j] = v;
-    }
-  };
-  auto store_w = [&]() {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      const int q = tid + j * 256;
-      const int c = q / 24, f = (q - c * 24) << 2;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int kk = f + m, ci_l = kk / 3, tap = kk - ci_l * 3;
-        Ws[c * WPH + tap * CC + ci_l] = (bf16_t)rw[j][m];
-      }
-    }
-  };
-  if (cr > 0) load_w(0);
+  for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;     // rows T..31 and the zero row
+}
+
+// the activated sequence tile of sequence b, once (coalesced 16-B loads, one ELU per element)
+template <bool BF>
+__device__ __forceinline__ void stage_one_fwd(const DtcFwdParams& p, float* a_lds, int b, int cz0, int cr, int AP, int tid) {
+  const int T = p.T, q4 = cr >> 2;
+  const bool act = p.scale != nullptr;
+  const DtcSrc row0 = dtc_src_row0(p, b);
+  for (int q = tid; q < T * q4; q += 256) {
+    const int r = q / q4, c4 = (q - r * q4) << 2;
+    f32x4 v = load4(p.src + dtc_src_row(p, row0, r) * p.cin + cz0 + c4);
+    if (act) v = activate4(v, load4(p.scale + cz0 + c4), load4(p.shift + cz0 + c4));
+    *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
+  }
+  stage_zero_rest<BF>(a_lds, T, cr, AP, tid);
+}
+
+template <bool BF>
+__global__ __launch_bounds__(256) void dtc_fwd_one_kernel(DtcFwdParams p) {
+  // fp32: 32 output channels, the four waves split each chunk's k-groups on the same 32x32 tile and are combined through
+  // the LDS.  bf16: 128 output channels, one 32-column block per wave, the whole contraction in that wave, no cross-wave
+  // reduction -- a sequence's tile is staged and activated by 4 workgroups instead of 16 (256 -> 512 layer)
+  constexpr int NT = BF ? NCT : 32;
+  constexpr int TILE_FLOATS = (ROWS + 1) * (MAX_CR + 4), W_FLOATS = BF ? NCT * WPH / 2 : 32 * WP, RED_FLOATS = BF ? 0 : 2 * 8 * 32;
+  __shared__ __attribute__((aligned(16))) float smem[TILE_FLOATS + W_FLOATS + RED_FLOATS + 1];
+  static_assert(BF || 4 * ROWS * 33 <= TILE_FLOATS, "partial tiles alias the sequence tile");
+  static_assert(TILE_FLOATS % 4 == 0, "the weight tile is 16-B aligned");
+  float* a_lds = smem;                                 // [ROWS + 1][cr + 4]; fp32: later the 4 partial tiles
+  float* Ws = smem + TILE_FLOATS;                      // fp32 [32][WP], bf16 [NCT][WPH]
+  float* red = Ws + W_FLOATS;                          // fp32 only: [2][8][32]
+  int* tail_flag = reinterpret_cast<int*>(red + RED_FLOATS);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
+  const int b = blockIdx.x, n0 = blockIdx.y * NT;
+  const int T = p.T, cin = p.cin, K = cin * 3, d = p.dil;
+  const bool split = gridDim.z > 1;
+  const ZRange z = split_range(cin);
+  const int cz0 = z.cz0, cr = z.cr, AP = cr + 4;
+
+  DTC_T0();
+  stage_one_fwd<BF>(p, a_lds, b, cz0, cr, AP, tid);
+  const float* Wz = p.W + (long)cz0 * 3;               // this split's weights: W[.][cz0 * 3 ...]
+  f32x4 rw[NT * 24 / 256];
+  if (cr > 0) chunk_load<false, NT>(rw, Wz, K, n0, p.cout, 0, cr, tid);
   __syncthreads();
+  DTC_MARK(0);      // staging
   if (p.col != nullptr) write_col(p.col + (long)b * T * K + (long)cz0 * 3, K, a_lds, AP, T, cr, d, tid);
-  const bool active = n0 + wave * 32 < p.cout;      // (wave-uniform) this wave's 32 columns exist
+  DTC_MARK(1);      // im2col
+  const bool active = !BF || n0 + wave * 32 < p.cout;   // (wave-uniform) bf16: this wave's 32 columns exist
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   for (int c0 = 0; c0 < cr; c0 += CC) {
-    if (c0 > 0) __syncthreads();
-    store_w();
+    if (c0 > 0) __syncthreads();          // previous trip's readers are done with the weight tile
+    chunk_store<false, BF, NT>(rw, Ws, tid);
     __syncthreads();
-    if (c0 + CC < cr) load_w(c0 + CC);
-    if (active) {
+    if (c0 + CC < cr) chunk_load<false, NT>(rw, Wz, K, n0, p.cout, c0 + CC, cr, tid);    // in flight while this chunk is consumed
+    if (active) contract_chunk<false, BF, BF ? 6 : 3>(acc, a_lds, AP, Ws, (BF ? wave * 32 : 0) + l31, BF ? 0 : wave * 3, c0, cr, T, d, l31, half);
+  }
+  DTC_MARK(2);      // contraction
+  Emit<false> emit{p.y + (long)blockIdx.z * p.slab_stride, T, p.cout, false, nullptr};
+  const bool want_stats = p.stats != nullptr && !split;
+  if (!BF) {
+    __syncthreads();                      // the sequence tile is dead by now
+    part_store(a_lds, wave, acc, l31, half);
+    __syncthreads();
+    const int colx = tid & 31, rg = tid >> 5, gn = n0 + colx;
 #pragma unroll
-      for (int st = 0; st < 6; ++st) {
-        // k' = tap * 32 + ci_l: step st covers k' = 16 st .. 16 st + 15, this lane's eight are 16 st + 8 half ...
-        const int tap = st >> 1, ci_l = ((st & 1) << 4) + (half << 3);
-        const int rs = l31 - (2 - tap) * d;
-        const float* ap = (rs >= 0 && c0 + ci_l < cr) ? &a_lds[rs * AP + c0 + ci_l] : &a_lds[ZROW * AP];
-        const bf16x8 av = cvt8(ap);
-        const bf16x8 wv = *reinterpret_cast<const bf16x8*>(&Ws[(wave * 32 + l31) * WPH + tap * CC + ci_l]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, acc, 0, 0, 0);
+    for (int i = 0; i < 4; ++i) {
+      const int r = rg + 8 * i;
+      const float v = (part_at(a_lds, 0, r, colx) + part_at(a_lds, 1, r, colx)) + (part_at(a_lds, 2, r, colx) + part_at(a_lds, 3, r, colx));
+      if (r < T && gn < p.cout) emit(v, b, r, gn);
+    }
+    DTC_MARK(3);    // combine + store
+    if (want_stats) commit_stats_rows(red, emit.s1, emit.s2, tid, p.stats, b % p.nrep, p.cout, n0);
+  } else {
+    const int gn = n0 + wave * 32 + l31;
+    if (active && gn < p.cout) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int r = acc_row(i, half);
+        if (r < T) emit(acc[i], b, r, gn);
       }
     }
+    DTC_MARK(3);    // store
+    if (want_stats) commit_stats_wave(emit.s1, emit.s2, active && half == 0 && gn < p.cout, p.stats, b % p.nrep, p.cout, gn);
   }
-  // accumulator i of lane (l31, half) is row (i & 3) + 8 (i >> 2) + 4 half, column l31 of the wave's block
-  const int gn = n0 + wave * 32 + l31;
-  float s1 = 0.f, s2 = 0.f;
-  if (active && gn < p.cout) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int r = (i & 3) + 8 * (i >> 2) + 4 * half;
-      if (r < T) {
-        const float v = acc[i];
-        yout[((long)b * T + r) * p.cout + gn] = v;
-        s1 += v;
-        s2 += v * v;
-      }
-    }
-  }
-  if (p.stats != nullptr && !split) {
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    if (active && half == 0 && gn < p.cout) {
-      unsafeAtomicAdd(&p.stats[((long)(b % p.nrep) * 2 + 0) * p.cout + gn], (double)s1);
-      unsafeAtomicAdd(&p.stats[((long)(b % p.nrep) * 2 + 1) * p.cout + gn], (double)s2);
-    }
-  }
-  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, &tail_flag);
+  DTC_MARK(4);      // statistics
+  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, tail_flag);
+  DTC_MARK(5);      // tail
 }
 
 // ------------------------------------------------------------------ backward w.r.t. the layer input
@@ -424,255 +452,97 @@ constexpr int DG_MAX_CR = 512;                       // contraction channels per
 constexpr int DG_PART_FLOATS = 4 * ROWS * 33;        // the four waves' partial tiles alias the sequence tile
 static inline int dg_tile_floats(int cr) { const int a = (ROWS + 1) * (cr + 4); return a > DG_PART_FLOATS ? a : DG_PART_FLOATS; }
 
-__global__ __launch_bounds__(256) void dtc_dgrad_kernel(DtcDgradParams p, int tile_floats) {
-  extern __shared__ __attribute__((aligned(16))) float dg_smem[];
-  float* a_lds = dg_smem;                            // [(ROWS+1)][cr+4], later part[4][ROWS][33]
-  float* Ws = dg_smem + tile_floats;                 // [32][WP]
-  float* red = Ws + 32 * WP;                         // [2][8][32]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const int b = blockIdx.x, n0 = blockIdx.y * 32;                 // n0: first input channel (output column)
-  const int T = p.T, cin = p.cin, cout = p.cout, d = p.dil;
-  const long wrow = (long)cin * 3;
-  float* out = p.out + (long)blockIdx.z * p.slab_stride;
-  const int per_z = ((cout + CC - 1) / CC + (int)gridDim.z - 1) / (int)gridDim.z * CC;
-  const int cz0 = blockIdx.z * per_z;
-  const int cr = max(0, min(cout, cz0 + per_z) - cz0);
-  const int AP = cr + 4;
-  DTC_T0();
-  {
-    const int q4 = cr >> 2;
-    const bool form = p.dy == nullptr;
-    const bool keep = p.dy_out != nullptr && blockIdx.y == 0;
-    for (int q = tid; q < T * q4; q += 256) {
-      const int r = q / q4, c4 = (q - r * q4) << 2;
-      const long g = ((long)b * T + r) * cout + cz0 + c4;
-      f32x4 v;
-      if (form) {
-        const f32x4 k0 = load4(p.coef + cz0 + c4), k1 = load4(p.coef + cout + cz0 + c4),
-                    k2 = load4(p.coef + 2 * cout + cz0 + c4);
-        v = k0 * load4(p.dz + g) + k1 * load4(p.y + g) + k2;
-      } else {
-        v = load4(p.dy + g);
-      }
-      *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
-      if (keep) store4(p.dy_out + g, v);
+// the gradient sequence tile of sequence b, once: dy as given or formed on load; the first column tile keeps it for the wgrad
+template <bool BF>
+__device__ __forceinline__ void stage_one_adj(const DtcDgradParams& p, float* a_lds, int b, int cz0, int cr, int AP, int tid) {
+  const int T = p.T, cout = p.cout, q4 = cr >> 2;
+  const bool form = p.dy == nullptr;
+  const bool keep = p.dy_out != nullptr && blockIdx.y == 0;
+  for (int q = tid; q < T * q4; q += 256) {
+    const int r = q / q4, c4 = (q - r * q4) << 2;
+    const long g = ((long)b * T + r) * cout + cz0 + c4;
+    f32x4 v;
+    if (form) {
+      const f32x4 k0 = load4(p.coef + cz0 + c4), k1 = load4(p.coef + cout + cz0 + c4),
+                  k2 = load4(p.coef + 2 * cout + cz0 + c4);
+      v = k0 * load4(p.dz + g) + k1 * load4(p.y + g) + k2;
+    } else {
+      v = load4(p.dy + g);
     }
-    for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;
+    *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
+    if (keep) store4(p.dy_out + g, v);
   }
-  f32x4 rw[3];
-  auto load_w = [&](int c0) {
-    // 32 contraction channels co x 96 contiguous floats W[cz0+c0+co_l][(n0 ...)*3 ...]
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = tid + j * 256;
-      const int co_l = q / 24, f = (q - co_l * 24) << 2;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c0 + co_l < cr && (long)n0 * 3 + f < wrow) v = load4(p.W + (long)(cz0 + c0 + co_l) * wrow + (long)n0 * 3 + f);
-      rw[j] = v;
-    }
-  };
-  auto store_w = [&]() {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = tid + j * 256;
-      const int co_l = q / 24, f = (q - co_l * 24) << 2;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int kk = f + m, ci_l = kk / 3, tap = kk - ci_l * 3;
-        Ws[ci_l * WP + tap * CC + co_l] = rw[j][m];
-      }
-    }
-  };
-  if (cr > 0) load_w(0);
-  __syncthreads();
-  DTC_MARK(8);      // staging
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  for (int c0 = 0; c0 < cr; c0 += CC) {
-    if (c0 > 0) __syncthreads();
-    store_w();
-    __syncthreads();
-    if (c0 + CC < cr) load_w(c0 + CC);
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      const int gg = wave * 3 + g;
-      const int tap = gg >> 2, co_l = ((gg & 3) << 3) + (half << 2);
-      const int rs = l31 + (2 - tap) * d;
-      const float* ap = (rs < T && c0 + co_l < cr) ? &a_lds[rs * AP + c0 + co_l] : &a_lds[ZROW * AP];
-      const f32x4 av = *reinterpret_cast<const f32x4*>(ap);
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(&Ws[l31 * WP + tap * CC + co_l]);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wv.x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wv.y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wv.z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wv.w, acc, 0, 0, 0);
-    }
-  }
-  __syncthreads();
-  DTC_MARK(9);      // contraction
-  float (*part)[ROWS][33] = reinterpret_cast<float (*)[ROWS][33]>(a_lds);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) part[wave][(i & 3) + 8 * (i >> 2) + 4 * half][l31] = acc[i];
-  __syncthreads();
-  const int colx = tid & 31, rg = tid >> 5, gn = n0 + colx;
-  const bool ep = p.ep_stats != nullptr;
-  float esc = 0.f, esh = 0.f, emu = 0.f, ers = 0.f;
-  if (ep && gn < cin) { esc = p.ep_scale[gn]; esh = p.ep_shift[gn]; emu = p.ep_mean[gn]; ers = p.ep_rstd[gn]; }
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = rg + 8 * i;
-    if (r < T && gn < cin) {
-      float v = (part[0][r][colx] + part[1][r][colx]) + (part[2][r][colx] + part[3][r][colx]);
-      const long g = ((long)b * T + r) * cin + gn;
-      if (ep) {
-        // first half of the BatchNorm+ELU backward of the layer below: dz = da * ELU'(z), its two column sums
-        const float yb = p.ep_y[g];
-        v *= elu_grad_from_pre(fmaf(yb, esc, esh));
-        s1 += v;
-        s2 += v * ((yb - emu) * ers);
-      }
-      out[g] = v;
-    }
-  }
-  DTC_MARK(10);     // combine + epilogue + store
-  if (ep) {
-    red[(0 * 8 + rg) * 32 + colx] = s1;
-    red[(1 * 8 + rg) * 32 + colx] = s2;
-    __syncthreads();
-    if (tid < 64) {
-      const int stat = tid >> 5, c = tid & 31;
-      if (n0 + c < cin) {
-        double v = 0.0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) v += (double)red[(stat * 8 + g) * 32 + c];
-        unsafeAtomicAdd(&p.ep_stats[((long)(b % p.nrep) * 2 + stat) * cin + n0 + c], v);
-      }
-    }
-  }
-  DTC_MARK(11);     // statistics
-  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, reinterpret_cast<int*>(red + 2 * 8 * 32));
-  DTC_MARK(12);     // tail
+  stage_zero_rest<BF>(a_lds, T, cr, AP, tid);
 }
 
-// the bf16 throughput mode's adjoint (round 4): 128 input channels per workgroup, one 32-column block per wave,
-// v_mfma_f32_32x32x16_bf16 on fragments rounded as they are built (see dtc_fwd_bf16_kernel)
-__global__ __launch_bounds__(256) void dtc_dgrad_bf16_kernel(DtcDgradParams p, int tile_floats) {
+// fp32: 32 input channels per workgroup, k-groups split over the waves;  bf16: 128, one 32-column block per wave
+template <bool BF>
+__global__ __launch_bounds__(256) void dtc_dgrad_one_kernel(DtcDgradParams p, int tile_floats) {
   extern __shared__ __attribute__((aligned(16))) float dg_smem[];
-  float* a_lds = dg_smem;                                            // [(ROWS+1)][cr+4]
-  bf16_t* Ws = reinterpret_cast<bf16_t*>(dg_smem + tile_floats);     // [NCT][WPH]
-  int* flag = reinterpret_cast<int*>(Ws + NCT * WPH);
+  constexpr int NT = BF ? NCT : 32;
+  constexpr int W_FLOATS = BF ? NCT * WPH / 2 : 32 * WP, RED_FLOATS = BF ? 0 : 2 * 8 * 32;
+  float* a_lds = dg_smem;                              // [ROWS + 1][cr + 4]; fp32: later the 4 partial tiles
+  float* Ws = dg_smem + tile_floats;                   // fp32 [32][WP], bf16 [NCT][WPH]
+  float* red = Ws + W_FLOATS;                          // fp32 only: [2][8][32]
+  int* tail_flag = reinterpret_cast<int*>(red + RED_FLOATS);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const int b = blockIdx.x, n0 = blockIdx.y * NCT;                 // n0: first input channel (output column)
-  const int T = p.T, cin = p.cin, cout = p.cout, d = p.dil;
+  const int b = blockIdx.x, n0 = blockIdx.y * NT;      // n0: first input channel (output column)
+  const int T = p.T, cin = p.cin, d = p.dil;
   const long wrow = (long)cin * 3;
-  float* out = p.out + (long)blockIdx.z * p.slab_stride;
-  const int per_z = ((cout + CC - 1) / CC + (int)gridDim.z - 1) / (int)gridDim.z * CC;
-  const int cz0 = blockIdx.z * per_z;
-  const int cr = max(0, min(cout, cz0 + per_z) - cz0);
-  const int AP = cr + 4;
-  {
-    const int q4 = cr >> 2;
-    const bool form = p.dy == nullptr;
-    const bool keep = p.dy_out != nullptr && blockIdx.y == 0;
-    for (int q = tid; q < T * q4; q += 256) {
-      const int r = q / q4, c4 = (q - r * q4) << 2;
-      const long g = ((long)b * T + r) * cout + cz0 + c4;
-      f32x4 v;
-      if (form) {
-        const f32x4 k0 = load4(p.coef + cz0 + c4), k1 = load4(p.coef + cout + cz0 + c4),
-                    k2 = load4(p.coef + 2 * cout + cz0 + c4);
-        v = k0 * load4(p.dz + g) + k1 * load4(p.y + g) + k2;
-      } else {
-        v = load4(p.dy + g);
-      }
-      *reinterpret_cast<f32x4*>(&a_lds[r * AP + c4]) = v;
-      if (keep) store4(p.dy_out + g, v);
-    }
-    for (int r = tid; r < T; r += 256) *reinterpret_cast<f32x4*>(&a_lds[r * AP + cr]) = f32x4{0.f, 0.f, 0.f, 0.f};   // the pad cvt8 reads
-    for (int q = tid; q < (ROWS + 1 - T) * AP; q += 256) a_lds[T * AP + q] = 0.f;
-  }
-  // weight chunk: 32 contraction channels co x (128 input channels x 3 taps = 384 contiguous floats)
-  // W[cz0 + c0 + co_l][(n0 ...) * 3 ...]: 12 float4 per thread, scattered transposed: Ws[ci_l][tap * 32 + co_l]
-  f32x4 rw[12];
-  auto load_w = [&](int c0) {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      const int q = tid + j * 256;
-      const int co_l = q / 96, f = (q - co_l * 96) << 2;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c0 + co_l < cr && (long)n0 * 3 + f < wrow) v = load4(p.W + (long)(cz0 + c0 + co_l) * wrow + (long)n0 * 3 + f);
-      rw[j] = v;
-    }
-  };
-  auto store_w = [&]() {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      const int q = tid + j * 256;
-      const int co_l = q / 96, f = (q - co_l * 96) << 2;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int kk = f + m, ci_l = kk / 3, tap = kk - ci_l * 3;
-        Ws[ci_l * WPH + tap * CC + co_l] = (bf16_t)rw[j][m];
-      }
-    }
-  };
-  if (cr > 0) load_w(0);
+  const ZRange z = split_range(p.cout);
+  const int cz0 = z.cz0, cr = z.cr, AP = cr + 4;
+
+  DTC_T0();
+  stage_one_adj<BF>(p, a_lds, b, cz0, cr, AP, tid);
+  const float* Wz = p.W + (long)cz0 * wrow;            // this split's weights: W[cz0 ...][.]
+  f32x4 rw[NT * 24 / 256];
+  if (cr > 0) chunk_load<true, NT>(rw, Wz, wrow, n0, cin, 0, cr, tid);
   __syncthreads();
-  const bool active = n0 + wave * 32 < cin;
+  DTC_MARK(8);      // staging
+  const bool active = !BF || n0 + wave * 32 < cin;      // (wave-uniform) bf16: this wave's 32 columns exist
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
   for (int c0 = 0; c0 < cr; c0 += CC) {
     if (c0 > 0) __syncthreads();
-    store_w();
+    chunk_store<true, BF, NT>(rw, Ws, tid);
     __syncthreads();
-    if (c0 + CC < cr) load_w(c0 + CC);
-    if (active) {
+    if (c0 + CC < cr) chunk_load<true, NT>(rw, Wz, wrow, n0, cin, c0 + CC, cr, tid);
+    if (active) contract_chunk<true, BF, BF ? 6 : 3>(acc, a_lds, AP, Ws, (BF ? wave * 32 : 0) + l31, BF ? 0 : wave * 3, c0, cr, T, d, l31, half);
+  }
+  DTC_MARK(9);      // contraction
+  Emit<true> emit{p.out + (long)blockIdx.z * p.slab_stride, T, cin, p.ep_stats != nullptr, p.ep_y};
+  if (!BF) {
+    __syncthreads();
+    part_store(a_lds, wave, acc, l31, half);
+    __syncthreads();
+    const int colx = tid & 31, rg = tid >> 5, gn = n0 + colx;
+    emit.column(p, gn);
 #pragma unroll
-      for (int st = 0; st < 6; ++st) {
-        const int tap = st >> 1, co_l = ((st & 1) << 4) + (half << 3);
-        const int rs = l31 + (2 - tap) * d;
-        const float* ap = (rs < T && c0 + co_l < cr) ? &a_lds[rs * AP + c0 + co_l] : &a_lds[ZROW * AP];
-        const bf16x8 av = cvt8(ap);
-        const bf16x8 wv = *reinterpret_cast<const bf16x8*>(&Ws[(wave * 32 + l31) * WPH + tap * CC + co_l]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, acc, 0, 0, 0);
+    for (int i = 0; i < 4; ++i) {
+      const int r = rg + 8 * i;
+      if (r < T && gn < cin)
+        emit((part_at(a_lds, 0, r, colx) + part_at(a_lds, 1, r, colx)) + (part_at(a_lds, 2, r, colx) + part_at(a_lds, 3, r, colx)), b, r, gn);
+    }
+    DTC_MARK(10);   // combine + epilogue + store
+    if (emit.ep) commit_stats_rows(red, emit.s1, emit.s2, tid, p.ep_stats, b % p.nrep, cin, n0);
+  } else {
+    const int gn = n0 + wave * 32 + l31;
+    emit.column(p, gn);
+    if (active && gn < cin) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int r = acc_row(i, half);
+        if (r < T) emit(acc[i], b, r, gn);
       }
     }
+    DTC_MARK(10);   // epilogue + store
+    if (emit.ep) commit_stats_wave(emit.s1, emit.s2, active && half == 0 && gn < cin, p.ep_stats, b % p.nrep, cin, gn);
   }
-  const int gn = n0 + wave * 32 + l31;
-  const bool ep = p.ep_stats != nullptr;
-  float esc = 0.f, esh = 0.f, emu = 0.f, ers = 0.f;
-  if (ep && gn < cin) { esc = p.ep_scale[gn]; esh = p.ep_shift[gn]; emu = p.ep_mean[gn]; ers = p.ep_rstd[gn]; }
-  float s1 = 0.f, s2 = 0.f;
-  if (active && gn < cin) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int r = (i & 3) + 8 * (i >> 2) + 4 * half;
-      if (r < T) {
-        float v = acc[i];
-        const long g = ((long)b * T + r) * cin + gn;
-        if (ep) {
-          const float yb = p.ep_y[g];
-          v *= elu_grad_from_pre(fmaf(yb, esc, esh));
-          s1 += v;
-          s2 += v * ((yb - emu) * ers);
-        }
-        out[g] = v;
-      }
-    }
-  }
-  if (ep) {
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    if (active && half == 0 && gn < cin) {
-      unsafeAtomicAdd(&p.ep_stats[((long)(b % p.nrep) * 2 + 0) * cin + gn], (double)s1);
-      unsafeAtomicAdd(&p.ep_stats[((long)(b % p.nrep) * 2 + 1) * cin + gn], (double)s2);
-    }
-  }
-  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, flag);
+  DTC_MARK(11);     // statistics
+  bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y * gridDim.z, tail_flag);
+  DTC_MARK(12);     // tail
 }
 
 // ------------------------------------------------------------------ round 4: two sequences per workgroup (layers 5, 6)
@@ -726,42 +596,8 @@ __global__ __launch_bounds__(256) void dtc_pair_kernel(DtcPairParams p, int tile
   DTC_T0();
 
   f32x4 rw0[NJ], rw1[NJ];
-  auto load_w = [&](f32x4 (&rw)[NJ], int c0g) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int q = tid + j * 256;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (!ADJ) {
-        // NT columns x 96 contiguous floats W[n0 + c][c0g * 3 ...]
-        const int c = q / 24, f = (q - c * 24) << 2;
-        if (n0 + c < nc && c0g * 3 + f < kc * 3) v = load4(p.W + (long)(n0 + c) * wrow + (long)c0g * 3 + f);
-      } else {
-        // 32 contraction rows x (NT * 3) contiguous floats W[c0g + co_l][n0 * 3 ...]
-        constexpr int RUN4 = NT * 3 / 4;
-        const int co_l = q / RUN4, f = (q - co_l * RUN4) << 2;
-        if (c0g + co_l < kc && (long)n0 * 3 + f < wrow) v = load4(p.W + (long)(c0g + co_l) * wrow + (long)n0 * 3 + f);
-      }
-      rw[j] = v;
-    }
-  };
-  auto store_w = [&](const f32x4 (&rw)[NJ], int buf) {
-    float* wf = Wsf + buf * NT * WROW;
-    bf16_t* wh = reinterpret_cast<bf16_t*>(wf);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int q = tid + j * 256;
-      int row0, f;          // forward: row0 = the column, k' from f;  adjoint: row0 = contraction channel, column from f
-      if (!ADJ) { row0 = q / 24; f = (q - row0 * 24) << 2; }
-      else { constexpr int RUN4 = NT * 3 / 4; row0 = q / RUN4; f = (q - row0 * RUN4) << 2; }
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int kk = f + m, a = kk / 3, tap = kk - a * 3;
-        const int col = ADJ ? a : row0, kl = ADJ ? row0 : a;      // LDS row = output column, k' = tap * 32 + channel
-        if (BF) wh[col * WPH + tap * CC + kl] = (bf16_t)rw[j][m];
-        else wf[col * WP + tap * CC + kl] = rw[j][m];
-      }
-    }
-  };
+  auto load_w = [&](f32x4 (&rw)[NJ], int c0g) { chunk_load<ADJ, NT>(rw, p.W, wrow, n0, nc, c0g, kc, tid); };
+  auto store_w = [&](const f32x4 (&rw)[NJ], int buf) { chunk_store<ADJ, BF, NT>(rw, Wsf + buf * NT * WROW, tid); };
   load_w(rw0, 0);
   if (nch > 1) load_w(rw1, CC);
 
@@ -770,38 +606,10 @@ __global__ __launch_bounds__(256) void dtc_pair_kernel(DtcPairParams p, int tile
   for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 
   auto contract = [&](int buf, int cl, int kr) {
-    // one 96-deep chunk: tile-local channels cl .. cl + 31 of the kr staged ones
-    const float* wf = Wsf + buf * NT * WROW;
-    const int wcol = (NT == 64 ? wsub * 32 : 0) + l31;
-    if (!BF) {
-      constexpr int NG = NT == 64 ? 12 : 6;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int gg = NT == 64 ? g : wsub * 6 + g;     // 12 groups of 8 per chunk: tap = gg / 4, 8 channels each
-        const int tap = gg >> 2, kl = ((gg & 3) << 3) + (half << 2);
-        const int rs = ADJ ? l31 + (2 - tap) * d : l31 - (2 - tap) * d;
-        const bool ok = (ADJ ? rs < T : rs >= 0) && cl + kl < kr;
-        const f32x4 av = *reinterpret_cast<const f32x4*>(ok ? &tile_s[rs * AP + cl + kl] : &tile_s[ZROW * AP]);
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(&wf[wcol * WP + tap * CC + kl]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wv.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wv.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wv.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wv.w, acc, 0, 0, 0);
-      }
-    } else {
-      const bf16_t* wh = reinterpret_cast<const bf16_t*>(wf);
-      constexpr int NS = NT == 64 ? 6 : 3;
-#pragma unroll
-      for (int g = 0; g < NS; ++g) {
-        const int st = NT == 64 ? g : wsub * 3 + g;     // k' = 16 st .. 16 st + 15, this lane's eight: + 8 half
-        const int tap = st >> 1, kl = ((st & 1) << 4) + (half << 3);
-        const int rs = ADJ ? l31 + (2 - tap) * d : l31 - (2 - tap) * d;
-        const bool ok = (ADJ ? rs < T : rs >= 0) && cl + kl < kr;
-        const bf16x8 av = cvt8(ok ? &tile_s[rs * AP + cl + kl] : &tile_s[ZROW * AP]);
-        const bf16x8 wv = *reinterpret_cast<const bf16x8*>(&wh[wcol * WPH + tap * CC + kl]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, wv, acc, 0, 0, 0);
-      }
-    }
+    // NT = 64: the wave's column block, all of the chunk's k-groups;  NT = 32: half of them on the one block
+    constexpr int NG = (BF ? 6 : 12) / (NT == 64 ? 1 : 2);
+    contract_chunk<ADJ, BF, NG>(acc, tile_s, AP, Wsf + buf * NT * WROW, (NT == 64 ? wsub * 32 : 0) + l31,
+                                NT == 64 ? 0 : wsub * NG, cl, kr, T, d, l31, half);
   };
 
   int c = 0;                                             // chunk index over the whole contraction
@@ -864,10 +672,7 @@ __global__ __launch_bounds__(256) void dtc_pair_kernel(DtcPairParams p, int tile
                 if (p.scale != nullptr) {
                   f32x4 sc = h0, sh = h1;
                   if (cj[j] != cq0) { sc = load4(p.scale + k0 + c4); sh = load4(p.shift + k0 + c4); }
-                  x.x = elu_stage(fmaf(sc.x, x.x, sh.x));
-                  x.y = elu_stage(fmaf(sc.y, x.y, sh.y));
-                  x.z = elu_stage(fmaf(sc.z, x.z, sh.z));
-                  x.w = elu_stage(fmaf(sc.w, x.w, sh.w));
+                  x = activate4(x, sc, sh);
                 }
               } else {
                 if (p.src == nullptr) {
@@ -913,41 +718,23 @@ __global__ __launch_bounds__(256) void dtc_pair_kernel(DtcPairParams p, int tile
   }
 
   // ---- results.  accumulator i of lane (l31, half) is row (i & 3) + 8 (i >> 2) + 4 half, column l31 of the wave's block
-  float s1 = 0.f, s2 = 0.f;
-  float esc = 0.f, esh = 0.f, emu = 0.f, ers = 0.f;
-  const bool ep = ADJ && p.stats != nullptr;
-  auto emit = [&](float v, int b, int r, int gn) {
-    const long g = ((long)b * T + r) * nc + gn;
-    if (!ADJ) {
-      p.out[g] = v;
-      s1 += v;
-      s2 += v * v;
-    } else {
-      if (ep) {
-        // first half of the BatchNorm+ELU backward of the layer below: dz = da * ELU'(z), its two column sums
-        const float yb = p.ep_y[g];
-        v *= elu_grad_from_pre(fmaf(yb, esc, esh));
-        s1 += v;
-        s2 += v * ((yb - emu) * ers);
-      }
-      p.out[g] = v;
-    }
-  };
+  Emit<ADJ> emit{p.out, T, nc, ADJ && p.stats != nullptr, p.ep_y};
   const bool want_stats = p.stats != nullptr;
   if (NT == 64) {
     const int gn = n0 + wsub * 32 + l31, b = b0 + sq;
-    if (ep && gn < nc) { esc = p.ep_scale[gn]; esh = p.ep_shift[gn]; emu = p.ep_mean[gn]; ers = p.ep_rstd[gn]; }
+    emit.column(p, gn);
     if (gn < nc && b < p.B) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int r = (i & 3) + 8 * (i >> 2) + 4 * half;
+        const int r = acc_row(i, half);
         if (r < T) emit(acc[i], b, r, gn);
       }
     }
     DTC_MARK(3);      // store
     if (want_stats) {
-      s1 += __shfl_xor(s1, 32, 64);
-      s2 += __shfl_xor(s2, 32, 64);
+      // the two sequences of a column block meet in ``red`` before the one atomic
+      const float s1 = emit.s1 + __shfl_xor(emit.s1, 32, 64);
+      const float s2 = emit.s2 + __shfl_xor(emit.s2, 32, 64);
       if (half == 0) {
         red[(0 * 8 + wave) * 32 + l31] = s1;
         red[(1 * 8 + wave) * 32 + l31] = s2;
@@ -964,36 +751,21 @@ __global__ __launch_bounds__(256) void dtc_pair_kernel(DtcPairParams p, int tile
   } else {
     __syncthreads();                                     // the sequence tiles are dead
     float* part = tile;                                  // [2][2][ROWS][33]
-#pragma unroll
-    for (int i = 0; i < 16; ++i) part[((sq * 2 + wsub) * ROWS + (i & 3) + 8 * (i >> 2) + 4 * half) * 33 + l31] = acc[i];
+    part_store(part, sq * 2 + wsub, acc, l31, half);
     __syncthreads();
     const int colx = tid & 31, rg = tid >> 5, gn = n0 + colx;
-    if (ep && gn < nc) { esc = p.ep_scale[gn]; esh = p.ep_shift[gn]; emu = p.ep_mean[gn]; ers = p.ep_rstd[gn]; }
+    emit.column(p, gn);
     if (gn < nc) {
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = rg + 8 * i;
-          if (r < T && b0 + s < p.B)
-            emit(part[((s * 2 + 0) * ROWS + r) * 33 + colx] + part[((s * 2 + 1) * ROWS + r) * 33 + colx], b0 + s, r, gn);
+          if (r < T && b0 + s < p.B) emit(part_at(part, s * 2 + 0, r, colx) + part_at(part, s * 2 + 1, r, colx), b0 + s, r, gn);
         }
     }
     DTC_MARK(3);      // combine + store
-    if (want_stats) {
-      red[(0 * 8 + rg) * 32 + colx] = s1;
-      red[(1 * 8 + rg) * 32 + colx] = s2;
-      __syncthreads();
-      if (tid < 64) {
-        const int stat = tid >> 5, cc = tid & 31;
-        if (n0 + cc < nc) {
-          double v = 0.0;
-#pragma unroll
-          for (int g = 0; g < 8; ++g) v += (double)red[(stat * 8 + g) * 32 + cc];
-          unsafeAtomicAdd(&p.stats[((long)(blockIdx.x % p.nrep) * 2 + stat) * nc + n0 + cc], v);
-        }
-      }
-    }
+    if (want_stats) commit_stats_rows(red, emit.s1, emit.s2, tid, p.stats, blockIdx.x % p.nrep, nc, n0);
   }
   DTC_MARK(4);        // statistics
   bn_tail_run(p.tail, tid, 256, gridDim.x * gridDim.y, flag);
@@ -1019,21 +791,31 @@ static inline bool pair_takes(int kc, int nc, int ksplit, bool adj) {
   return (which & (adj ? 2 : 1)) != 0 && ksplit == 1 && kc >= 128 && kc % CC == 0 && nc >= 64 && nc % 4 == 0;
 }
 
-template <bool ADJ, bool BF, int NT>
-static int launch_pair(const DtcPairParams& p, hipStream_t s) {
-  constexpr int WROW = BF ? WPH / 2 : WP;
-  auto kern = dtc_pair_kernel<ADJ, BF, NT>;
-  const int tile = pair_tile_floats(p.kc);
-  const size_t lds = (size_t)(tile + 2 * NT * WROW + 2 * 8 * 32 + 4) * sizeof(float);
+// Launch KERN(p, tile) with ``lds`` bytes of dynamic LDS, more than the default limit allows: the limit is raised once per
+// kernel, to ``cap`` (the most any launch of it asks for).  If that fails the launch did not happen: the BatchNorm tail
+// taken for it is re-armed and the error is ``who``'s.
+template <auto KERN, class Params>
+static int launch_dyn_lds(size_t cap, dim3 grid, size_t lds, hipStream_t s, const Params& p, int tile, const char* who) {
   static bool configured = false;
   if (!configured) {
-    const size_t cap = (size_t)(pair_tile_floats(PAIR_KC) + 2 * NT * WROW + 2 * 8 * 32 + 4) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess)
-      return 1;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) {
+      pcaa_rearm_bn_tail(p.tail);
+      pcaa_set_error("%s: cannot raise the dynamic LDS limit", who);
+      return PCAA_ERR_LAUNCH;
+    }
     configured = true;
   }
-  hipLaunchKernelGGL(kern, dim3((p.B + 1) / 2, (p.nc + NT - 1) / NT), dim3(256), lds, s, p, tile);
-  return 0;
+  hipLaunchKernelGGL(KERN, grid, dim3(256), lds, s, p, tile);
+  PCAA_RETURN_LAUNCH_STATUS(who);
+}
+
+template <bool ADJ, bool BF, int NT>
+static int launch_pair(const DtcPairParams& p, hipStream_t s, const char* who) {
+  constexpr int REST = 2 * NT * (BF ? WPH / 2 : WP) + 2 * 8 * 32 + 4;      // two weight tiles, red, the finalize flag
+  const int tile = pair_tile_floats(p.kc);
+  return launch_dyn_lds<dtc_pair_kernel<ADJ, BF, NT>>((size_t)(pair_tile_floats(PAIR_KC) + REST) * sizeof(float),
+                                                      dim3((p.B + 1) / 2, (p.nc + NT - 1) / NT),
+                                                      (size_t)(tile + REST) * sizeof(float), s, p, tile, who);
 }
 
 // 64-column workgroups when they still fill the chip (the 256 -> 512 layer's forward: 32 pairs x 8), else 32
@@ -1049,12 +831,12 @@ static inline int dtc_route(bool adj, bool bf16, int B, int cin, int cout, int k
 }
 
 template <bool ADJ>
-static int launch_pair_route(const DtcPairParams& p, int route, hipStream_t s) {
+static int launch_pair_route(const DtcPairParams& p, int route, hipStream_t s, const char* who) {
   switch (route) {
-    case PCAA_DTC_ROUTE_PAIR64_BF16: return launch_pair<ADJ, true, 64>(p, s);
-    case PCAA_DTC_ROUTE_PAIR64_F32: return launch_pair<ADJ, false, 64>(p, s);
-    case PCAA_DTC_ROUTE_PAIR32_BF16: return launch_pair<ADJ, true, 32>(p, s);
-    default: return launch_pair<ADJ, false, 32>(p, s);
+    case PCAA_DTC_ROUTE_PAIR64_BF16: return launch_pair<ADJ, true, 64>(p, s, who);
+    case PCAA_DTC_ROUTE_PAIR64_F32: return launch_pair<ADJ, false, 64>(p, s, who);
+    case PCAA_DTC_ROUTE_PAIR32_BF16: return launch_pair<ADJ, true, 32>(p, s, who);
+    default: return launch_pair<ADJ, false, 32>(p, s, who);
   }
 }
 
@@ -1100,17 +882,12 @@ static int dtc_conv_fwd_impl(bool bf16, const float* src, const float* scale, co
     DtcPairParams pp{src, scale, shift, nullptr, nullptr, nullptr, nullptr, W, y, col, stats, nrep,
                      nullptr, nullptr, nullptr, nullptr, nullptr, B, T, cin, cout, dilation,
                      stats != nullptr ? pcaa_take_bn_tail(stats) : BnTail{}};
-    if (launch_pair_route<false>(pp, route, as_stream(stream)) != 0) {
-      pcaa_rearm_bn_tail(pp.tail);
-      pcaa_set_error("pcaa_dtc_conv_fwd: cannot raise the dynamic LDS limit");
-      return PCAA_ERR_LAUNCH;
-    }
-    PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
+    return launch_pair_route<false>(pp, route, as_stream(stream), "pcaa_dtc_conv_fwd");
   }
   DtcFwdParams p{src, scale, shift, W, y, col, stats, B, T, cin, cout, dilation, nrep, ksplit > 1 ? slab_stride : 0,
                  (stats != nullptr && ksplit == 1) ? pcaa_take_bn_tail(stats) : BnTail{}, win_row, ring_rows, seg};
-  if (route == PCAA_DTC_ROUTE_ONE_BF16) hipLaunchKernelGGL(dtc_fwd_bf16_kernel, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
-  else hipLaunchKernelGGL(dtc_fwd_kernel, dim3(B, (cout + 31) / 32, ksplit), dim3(256), 0, as_stream(stream), p);
+  if (route == PCAA_DTC_ROUTE_ONE_BF16) hipLaunchKernelGGL(dtc_fwd_one_kernel<true>, dim3(B, (cout + NCT - 1) / NCT, ksplit), dim3(256), 0, as_stream(stream), p);
+  else hipLaunchKernelGGL(dtc_fwd_one_kernel<false>, dim3(B, (cout + 31) / 32, ksplit), dim3(256), 0, as_stream(stream), p);
   PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_fwd");
 }
 extern "C" int pcaa_dtc_conv_fwd(const float* src, const float* scale, const float* shift, const float* W, float* y,
@@ -1209,47 +986,20 @@ static int dtc_conv_dgrad_impl(bool bf16, const float* dy, const float* dz, cons
     DtcPairParams pp{dy, nullptr, nullptr, dz, y, coef, dy_out, W, out, nullptr, ep_stats, nrep,
                      ep_y, ep_scale, ep_shift, ep_mean, ep_rstd, B, T, cout, cin, dilation,
                      ep ? pcaa_take_bn_tail(ep_stats) : BnTail{}};
-    if (launch_pair_route<true>(pp, route, as_stream(stream)) != 0) {
-      pcaa_rearm_bn_tail(pp.tail);
-      pcaa_set_error("pcaa_dtc_conv_dgrad: cannot raise the dynamic LDS limit");
-      return PCAA_ERR_LAUNCH;
-    }
-    PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_dgrad");
+    return launch_pair_route<true>(pp, route, as_stream(stream), "pcaa_dtc_conv_dgrad");
   }
   const int tile = dg_tile_floats(per_z);
   DtcDgradParams p{dy, dz, y, coef, dy_out, W, out, ep_y, ep_scale, ep_shift, ep_mean, ep_rstd, ep_stats, nrep,
                    B, T, cin, cout, dilation, ksplit > 1 ? slab_stride : 0,
                    ep ? pcaa_take_bn_tail(ep_stats) : BnTail{}};
-  if (route == PCAA_DTC_ROUTE_ONE_BF16) {
-    const size_t lds16 = (size_t)tile * sizeof(float) + (size_t)NCT * WPH * sizeof(bf16_t) + 16;
-    static bool configured16 = false;
-    if (!configured16) {
-      const size_t cap = (size_t)dg_tile_floats(DG_MAX_CR) * sizeof(float) + (size_t)NCT * WPH * sizeof(bf16_t) + 16;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(dtc_dgrad_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)cap) != hipSuccess) {
-        pcaa_rearm_bn_tail(p.tail);
-        pcaa_set_error("pcaa_dtc_conv_dgrad_bf16: cannot raise the dynamic LDS limit");
-        return PCAA_ERR_LAUNCH;
-      }
-      configured16 = true;
-    }
-    hipLaunchKernelGGL(dtc_dgrad_bf16_kernel, dim3(B, (cin + NCT - 1) / NCT, ksplit), dim3(256), lds16, as_stream(stream), p, tile);
-    PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_dgrad_bf16");
-  }
-  const size_t lds = (size_t)(tile + 32 * WP + 2 * 8 * 32 + 4) * sizeof(float);     // + the finalize flag
-  static bool configured = false;
-  if (!configured) {
-    const size_t cap = (size_t)(dg_tile_floats(DG_MAX_CR) + 32 * WP + 2 * 8 * 32 + 4) * sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(dtc_dgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)cap) != hipSuccess) {
-      pcaa_rearm_bn_tail(p.tail);
-      pcaa_set_error("pcaa_dtc_conv_dgrad: cannot raise the dynamic LDS limit");
-      return PCAA_ERR_LAUNCH;
-    }
-    configured = true;
-  }
-  hipLaunchKernelGGL(dtc_dgrad_kernel, dim3(B, (cin + 31) / 32, ksplit), dim3(256), lds, as_stream(stream), p, tile);
-  PCAA_RETURN_LAUNCH_STATUS("pcaa_dtc_conv_dgrad");
+  // behind the sequence tile: the weight tile, (fp32) red, the finalize flag
+  const int rest = (route == PCAA_DTC_ROUTE_ONE_BF16 ? NCT * WPH / 2 : 32 * WP + 2 * 8 * 32) + 4;
+  const size_t lds = (size_t)(tile + rest) * sizeof(float), cap = (size_t)(dg_tile_floats(DG_MAX_CR) + rest) * sizeof(float);
+  if (route == PCAA_DTC_ROUTE_ONE_BF16)
+    return launch_dyn_lds<dtc_dgrad_one_kernel<true>>(cap, dim3(B, (cin + NCT - 1) / NCT, ksplit), lds, as_stream(stream), p, tile,
+                                                      "pcaa_dtc_conv_dgrad_bf16");
+  return launch_dyn_lds<dtc_dgrad_one_kernel<false>>(cap, dim3(B, (cin + 31) / 32, ksplit), lds, as_stream(stream), p, tile,
+                                                     "pcaa_dtc_conv_dgrad");
 }
 extern "C" int pcaa_dtc_conv_dgrad(const float* dy, const float* dz, const float* y, const float* coef, float* dy_out,
                                    const float* W, float* out, const float* ep_y, const float* ep_scale,

@@ -10,7 +10,7 @@ test_carried_finalize drives.
 
   test                         entry points                                         branches
   ---------------------------  ---------------------------------------------------  -----------------------------------------
-  test_forward[case-dtype]     pcaa_dtc_conv_fwd, _fwd_bf16, pcaa_splitk_reduce      dtc_fwd_kernel, dtc_fwd_bf16_kernel (second
+  test_forward[case-dtype]     pcaa_dtc_conv_fwd, _fwd_bf16, pcaa_splitk_reduce      dtc_fwd_one_kernel<false>, <true> (second
                                                                                     128-column workgroup with one live wave,
                                                                                     ragged chunk, ragged column tile, T = 1,
                                                                                     T = 32, d >= T, 2d >= T), dtc_pair_kernel
@@ -19,7 +19,7 @@ test_carried_finalize drives.
                                                                                     boundary from both sides), ksplit > 1 (empty
                                                                                     splits, one chunk per split, uneven, stride
                                                                                     > slab, col under a split), nrep 1 and > B
-  test_adjoint[case-dtype]     pcaa_dtc_conv_dgrad, _dgrad_bf16, pcaa_splitk_reduce  dtc_dgrad_kernel, dtc_dgrad_bf16_kernel,
+  test_adjoint[case-dtype]     pcaa_dtc_conv_dgrad, _dgrad_bf16, pcaa_splitk_reduce  dtc_dgrad_one_kernel<false>, <true>,
                                                                                     dtc_pair_kernel<adj, ...>; dy given / formed /
                                                                                     + dy_out / + epilogue and its statistics;
                                                                                     ksplit > 1 with dy_out slices per split
