@@ -14,7 +14,8 @@
 //   ever waits for another workgroup, so no placement or dispatch-order assumption).  The counter is zeroed with the statistics (ops.StatsPool clears its whole used range once per step)
 //   and reset by the finalizer, so a replayed hipGraph starts from zero as well.
 //
-// The arithmetic is the one of the stand-alone kernels (elementwise.hip), which remain for SyncBN (the all-reduce of
+// The stand-alone kernel (bn_finalize_kernel, elementwise.hip) runs the same replica sum and the same
+// bn_tail_channel on a BnTail of its own; it remains for SyncBN (the all-reduce of
 // the statistics sits between producer and finalize) and for producers that do not carry a tail.
 #pragma once
 #include "common.h"
@@ -45,17 +46,45 @@ struct BnTail {
 BnTail pcaa_take_bn_tail(const double* stats);
 void pcaa_rearm_bn_tail(const BnTail& t);      // give a taken tail back when the launch did not happen
 
-__device__ __forceinline__ double bn_tail_ld(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// how a replica word is loaded: plainly by a kernel launched behind the producer (stream order made the atomics
+// visible), agent-scope (sc1) by the last workgroup of the producer itself (bn_tail_run)
+template <bool AGENT> __device__ __forceinline__ double bn_tail_ld(const double* p) {
+  if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
 }
 
-// the finalize of ONE channel from its two reduced sums (== bn_finalize_kernel / bn_bwd_finalize_kernel, elementwise.hip)
+// sum of the nrep replicas of one channel's two statistics; 8 replicas (16 loads) in flight per trip, then the
+// remainder -- the one-at-a-time loop made the single-workgroup finalize kernels 8-10 us of pure load latency
+template <bool AGENT>
+__device__ __forceinline__ void bn_replica_sums(const double* stats, int nrep, int ch, int c, double& s1, double& s2) {
+  int r = 0;
+  for (; r + 8 <= nrep; r += 8) {
+    double a[8], b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      a[u] = bn_tail_ld<AGENT>(stats + ((long)(r + u) * 2 + 0) * ch + c);
+      b[u] = bn_tail_ld<AGENT>(stats + ((long)(r + u) * 2 + 1) * ch + c);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { s1 += a[u]; s2 += b[u]; }
+  }
+  for (; r < nrep; ++r) {
+    s1 += bn_tail_ld<AGENT>(stats + ((long)r * 2 + 0) * ch + c);
+    s2 += bn_tail_ld<AGENT>(stats + ((long)r * 2 + 1) * ch + c);
+  }
+}
+
+// the finalize of ONE channel from its two reduced sums: the one statement of both finalizes (bn_finalize_kernel in
+// elementwise.hip and the carried tail below call it)
 __device__ __forceinline__ void bn_tail_channel(const BnTail& t, int c, double s1, double s2) {
   const int ch = t.ch;
   if (t.kind == 1) {
     const double m0 = s1 * t.inv_count;
     double var = s2 * t.inv_count - m0 * m0;
     if (var < 0.0) var = 0.0;
+    // The linear layer's bias is NOT in the stored pre-BN tensor y (= the bias-free accumulator):
+    // BatchNorm subtracts the batch mean, so in train mode the bias cancels exactly --
+    // BN(acc + b) = gamma*(acc - mean(acc))*rstd + beta.  It only enters the running mean.
     const double mean = m0 + (t.lin_bias ? (double)t.lin_bias[c] : 0.0);
     const double rstd = 1.0 / sqrt(var + (double)t.eps);
     t.scale[c] = (float)((double)t.gamma[c] * rstd);
@@ -105,21 +134,7 @@ __device__ __forceinline__ void bn_tail_run(const BnTail& t, int tid, int nthrea
   const int ch = t.ch;
   for (int c = tid; c < ch; c += nthreads) {
     double s1 = 0.0, s2 = 0.0;
-    int r = 0;
-    for (; r + 8 <= t.nrep; r += 8) {          // 16 loads in flight (same summation order as replica_sums)
-      double a[8], b[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        a[u] = bn_tail_ld(t.stats + ((long)(r + u) * 2 + 0) * ch + c);
-        b[u] = bn_tail_ld(t.stats + ((long)(r + u) * 2 + 1) * ch + c);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s1 += a[u]; s2 += b[u]; }
-    }
-    for (; r < t.nrep; ++r) {
-      s1 += bn_tail_ld(t.stats + ((long)r * 2 + 0) * ch + c);
-      s2 += bn_tail_ld(t.stats + ((long)r * 2 + 1) * ch + c);
-    }
+    bn_replica_sums<true>(t.stats, t.nrep, ch, c, s1, s2);
     bn_tail_channel(t, c, s1, s2);
   }
 }

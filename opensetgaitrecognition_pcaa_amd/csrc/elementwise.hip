@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 #include "bn_tail.h"
@@ -37,56 +38,39 @@ inline bool ch_ok(int ch) {
   return (256 % q) == 0;
 }
 
-// sum of the nrep replicas of one channel's two statistics; 8 replicas (16 loads) in flight per trip --
-// the one-at-a-time loop made these single-workgroup kernels 8-10 us of pure load latency
-__device__ __forceinline__ void replica_sums(const double* __restrict__ stats, int nrep, int ch, int c, double& s1,
-                                             double& s2) {
-  int r = 0;
-  for (; r + 8 <= nrep; r += 8) {
-    double a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = stats[((long)(r + u) * 2 + 0) * ch + c];
-      b[u] = stats[((long)(r + u) * 2 + 1) * ch + c];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { s1 += a[u]; s2 += b[u]; }
-  }
-  for (; r < nrep; ++r) {
-    s1 += stats[((long)r * 2 + 0) * ch + c];
-    s2 += stats[((long)r * 2 + 1) * ch + c];
-  }
+// ---------------------------------------------------------------- BN finalize, forward (t.kind 1) and backward (2)
+// the stand-alone form of the finalize a producer can carry (bn_tail.h): its replica sum with plain loads, its arithmetic
+__global__ void bn_finalize_kernel(BnTail t) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0 && t.kind == 1 && t.nbt) *t.nbt += 1;
+  if (c >= t.ch) return;
+  double s1 = 0.0, s2 = 0.0;
+  bn_replica_sums<false>(t.stats, t.nrep, t.ch, c, s1, s2);
+  bn_tail_channel(t, c, s1, s2);
 }
 
-// ---------------------------------------------------------------- BN finalize (forward)
-__global__ void bn_finalize_kernel(const double* __restrict__ stats, int nrep, double inv_count,
-                                   double unbias, const float* __restrict__ lin_bias,
-                                   const float* __restrict__ gamma, const float* __restrict__ beta,
-                                   float* running_mean, float* running_var, long long* nbt,
-                                   float momentum, float eps, float* scale, float* shift,
-                                   float* mean_out, float* rstd_out, int ch) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0 && nbt) *nbt += 1;
-  if (c >= ch) return;
-  double s1 = 0.0, s2 = 0.0;
-  replica_sums(stats, nrep, ch, c, s1, s2);
-  const double m0 = s1 * inv_count;                 // mean of the bias-free linear output
-  double var = s2 * inv_count - m0 * m0;            // biased variance
-  if (var < 0.0) var = 0.0;
-  // The linear layer's bias is NOT in the stored pre-BN tensor y (= the bias-free accumulator):
-  // BatchNorm subtracts the batch mean, so in train mode the bias cancels exactly --
-  // BN(acc + b) = gamma*(acc - mean(acc))*rstd + beta.  It only enters the running mean.
-  const double mean = m0 + (lin_bias ? (double)lin_bias[c] : 0.0);
-  const double rstd = 1.0 / sqrt(var + (double)eps);
-  const float sc = (float)((double)gamma[c] * rstd);
-  scale[c] = sc;
-  shift[c] = (float)((double)beta[c] - m0 * (double)gamma[c] * rstd);
-  mean_out[c] = (float)m0;
-  rstd_out[c] = (float)rstd;
-  if (running_mean) {
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)(var * unbias);
-  }
+// the BnTail of a forward / backward finalize, for the stand-alone launch and for arming a producer alike
+BnTail bn_tail_fwd(const double* stats, int nrep, long count, const float* lin_bias, const float* gamma,
+                   const float* beta, float* running_mean, float* running_var, long long* nbt, float momentum, float eps,
+                   float* scale, float* shift, float* mean, float* rstd, int ch, unsigned* counter) {
+  BnTail t = {};
+  t.kind = 1; t.nrep = nrep; t.ch = ch; t.counter = counter; t.stats = stats;
+  t.inv_count = 1.0 / (double)count;
+  t.unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
+  t.lin_bias = lin_bias; t.gamma = gamma; t.beta = beta;
+  t.running_mean = running_mean; t.running_var = running_var; t.nbt = nbt;
+  t.momentum = momentum; t.eps = eps;
+  t.scale = scale; t.shift = shift; t.mean = mean; t.rstd = rstd;
+  return t;
+}
+BnTail bn_tail_bwd(const double* stats, int nrep, long count, const float* gamma, const float* mean, const float* rstd,
+                   float* coef, float* dgamma, float* dbeta, int ch, unsigned* counter) {
+  BnTail t = {};
+  t.kind = 2; t.nrep = nrep; t.ch = ch; t.counter = counter; t.stats = stats;
+  t.inv_count = 1.0 / (double)count;
+  t.gamma = gamma; t.mean = const_cast<float*>(mean); t.rstd = const_cast<float*>(rstd);
+  t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
+  return t;
 }
 
 __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, const float* rm,
@@ -161,8 +145,69 @@ __global__ void split_f16_kernel(const float* __restrict__ src, split_t* __restr
   }
 }
 
+// ---------------------------------------------------------------- row lanes: thread = channel quad x row lane
+// A 256-thread workgroup holds ch/4 channel quads (ch_ok) and 256 / (ch/4) row lanes; lane l takes rows l, l + rl, ...
+struct RowLanes {
+  int qpr, rl, cq, rlane, c;            // quads per row, row lanes, this thread's quad, lane and first channel
+  __device__ __forceinline__ explicit RowLanes(int ch)
+      : qpr(ch >> 2), rl(256 / qpr), cq(threadIdx.x % qpr), rlane(threadIdx.x / qpr), c(cq * 4) {}
+};
+
+// d = g * ELU'(sc*y + sh) of one quad
+template <typename T>
+__device__ __forceinline__ f32x4 elu_bwd_quad(f32x4 g, f32x4 y, f32x4 sc, f32x4 sh) {
+  f32x4 d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = g[e] * elu_grad_from_pre_t<T>(y[e] * sc[e] + sh[e]);
+  return d;
+}
+// the BatchNorm-backward statistics a lane keeps in fp32: s1 += d, s2 += d * yhat with yhat = (y - mu) * rs.  A plain
+// aggregate handed in and out by value: as two f32x4 references the update cost bn_eval_act_bwd_kernel<float, false>
+// 12 registers and a wave per SIMD when this was written; check that kernel's count (96) before changing the form
+struct DzSums { f32x4 s1, s2; };
+__device__ __forceinline__ DzSums accumulate_dz(DzSums s, f32x4 d, f32x4 y, f32x4 mu, f32x4 rs) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    s.s1[e] += d[e];
+    s.s2[e] += d[e] * ((y[e] - mu[e]) * rs[e]);
+  }
+  return s;
+}
+
+// the lanes' fp32 sums meet in LDS; each (statistic, channel) of the workgroup is folded in fp64 and leaves through
+// ONE fp64 atomic into replica blockIdx.x % nrep of stats [nrep][2][ch]
+__device__ __forceinline__ void commit_row_lanes(RowLanes L, f32x4 (*red)[256], DzSums s,
+                                                 double* __restrict__ stats, int nrep, int ch) {
+  red[0][threadIdx.x] = s.s1;
+  red[1][threadIdx.x] = s.s2;
+  __syncthreads();
+  for (int o = threadIdx.x; o < 2 * ch; o += 256) {
+    const int stat = o / ch, cc = o - stat * ch;
+    const int q = cc >> 2, e = cc & 3;
+    double v = 0.0;
+    for (int l = 0; l < L.rl; ++l) v += (double)red[stat][l * L.qpr + q][e];
+    unsafeAtomicAdd(&stats[((long)(blockIdx.x % nrep) * 2 + stat) * ch + cc], v);
+  }
+}
+
+// A pooled gradient is one value per (group, channel), constant over the group's group_rows rows.  A thread whose rows
+// advance by a constant step keeps (group, row in group) and advances both by constants: no per-quad division (the
+// first version of bn_bwd_dy_fused_kernel spent more vector-ALU time on r / group_rows than the pass spends on HBM:
+// 237 us for 1 GB at config[1], round 2's trace).  rows < 2^31, host-checked.
+struct GroupWalk {
+  unsigned grp = 0u, rem = 0u, gstep = 0u, rrem = 0u, group_rows = 0u;
+  __device__ __forceinline__ GroupWalk() {}
+  __device__ __forceinline__ GroupWalk(unsigned row, unsigned step, unsigned group_rows_)
+      : grp(row / group_rows_), rem(row - grp * group_rows_), gstep(step / group_rows_),
+        rrem(step - gstep * group_rows_), group_rows(group_rows_) {}
+  __device__ __forceinline__ void advance() {
+    rem += rrem; grp += gstep;
+    if (rem >= group_rows) { rem -= group_rows; ++grp; }
+  }
+};
+
 // ---------------------------------------------------------------- mean-pool of ELU(BN(y)) over group_rows
-// one workgroup per (group, 1024-channel slab): thread = channel quad x row lane
+// one workgroup per (group, 1024-channel slab): thread = channel quad x row lane (RowLanes)
 // TRAIN: also emits, per (group, channel), E1 = sum_r ELU'(z) and E2 = sum_r ELU'(z) * yhat.  The
 // gradient that comes back is one value per (group, channel), so the BatchNorm-backward statistics
 // of this layer are sum_g dpool * E1 and sum_g dpool * E2 (pcaa_bn_pool_bwd_stats): a pass over
@@ -176,18 +221,16 @@ __global__ __launch_bounds__(256) void bn_act_meanpool_kernel(const T* __restric
                                                               float* __restrict__ pooled, float* __restrict__ e1,
                                                               float* __restrict__ e2, int group_rows, int ch) {
   __shared__ f32x4 red[TRAIN ? 3 : 1][256];
-  const int qpr = ch >> 2;              // quads per row
-  const int rl = 256 / qpr;             // row lanes
-  const int cq = threadIdx.x % qpr, rlane = threadIdx.x / qpr;
+  const RowLanes L(ch);
   const long g = blockIdx.x;
-  const T* base = y + g * (long)group_rows * ch + cq * 4;
-  const f32x4 sc = load4(scale + cq * 4), sh = load4(shift + cq * 4);
+  const T* base = y + g * (long)group_rows * ch + L.c;
+  const f32x4 sc = load4(scale + L.c), sh = load4(shift + L.c);
   f32x4 mu = {0.f, 0.f, 0.f, 0.f}, rs = mu;
-  if (TRAIN) { mu = load4(mean + cq * 4); rs = load4(rstd + cq * 4); }
+  if (TRAIN) { mu = load4(mean + L.c); rs = load4(rstd + L.c); }
   f32x4 acc = {0.f, 0.f, 0.f, 0.f}, a1 = acc, a2 = acc;
   // (one 8-B load per row and thread; batching 8 rows per trip measured SLOWER -- 184 vs 140 us -- the 32 extra
   // live registers cost more occupancy than the deeper queue gains)
-  for (int r = rlane; r < group_rows; r += rl) {
+  for (int r = L.rlane; r < group_rows; r += L.rl) {
     const f32x4 v = load4(base + (long)r * ch);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -204,17 +247,17 @@ __global__ __launch_bounds__(256) void bn_act_meanpool_kernel(const T* __restric
   red[0][threadIdx.x] = acc;
   if (TRAIN) { red[1][threadIdx.x] = a1; red[2][threadIdx.x] = a2; }
   __syncthreads();
-  if (rlane == 0) {
-    for (int l = 1; l < rl; ++l) {
-      acc += red[0][l * qpr + cq];
-      if (TRAIN) { a1 += red[1][l * qpr + cq]; a2 += red[2][l * qpr + cq]; }
+  if (L.rlane == 0) {
+    for (int l = 1; l < L.rl; ++l) {
+      acc += red[0][l * L.qpr + L.cq];
+      if (TRAIN) { a1 += red[1][l * L.qpr + L.cq]; a2 += red[2][l * L.qpr + L.cq]; }
     }
     const float inv = 1.f / (float)group_rows;
     acc *= inv;
-    store4(pooled + g * (long)ch + cq * 4, acc);
+    store4(pooled + g * (long)ch + L.c, acc);
     if (TRAIN) {
-      store4(e1 + g * (long)ch + cq * 4, a1);
-      store4(e2 + g * (long)ch + cq * 4, a2);
+      store4(e1 + g * (long)ch + L.c, a1);
+      store4(e2 + g * (long)ch + L.c, a2);
     }
   }
 }
@@ -348,72 +391,35 @@ __global__ __launch_bounds__(256) void bn_act_bwd_dz_kernel(const T* __restrict_
                                                             double* __restrict__ stats, int nrep,
                                                             long rows, int ch) {
   __shared__ f32x4 red[2][256];
-  const int qpr = ch >> 2;
-  const int rl = 256 / qpr;
-  const int cq = threadIdx.x % qpr, rlane = threadIdx.x / qpr;
-  const int c = cq * 4;
+  const RowLanes L(ch);
+  const int c = L.c;
   const f32x4 sc = load4(scale + c), sh = load4(shift + c), mu = load4(mean + c), rs = load4(rstd + c);
   const long r0 = (long)blockIdx.x * ROWS_PER_BLOCK;
   const long r1 = min(rows, r0 + ROWS_PER_BLOCK);
-  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-  for (long r = r0 + rlane; r < r1; r += rl) {
+  DzSums sums = {};
+  for (long r = r0 + L.rlane; r < r1; r += L.rl) {
     const f32x4 yv = load4(y + r * ch + c);
     f32x4 g;
     if (POOL) {
+      // (a division per quad, not the GroupWalk: on the train step's critical path, it keeps the code it was measured with)
       g = load4(dpool + (size_t)((unsigned)r / (unsigned)group_rows) * ch + c);   // rows < 2^31 (host-checked)
       g.x *= pool_scale; g.y *= pool_scale; g.z *= pool_scale; g.w *= pool_scale;
     } else {
       g = load4(da + r * ch + c);
     }
-    f32x4 d;
-    d.x = g.x * elu_grad_from_pre_t<T>(yv.x * sc.x + sh.x);
-    d.y = g.y * elu_grad_from_pre_t<T>(yv.y * sc.y + sh.y);
-    d.z = g.z * elu_grad_from_pre_t<T>(yv.z * sc.z + sh.z);
-    d.w = g.w * elu_grad_from_pre_t<T>(yv.w * sc.w + sh.w);
+    const f32x4 d = elu_bwd_quad<T>(g, yv, sc, sh);
     if (dz) store4(dz + r * ch + c, d);       // dz == NULL: statistics-only pass
-    s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-    s2.x += d.x * ((yv.x - mu.x) * rs.x);
-    s2.y += d.y * ((yv.y - mu.y) * rs.y);
-    s2.z += d.z * ((yv.z - mu.z) * rs.z);
-    s2.w += d.w * ((yv.w - mu.w) * rs.w);
+    sums = accumulate_dz(sums, d, yv, mu, rs);
   }
-  red[0][threadIdx.x] = s1;
-  red[1][threadIdx.x] = s2;
-  __syncthreads();
-  // 2*ch outputs; thread t handles stat = t / (ch/... ) -- walk all (stat, channel) pairs
-  for (int o = threadIdx.x; o < 2 * ch; o += 256) {
-    const int stat = o / ch, cc = o - stat * ch;
-    const int q = cc >> 2, e = cc & 3;
-    double v = 0.0;
-    for (int l = 0; l < rl; ++l) v += (double)red[stat][l * qpr + q][e];
-    unsafeAtomicAdd(&stats[((long)(blockIdx.x % nrep) * 2 + stat) * ch + cc], v);
-  }
-}
-
-__global__ void bn_bwd_finalize_kernel(const double* __restrict__ stats, int nrep, double inv_count,
-                                       const float* __restrict__ gamma, const float* __restrict__ mean,
-                                       const float* __restrict__ rstd, float* coef, float* dgamma,
-                                       float* dbeta, int ch) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ch) return;
-  double s1 = 0.0, s2 = 0.0;
-  replica_sums(stats, nrep, ch, c, s1, s2);
-  if (dbeta) dbeta[c] = (float)s1;
-  if (dgamma) dgamma[c] = (float)s2;
-  const double c1 = s1 * inv_count, c2 = s2 * inv_count;
-  const double rs = rstd[c], mu = mean[c];
-  const double g = (double)gamma[c] * rs;
-  coef[0 * ch + c] = (float)g;
-  coef[1 * ch + c] = (float)(-g * c2 * rs);
-  coef[2 * ch + c] = (float)(-g * c1 + g * c2 * rs * mu);
+  commit_row_lanes(L, red, sums, stats, nrep, ch);
 }
 
 // ---------------------------------------------------------------- eval-mode BatchNorm + ELU backward, one pass
 // BatchNorm in eval mode is the fixed map z = scale*y + shift (scale = gamma*r, r = 1/sqrt(running_var + eps)), so
 // dy = scale * dz needs no batch statistic: ONE pass over (da, y) writes dy and reduces {sum dz, sum dz*xhat} with
 // xhat = (y - m')*r, m' = running_mean - bias (y is stored bias-free) -- dbeta and dgamma.  Layout and reduction of
-// bn_act_bwd_dz_kernel (thread = channel quad x row lane, 128 rows per workgroup, fp32 per lane, one fp64 atomic per
-// (workgroup, statistic, channel)); a lane's rows go four at a time so their loads are in flight together.
+// bn_act_bwd_dz_kernel (RowLanes over 128 rows per workgroup, accumulate_dz, commit_row_lanes); a lane's rows go four at
+// a time so their loads are in flight together.
 // dy may alias da (a thread reads exactly the quads it overwrites, before it does): neither is __restrict__.
 __global__ void bn_eval_moments_kernel(const float* __restrict__ rm, const float* __restrict__ rv,
                                        const float* __restrict__ lin_bias, float eps, float* mean, float* rstd, int ch) {
@@ -434,36 +440,24 @@ __global__ __launch_bounds__(256) void bn_eval_act_bwd_kernel(const T* da, const
                                                               double* __restrict__ stats, int nrep, long rows, int ch) {
   __shared__ f32x4 red[2][256];
   constexpr int U = 4;
-  const int qpr = ch >> 2;
-  const int rl = 256 / qpr;
-  const int cq = threadIdx.x % qpr, rlane = threadIdx.x / qpr;
-  const int c = cq * 4;
+  const RowLanes L(ch);
+  const int c = L.c, rl = L.rl;
   const f32x4 sc = load4(scale + c), sh = load4(shift + c), mu = load4(mean + c), rs = load4(rstd + c);
   const long r0 = (long)blockIdx.x * ROWS_PER_BLOCK;
   const long r1 = min(rows, r0 + ROWS_PER_BLOCK);
-  // the pooled gradient's group index advances with the rows by constants: no per-quad division (rows < 2^31, host-checked)
-  unsigned grp = 0u, rem = 0u, gstep = 0u, rrem = 0u;
-  if (POOL) {
-    grp = (unsigned)(r0 + rlane) / group_rows;
-    rem = (unsigned)(r0 + rlane) - grp * group_rows;
-    gstep = (unsigned)rl / group_rows;
-    rrem = (unsigned)rl - gstep * group_rows;
-  }
-  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-  for (long r = r0 + rlane; r < r1; r += (long)U * rl) {
+  GroupWalk walk;
+  if (POOL) walk = GroupWalk((unsigned)(r0 + L.rlane), (unsigned)rl, group_rows);
+  DzSums sums = {};
+  for (long r = r0 + L.rlane; r < r1; r += (long)U * rl) {
     f32x4 yv[U], g[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long rr = r + (long)u * rl;
       if (rr < r1) {
         yv[u] = load4(y + rr * ch + c);
-        g[u] = POOL ? load4(dpool + (size_t)grp * ch + c) : load4(da + rr * ch + c);
+        g[u] = POOL ? load4(dpool + (size_t)walk.grp * ch + c) : load4(da + rr * ch + c);
       }
-      if (POOL) {
-        rem += rrem;
-        grp += gstep;
-        if (rem >= group_rows) { rem -= group_rows; ++grp; }
-      }
+      if (POOL) walk.advance();
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -471,30 +465,12 @@ __global__ __launch_bounds__(256) void bn_eval_act_bwd_kernel(const T* da, const
       if (rr >= r1) break;
       f32x4 gg = g[u];
       if (POOL) gg *= pool_scale;
-      const f32x4 v = yv[u];
-      f32x4 d;
-      d.x = gg.x * elu_grad_from_pre_t<T>(v.x * sc.x + sh.x);
-      d.y = gg.y * elu_grad_from_pre_t<T>(v.y * sc.y + sh.y);
-      d.z = gg.z * elu_grad_from_pre_t<T>(v.z * sc.z + sh.z);
-      d.w = gg.w * elu_grad_from_pre_t<T>(v.w * sc.w + sh.w);
+      const f32x4 d = elu_bwd_quad<T>(gg, yv[u], sc, sh);
       store4(dy + rr * ch + c, sc * d);
-      s1 += d;
-      s2.x += d.x * ((v.x - mu.x) * rs.x);
-      s2.y += d.y * ((v.y - mu.y) * rs.y);
-      s2.z += d.z * ((v.z - mu.z) * rs.z);
-      s2.w += d.w * ((v.w - mu.w) * rs.w);
+      sums = accumulate_dz(sums, d, yv[u], mu, rs);
     }
   }
-  red[0][threadIdx.x] = s1;
-  red[1][threadIdx.x] = s2;
-  __syncthreads();
-  for (int o = threadIdx.x; o < 2 * ch; o += 256) {
-    const int stat = o / ch, cc = o - stat * ch;
-    const int q = cc >> 2, e = cc & 3;
-    double v = 0.0;
-    for (int l = 0; l < rl; ++l) v += (double)red[stat][l * qpr + q][e];
-    unsafeAtomicAdd(&stats[((long)(blockIdx.x % nrep) * 2 + stat) * ch + cc], v);
-  }
+  commit_row_lanes(L, red, sums, stats, nrep, ch);
 }
 
 // dbeta = sum dz, dgamma = sum dz*xhat, dbias = scale * dbeta: fp64 on the fp64 sums, one rounding to fp32
@@ -503,7 +479,7 @@ __global__ void bn_eval_bwd_finalize_kernel(const double* __restrict__ stats, in
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ch) return;
   double s1 = 0.0, s2 = 0.0;
-  replica_sums(stats, nrep, ch, c, s1, s2);
+  bn_replica_sums<false>(stats, nrep, ch, c, s1, s2);
   if (dbeta) dbeta[c] = (float)s1;
   if (dgamma) dgamma[c] = (float)s2;
   if (dbias) dbias[c] = (float)((double)scale[c] * s1);
@@ -774,6 +750,46 @@ inline bool aligned16(const void* a, const void* b, const void* c) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
+// ---- the launchers' shared preambles: each reports under the entry's own name (who) and returns false on refusal
+inline bool refuse(const char* fmt, const char* who) { return pcaa_set_error(fmt, who), false; }
+// f(TypeTag<T>) for the storage dtype; false: dtype is neither -- the entry then returns bad_dtype(who)
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> inline bool dispatch_dtype(int dtype, F&& f) {
+  if (dtype == PCAA_F32) f(TypeTag<float>{});
+  else if (dtype == PCAA_BF16) f(TypeTag<bf16_t>{});
+  else return false;
+  return true;
+}
+// ... and f(TypeTag<T>, std::true_type / std::false_type) for dtype x flag (pooled gradient, train mode)
+template <typename F> inline bool dispatch_dtype_flag(int dtype, bool flag, F&& f) {
+  return dispatch_dtype(dtype, [&](auto t) { flag ? f(t, std::true_type{}) : f(t, std::false_type{}); });
+}
+inline int bad_dtype(const char* who) {
+  pcaa_set_error("%s: bad dtype", who);
+  return PCAA_ERR_INVALID_ARG;
+}
+
+// the column-invariant quad pass (bn_act_fwd_kernel) in two steps, each where the entries had its refusal: whole channel
+// quads; then, behind the entry's own checks, 32-bit quad indices and the grid
+struct QuadPass { long nq; int grid; };
+inline bool quad_rows_ok(const char* who, long rows, int ch) {
+  return (rows >= 1 && ch >= 4 && (ch & 3) == 0) || refuse("%s: ch must be a multiple of 4", who);
+}
+inline bool quad_pass(const char* who, long rows, int ch, QuadPass& p) {
+  p.nq = rows * (ch >> 2);
+  if (!(p.nq < (1L << 31))) return refuse("%s: tensor too large for 32-bit quad indices", who);
+  p.grid = col_invariant_grid(p.nq, ch >> 2);
+  return true;
+}
+
+// the gradient comes dense (da) or pooled (dpool: one row per group_rows rows), never both; again in the entries' two steps
+inline bool grad_source_ok(const char* who, const void* da, const float* dpool) {
+  return ((da != nullptr) != (dpool != nullptr)) || refuse("%s: exactly one of da / dpool", who);
+}
+inline bool group_rows_ok(const char* who, const float* dpool, int group_rows) {
+  return (!dpool || group_rows >= 1) || refuse("%s: bad group_rows", who);
+}
+
 }  // namespace
 
 int ew::cu_count() {
@@ -811,10 +827,9 @@ extern "C" int pcaa_bn_finalize(const double* stats, int nrep, long count, const
   PCAA_CHECK_ARG(stats && gamma && beta && scale && shift && mean && rstd, "pcaa_bn_finalize: null pointer");
   PCAA_CHECK_ARG(nrep >= 1 && count >= 1 && ch >= 1, "pcaa_bn_finalize: bad sizes");
   PCAA_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "pcaa_bn_finalize: running stats must come together");
-  const double unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
-                     stats, nrep, 1.0 / (double)count, unbias, lin_bias, gamma, beta, running_mean,
-                     running_var, num_batches_tracked, momentum, eps, scale, shift, mean, rstd, ch);
+                     bn_tail_fwd(stats, nrep, count, lin_bias, gamma, beta, running_mean, running_var, num_batches_tracked,
+                                 momentum, eps, scale, shift, mean, rstd, ch, nullptr));
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_finalize");
 }
 
@@ -830,34 +845,30 @@ extern "C" int pcaa_bn_eval_coeffs(const float* gamma, const float* beta, const 
 extern "C" int pcaa_bn_act_fwd(const void* y, void* a, int dtype, const float* scale, const float* shift,
                                long rows, int ch, void* stream) {
   PCAA_CHECK_ARG(y && a && scale && shift, "pcaa_bn_act_fwd: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_act_fwd: ch must be a multiple of 4");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_act_fwd: tensor too large for 32-bit quad indices");
+  QuadPass p;
+  if (!quad_rows_ok("pcaa_bn_act_fwd", rows, ch) || !quad_pass("pcaa_bn_act_fwd", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
   if (ew_route_stream(PCAA_EW_ACT_FWD, dtype, rows, ch, aligned16(y, a, nullptr))) {
     ew::launch<1, ew::ActFwdPolicy>((const bf16_t*)y, nullptr, (bf16_t*)a, ew::ActFwd{scale, shift}, rows, ch,
                                     as_stream(stream));
     PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_fwd");
   }
-  const int grid = col_invariant_grid(nq, ch >> 2);
-  if (dtype == PCAA_F32)
-    hipLaunchKernelGGL(bn_act_fwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream),
-                       (const float*)y, (float*)a, scale, shift, (unsigned)nq, (unsigned)(ch >> 2));
-  else if (dtype == PCAA_BF16)
-    hipLaunchKernelGGL(bn_act_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream),
-                       (const bf16_t*)y, (bf16_t*)a, scale, shift, (unsigned)nq, (unsigned)(ch >> 2));
-  else { pcaa_set_error("pcaa_bn_act_fwd: bad dtype"); return PCAA_ERR_INVALID_ARG; }
+  if (!dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(bn_act_fwd_kernel<T>, dim3(p.grid), dim3(256), 0, as_stream(stream), (const T*)y, (T*)a, scale,
+                           shift, (unsigned)p.nq, (unsigned)(ch >> 2));
+      }))
+    return bad_dtype("pcaa_bn_act_fwd");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_fwd");
 }
 
 extern "C" int pcaa_bn_act_fwd_split(const float* y, void* a_img, const float* scale, const float* shift, long rows,
                                      int ch, float img_scale, void* stream) {
   PCAA_CHECK_ARG(y && a_img && scale && shift, "pcaa_bn_act_fwd_split: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_act_fwd_split: ch must be a multiple of 4");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_act_fwd_split: tensor too large for 32-bit quad indices");
-  const int grid = col_invariant_grid(nq, ch >> 2);
-  hipLaunchKernelGGL(bn_act_fwd_split_kernel, dim3(grid), dim3(256), 0, as_stream(stream), y, (split_t*)a_img, scale, shift,
-                     (unsigned)nq, (unsigned)(ch >> 2), img_scale, pcaa_range_flag_ptr());
+  QuadPass p;
+  if (!quad_rows_ok("pcaa_bn_act_fwd_split", rows, ch)) return PCAA_ERR_INVALID_ARG;
+  if (!quad_pass("pcaa_bn_act_fwd_split", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(bn_act_fwd_split_kernel, dim3(p.grid), dim3(256), 0, as_stream(stream), y, (split_t*)a_img, scale, shift,
+                     (unsigned)p.nq, (unsigned)(ch >> 2), img_scale, pcaa_range_flag_ptr());
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_fwd_split");
 }
 
@@ -880,9 +891,6 @@ extern "C" int pcaa_bn_act_meanpool_fwd(const void* y, int dtype, const float* s
   PCAA_CHECK_ARG((e2 != nullptr) == train && (!train || (mean && rstd)),
                  "pcaa_bn_act_meanpool_fwd: e1, e2, mean, rstd come together");
   hipStream_t s = as_stream(stream);
-#define LAUNCH_MP(T, TRAIN)                                                                                   \
-  hipLaunchKernelGGL((bn_act_meanpool_kernel<T, TRAIN>), dim3((unsigned)groups), dim3(256), 0, s, (const T*)y, \
-                     scale, shift, mean, rstd, pooled, e1, e2, group_rows, ch)
   if (dtype == PCAA_BF16 && ch == 1024 && group_rows % 4 == 0 && groups >= 512) {
     // the PointNet block's last layer at the shapes that matter: the streaming form
     const unsigned grid = (unsigned)std::min<long>(groups, 1024);
@@ -893,10 +901,12 @@ extern "C" int pcaa_bn_act_meanpool_fwd(const void* y, int dtype, const float* s
       hipLaunchKernelGGL(bn_act_meanpool_stream_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)y, scale, shift,
                          mean, rstd, pooled, e1, e2, groups, group_rows, ch);
   }
-  else if (dtype == PCAA_F32) { if (train) LAUNCH_MP(float, true); else LAUNCH_MP(float, false); }
-  else if (dtype == PCAA_BF16) { if (train) LAUNCH_MP(bf16_t, true); else LAUNCH_MP(bf16_t, false); }
-  else { pcaa_set_error("pcaa_bn_act_meanpool_fwd: bad dtype"); return PCAA_ERR_INVALID_ARG; }
-#undef LAUNCH_MP
+  else if (!dispatch_dtype_flag(dtype, train, [&](auto t, auto tr) {
+             using T = typename decltype(t)::type;
+             hipLaunchKernelGGL((bn_act_meanpool_kernel<T, decltype(tr)::value>), dim3((unsigned)groups), dim3(256), 0, s,
+                                (const T*)y, scale, shift, mean, rstd, pooled, e1, e2, group_rows, ch);
+           }))
+    return bad_dtype("pcaa_bn_act_meanpool_fwd");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_meanpool_fwd");
 }
 
@@ -914,21 +924,20 @@ extern "C" int pcaa_bn_act_bwd_dz(const void* da, const float* dpool, int group_
                                   const void* y, void* dz, int dtype, const float* scale,
                                   const float* shift, const float* mean, const float* rstd,
                                   double* stats, int nrep, long rows, int ch, void* stream) {
-  PCAA_CHECK_ARG((da != nullptr) != (dpool != nullptr), "pcaa_bn_act_bwd_dz: exactly one of da / dpool");
+  if (!grad_source_ok("pcaa_bn_act_bwd_dz", da, dpool)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG(y && scale && shift && mean && rstd && stats, "pcaa_bn_act_bwd_dz: null pointer");
   PCAA_CHECK_ARG(rows >= 1 && rows < (1L << 31) && nrep >= 1 && ch_ok(ch),
                  "pcaa_bn_act_bwd_dz: ch/4 must divide 256 (ch=%d), rows < 2^31", ch);
-  PCAA_CHECK_ARG(!dpool || group_rows >= 1, "pcaa_bn_act_bwd_dz: bad group_rows");
+  if (!group_rows_ok("pcaa_bn_act_bwd_dz", dpool, group_rows)) return PCAA_ERR_INVALID_ARG;
   const unsigned grid = (unsigned)cdiv(rows, ROWS_PER_BLOCK);
   hipStream_t s = as_stream(stream);
-#define LAUNCH_DZ(T, POOL)                                                                       \
-  hipLaunchKernelGGL((bn_act_bwd_dz_kernel<T, POOL>), dim3(grid), dim3(256), 0, s, (const T*)da, \
-                     dpool, group_rows, pool_scale, (const T*)y, (T*)dz, scale, shift, mean,     \
-                     rstd, stats, nrep, rows, ch)
-  if (dtype == PCAA_F32) { if (dpool) LAUNCH_DZ(float, true); else LAUNCH_DZ(float, false); }
-  else if (dtype == PCAA_BF16) { if (dpool) LAUNCH_DZ(bf16_t, true); else LAUNCH_DZ(bf16_t, false); }
-  else { pcaa_set_error("pcaa_bn_act_bwd_dz: bad dtype"); return PCAA_ERR_INVALID_ARG; }
-#undef LAUNCH_DZ
+  if (!dispatch_dtype_flag(dtype, dpool != nullptr, [&](auto t, auto pool) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_act_bwd_dz_kernel<T, decltype(pool)::value>), dim3(grid), dim3(256), 0, s, (const T*)da,
+                           dpool, group_rows, pool_scale, (const T*)y, (T*)dz, scale, shift, mean, rstd, stats, nrep, rows,
+                           ch);
+      }))
+    return bad_dtype("pcaa_bn_act_bwd_dz");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_act_bwd_dz");
 }
 
@@ -945,7 +954,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dy_fused_kernel(const T* __restric
                                                               unsigned qpr, unsigned ch, float img_scale = 1.f,
                                                               int* oflow = nullptr) {
   // column-invariant grid (see bn_act_fwd_kernel): coefficients in registers, rows advance by a
-  // constant; the pooled variant's group index is one 32-bit division per quad
+  // constant; the pooled variant's group index follows them on a GroupWalk
   const unsigned q0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
   const unsigned c = (q0 % qpr) << 2;
   const unsigned rstep = stride / qpr;
@@ -954,27 +963,22 @@ __global__ __launch_bounds__(256) void bn_bwd_dy_fused_kernel(const T* __restric
   const f32x4 k0 = load4(coef + c), k1 = load4(coef + ch + c), k2 = load4(coef + 2 * ch + c);
   constexpr bool kFast = sizeof(T) == 2;      // bf16 storage: ELU'(z) = exp2(min(z log2e, 0)), log2e folded into the affine
   if (kFast) { sc *= 1.4426950408889634f; sh *= 1.4426950408889634f; }
-  // the pooled gradient is constant over a group's rows: the thread's (group, row in group) advance by constants --
-  // no per-quad division (the first version spent more vector-ALU time on r / group_rows than the pass spends on HBM:
-  // 237 us for 1 GB at config[1], round 2's trace)
-  unsigned grp = POOL ? r / group_rows : 0u, rem = POOL ? r - grp * group_rows : 0u;
-  const unsigned gstep = POOL ? rstep / group_rows : 0u, rrem = POOL ? rstep - gstep * group_rows : 0u;
-  unsigned cur_group = 0xffffffffu;
+  GroupWalk walk;
+  if (POOL) walk = GroupWalk(r, rstep, group_rows);
+  unsigned cur_group = 0xffffffffu;      // the group whose gradient is in gpool: reloaded only when the walk leaves it
   unsigned rr = r;
   f32x4 gpool = {0.f, 0.f, 0.f, 0.f};
   for (unsigned q = q0; q < nquads; q += stride) {
     const f32x4 yv = load4(y + (size_t)q * 4);
     f32x4 g;
     if (POOL) {
-      if (grp != cur_group) {
-        cur_group = grp;
-        gpool = load4(dpool + (size_t)grp * ch + c);
+      if (walk.grp != cur_group) {
+        cur_group = walk.grp;
+        gpool = load4(dpool + (size_t)walk.grp * ch + c);
         gpool *= pool_scale;
       }
       g = gpool;
-      rem += rrem;
-      grp += gstep;
-      if (rem >= group_rows) { rem -= group_rows; ++grp; }
+      walk.advance();
     } else {
       g = load4(da + (size_t)q * 4);
     }
@@ -1001,22 +1005,20 @@ __global__ __launch_bounds__(256) void bn_bwd_dy_fused_kernel(const T* __restric
 extern "C" int pcaa_bn_bwd_dy_fused(const void* da, const float* dpool, int group_rows, float pool_scale,
                                     const void* y, void* dy, int dtype, const float* scale, const float* shift,
                                     const float* coef, long rows, int ch, void* stream) {
-  PCAA_CHECK_ARG((da != nullptr) != (dpool != nullptr), "pcaa_bn_bwd_dy_fused: exactly one of da / dpool");
+  if (!grad_source_ok("pcaa_bn_bwd_dy_fused", da, dpool)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG(y && dy && scale && shift && coef, "pcaa_bn_bwd_dy_fused: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_bwd_dy_fused: ch must be a multiple of 4");
-  PCAA_CHECK_ARG(!dpool || group_rows >= 1, "pcaa_bn_bwd_dy_fused: bad group_rows");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_bwd_dy_fused: tensor too large for 32-bit quad indices");
-  const int grid = col_invariant_grid(nq, ch >> 2);
+  if (!quad_rows_ok("pcaa_bn_bwd_dy_fused", rows, ch)) return PCAA_ERR_INVALID_ARG;
+  if (!group_rows_ok("pcaa_bn_bwd_dy_fused", dpool, group_rows)) return PCAA_ERR_INVALID_ARG;
+  QuadPass p;
+  if (!quad_pass("pcaa_bn_bwd_dy_fused", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
   hipStream_t s = as_stream(stream);
-#define LAUNCH_DYF(T, POOL)                                                                             \
-  hipLaunchKernelGGL((bn_bwd_dy_fused_kernel<T, POOL>), dim3(grid), dim3(256), 0, s, (const T*)da, dpool, \
-                     (unsigned)group_rows, pool_scale, (const T*)y, (T*)dy, scale, shift, coef, (unsigned)nq, \
-                     (unsigned)(ch >> 2), (unsigned)ch)
-  if (dtype == PCAA_F32) { if (dpool) LAUNCH_DYF(float, true); else LAUNCH_DYF(float, false); }
-  else if (dtype == PCAA_BF16) { if (dpool) LAUNCH_DYF(bf16_t, true); else LAUNCH_DYF(bf16_t, false); }
-  else { pcaa_set_error("pcaa_bn_bwd_dy_fused: bad dtype"); return PCAA_ERR_INVALID_ARG; }
-#undef LAUNCH_DYF
+  if (!dispatch_dtype_flag(dtype, dpool != nullptr, [&](auto t, auto pool) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_bwd_dy_fused_kernel<T, decltype(pool)::value>), dim3(p.grid), dim3(256), 0, s, (const T*)da,
+                           dpool, (unsigned)group_rows, pool_scale, (const T*)y, (T*)dy, scale, shift, coef, (unsigned)p.nq,
+                           (unsigned)(ch >> 2), (unsigned)ch);
+      }))
+    return bad_dtype("pcaa_bn_bwd_dy_fused");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy_fused");
 }
 
@@ -1024,23 +1026,21 @@ extern "C" int pcaa_bn_bwd_dy_fused(const void* da, const float* dpool, int grou
 extern "C" int pcaa_bn_bwd_dy_fused_split(const float* da, const float* dpool, int group_rows, float pool_scale,
                                           const float* y, void* dy_img, const float* scale, const float* shift,
                                           const float* coef, long rows, int ch, float img_scale, void* stream) {
-  PCAA_CHECK_ARG((da != nullptr) != (dpool != nullptr), "pcaa_bn_bwd_dy_fused_split: exactly one of da / dpool");
+  if (!grad_source_ok("pcaa_bn_bwd_dy_fused_split", da, dpool)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG(y && dy_img && scale && shift && coef, "pcaa_bn_bwd_dy_fused_split: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_bwd_dy_fused_split: ch must be a multiple of 4");
-  PCAA_CHECK_ARG(!dpool || group_rows >= 1, "pcaa_bn_bwd_dy_fused_split: bad group_rows");
+  if (!quad_rows_ok("pcaa_bn_bwd_dy_fused_split", rows, ch)) return PCAA_ERR_INVALID_ARG;
+  if (!group_rows_ok("pcaa_bn_bwd_dy_fused_split", dpool, group_rows)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG((const void*)da != dy_img, "pcaa_bn_bwd_dy_fused_split: the image cannot alias da");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_bwd_dy_fused_split: tensor too large for 32-bit quad indices");
-  const int grid = col_invariant_grid(nq, ch >> 2);
+  QuadPass p;
+  if (!quad_pass("pcaa_bn_bwd_dy_fused_split", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
   hipStream_t s = as_stream(stream);
-  if (dpool)
-    hipLaunchKernelGGL((bn_bwd_dy_fused_kernel<float, true, true>), dim3(grid), dim3(256), 0, s, da, dpool,
-                       (unsigned)group_rows, pool_scale, y, (float*)dy_img, scale, shift, coef, (unsigned)nq,
+  auto launch = [&](auto pool) {
+    hipLaunchKernelGGL((bn_bwd_dy_fused_kernel<float, decltype(pool)::value, true>), dim3(p.grid), dim3(256), 0, s, da,
+                       dpool, (unsigned)group_rows, pool_scale, y, (float*)dy_img, scale, shift, coef, (unsigned)p.nq,
                        (unsigned)(ch >> 2), (unsigned)ch, img_scale, pcaa_range_flag_ptr());
-  else
-    hipLaunchKernelGGL((bn_bwd_dy_fused_kernel<float, false, true>), dim3(grid), dim3(256), 0, s, da, dpool,
-                       (unsigned)group_rows, pool_scale, y, (float*)dy_img, scale, shift, coef, (unsigned)nq,
-                       (unsigned)(ch >> 2), (unsigned)ch, img_scale, pcaa_range_flag_ptr());
+  };
+  if (dpool) launch(std::true_type{});
+  else launch(std::false_type{});
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy_fused_split");
 }
 
@@ -1049,8 +1049,8 @@ extern "C" int pcaa_bn_bwd_finalize(const double* stats, int nrep, long count, c
                                     float* dbeta, int ch, void* stream) {
   PCAA_CHECK_ARG(stats && gamma && mean && rstd && coef, "pcaa_bn_bwd_finalize: null pointer");
   PCAA_CHECK_ARG(nrep >= 1 && count >= 1 && ch >= 1, "pcaa_bn_bwd_finalize: bad sizes");
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
-                     stats, nrep, 1.0 / (double)count, gamma, mean, rstd, coef, dgamma, dbeta, ch);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((unsigned)cdiv(ch, 256)), dim3(256), 0, as_stream(stream),
+                     bn_tail_bwd(stats, nrep, count, gamma, mean, rstd, coef, dgamma, dbeta, ch, nullptr));
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_finalize");
 }
 
@@ -1067,22 +1067,21 @@ extern "C" int pcaa_bn_eval_act_bwd(const void* da, const float* dpool, int grou
                                     const void* y, void* dy, int dtype, const float* scale, const float* shift,
                                     const float* mean, const float* rstd, double* stats, int nrep, long rows, int ch,
                                     void* stream) {
-  PCAA_CHECK_ARG((da != nullptr) != (dpool != nullptr), "pcaa_bn_eval_act_bwd: exactly one of da / dpool");
+  if (!grad_source_ok("pcaa_bn_eval_act_bwd", da, dpool)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG(y && dy && scale && shift && mean && rstd && stats, "pcaa_bn_eval_act_bwd: null pointer");
   PCAA_CHECK_ARG(rows >= 1 && rows < (1L << 31) && nrep >= 1 && ch_ok(ch),
                  "pcaa_bn_eval_act_bwd: ch/4 must divide 256 (ch=%d), rows < 2^31", ch);
-  PCAA_CHECK_ARG(!dpool || group_rows >= 1, "pcaa_bn_eval_act_bwd: bad group_rows");
+  if (!group_rows_ok("pcaa_bn_eval_act_bwd", dpool, group_rows)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG(dy != y, "pcaa_bn_eval_act_bwd: dy may alias da, not y");
   const unsigned grid = (unsigned)cdiv(rows, ROWS_PER_BLOCK);
   hipStream_t s = as_stream(stream);
-#define LAUNCH_EV(T, POOL)                                                                         \
-  hipLaunchKernelGGL((bn_eval_act_bwd_kernel<T, POOL>), dim3(grid), dim3(256), 0, s, (const T*)da, \
-                     dpool, (unsigned)group_rows, pool_scale, (const T*)y, (T*)dy, scale, shift,   \
-                     mean, rstd, stats, nrep, rows, ch)
-  if (dtype == PCAA_F32) { if (dpool) LAUNCH_EV(float, true); else LAUNCH_EV(float, false); }
-  else if (dtype == PCAA_BF16) { if (dpool) LAUNCH_EV(bf16_t, true); else LAUNCH_EV(bf16_t, false); }
-  else { pcaa_set_error("pcaa_bn_eval_act_bwd: bad dtype"); return PCAA_ERR_INVALID_ARG; }
-#undef LAUNCH_EV
+  if (!dispatch_dtype_flag(dtype, dpool != nullptr, [&](auto t, auto pool) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bn_eval_act_bwd_kernel<T, decltype(pool)::value>), dim3(grid), dim3(256), 0, s, (const T*)da,
+                           dpool, (unsigned)group_rows, pool_scale, (const T*)y, (T*)dy, scale, shift, mean, rstd, stats,
+                           nrep, rows, ch);
+      }))
+    return bad_dtype("pcaa_bn_eval_act_bwd");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_eval_act_bwd");
 }
 
@@ -1114,15 +1113,8 @@ extern "C" int pcaa_bn_tail_arm_fwd(const double* stats, int nrep, long count, c
   PCAA_CHECK_ARG(stats && gamma && beta && scale && shift && mean && rstd && counter, "pcaa_bn_tail_arm_fwd: null pointer");
   PCAA_CHECK_ARG(nrep >= 1 && count >= 1 && ch >= 1, "pcaa_bn_tail_arm_fwd: bad sizes");
   PCAA_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "pcaa_bn_tail_arm_fwd: running stats must come together");
-  BnTail t = {};
-  t.kind = 1; t.nrep = nrep; t.ch = ch; t.counter = counter; t.stats = stats;
-  t.inv_count = 1.0 / (double)count;
-  t.unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
-  t.lin_bias = lin_bias; t.gamma = gamma; t.beta = beta;
-  t.running_mean = running_mean; t.running_var = running_var; t.nbt = num_batches_tracked;
-  t.momentum = momentum; t.eps = eps;
-  t.scale = scale; t.shift = shift; t.mean = mean; t.rstd = rstd;
-  g_tail = t;
+  g_tail = bn_tail_fwd(stats, nrep, count, lin_bias, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
+                       eps, scale, shift, mean, rstd, ch, counter);
   return PCAA_OK;
 }
 extern "C" int pcaa_bn_tail_arm_bwd(const double* stats, int nrep, long count, const float* gamma, const float* mean,
@@ -1130,12 +1122,7 @@ extern "C" int pcaa_bn_tail_arm_bwd(const double* stats, int nrep, long count, c
                                     unsigned* counter) {
   PCAA_CHECK_ARG(stats && gamma && mean && rstd && coef && counter, "pcaa_bn_tail_arm_bwd: null pointer");
   PCAA_CHECK_ARG(nrep >= 1 && count >= 1 && ch >= 1, "pcaa_bn_tail_arm_bwd: bad sizes");
-  BnTail t = {};
-  t.kind = 2; t.nrep = nrep; t.ch = ch; t.counter = counter; t.stats = stats;
-  t.inv_count = 1.0 / (double)count;
-  t.gamma = gamma; t.mean = const_cast<float*>(mean); t.rstd = const_cast<float*>(rstd);
-  t.coef = coef; t.dgamma = dgamma; t.dbeta = dbeta;
-  g_tail = t;
+  g_tail = bn_tail_bwd(stats, nrep, count, gamma, mean, rstd, coef, dgamma, dbeta, ch, counter);
   return PCAA_OK;
 }
 // a launcher that took the tail and then could NOT launch hands it back: the stand-alone finalize then runs
@@ -1152,36 +1139,32 @@ extern "C" int pcaa_bn_tail_disarm(void) {
 extern "C" int pcaa_bn_bwd_dy(const void* dz, const void* y, void* dy, int dtype, const float* coef,
                               long rows, int ch, void* stream) {
   PCAA_CHECK_ARG(dz && y && dy && coef, "pcaa_bn_bwd_dy: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_bwd_dy: ch must be a multiple of 4");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_bwd_dy: tensor too large for 32-bit quad indices");
+  QuadPass p;
+  if (!quad_rows_ok("pcaa_bn_bwd_dy", rows, ch) || !quad_pass("pcaa_bn_bwd_dy", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
   if (ew_route_stream(PCAA_EW_BWD_DY, dtype, rows, ch, aligned16(dz, y, dy))) {
     // dy may be dz (ew_stream.h: aliasing)
     ew::launch<2, ew::BwdDyPolicy>((const bf16_t*)y, (const bf16_t*)dz, (bf16_t*)dy, ew::BwdDy{coef}, rows, ch,
                                    as_stream(stream));
     PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy");
   }
-  const int grid = col_invariant_grid(nq, ch >> 2);
-  if (dtype == PCAA_F32)
-    hipLaunchKernelGGL(bn_bwd_dy_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float*)dz,
-                       (const float*)y, (float*)dy, coef, (unsigned)nq, (unsigned)(ch >> 2), (unsigned)ch);
-  else if (dtype == PCAA_BF16)
-    hipLaunchKernelGGL(bn_bwd_dy_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t*)dz,
-                       (const bf16_t*)y, (bf16_t*)dy, coef, (unsigned)nq, (unsigned)(ch >> 2), (unsigned)ch);
-  else { pcaa_set_error("pcaa_bn_bwd_dy: bad dtype"); return PCAA_ERR_INVALID_ARG; }
+  if (!dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(bn_bwd_dy_kernel<T>, dim3(p.grid), dim3(256), 0, as_stream(stream), (const T*)dz, (const T*)y,
+                           (T*)dy, coef, (unsigned)p.nq, (unsigned)(ch >> 2), (unsigned)ch);
+      }))
+    return bad_dtype("pcaa_bn_bwd_dy");
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy");
 }
 
 extern "C" int pcaa_bn_bwd_dy_split(const float* dz, const float* y, void* dy_img, const float* coef, long rows, int ch,
                                     float img_scale, void* stream) {
   PCAA_CHECK_ARG(dz && y && dy_img && coef, "pcaa_bn_bwd_dy_split: null pointer");
-  PCAA_CHECK_ARG(rows >= 1 && ch >= 4 && (ch & 3) == 0, "pcaa_bn_bwd_dy_split: ch must be a multiple of 4");
+  if (!quad_rows_ok("pcaa_bn_bwd_dy_split", rows, ch)) return PCAA_ERR_INVALID_ARG;
   PCAA_CHECK_ARG((const void*)dz != dy_img && (const void*)y != dy_img, "pcaa_bn_bwd_dy_split: the image cannot alias an input");
-  const long nq = rows * (ch >> 2);
-  PCAA_CHECK_ARG(nq < (1L << 31), "pcaa_bn_bwd_dy_split: tensor too large for 32-bit quad indices");
-  const int grid = col_invariant_grid(nq, ch >> 2);
-  hipLaunchKernelGGL(bn_bwd_dy_split_kernel, dim3(grid), dim3(256), 0, as_stream(stream), dz, y, (split_t*)dy_img, coef,
-                     (unsigned)nq, (unsigned)(ch >> 2), (unsigned)ch, img_scale, pcaa_range_flag_ptr());
+  QuadPass p;
+  if (!quad_pass("pcaa_bn_bwd_dy_split", rows, ch, p)) return PCAA_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(bn_bwd_dy_split_kernel, dim3(p.grid), dim3(256), 0, as_stream(stream), dz, y, (split_t*)dy_img, coef,
+                     (unsigned)p.nq, (unsigned)(ch >> 2), (unsigned)ch, img_scale, pcaa_range_flag_ptr());
   PCAA_RETURN_LAUNCH_STATUS("pcaa_bn_bwd_dy_split");
 }
 

@@ -1068,17 +1068,24 @@ def bn_pool_bwd_stats(dpool, e, pool_scale, tail=None):
     return stats
 
 
-def bn_act_bwd_dz(y, scale, shift, mean, rstd, *, da=None, dpool=None, group_rows=0, pool_scale=1.0, out=None):
-    _chk(y, "bn_act_bwd_dz.y", dim=2)
+def _grad_source(who, y, da, dpool, group_rows):
+    """the checks of a [rows, ch] pass whose gradient comes dense (da, like y) or pooled (dpool fp32, one row per
+    group_rows rows of y) -> (rows, ch)"""
+    _chk(y, f"{who}.y", dim=2)
     rows, ch = y.shape
     if da is not None:
-        _chk(da, "bn_act_bwd_dz.da", y.dtype, 2)
+        _chk(da, f"{who}.da", y.dtype, 2)
         if da.shape != y.shape:
-            raise ValueError("bn_act_bwd_dz: da shape")
+            raise ValueError(f"{who}: da shape")
     else:
-        _chk(dpool, "bn_act_bwd_dz.dpool", torch.float32, 2)
+        _chk(dpool, f"{who}.dpool", torch.float32, 2)
         if dpool.shape[0] * group_rows != rows or dpool.shape[1] != ch:
-            raise ValueError("bn_act_bwd_dz: dpool shape")
+            raise ValueError(f"{who}: dpool shape")
+    return rows, ch
+
+
+def bn_act_bwd_dz(y, scale, shift, mean, rstd, *, da=None, dpool=None, group_rows=0, pool_scale=1.0, out=None):
+    rows, ch = _grad_source("bn_act_bwd_dz", y, da, dpool, group_rows)
     dz = out if out is not None else torch.empty_like(y)
     stats = new_stats(ch, y.device)
     check(_lib.load().pcaa_bn_act_bwd_dz(_p(da), _p(dpool), int(group_rows), float(pool_scale), _p(y), _p(dz),
@@ -1134,16 +1141,7 @@ def bn_eval_moments(bn, ch, lin_bias=None):
 def bn_eval_act_bwd(y, scale, shift, mean, rstd, *, da=None, dpool=None, group_rows=0, pool_scale=1.0, out=None):
     """Backward through eval-mode BatchNorm + ELU in one pass: dy = scale * (g * ELU'(scale*y + shift)) (``out`` may be
     ``da``) and the statistics {sum dz, sum dz*xhat} for bn_eval_bwd_finalize.  -> (dy, stats)"""
-    _chk(y, "bn_eval_act_bwd.y", dim=2)
-    rows, ch = y.shape
-    if da is not None:
-        _chk(da, "bn_eval_act_bwd.da", y.dtype, 2)
-        if da.shape != y.shape:
-            raise ValueError("bn_eval_act_bwd: da shape")
-    else:
-        _chk(dpool, "bn_eval_act_bwd.dpool", torch.float32, 2)
-        if dpool.shape[0] * group_rows != rows or dpool.shape[1] != ch:
-            raise ValueError("bn_eval_act_bwd: dpool shape")
+    rows, ch = _grad_source("bn_eval_act_bwd", y, da, dpool, group_rows)
     dy = out if out is not None else torch.empty_like(y)
     if dy.shape != y.shape or dy.dtype != y.dtype or not dy.is_contiguous():
         raise ValueError("bn_eval_act_bwd: out must be contiguous with y's shape and dtype")

@@ -20,6 +20,9 @@ Every comparison prints ``worst |err| / gate`` of its case (pytest -rP); the num
     bn_pool_bwd_stats: groups per block 1 / 3 / 32, channel loop    test_bn_pool_bwd_stats
     bn_finalize (bias, running stats on / off), bn_bwd_finalize,    test_bn_finalize_family
       bn_eval_coeffs
+    the replica sum of the three finalizes and of the carried     test_finalize_replica_counts
+      tail: nrep 1 / 11 / 16 (remainder only, trip + remainder,
+      trips only), ch 260 (ragged second workgroup)
     splitk_reduce (accumulate on / off), splitk_reduce_stats        test_splitk_reduce
     adam: max_blocks <= 1024 (4 quads per thread) / above,          test_adam_against_fp64, test_adam_kernels_agree_bitwise,
       host step / device step, fp32 / bf16 gradient, n % 4 tail       test_adam_device_step_equals_host_step,
@@ -35,6 +38,7 @@ import pytest
 import torch
 
 import elementwise_ref as R
+import eval_bwd_ref as E
 from opensetgaitrecognition_pcaa_amd import _lib, ops
 from opensetgaitrecognition_pcaa_amd._lib import ACT_ELU, ACT_NONE, PcaaError
 
@@ -296,6 +300,89 @@ def test_bn_finalize_family(ch, lin_bias, update_running):
         want = m(acc + (case["lin_bias"].double() if lin_bias else 0.0))
     check(f"bn_eval_coeffs ch={ch} bias={lin_bias} vs BatchNorm1d.eval()", acc * sc.double() + sft.double(), want,
           acc.abs() * gsc + gsft)
+
+
+def _same_bits(a, b):
+    return torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+@pytest.mark.parametrize("ch", [4, 260])
+@pytest.mark.parametrize("nrep", [1, 11, 16])
+def test_finalize_replica_counts(nrep, ch):
+    """ops always passes NREP = 16, i.e. two 8-deep trips of the replica sum and no remainder: through the C ABI,
+    nrep = 1 (remainder only), 11 (one trip and three) and 16; ch = 260: the second workgroup of the stand-alone
+    finalize has a ragged end.  The stand-alone finalizes against fp64, and bitwise against the finalize carried by a
+    producer (bn_pool_bwd_stats, one group: one workgroup, which is then the last to arrive) on the same statistics."""
+    lib, s = _lib.load(), ops._s()
+    count = 176                                                    # a multiple of 11 and of 16
+    case = R.finalize_case(ch, True, DEV, count=count, nrep=nrep)
+    buf = torch.zeros(nrep * 2 * ch + 2, dtype=torch.float64, device=DEV)
+    stats = buf[:nrep * 2 * ch].view(nrep, 2, ch)
+    stats.copy_(case["stats"])
+    counter = buf[nrep * 2 * ch:].view(torch.int32)
+    # the producer adds a little to replica 0 (nothing to the constant column 0) before its last workgroup finalizes
+    dpool = R.gradient(1, ch, F32, R.seed_of(ch, nrep), DEV)
+    dpool[:, 0] = 0.0
+    e = R.uniform(2 * ch, R.seed_of(nrep, ch), DEV, -1.0, 1.0).float().view(2, 1, ch).contiguous()
+
+    def produce():
+        _lib.check(lib.pcaa_bn_pool_bwd_stats(dpool.data_ptr(), e[0].data_ptr(), e[1].data_ptr(), 1.0 / 128, stats.data_ptr(),
+                                              nrep, 1, ch, s), "pcaa_bn_pool_bwd_stats")
+        assert lib.pcaa_bn_tail_pending() == 0, "the producer must have carried the finalize"
+        assert int(counter[0]) == 0, "the finalizer leaves the arrival counter at zero"
+
+    eps, mom = R.f32(1e-5), 0.1
+    g, b, lb = case["gamma"], case["beta"], case["lin_bias"]
+    tag = f"finalize nrep={nrep} ch={ch}"
+    # ---- forward: carried, then stand-alone on the statistics the carried one saw
+    run = {}
+    for form in ("carried", "alone"):
+        o = {k: torch.empty(ch, device=DEV) for k in ("scale", "shift", "mean", "rstd")}
+        o["running_mean"], o["running_var"] = case["rm"].clone(), case["rv"].clone()
+        o["nbt"] = torch.full((), 5, dtype=torch.int64, device=DEV)
+        args = (stats.data_ptr(), nrep, count, lb.data_ptr(), g.data_ptr(), b.data_ptr(), o["running_mean"].data_ptr(),
+                o["running_var"].data_ptr(), o["nbt"].data_ptr(), mom, eps, o["scale"].data_ptr(), o["shift"].data_ptr(),
+                o["mean"].data_ptr(), o["rstd"].data_ptr(), ch)
+        if form == "carried":
+            _lib.check(lib.pcaa_bn_tail_arm_fwd(*args, counter.data_ptr()), "pcaa_bn_tail_arm_fwd")
+            produce()
+        else:
+            _lib.check(lib.pcaa_bn_finalize(*args, s), "pcaa_bn_finalize")
+        run[form] = o
+    ref = R.bn_finalize_ref(stats, count, lb, g, b, case["rm"], case["rv"], mom, eps)
+    for k in ("scale", "shift", "mean", "rstd", "running_mean", "running_var"):
+        check(f"{tag} bn_finalize {k}", run["alone"][k], *ref[k])
+        assert _same_bits(run["carried"][k], run["alone"][k]), (tag, k)
+    assert int(run["alone"]["nbt"]) == 6 and int(run["carried"]["nbt"]) == 6
+    assert abs(float(run["alone"]["rstd"][0]) * eps ** 0.5 - 1.0) <= 1e-6
+    mean, rstd = run["alone"]["mean"], run["alone"]["rstd"]
+    # ---- backward
+    runb = {}
+    for form in ("carried", "alone"):
+        o = {"coef": torch.empty(3, ch, device=DEV), "dgamma": torch.empty(ch, device=DEV), "dbeta": torch.empty(ch, device=DEV)}
+        args = (stats.data_ptr(), nrep, count, g.data_ptr(), mean.data_ptr(), rstd.data_ptr(), o["coef"].data_ptr(),
+                o["dgamma"].data_ptr(), o["dbeta"].data_ptr(), ch)
+        if form == "carried":
+            _lib.check(lib.pcaa_bn_tail_arm_bwd(*args, counter.data_ptr()), "pcaa_bn_tail_arm_bwd")
+            produce()
+        else:
+            _lib.check(lib.pcaa_bn_bwd_finalize(*args, s), "pcaa_bn_bwd_finalize")
+        runb[form] = o
+    refb = R.bn_bwd_finalize_ref(stats, count, g, mean, rstd)
+    got = runb["alone"]
+    for k, t in (("coef0", got["coef"][0]), ("coef1", got["coef"][1]), ("coef2", got["coef"][2]), ("dgamma", got["dgamma"]),
+                 ("dbeta", got["dbeta"])):
+        check(f"{tag} bn_bwd_finalize {k}", t, *refb[k])
+    for k in ("coef", "dgamma", "dbeta"):
+        assert _same_bits(runb["carried"][k], runb["alone"][k]), (tag, k)
+    # ---- eval-mode backward finalize (never carried)
+    sc = run["alone"]["scale"]
+    oe = {k: torch.empty(ch, device=DEV) for k in ("dgamma", "dbeta", "dbias")}
+    _lib.check(lib.pcaa_bn_eval_bwd_finalize(stats.data_ptr(), nrep, sc.data_ptr(), oe["dgamma"].data_ptr(),
+                                             oe["dbeta"].data_ptr(), oe["dbias"].data_ptr(), ch, s), "pcaa_bn_eval_bwd_finalize")
+    refe = E.bn_eval_bwd_finalize_ref(stats, sc)
+    for k in ("dgamma", "dbeta", "dbias"):
+        check(f"{tag} bn_eval_bwd_finalize {k}", oe[k], *refe[k])
 
 
 # ===================================================================================================== split-K reduction
