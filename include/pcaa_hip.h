@@ -857,6 +857,40 @@ int pcaa_frames_from_raw_unique_aug(const void* points, int points_f64, long P, 
                                     const int* pick, const int* frame_key, long seed, int N, int C, int standardize,
                                     int divide_by_std, float* rows, float* weight, int* u_off, long M, int* pick_out,
                                     int* err_flag, void* stream, int keep, int keep_min, int keep_rule, const double* aug);
+/* ------------------------------------------------------------------ scene frames -> people (scene.hip)
+ * Added after ABI 29 like pcaa_crops_from_raw (the version is unchanged: a library without these entry points fails to
+ * load by name).  A scene frame is one radar frame with everybody in view plus clutter, in the layout of
+ * pcaa_frames_from_raw: points [P, 5] fp32 / fp64 (x, y, z, doppler, linear power), offsets [n + 1].
+ * pcaa_scene_cluster clusters every frame by density, one workgroup per frame, one launch:
+ *   d2(i, j) = dx*dx + dy*dy + wz2*dz*dz + wv2*dv*dv in fp64 from the stored values, in that order, no contraction;
+ *   i, j neighbours iff d2 <= eps2 (self included); i core iff it has >= min_points neighbours; clusters = connected
+ *   components of the core points; a non-core point with a core neighbour joins the cluster of its nearest one (smallest
+ *   d2, lowest index on exact ties) and links nothing; the rest is noise (-1); ids 0 .. c - 1 by ascending lowest core
+ *   index; clusters with id >= Cmax become noise and set bit 1 of *err.  scene.cluster_host restates it bit for bit.
+ * Outputs: label int32 [P]; n_clusters int32 [n] (= min(c, Cmax)); cluster_count int32 [n, Cmax]; centroid fp32
+ * [n, Cmax, 4] = (float)(sum64 / count) of x, y, z, doppler, the fp64 sum in ascending detection order, unused entries
+ * zero; grouped [P, 5] in the input type: frame f's rows as cluster 0, cluster 1, ..., then noise, each group in ascending
+ * detection order and bit-equal to the input rows; seg_off int32 [n, Cmax + 1], absolute rows: cluster c of frame f owns
+ * grouped[seg_off[f, c] : seg_off[f, c + 1]], the noise grouped[seg_off[f, Cmax] : offsets[f + 1]].
+ * A frame without detections is legal (zero clusters, seg_off = offsets[f]).  A frame with more than PCAA_RAW_MAX_CARD
+ * detections sets bit 0 of *err and is all noise (grouped = its rows, seg_off = offsets[f]); a frame whose offsets leave
+ * [0, P] or run backwards sets bit 0, has zero clusters, seg_off = 0, and none of its rows is read or written.  Rows of
+ * label / grouped that no frame owns are not written.  Frames are checked one by one, not against each other: offsets that
+ * are not monotone (0, 10, 5, 15) give two valid frames that share rows, and those rows of label / grouped then hold
+ * either frame's values -- in bounds, *err not set; the per-frame tables stay exact.  The centroid's fp64 sum starts from the
+ * cluster's first member (np.cumsum(...)[-1] / count on the host, bit for bit).  Every loop of the kernel is bounded by the frame's cardinality:
+ * no input can hang it; *err (required) is its only report.  1 <= Cmax <= PCAA_SCENE_MAX_CLUSTERS, min_points >= 1,
+ * eps2 / wz2 / wv2 finite and >= 0, P < 2^31; grouped may not alias points. */
+#define PCAA_SCENE_MAX_CLUSTERS 64
+int pcaa_scene_cluster(const void* points, int points_f64, long P, const int* offsets, int n, double eps2, double wz2,
+                       double wv2, int min_points, int Cmax, int* label, int* n_clusters, int* cluster_count,
+                       float* centroid, void* grouped, int* seg_off, int* err, void* stream);
+/* out rows out_off[o] .. out_off[o + 1] - 1 = the rows of src [P, 5] from seg_start[o] on, o < M, one launch: the
+ * (points, offsets = out_off) that pcaa_frames_from_raw takes, from the segments the host chose.  out [R, 5] in src's
+ * type.  A segment that leaves [0, P], or whose out rows leave [0, R] or run backwards, is skipped and sets *err (may be
+ * NULL). */
+int pcaa_gather_segments(const void* src, int src_f64, long P, const int* seg_start, const int* out_off, int M, void* out,
+                         long R, int* err, void* stream);
 /* ABI 25 (segment_pool.hip): out[f, c] = (1 / N) sum_{r = u_off[f]}^{u_off[f + 1] - 1} weight[r] * v(a[r * lda + c]) for
  * n frames, a [M, ch] fp32 or bf16 (dtype) with leading dimension lda, out [n, ch] fp32.  v = identity; with scale / shift
  * [ch] (both or neither) a is a pre-BatchNorm y and v = ELU(a * scale[c] + shift[c]) (fused multiply-add, expm1f).  fp32

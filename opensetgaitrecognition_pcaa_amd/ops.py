@@ -1785,6 +1785,78 @@ def frames_from_raw_unique(points, offsets, N, C, *, pick=None, seed=0, frame_ke
     return rows, weight, u_off
 
 
+SCENE_MAX_CLUSTERS = 64   # PCAA_SCENE_MAX_CLUSTERS of include/pcaa_hip.h
+
+
+def _chk_rows5(t, name):
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{name}: expected a float32 or float64 tensor")
+    _chk(t, name, None, 2)
+    if t.shape[1] != 5 or t.shape[0] >= 2 ** 31:
+        raise ValueError(f"{name}: needs [P, 5] with P < 2^31, got {tuple(t.shape)}")
+
+
+def scene_cluster(points, offsets, eps2, wz2, wv2, min_points, max_clusters, err, zero_fill=True):
+    """Density clustering of n scene frames in one launch (pcaa_scene_cluster): ``points`` [P, 5] fp32 or fp64 (x, y, z,
+    doppler, linear power: ``datasets.pack_raw_frames``' layout), ``offsets`` int32 [n + 1] -> ``(label int32 [P],
+    n_clusters int32 [n], cluster_count int32 [n, Cmax], centroid fp32 [n, Cmax, 4], grouped [P, 5], seg_off int32
+    [n, Cmax + 1])``.  Neighbours: ``dx*dx + dy*dy + wz2*dz*dz + wv2*dv*dv <= eps2`` in fp64; core: ``>= min_points``
+    neighbours, self included; clusters: components of the core points, border points with their nearest core neighbour,
+    ids by lowest core index; noise -1 (``scene.cluster_host`` restates the rule bit for bit).  ``grouped`` holds every
+    frame's rows cluster by cluster, then the noise; cluster c of frame f owns ``grouped[seg_off[f, c] : seg_off[f, c +
+    1]]``.  ``err`` int32 [1] (required): bit 0 is set by a frame of more than RAW_MAX_CARD detections or with offsets
+    outside the points (zero clusters), bit 1 by a frame with more than ``max_clusters`` clusters (the rest is noise);
+    nothing is checked on the host.  Rows that no frame owns are zero (``label``: -1); ``zero_fill=False`` leaves them
+    unwritten and saves the two fills (the live front end: no ``seg_off`` entry ever points at such a row)."""
+    _chk_rows5(points, "scene_cluster.points")
+    _chk(offsets, "scene_cluster.offsets", torch.int32, 1)
+    _chk(err, "scene_cluster.err", torch.int32)
+    n, Cmax, min_points = offsets.numel() - 1, int(max_clusters), int(min_points)
+    eps2, wz2, wv2 = float(eps2), float(wz2), float(wv2)
+    if n < 0 or not 1 <= Cmax <= SCENE_MAX_CLUSTERS or min_points < 1 or err.numel() < 1:
+        raise ValueError(f"scene_cluster: needs offsets [n + 1], 1 <= max_clusters <= {SCENE_MAX_CLUSTERS}, min_points >= 1; "
+                         f"got n={n}, max_clusters={Cmax}, min_points={min_points}")
+    if not all(0.0 <= v < float("inf") for v in (eps2, wz2, wv2)):
+        raise ValueError(f"scene_cluster: eps2, wz2 and wv2 must be finite and >= 0, got {eps2}, {wz2}, {wv2}")
+    dev, P = points.device, points.shape[0]
+    if zero_fill:
+        label, grouped = torch.full((P,), -1, dtype=torch.int32, device=dev), torch.zeros_like(points)
+    else:
+        label, grouped = torch.empty((P,), dtype=torch.int32, device=dev), torch.empty_like(points)
+    n_clusters = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty((n, Cmax), dtype=torch.int32, device=dev)
+    centroid = torch.empty((n, Cmax, 4), dtype=torch.float32, device=dev)
+    seg_off = torch.empty((n, Cmax + 1), dtype=torch.int32, device=dev)
+    if n:
+        _timed("scene_cluster_kernel", lambda: check(_lib.load().pcaa_scene_cluster(
+            _p(points), int(points.dtype == torch.float64), P, _p(offsets), n, eps2, wz2, wv2, min_points, Cmax, _p(label),
+            _p(n_clusters), _p(count), _p(centroid), _p(grouped), _p(seg_off), _p(err), _s()), "pcaa_scene_cluster"),
+            0.0, 2 * P * 5 * points.element_size())
+    return label, n_clusters, count, centroid, grouped, seg_off
+
+
+def gather_segments(src, seg_start, out_off, rows, err_flag=None, zero_fill=True):
+    """``out[out_off[o] : out_off[o + 1]] = src[seg_start[o] : seg_start[o] + out_off[o + 1] - out_off[o]]`` for the M
+    segments, one launch (pcaa_gather_segments): ``src`` [P, 5] fp32 or fp64, ``seg_start`` int32 [M] and ``out_off``
+    int32 [M + 1] on the device, ``rows`` = ``out_off[M]`` as the host knows it -> ``out`` [rows, 5] in ``src``'s dtype:
+    with ``offsets = out_off`` the layout ``frames_from_raw`` and ``push_raw`` take.  A segment that leaves the source or
+    the output is skipped (its rows stay zero; unwritten with ``zero_fill=False``) and sets ``err_flag`` (int32 [1])."""
+    _chk_rows5(src, "gather_segments.src")
+    _chk(seg_start, "gather_segments.seg_start", torch.int32, 1)
+    _chk(out_off, "gather_segments.out_off", torch.int32, 1)
+    M, rows = seg_start.numel(), int(rows)
+    if out_off.numel() != M + 1 or not 0 <= rows < 2 ** 31:
+        raise ValueError(f"gather_segments: needs seg_start [M], out_off [M + 1] and 0 <= rows < 2^31; got M={M}, out_off "
+                         f"{tuple(out_off.shape)}, rows={rows}")
+    if err_flag is not None:
+        _chk(err_flag, "gather_segments.err_flag", torch.int32)
+    out = (torch.zeros if zero_fill else torch.empty)((rows, 5), dtype=src.dtype, device=src.device)
+    if M:
+        check(_lib.load().pcaa_gather_segments(_p(src), int(src.dtype == torch.float64), src.shape[0], _p(seg_start),
+                                               _p(out_off), M, _p(out), rows, _p(err_flag), _s()), "pcaa_gather_segments")
+    return out
+
+
 def _chk_padded_frames(frames, who):
     """what frames_unique_offsets and frames_unique refuse before any launch -> (n, N, C)"""
     _chk(frames, who + ".frames", torch.float32, 3)

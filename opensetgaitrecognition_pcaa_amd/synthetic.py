@@ -143,3 +143,73 @@ def synthetic_raw_track(seed: int, n_frames: int, max_points: int = 40) -> list:
         })
     return frames
 
+
+def _as_raw_frame(p):
+    """rows (x, y, z, doppler, power) -> a raw frame dict of ``synthetic_raw_track``'s format"""
+    return {"cardinality": np.array([len(p)]), "elements": p[:, :2].copy(), "z_coord": p[:, 2].copy(),
+            "dopplers": p[:, 3].copy(), "powers": p[:, 4].copy()}
+
+
+def synthetic_scene(seed: int, n_frames: int, people, clutter: int, eps: float, z_weight: float = 0.1,
+                    doppler_weight: float = 0.0, min_card: int = 8, max_card: int = 20):
+    """Scene frames for ``scene.SceneSplitter`` with the people that went into them -> ``(scene, persons)``: ``scene`` a
+    list of ``n_frames`` raw frame dicts (the format of ``synthetic_raw_track``), ``persons[k]`` a list of ``n_frames``
+    entries, person k's own frame dict or None where they are not in view.  ``people``: their number, or a list of
+    ``(first, last)`` frame spans (``last`` exclusive).  Under the metric ``dx^2 + dy^2 + z_weight dz^2 + doppler_weight
+    dv^2``:
+
+    * person k walks along x at constant velocity (0.05 - 0.15 m per frame) in a lane of their own, the lanes ``3.5 eps``
+      apart: centres stay >= 3 eps apart;
+    * a person's ``min_card .. max_card`` detections lie inside a ball of radius ``eps / 2`` around the centre (drawn
+      within ``0.49 eps``, so that rounding to fp32 keeps them inside): all of them within ``eps`` of each other, one
+      cluster whatever ``min_points <= min_card``;
+    * ``clutter`` detections per frame sit on a lattice of pitch ``2 eps`` at least ``3 eps`` from every lane: isolated by
+      more than ``eps`` from everything.
+
+    A scene frame holds its people's and the clutter's detections in a random order; a person's own frame lists theirs in
+    the order they have in the scene frame (what a stable regrouping of the scene frame gives back), bit for bit."""
+    rng = np.random.default_rng(seed)
+    eps = float(eps)
+    spans = [(0, n_frames)] * people if isinstance(people, int) else [tuple(int(v) for v in s) for s in people]
+    K = len(spans)
+    x0 = rng.uniform(-1.0, 1.0, K)
+    vx = rng.uniform(0.05, 0.15, K) * rng.choice([-1.0, 1.0], K)
+    lane = 3.5 * eps * np.arange(K)
+    sz, sv = np.sqrt(z_weight), np.sqrt(doppler_weight)
+    slots = [(2.0 * eps * i, -3.0 * eps - 2.0 * eps * j) for i in range(-8, 9) for j in range(4)]
+    scene, persons = [], [[None] * n_frames for _ in range(K)]
+    for f in range(n_frames):
+        rows, owner = [], []
+        for k, (a, b) in enumerate(spans):
+            if not a <= f < b:
+                continue
+            n = int(rng.integers(min_card, max_card + 1))
+            u = rng.standard_normal((n, 4))
+            u *= (0.49 * eps * rng.random(n) ** 0.25 / np.linalg.norm(u, axis=1))[:, None]      # inside the metric's ball
+            pts = np.empty((n, 5))
+            pts[:, 0] = x0[k] + vx[k] * f + u[:, 0]
+            pts[:, 1] = lane[k] + u[:, 1]
+            pts[:, 2] = 1.0 + (u[:, 2] / sz if sz > 0 else rng.standard_normal(n) * 0.4)
+            pts[:, 3] = vx[k] * 10.0 + (u[:, 3] / sv if sv > 0 else rng.standard_normal(n) * 0.5)
+            pts[:, 4] = np.exp(rng.standard_normal(n) * 1.5)
+            rows.append(pts)
+            owner += [k] * n
+        if clutter:
+            where = rng.choice(len(slots), size=clutter, replace=False)
+            pts = np.empty((clutter, 5))
+            pts[:, :2] = np.array(slots)[where]
+            pts[:, 2] = rng.uniform(0.0, 2.0, clutter)
+            pts[:, 3] = rng.standard_normal(clutter)
+            pts[:, 4] = np.exp(rng.standard_normal(clutter))
+            rows.append(pts)
+            owner += [-1] * clutter
+        allp = np.concatenate(rows) if rows else np.zeros((0, 5))
+        owner = np.array(owner, dtype=np.int64)
+        order = rng.permutation(len(owner))
+        allp, owner = allp[order], owner[order]
+
+        scene.append(_as_raw_frame(allp))
+        for k in range(K):
+            if (owner == k).any():
+                persons[k][f] = _as_raw_frame(allp[owner == k])
+    return scene, persons
