@@ -2477,18 +2477,44 @@ def heads_supported(B, K, d_in, d_sup, d_head, d_proj, backward):
                                                  1 if backward else 0))
 
 
+HEADS_D_IN, HEADS_D_SUP, HEADS_D_HEAD, HEADS_D_PROJ = 512, 32, 16, 64      # the widths heads.hip is written for
+
+
+def _chk_heads_shapes(who, named):
+    """every (name, tensor, shape) is a contiguous fp32 device tensor of exactly the shape the kernel addresses"""
+    for nm, t, shape in named:
+        _chk(t, f"{who}.{nm}", torch.float32)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}.{nm}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _heads_dims(who, x4, W2, Wh, Wg, backward):
+    """-> (B, K, width of W2's rows); refuses what pcaa_heads_supported refuses, before anything else is looked at"""
+    _chk(x4, f"{who}.x4", torch.float32, 2)
+    _chk(W2, f"{who}.W2", torch.float32, 2)
+    B, K = x4.shape[0], W2.shape[0]
+    if not heads_supported(B, K, x4.shape[1], HEADS_D_SUP, HEADS_D_HEAD if Wh is not None else 0,
+                           HEADS_D_PROJ if Wg is not None else 0, backward):
+        raise ValueError(f"{who}: x4 {tuple(x4.shape)} / W2 {tuple(W2.shape)}: takes x4 [B >= 1, {HEADS_D_IN}] and W2 with "
+                         "K >= 1 rows" + (", B <= 64 and K <= 8 in the backward" if backward else ""))
+    return B, K, HEADS_D_HEAD if Wh is not None else HEADS_D_SUP
+
+
 def heads_fwd(x4, W1, b1, Wh, bh, W2, b2, Wg=None, bg=None):
     """One launch for MLP_sup1 -> (MLP_head) -> MLP_sup2 and, if given, the decoder projection head.
     Returns (sup_fv [B,32], h [B,16] or None, logits [B,K], hproj [B,64] or None)."""
-    _chk(x4, "heads_fwd.x4", torch.float32, 2)
-    for nm, t in (("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2)):
-        _chk(t, f"heads_fwd.{nm}", torch.float32)
-    B, K = x4.shape[0], W2.shape[0]
-    d_head = Wh.shape[0] if Wh is not None else 0
-    d_proj = Wg.shape[0] if Wg is not None else 0
-    if (tuple(W1.shape) != (32, x4.shape[1]) or W2.shape[1] != (d_head or 32)
-            or not heads_supported(B, K, x4.shape[1], 32, d_head, d_proj, False)):
-        raise ValueError(f"heads_fwd: unsupported shapes x4 {tuple(x4.shape)} W1 {tuple(W1.shape)} W2 {tuple(W2.shape)}")
+    if (Wh is None) != (bh is None):
+        raise ValueError("heads_fwd: Wh and bh go together")
+    if (Wg is None) != (bg is None):
+        raise ValueError("heads_fwd: Wg and bg go together")
+    B, K, din2 = _heads_dims("heads_fwd", x4, W2, Wh, Wg, False)
+    d_head, d_proj = HEADS_D_HEAD, HEADS_D_PROJ
+    named = [("W1", W1, (HEADS_D_SUP, HEADS_D_IN)), ("b1", b1, (HEADS_D_SUP,)), ("W2", W2, (K, din2)), ("b2", b2, (K,))]
+    if Wh is not None:
+        named += [("Wh", Wh, (d_head, HEADS_D_SUP)), ("bh", bh, (d_head,))]
+    if Wg is not None:
+        named += [("Wg", Wg, (d_proj, HEADS_D_SUP)), ("bg", bg, (d_proj,))]
+    _chk_heads_shapes("heads_fwd", named)
     dev = x4.device
     sup = torch.empty((B, 32), dtype=torch.float32, device=dev)
     h = torch.empty((B, d_head), dtype=torch.float32, device=dev) if Wh is not None else None
@@ -2502,26 +2528,26 @@ def heads_fwd(x4, W1, b1, Wh, bh, W2, b2, Wg=None, bg=None):
 def heads_bwd(x4, sup_fv, h, logits, hproj, W1, Wh, W2, Wg, d_logits, d_sup, d_hproj, outs=None):
     """One launch for the backward of heads_fwd.  ``outs``: optional dict of destination views
     (dW1, db1, dWh, dbh, dW2, db2, dWg, dbg) -- missing ones are allocated.  Returns (grads dict, dx4)."""
-    B, K = x4.shape[0], W2.shape[0]
-    for nm, t in (("x4", x4), ("sup_fv", sup_fv), ("logits", logits), ("W1", W1), ("W2", W2)):
-        _chk(t, f"heads_bwd.{nm}", torch.float32)
-    for nm, t, shape in (("d_logits", d_logits, (B, K)), ("d_sup", d_sup, (B, 32)), ("d_hproj", d_hproj, (B, 64))):
-        if t is not None:
-            _chk(t, f"heads_bwd.{nm}", torch.float32)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"heads_bwd.{nm}: shape {tuple(t.shape)}, expected {shape}")
+    if (Wh is None) != (h is None):
+        raise ValueError("heads_bwd: Wh and h go together")
+    if d_hproj is not None and (Wg is None or hproj is None):
+        raise ValueError("heads_bwd: d_hproj needs Wg and hproj")
+    B, K, din2 = _heads_dims("heads_bwd", x4, W2, Wh, Wg, True)
+    d_sup_, d_head, d_proj = HEADS_D_SUP, HEADS_D_HEAD, HEADS_D_PROJ
+    shapes = {"dW1": (d_sup_, HEADS_D_IN), "db1": (d_sup_,), "dW2": (K, din2), "db2": (K,), "dWh": (d_head, d_sup_),
+              "dbh": (d_head,), "dWg": (d_proj, d_sup_), "dbg": (d_proj,)}
+    named = [("sup_fv", sup_fv, (B, d_sup_)), ("h", h, (B, d_head)), ("logits", logits, (B, K)), ("hproj", hproj, (B, d_proj)),
+             ("W1", W1, shapes["dW1"]), ("Wh", Wh, shapes["dWh"]), ("W2", W2, shapes["dW2"]), ("Wg", Wg, shapes["dWg"]),
+             ("d_logits", d_logits, (B, K)), ("d_sup", d_sup, (B, d_sup_)), ("d_hproj", d_hproj, (B, d_proj))]
+    _chk_heads_shapes("heads_bwd", [n for n in named if n[1] is not None or n[0] in ("sup_fv", "logits", "W1")])
     outs = dict(outs or {})
     dev = x4.device
-    want = {"dW1": W1, "db1": W1.shape[0], "dW2": W2, "db2": K}
-    if Wh is not None:
-        want.update(dWh=Wh, dbh=Wh.shape[0])
-    if d_hproj is not None:
-        want.update(dWg=Wg, dbg=Wg.shape[0])
-    for k, like in want.items():
+    want = ["dW1", "db1", "dW2", "db2"] + (["dWh", "dbh"] if Wh is not None else []) + \
+        (["dWg", "dbg"] if d_hproj is not None else [])
+    for k in want:
         if outs.get(k) is None:
-            outs[k] = (torch.empty_like(like) if isinstance(like, torch.Tensor)
-                       else torch.empty(like, dtype=torch.float32, device=dev))
-        _chk(outs[k], f"heads_bwd.{k}", torch.float32)
+            outs[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+    _chk_heads_shapes("heads_bwd", [(k, outs[k], shapes[k]) for k in shapes if outs.get(k) is not None])
     dx4 = torch.empty_like(x4)
     check(_lib.load().pcaa_heads_bwd(_p(x4), _p(sup_fv), _p(h), _p(logits), _p(hproj), _p(W1), _p(Wh), _p(W2),
                                      _p(Wg), _p(d_logits), _p(d_sup), _p(d_hproj), _p(outs["dW1"]), _p(outs["db1"]),
